@@ -3,7 +3,11 @@
 config 2: N = 169,343, ~2.33 M symmetrised edges + N self loops, d = 128, H = 8, B = 4,
 aggregators sum+mean+max+symnorm, fp32).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+With ``--dump-outputs DIR`` (one GPU, the default workload) the layer output of the last timed step is written to DIR
+as ``.npy`` files: a fixed, seeded sample of its rows (the full output is 87 MB) and the indices of those rows.  The
+inputs depend on ``--seed`` alone, so two builds of the project can be compared output for output.
 
 A "step" is one full layer forward through the C ABI (basis GEMM + fused aggregate/combine) with every input
 already resident in HBM and the CSR pre-built (static graph, the reference's ``cached=True``).  Rank 0 prints
@@ -31,6 +35,7 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -197,6 +202,28 @@ def roofline_terms(n, e_eff, f_in, f_g, f_out, w_cols, symnorm):
 # -------------------------------------------------------------------------------------------------
 LINE_LIMIT_BYTES = 6000
 DETAIL_FILE = "bench_detail.json"
+
+# --dump-outputs: 120,000 of the 169,343 output rows (61.4 MB float32 + their indices) stay under the 64 MB budget
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_ROWS = 120_000
+DUMP_SEED = 1234   # the sample does not depend on --seed: the same rows are compared whatever the inputs
+
+
+def dump_sample_rows(n):
+    """Sorted indices of the output rows --dump-outputs writes (the same on every run)."""
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.sort(rng.choice(n, size=min(DUMP_ROWS, n), replace=False))
+
+
+def dump_outputs(path, arrays):
+    """Write each float32 / float64 array as path/<name>.npy; refuses to write more than DUMP_LIMIT_BYTES in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte budget"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), f"--dump-outputs: {name} is {a.dtype}"
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"dumped {', '.join(f'{k}{list(v.shape)}' for k, v in arrays.items())} ({total / 1e6:.1f} MB) to {path}")
 
 
 def _r(v, sig=6):
@@ -751,7 +778,15 @@ def main():
                          "headline with config 5 (homogeneous mag, typed rmag through a partitioned REGConv) nested; "
                          "arxiv / mag / rmag run one of them alone")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the layer output of the last timed step (a fixed sample of its rows) to DIR/*.npy; "
+                         "one GPU, default workload")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    forced = os.environ.get("EGC_BENCH_FORCE_PARTITION", "0") not in ("", "0") and "RANK" in os.environ
+    if args.dump_outputs and (args.gpus > 1 or args.workload not in (None, "arxiv") or forced):
+        ap.error("--dump-outputs is implemented for the one-GPU arxiv workload (the default) only")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         spawn_ranks(args.gpus, sys.argv[1:])     # does not return
@@ -762,7 +797,6 @@ def main():
     workload = args.workload or ("arxiv" if world == 1 else "all")
     if workload == "rmag" and world == 1:
         return bench_rmag(args, world, dev)
-    forced = os.environ.get("EGC_BENCH_FORCE_PARTITION", "0") not in ("", "0") and "RANK" in os.environ
     if forced and args.workload is None:
         workload = "all"
     if workload != "arxiv" or world > 1 or forced:
@@ -858,6 +892,9 @@ def main():
     elapsed = time.perf_counter() - t0
     ms_per_step = elapsed / args.steps * 1e3
     value = float(e_eff) / (elapsed / args.steps)
+    if args.dump_outputs:   # the last timed step's output, before anything below overwrites `out`
+        dump_rows = dump_sample_rows(n)
+        dump_out = out.index_select(0, torch.from_numpy(dump_rows).to(dev)).cpu().numpy()
     # robustness of the headline (not part of its definition): four more regions of the same length, the median of the five
     regions = [ms_per_step]
     for _ in range(4):
@@ -976,6 +1013,8 @@ def main():
             log(f"cpu baseline failed: {ex!r}")
             result["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": 0, "kind": "port", "sample": "failed",
                                       "error": repr(ex)[:500]}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"layer_out_rows_sample": dump_out, "layer_out_row_ids": dump_rows.astype(np.float64)})
     emit(result)
 
 

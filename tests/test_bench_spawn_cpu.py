@@ -61,3 +61,34 @@ def test_bench_line_is_compact_and_keeps_the_contract(tmp_path, capsys, monkeypa
                             "cpu_edges_per_s", "cpu_cores", "error"}
     detail = json.load(open(tmp_path / "detail.json"))
     assert detail["roofline"]["note"] == "n" * 3000 and len(detail["other_configs"]) == len(full["other_configs"])
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget(tmp_path):
+    """--dump-outputs: the same rows of the config-2 output every run, float arrays only, under the 64 MB budget."""
+    import numpy as np
+    bench = _load_bench()
+    n = 169343
+    rows = bench.dump_sample_rows(n)
+    assert np.array_equal(rows, bench.dump_sample_rows(n))
+    assert rows.min() >= 0 and rows.max() < n and np.all(np.diff(rows) > 0)
+    arrays = {"layer_out_rows_sample": np.ones((len(rows), 128), np.float32), "layer_out_row_ids": rows.astype(np.float64)}
+    bench.dump_outputs(str(tmp_path / "d"), arrays)
+    assert sum(os.path.getsize(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")) <= 64_000_000
+    for name, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "d" / f"{name}.npy"), a)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"ids": rows})                          # int64: not a float array
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"big": np.zeros(16_000_001, np.float32)})   # over the budget
+
+
+@pytest.mark.parametrize("argv, message", [
+    (["--steps", "0"], "--steps must be at least 1"),
+    (["--gpus", "2", "--dump-outputs", "d"], "--dump-outputs is implemented for the one-GPU arxiv workload"),
+    (["--workload", "mag", "--dump-outputs", "d"], "--dump-outputs is implemented for the one-GPU arxiv workload"),
+])
+def test_bench_refuses_arguments_it_cannot_honour(argv, message):
+    """Refused at argument parsing, before any rank is started or the GPU is touched."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 2 and message in r.stderr
+    assert "starting" not in r.stderr and not r.stdout
