@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "egc_aggregate_dev.h"
+#include "egc_gemm_split.h"
 #include "egc_pack_map.h"
 
 namespace egc {
@@ -803,6 +804,28 @@ int egc_layer_forward_f32(const egc_graph* graph, const egc_layer* layer, const 
                                    workspace_bytes, stream);
 }
 
+// Folded weightings (egc_hip.h, egc_layer_forward_packed): the places of sum (*fs) and mean (*fm) in an aggregator list of four
+// that holds each once, and the deg^-1/2 table of the aggregators' edge set, whose inverse square is the count mean divides by
+// -- taken only where symnorm over the same edge set makes the aggregate read that very table -- else false.  The count is
+// rint(dis^-2): exact while every producer of dis_raw / dis_looped writes 1 / sqrt(entry count of that set) to within a few ulps
+// (egc_graph.hip says so at each of them); a weighted degree in those tables would break the fold, not only symnorm.
+static bool fold_mean(const egc_graph* graph, const egc_layer* layer, int* fs, int* fm, const float** dis) {
+  if (layer->num_aggrs != 4 || layer->weight_layout != EGC_LAYOUT_HBA || layer->weight_act != EGC_ACT_NONE) return false;
+  int s = -1, m = -1, y = 0;
+  for (int t = 0; t < 4; ++t) {
+    const int c = layer->aggrs[t];
+    if (c == EGC_AGGR_SUM) s = s < 0 ? t : 4;
+    if (c == EGC_AGGR_MEAN) m = m < 0 ? t : 4;
+    if (c == EGC_AGGR_SYMNORM) y = 1;
+  }
+  if (s < 0 || m < 0 || s > 3 || m > 3 || !y || layer->sym_set != layer->agg_set) return false;
+  *dis = layer->agg_set == EGC_SET_LOOPED ? graph->dis_looped : graph->dis_raw;
+  if (*dis == nullptr) return false;
+  *fs = s;
+  *fm = m;
+  return true;
+}
+
 int egc_layer_forward_packed(const egc_graph* graph, const egc_layer* layer, const float* x, const void* packed,
                              const float* bcat, const float* bias, float* bases, int32_t ldb, float* weightings,
                              float* out, void* workspace, size_t workspace_bytes, egc_stream_t stream) {
@@ -811,6 +834,21 @@ int egc_layer_forward_packed(const egc_graph* graph, const egc_layer* layer, con
   if (st != EGC_OK) return st;
   const int fg = layer->num_bases * layer_basis_stride(layer);  // padded bases are GEMM columns too (zero weights)
   const int w = layer->num_heads * layer->num_bases * layer->num_aggrs;
+  int fs, fm;
+  const float* dis;
+  if (fold_mean(graph, layer, &fs, &fm, &dis)) {
+    st = egc::basis_transform_packed_folded(x, packed, bcat, graph->n_nodes, layer->in_channels, fg, w, egc_layer_gemm_flags(layer),
+                                            bases, ldb, weightings, dis, fs, fm, (hipStream_t)stream);
+    if (st == EGC_OK) {   // the aggregate of the same layer without mean, on the [N, H B 3] weightings
+      egc_layer folded = *layer;
+      folded.num_aggrs = 3;
+      for (int t = fm; t < 3; ++t) folded.aggrs[t] = layer->aggrs[t + 1];
+      folded.aggrs[3] = 0;
+      return egc_aggregate_combine_f32(graph, &folded, bases, ldb, weightings, bias, out, nullptr, nullptr, workspace,
+                                       workspace_bytes, stream);
+    }
+    if (st != EGC_ERR_UNSUPPORTED) return st;   // (UNSUPPORTED: the shape runs another GEMM kernel -- the unfolded form below)
+  }
   st = egc_basis_transform_packed_ex(x, packed, bcat, graph->n_nodes, layer->in_channels, fg, w, egc_layer_gemm_flags(layer),
                                      bases, ldb, weightings, stream);
   if (st != EGC_OK) return st;

@@ -622,6 +622,8 @@ int launch_fast(AggArgs a, int64_t n_nodes, const PlanCaps& caps, hipStream_t st
     constexpr int S = EGC_AGGR_SUM, M = EGC_AGGR_MEAN, X = EGC_AGGR_MAX, Y = EGC_AGGR_SYMNORM;
     // EGConv / EGC-M north star: d=128, H=8, B=4, sum+mean+max+symnorm, gcn_norm self-loops on every node
     EGC_STATIC_CFG(8, 4, 16, 4, agg_pack(S, M, X, Y), EGC_ACT_NONE, true, true, true, 0)
+    // the same layer through egc_layer_forward_packed: the mean's weighting folded into the sum's by the GEMM (3 weightings per (h, b))
+    EGC_STATIC_CFG(8, 4, 16, 3, agg_pack(S, X, Y), EGC_ACT_NONE, true, true, true, 0)
     // the same layer with `std` in place of `mean` (bench.py: std_layer): the squares about the row's first entry
     EGC_STATIC_CFG(8, 4, 16, 4, agg_pack(S, EGC_AGGR_STD, X, Y), EGC_ACT_NONE, true, true, true, NEED_SQ)
     // EGConv / EGC-S default: symnorm only (optimized_layers.py:77)

@@ -577,6 +577,18 @@ static int launch_ws(const float* x, const u16* packed, const float* bcat, int64
 
 static inline int round_up32(int v) { return (v + 31) & ~31; }
 
+// (egc_layer_forward_packed, egc_aggregate.hip)
+int basis_transform_packed_folded(const float* x, const void* packed, const float* bcat, int64_t n_nodes, int32_t f_in,
+                                  int32_t f_g, int32_t w_cols, int32_t flags, float* bases, int32_t ldb, float* weightings,
+                                  const float* dis, int fold_s, int fold_m, hipStream_t stream) {
+  if (n_nodes < 0 || f_in <= 0 || f_g <= 0 || w_cols <= 0 || ldb != ((f_g + 3) & ~3)) return EGC_ERR_INVALID;
+  if (x == nullptr || packed == nullptr || bases == nullptr || weightings == nullptr || dis == nullptr) return EGC_ERR_INVALID;
+  const int NV = round_up32(ldb + w_cols);
+  if ((flags & EGC_GEMM_24BIT) != 0 || !f16x2_shape(f_in, ldb, NV, w_cols) || w_cols % 32 != 0) return EGC_ERR_UNSUPPORTED;  // (= use_f16x2)
+  if (n_nodes == 0) return EGC_OK;
+  return f16x2_launch(x, packed, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, stream, dis, fold_s, fold_m);
+}
+
 }  // namespace egc
 
 using namespace egc;

@@ -119,15 +119,28 @@ constexpr int F16X2_LDX = F16X2_KP + 8;
 constexpr int F16X2_RAW_BYTES = F16X2_ROWS * F16X2_KP * 4;                  // one raw fp32 tile
 constexpr int F16X2_PLANE_BYTES = 2 * 2 * F16X2_ROWS * F16X2_LDX * 2;       // two buffers x two planes
 constexpr int F16X2_STORES_PER_TILE = 16;  // per wavefront (vmcnt arithmetic below)
+constexpr int F16X2_CNT_SLOTS = 8;         // ring of per-row 1 / max(cnt, 1) of the folded form (a tile's slot lives 5 tiles)
+constexpr int F16X2_LDS_BYTES = F16X2_PLANE_BYTES + 2 * F16X2_RAW_BYTES + 3 * F16X2_ROWS * 4 + (F16X2_CNT_SLOTS * F16X2_ROWS + 4) * 4;
+
+// Folded weightings (FM >= 0: egc_layer_forward_packed with sum and mean in the aggregator list, egc_hip.h).  mean = sum /
+// max(cnt, 1) over the same entries, so  w_sum sum + w_mean mean = (w_sum + w_mean / max(cnt, 1)) sum:  the GEMM writes
+// H B (A - 1) weightings per row, the sum column carrying the mean's weighting, and the aggregate forms no mean.  In the
+// HBA order the A = 4 weightings of a (h, b) pair are one lane quad of a wavefront, FM is the mean's place in it: one DPP
+// broadcast inside the quad and one fma per element fold them, the mean lane's store is dropped and the others close ranks
+// (output column 3 pair + a - (a > FM)).  cnt comes from the graph's deg^-1/2 table of the aggregators' edge set (dis^-2 =
+// cnt exactly after rounding to an integer, for rows of fewer than 2^20 entries), brought in by LDS-DMA like the x tiles
+// and turned into the aggregate's own rcp(max(cnt, 1)) once per tile.
 
 #define EGC_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 
+template <int FM>
 __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const float* __restrict__ x,
                                                                           const u16* __restrict__ packed,
                                                                           const float* __restrict__ bcat, int64_t M, int K,
                                                                           int W, float* __restrict__ bases, int ldb,
                                                                           float* __restrict__ weightings, int NV,
-                                                                          int rows_per_block) {
+                                                                          int rows_per_block, const float* __restrict__ dis,
+                                                                          int fold_s) {
   constexpr int KP = F16X2_KP;
   constexpr int KSUB = KP / 16;         // 16-k MFMA steps
   constexpr int LDX = F16X2_LDX;
@@ -140,6 +153,8 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   // inverse row scales of tile t live in row_inv[t % 3]: tile t-1's are still being read by its deferred
   // epilogue while the split of tile t+1 writes its own
   float* row_inv = reinterpret_cast<float*>(raw + 2 * F16X2_RAW_BYTES);          // [3][ROWS]
+  float* icnt = row_inv + 3 * ROWS;                   // FM >= 0: [F16X2_CNT_SLOTS][ROWS] dis, then 1 / max(cnt, 1), of tile t at t % 8
+  float* zero4 = icnt + F16X2_CNT_SLOTS * ROWS;  // 16 zero bytes: what the lanes other than the sum lanes fold with
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -166,16 +181,27 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   const u32x4 rx = {(unsigned)(uintptr_t)x, (unsigned)((uintptr_t)x >> 32) & 0xffffu, (unsigned)(M * K * 4), 0x00020000u};
   // this wavefront's 32 columns lie either in `bases` or in `weightings` (host: ldb % 32 == 0, or W == 0: every tile in `bases`)
   const bool to_bases = cb < ldb;
+  const int wcol_v = cb - ldb + l31;                  // weightings column of this lane (to_bases == false)
+  const int qa = wcol_v & 3;                          // FM >= 0: place in the (h, b) pair's quad
+#ifdef EGC_DIAG_FOLD_W128   // diagnostic build: the fold's arithmetic with the unfolded store pattern (all 128 columns, whole lines;
+  constexpr int FMS = -1;   // results are wrong, times are not) -- what the fold's instructions cost apart from its store layout
+#else
+  constexpr int FMS = FM;   // the store layout's FM
+#endif
+  const int W_out = FMS >= 0 ? W / 4 * 3 : W;         // row length of the weightings written
   const __amdgpu_buffer_rsrc_t ro =
       to_bases ? __builtin_amdgcn_make_buffer_rsrc((void*)bases, 0, (unsigned)(row_hi * ldb * 4), 0x00020000)
-               : __builtin_amdgcn_make_buffer_rsrc((void*)weightings, 0, (unsigned)(row_hi * (int64_t)W * 4), 0x00020000);
-  const int out_ld = to_bases ? ldb : W;
-  const int out_col = (to_bases ? cb : cb - ldb) + l31;
+               : __builtin_amdgcn_make_buffer_rsrc((void*)weightings, 0, (unsigned)(row_hi * (int64_t)W_out * 4), 0x00020000);
+  const int out_ld = to_bases ? ldb : W_out;
+  const int out_col = to_bases ? cb + l31 : FMS >= 0 ? 3 * (wcol_v >> 2) + qa - (qa > FMS ? 1 : 0) : wcol_v;
 #if defined(EGC_DIAG_GEMM_NO_W_STORE) || defined(EGC_DIAG_GEMM_NO_W)   // diagnostic builds (tools/f3_roundtrip_cost.py): the weightings are
   const bool col_ok = to_bases && out_col < ldb;                        // not written / not computed at all (wrong results, honest times)
 #else
-  const bool col_ok = out_col < (to_bases ? ldb : W);
+  const bool col_ok = to_bases ? out_col < ldb : (wcol_v < W && (FMS < 0 || qa != FMS));
 #endif
+  const bool is_sum = FM >= 0 && !to_bases && qa == fold_s;
+  const u32x4 rd = {(unsigned)(uintptr_t)dis, (unsigned)((uintptr_t)dis >> 32) & 0xffffu, (unsigned)(M * 4), 0x00020000u};
+  const unsigned icnt_lds = (unsigned)(uintptr_t)icnt;
   const unsigned raw_lds = (unsigned)(uintptr_t)raw;  // LDS byte address of the ring
   const bool third = wave < 8;
 
@@ -195,10 +221,32 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
                  : "v"(voff), "s"(dst), "s"(rx)
                  : "memory");
   };
+  // FM >= 0: the tile's 64 dis values (one dword per lane) -> its slot of the count ring, by wavefront 8 (one of the
+  // wavefronts with two x pieces per tile: its DMA group then has three operations, like those of wavefronts 0-7)
+  auto dma_cnt = [&](int tile) {
+    const int64_t gm = row_lo + (int64_t)tile * ROWS + lane;
+    const bool ok = (tile < n_tiles) & (gm < row_hi);
+    const unsigned voff = ok ? (unsigned)(gm * 4) : GOOB;
+    const unsigned dst = __builtin_amdgcn_readfirstlane(icnt_lds + (tile & (F16X2_CNT_SLOTS - 1)) * ROWS * 4);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dword %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(dst), "s"(rd)
+                 : "memory");
+  };
   auto dma_tile = [&](int tile, int slot) {
     dma_piece(tile, slot, 0);
     dma_piece(tile, slot, 1);
     if (third) dma_piece(tile, slot, 2);
+    if (FM >= 0 && wave == 8) dma_cnt(tile);
+  };
+  // dis -> 1 / max(cnt, 1) in place (wavefront 8, once its own DMA of the slot has retired): cnt = dis^-2 rounded to an integer,
+  // then the aggregate's own reciprocal.  dis == 0 (no entries, or rows past the range) gives 0.
+  auto cnt_inverse = [&](int tile) {
+    float* p = icnt + (tile & (F16X2_CNT_SLOTS - 1)) * ROWS + lane;
+    const float d = *p;
+    const float c = __builtin_rintf(__builtin_amdgcn_rcpf(d * d));
+    *p = __builtin_amdgcn_rcpf(fmaxf(c, 1.f));
   };
   // A row is 32 consecutive pieces = one half wavefront: its largest magnitude is an all-reduce over 32 lanes
   // (4 DPP steps inside the rows of 16, one cross-row exchange).  NaNs drop out of the maxima and propagate
@@ -264,13 +312,27 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   // full 128-byte lines.  (With x as B a lane would hold 4 consecutive columns of one row and a dwordx4 store
   // would touch 32 lines: the stores, not the arithmetic, then set the tile time.)  Rows past M fall outside
   // the buffer and are dropped by its range check; the row part of the address is a scalar offset.
-  auto epilogue = [&](unsigned voff, int j, const float* rinv_t) {
+  auto epilogue = [&](unsigned voff, int j, const float* rinv_t, const float* icnt_t) {
     const float4 ri = *reinterpret_cast<const float4*>(rinv_t + 32 * rt + 8 * j + 4 * hh);
     // 2^ex 2^ew (acc0 + 2^-11 acc1) + bias; the scale product is a power of two, so the fma rounds once
-    const float v0 = __builtin_fmaf(t[4 * j], col_inv * ri.x, col_bias);
-    const float v1 = __builtin_fmaf(t[4 * j + 1], col_inv * ri.y, col_bias);
-    const float v2 = __builtin_fmaf(t[4 * j + 2], col_inv * ri.z, col_bias);
-    const float v3 = __builtin_fmaf(t[4 * j + 3], col_inv * ri.w, col_bias);
+    float v0 = __builtin_fmaf(t[4 * j], col_inv * ri.x, col_bias);
+    float v1 = __builtin_fmaf(t[4 * j + 1], col_inv * ri.y, col_bias);
+    float v2 = __builtin_fmaf(t[4 * j + 2], col_inv * ri.z, col_bias);
+    float v3 = __builtin_fmaf(t[4 * j + 3], col_inv * ri.w, col_bias);
+#ifdef EGC_DIAG_FOLD_NO_MATH   // diagnostic build: the folded store layout without the fold's arithmetic (wrong results, honest times)
+    if constexpr (false) {
+#else
+    if constexpr (FM >= 0) {
+#endif
+      if (!to_bases) {  // (wave-uniform) sum lane += mean lane's weighting x 1 / max(cnt, 1); the other lanes add 0 x it
+        const float4 ic = *reinterpret_cast<const float4*>(is_sum ? icnt_t + 32 * rt + 8 * j + 4 * hh : zero4);
+        constexpr int QP = FM | (FM << 2) | (FM << 4) | (FM << 6);  // quad_perm: every lane reads lane FM of its quad
+        v0 = __builtin_fmaf(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v0), QP, 0xf, 0xf, false)), ic.x, v0);
+        v1 = __builtin_fmaf(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v1), QP, 0xf, 0xf, false)), ic.y, v1);
+        v2 = __builtin_fmaf(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v2), QP, 0xf, 0xf, false)), ic.z, v2);
+        v3 = __builtin_fmaf(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v3), QP, 0xf, 0xf, false)), ic.w, v3);
+      }
+    }
     const int so = (8 * j) * out_ld * 4;
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v0), ro, voff, so, 0);
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v1), ro, voff, so + out_ld * 4, 0);
@@ -285,6 +347,7 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   constexpr int stride = 1;   // (tiles of this block's own range, in order)
   int tile = 0;
   if (n_tiles <= 0) return;
+  if (FM >= 0 && tid < 4) zero4[tid] = 0.f;   // (made visible by the barrier before the loop)
   if (K < KP) {  // columns k >= K of a tile are out of range for the DMA and must read as 0
     for (int i = tid; i < 2 * F16X2_RAW_BYTES / 16; i += nthreads) reinterpret_cast<u32x4*>(raw)[i] = u32x4{0, 0, 0, 0};
     lds_barrier2();
@@ -326,6 +389,7 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   int ri_cur = 0;                 // row_inv slot of the tile being multiplied (tile index mod 3)
   unsigned prev_off = SOOB;       // no previous tile yet: its stores are dropped
   const float* prev_ri = row_inv;
+  const float* prev_ic = icnt;
 #pragma unroll
   for (int r = 0; r < 16; ++r) t[r] = 0.f;
 #ifdef EGC_GEMM_STAMPS
@@ -342,7 +406,9 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   // i are the rest of that DMA group, one whole tile of stores + DMA, and this tile's stores:
   //     piece 0: (2|1) + 16 + (3|2) + 16 = 37 | 35     piece 1: (1|0) + 16 + (3|2) + 16 = 36 | 34
   //     piece 2 (wavefronts 0-7 only):   0 + 16 +  3    + 16 = 35
-  // A smaller count is always safe: one wait for 34 covers every piece of every wavefront.
+  // A smaller count is always safe: one wait for 34 covers every piece of every wavefront.  (Folded form: wavefront 8 issues
+  // the tile's count DMA after its two x pieces, so its pieces sit at 2 + 16 + 3 + 16 = 37 and 1 + 16 + 3 + 16 = 36.  Tile t's count
+  // DMA, issued in iteration t - 3, is read after the wait of iteration t, with 16 + 3 + 16 + 3 + 16 = 54 operations behind it.)
   static_assert(F16X2_STORES_PER_TILE == 16, "vmcnt count below");
   for (; tile < n_tiles; tile += stride) {
     const int slot = buf ^ 1;  // ring slot of the next tile (tile index parity == plane buffer parity)
@@ -354,23 +420,24 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
     // k-steps 0-3: the previous tile leaves
     frag(buf, 1, yh, yl);
     mfma_step(0, xh, xl);
-    epilogue(prev_off, 0, prev_ri);
+    epilogue(prev_off, 0, prev_ri, prev_ic);
     EGC_PIN;
     frag(buf, 2, xh, xl);
     mfma_step(1, yh, yl);
-    epilogue(prev_off, 1, prev_ri);
+    epilogue(prev_off, 1, prev_ri, prev_ic);
     EGC_PIN;
     frag(buf, 3, yh, yl);
     mfma_step(2, xh, xl);
-    epilogue(prev_off, 2, prev_ri);
+    epilogue(prev_off, 2, prev_ri, prev_ic);
     EGC_PIN;
     frag(buf, 4, xh, xl);
     mfma_step(3, yh, yl);
-    epilogue(prev_off, 3, prev_ri);
+    epilogue(prev_off, 3, prev_ri, prev_ic);
     EGC_PIN;
     EGC_STAMP(0)
     // k-steps 4-7: the next tile is split and staged, its ring slot re-armed
     EGC_VMCNT(34);
+    if (FM >= 0 && wave == 8) cnt_inverse(tile);   // (this tile's dis arrived with the DMA of three tiles ago)
     frag(buf, 5, yh, yl);
     mfma_step(4, xh, xl);
     stage(buf ^ 1, ri_next, slot, 0);
@@ -391,16 +458,17 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
     for (int r = 0; r < 16; ++r) t[r] = __builtin_fmaf(acc1[r], 1.f / 2048.f, acc0[r]);
     prev_off = out_offset(tile, true);
     prev_ri = row_inv + ri_cur * ROWS;
+    prev_ic = icnt + (tile & (F16X2_CNT_SLOTS - 1)) * ROWS;
     ri_cur = ri_cur == 2 ? 0 : ri_cur + 1;
     EGC_STAMP(2)
     lds_barrier2();
     EGC_STAMP(3)
     buf ^= 1;
   }
-  epilogue(prev_off, 0, prev_ri);
-  epilogue(prev_off, 1, prev_ri);
-  epilogue(prev_off, 2, prev_ri);
-  epilogue(prev_off, 3, prev_ri);
+  epilogue(prev_off, 0, prev_ri, prev_ic);
+  epilogue(prev_off, 1, prev_ri, prev_ic);
+  epilogue(prev_off, 2, prev_ri, prev_ic);
+  epilogue(prev_off, 3, prev_ri, prev_ic);
   EGC_VMCNT(0);  // no DMA may still be writing this block's LDS when it is handed to the next block
 #ifdef EGC_GEMM_STAMPS
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r1) :: "memory");
@@ -424,21 +492,34 @@ int f16x2_pack(const float* wcat, int64_t rs, int64_t cs, int f_in, int f_g, int
   return EGC_OK;
 }
 
-static int f16x2_launch_rows(const float* x, const void* packed, const float* bcat, int64_t M, int K, int W, float* bases,
-                             int ldb, float* weightings, int NV, hipStream_t stream) {
-  constexpr int ROWS = F16X2_ROWS;
-  const int threads = F16X2_THREADS;
-  const int64_t n_tiles64 = (M + ROWS - 1) / ROWS;
-  if (n_tiles64 >= ((int64_t)1 << 31)) return EGC_ERR_INVALID;
-  const int n_tiles = (int)n_tiles64;
-  const size_t lds = (size_t)F16X2_PLANE_BYTES + 2 * (size_t)F16X2_RAW_BYTES + (size_t)(3 * ROWS) * sizeof(float);
+// one instantiation per place of the mean in the quad (FM) and the plain form (FM = -1)
+template <int FM>
+static int f16x2_launch_fm(int grid, size_t lds, const float* x, const void* packed, const float* bcat, int64_t M, int K, int W,
+                           float* bases, int ldb, float* weightings, int NV, int rows_per_block, const float* dis, int fold_s,
+                           hipStream_t stream) {
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&basis_gemm_f16x2_kernel),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&basis_gemm_f16x2_kernel<FM>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2)", e); return EGC_ERR_HIP; }
     attr_set = true;
   }
+  basis_gemm_f16x2_kernel<FM><<<grid, F16X2_THREADS, lds, stream>>>(x, (const u16*)packed, bcat, M, K, W, bases, ldb, weightings,
+                                                                    NV, rows_per_block, dis, fold_s);
+  EGC_LAUNCH_CHECK("basis_gemm_f16x2_kernel");
+  return EGC_OK;
+}
+
+static int f16x2_launch_rows(const float* x, const void* packed, const float* bcat, int64_t M, int K, int W, float* bases,
+                             int ldb, float* weightings, int NV, const float* dis, int fold_s, int fold_m, hipStream_t stream) {
+  constexpr int ROWS = F16X2_ROWS;
+  const int threads = F16X2_THREADS;
+  (void)threads;
+  const int64_t n_tiles64 = (M + ROWS - 1) / ROWS;
+  if (n_tiles64 >= ((int64_t)1 << 31)) return EGC_ERR_INVALID;
+  const int n_tiles = (int)n_tiles64;
+  const size_t lds = (size_t)F16X2_LDS_BYTES;
+  static_assert(F16X2_LDS_BYTES <= 160 * 1024, "LDS of one CU");
   int grid = 256;  // one 12-wavefront block per CU (registers: 3 wavefronts per SIMD)
   if (grid > n_tiles) grid = n_tiles;
   const int rows_per_block = (int)((M + grid - 1) / grid);   // contiguous, equal row ranges
@@ -450,9 +531,15 @@ static int f16x2_launch_rows(const float* x, const void* packed, const float* bc
   }
   hipMemset(dbuf, 0, 1024 * 16 * 8 * 8);
 #endif
-  basis_gemm_f16x2_kernel<<<grid, threads, lds, stream>>>(x, (const u16*)packed, bcat, M, K, W, bases, ldb, weightings,
-                                                               NV, rows_per_block);
-  EGC_LAUNCH_CHECK("basis_gemm_f16x2_kernel");
+  int st;
+  switch (fold_m) {
+    case 0: st = f16x2_launch_fm<0>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, dis, fold_s, stream); break;
+    case 1: st = f16x2_launch_fm<1>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, dis, fold_s, stream); break;
+    case 2: st = f16x2_launch_fm<2>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, dis, fold_s, stream); break;
+    case 3: st = f16x2_launch_fm<3>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, dis, fold_s, stream); break;
+    default: st = f16x2_launch_fm<-1>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, nullptr, -1, stream);
+  }
+  if (st != EGC_OK) return st;
 #ifdef EGC_GEMM_STAMPS
   {
     hipDeviceSynchronize();
@@ -498,16 +585,20 @@ static int f16x2_launch_rows(const float* x, const void* packed, const float* bc
 // The kernel addresses x, bases and weightings through 32-bit buffer offsets (and drops masked stores at
 // offset 2^31 + scalar row offset): row ranges of less than 2 GiB per array are launched one after another.
 int f16x2_launch(const float* x, const void* packed, const float* bcat, int64_t M, int K, int W, float* bases, int ldb,
-                 float* weightings, int NV, hipStream_t stream) {
+                 float* weightings, int NV, hipStream_t stream, const float* dis, int fold_s, int fold_m) {
   if (NV != 192 || K > F16X2_KP || K % 4 != 0 || (ldb % 32 != 0 && W != 0) || (reinterpret_cast<uintptr_t>(x) & 15) != 0)
     return EGC_ERR_UNSUPPORTED;
+  const bool fold = fold_m >= 0;
+  if (fold && (dis == nullptr || W % 32 != 0 || fold_m > 3 || fold_s < 0 || fold_s > 3 || fold_s == fold_m)) return EGC_ERR_INVALID;
+  const int W_out = fold ? W / 4 * 3 : W;
   const int64_t widest = std::max(std::max(K, ldb), W);
   int64_t max_rows = ((int64_t)0x7FFFFFF0 / (4 * widest)) & ~(int64_t)(F16X2_ROWS - 1);
   if (const char* e = getenv("EGC_GEMM_MAX_ROWS")) max_rows = std::max<int64_t>(F16X2_ROWS, atoll(e) & ~(int64_t)(F16X2_ROWS - 1));  // tests
   for (int64_t r0 = 0; r0 < M; r0 += max_rows) {
     const int64_t rows = std::min(max_rows, M - r0);
     const int st = f16x2_launch_rows(x + r0 * K, packed, bcat, rows, K, W, bases + r0 * ldb, ldb,
-                                     weightings != nullptr ? weightings + r0 * W : nullptr, NV, stream);
+                                     weightings != nullptr ? weightings + r0 * W_out : nullptr, NV, fold ? dis + r0 : nullptr,
+                                     fold_s, fold ? fold_m : -1, stream);
     if (st != EGC_OK) return st;
   }
   return EGC_OK;

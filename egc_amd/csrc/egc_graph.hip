@@ -118,6 +118,7 @@ __global__ void __launch_bounds__(16 * PREP_ROWS) prepare_kernel(int64_t n_nodes
       for (int p = start + sl; p < end; p += 16) nonself += (col[p] != (int)row);
 #pragma unroll
       for (int off = 8; off > 0; off >>= 1) nonself += __shfl_xor(nonself, off);
+      // (exactly 1 / sqrtf(entry count): egc_layer_forward_packed's folded weightings recover the count from it)
       if (live && sl == 0) dis_looped[row] = 1.0f / sqrtf((float)(nonself + 1));
     }
     __syncthreads();
@@ -130,9 +131,11 @@ __global__ void __launch_bounds__(16 * PREP_ROWS) prepare_kernel(int64_t n_nodes
       for (int off = 32; off > 0; off >>= 1) nonself += __shfl_xor(nonself, off);
       if ((threadIdx.x & 63) == 0 && nonself != 0) atomicAdd(&s_huge_cnt[h], nonself);
       __syncthreads();
+      // (exactly 1 / sqrtf(entry count): egc_layer_forward_packed's folded weightings recover the count from it)
       if (threadIdx.x == 0) dis_looped[hr] = 1.0f / sqrtf((float)(s_huge_cnt[h] + 1));
     }
   }
+  // (exactly 1 / sqrtf(entry count): egc_layer_forward_packed's folded weightings recover the count from it)
   if (live && sl == 0 && dis_raw != nullptr) dis_raw[row] = deg > 0 ? 1.0f / sqrtf((float)deg) : 0.0f;
   const bool is_long = live && deg > EGC_LONG_ROW_THRESHOLD;
   const int nch = is_long ? (deg + EGC_LONG_ROW_CHUNK - 1) / EGC_LONG_ROW_CHUNK : 0;
@@ -385,7 +388,9 @@ __global__ void __launch_bounds__(1024) build_scan_kernel(const int* __restrict_
   for (int k = 0; k < 4; ++k) {
     if (base + k < n_nodes) {
       rowptr[base + k] = run;
+      // (exactly 1 / sqrtf(entry count): egc_layer_forward_packed's folded weightings recover the count from it)
       if (dis_raw != nullptr) dis_raw[base + k] = d[k] > 0 ? 1.0f / sqrtf((float)d[k]) : 0.0f;
+      // (exactly 1 / sqrtf(entry count): egc_layer_forward_packed's folded weightings recover the count from it)
       if (dis_looped != nullptr) dis_looped[base + k] = 1.0f / sqrtf((float)(dn[k] + 1));
       deg_ns[base + k] = 0;   // workspace left zero
       if (d[k] > EGC_LONG_ROW_THRESHOLD) {  // long row: a slot of the plan and a run of chunk slots (entries: rows kernel)

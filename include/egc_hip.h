@@ -639,7 +639,12 @@ int egc_layer_forward_f32(const egc_graph* graph, const egc_layer* layer, const 
                           const float* bcat, const float* bias, float* bases, int32_t ldb, float* weightings,
                           float* out, void* workspace, size_t workspace_bytes, egc_stream_t stream);
 
-/* Same as egc_layer_forward_f32 with the GEMM in its packed split-precision form (the default production path). */
+/* Same as egc_layer_forward_f32 with the GEMM in its packed split-precision form (the default production path).
+ * Folded weightings: when the layer's four aggregators hold sum and mean once each and symnorm over the same edge set,
+ * in HBA order with no weight nonlinearity, and the GEMM is the fp16x2 kernel, mean's weighting is folded into sum's
+ * (w_sum + w_mean / max(cnt, 1), cnt = the row's entry count, from the graph's deg^-1/2 table of that edge set) and
+ * `weightings` then holds [N, H*B*3]: the (h, b) pairs in HBA order, each with the layer's aggregators minus mean, in
+ * their order.  The aggregate forms no mean.  Results agree with the unfolded calls to a few fp32 roundings. */
 int egc_layer_forward_packed(const egc_graph* graph, const egc_layer* layer, const float* x, const void* packed,
                              const float* bcat, const float* bias, float* bases, int32_t ldb, float* weightings,
                              float* out, void* workspace, size_t workspace_bytes, egc_stream_t stream);
