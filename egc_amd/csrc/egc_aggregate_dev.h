@@ -11,10 +11,37 @@
 
 namespace egc {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-
 constexpr unsigned OOB = 0xFFFFFFF0u;  // any offset >= num_records makes a buffer load return 0
+
+// first index i in [0, n) with arr[i] >= key (n if none), by HALF a wavefront (lanes [32 h, 32 h + 32) share `key`): 32-ary
+// narrowing, then one probe per lane -- the two halves of a wavefront run two searches side by side.  On an array that
+// is not sorted the result is still a deterministic function of (arr, key): the tiles' edge ranges therefore always
+// partition [0, E), and the tile kernel's per-edge range check reports what the search got wrong.
+// I: the index type -- int64_t, or int where n < 2^31 (the fused tile kernel: it runs in wavefronts whose registers carry a
+// tile of x).
+template <class I>
+__device__ inline I half_wave_lower_bound(const int64_t* __restrict__ arr, I n, int64_t key, int lane) {
+  const int l32 = lane & 31, sh = lane & 32;
+  I lo = 0, hi = n;   // answer in [lo, hi]; everything before lo is < key, arr[hi] (if hi < n) is >= key
+  while (__ballot(hi - lo > 32) != 0) {            // (the other half may still be narrowing: keep probing in step)
+    const bool live = hi - lo > 32;
+    const I step = live ? (hi - lo + 31) / 32 : 1;
+    const I i = lo + (I)l32 * step;
+    const bool ge = (live && i < hi) ? arr[i] >= key : true;
+    const unsigned m = (unsigned)(__ballot(ge) >> sh);
+    if (!live) continue;
+    const int f = __ffs((int)m) - 1;               // first probe that is >= key
+    if (f < 0) { lo = lo + 31 * step + 1; if (lo > hi) lo = hi; continue; }   // all probes < key: the answer lies behind the last
+    const I nhi = lo + (I)f * step;
+    lo = f > 0 ? lo + (I)(f - 1) * step + 1 : lo;
+    hi = nhi < hi ? nhi : hi;
+  }
+  const I i = lo + l32;
+  const bool ge = i < hi ? arr[i] >= key : true;
+  const unsigned m = (unsigned)(__ballot(ge) >> sh);
+  const int f = __ffs((int)m) - 1;
+  return f < 0 ? hi : (lo + f < hi ? lo + f : hi);
+}
 
 // In-row arg positions in 8 bits (training forward -> backward).  The backward's source side compares, per transposed
 // entry, the arg positions of the destination row with the entry's own position: as int32 that is a 256-byte row per

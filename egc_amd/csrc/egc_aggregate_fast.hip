@@ -319,8 +319,8 @@ __device__ inline void wide_long_row_chunk(const AggArgs& a, const FastRsrc& R, 
         (void*)(reinterpret_cast<f4*>(a.partial) + (int64_t)c * WREC), 0, (unsigned)WREC * 16u, 0x00020000);
     const unsigned po = (unsigned)lane * 16u;
     auto put = [&](int k, f4 v0, f4 v1) {
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v0), pw, po, (k * 2 + 0) * 64 * 16, WT);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v1), pw, po, (k * 2 + 1) * 64 * 16, WT);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v0), pw, po, (k * 2 + 0) * 64 * 16, WT);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v1), pw, po, (k * 2 + 1) * 64 * 16, WT);
     };
     put(0, acc0.sum, acc1.sum);
     put(2, acc0.mx, acc1.mx);

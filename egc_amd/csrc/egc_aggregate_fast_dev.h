@@ -175,13 +175,6 @@ __device__ inline f4 combine_share(const f4 (&val)[4], f4 wv, int A) {
   }
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
 }
-__device__ inline constexpr bool getenv_scatter4() {
-#ifdef EGC_NO_SCATTER4
-  return false;
-#else
-  return true;
-#endif
-}
 
 __device__ inline float bperm(int byte_addr, float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(byte_addr, __builtin_bit_cast(int, v)));
@@ -484,8 +477,7 @@ __device__ inline void finish_group(const AggArgs& a, const FastRsrc& R, int lan
   // B = 4 bases x 4 slots in one 16-lane DPP row (every d = 128 / H = 8 / B = 4 layer): each lane forms the shares of the
   // four heads of a block in ITS OWN order -- head (b + j) mod 4 at step j, the weights come from a lane-dependent LDS
   // address -- and one reduce-scatter leaves every lane with the complete sum of the head it stores
-  const bool scatter4 = C::pow2(a) && LPR == 16 && C::lpb_log2(a) == 2 && C::slots(a) == 16 && B == 4 && (H & 3) == 0 &&
-                        getenv_scatter4();
+  const bool scatter4 = C::pow2(a) && LPR == 16 && C::lpb_log2(a) == 2 && C::slots(a) == 16 && B == 4 && (H & 3) == 0;
   if (scatter4) {
 #pragma unroll
     for (int hb = 0; hb < HPB; ++hb) {
@@ -586,7 +578,7 @@ __device__ inline void finish_group(const AggArgs& a, const FastRsrc& R, int lan
       r = r + *reinterpret_cast<const f4*>(lds_bias + (mine ? oc : 0));
       if (a.post_relu) r = f4{fmaxf(r.x, 0.f), fmaxf(r.y, 0.f), fmaxf(r.z, 0.f), fmaxf(r.w, 0.f)};
       if (a.residual != nullptr) r = r + load_slot(R.res, mine ? orow + (unsigned)oc * 4u : OOB);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, r), R.out, mine ? orow + (unsigned)oc * 4u : OOB, 0, OUT_NT);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, r), R.out, mine ? orow + (unsigned)oc * 4u : OOB, 0, OUT_NT);
     } else {
       // padded bases (L % 4 != 0): the bias strip is padded the same way, head rows are only 4-byte aligned
       // and the last slot of a head is ragged -> four dword stores, out-of-range where the channel does not exist
@@ -627,12 +619,7 @@ __device__ inline void load_row_operands(const AggArgs& a, const FastRsrc& R, in
   }
   // (a masked lane group reads the first row of the launch's own range: a caller that finishes rows [b, e) only needs
   // the weightings of those rows to exist)
-#ifdef EGC_DIAG_W_ROW0     // diagnostic build (tools/f3_roundtrip_cost.py): every row reads the SAME weightings row -- the launch with
-                           // the instruction stream unchanged and the weightings' HBM traffic gone (results are wrong, times are not)
-  const float* wrow = a.weightings + (int64_t)a.row_begin * a.ldw;
-#else
   const float* wrow = a.weightings + (int64_t)(row_ok ? row : a.row_begin) * a.ldw;
-#endif
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int c0 = (q + k * LPR) * 4;
@@ -720,17 +707,17 @@ __device__ inline void long_row_chunk(const AggArgs& a, const FastRsrc& R, int c
     const __amdgpu_buffer_rsrc_t pw = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(reinterpret_cast<f4*>(a.partial) + (int64_t)c * REC * LPR), 0, (unsigned)REC * LPR * 16u, 0x00020000);
     const unsigned po = (g == 0 && lane_live) ? (unsigned)q * 16u : OOB;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, acc.sum), pw, po, 0 * LPR * 16, WT);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, acc.mx), pw, po, 2 * LPR * 16, WT);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, acc.ws), pw, po, 4 * LPR * 16, WT);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc.sum), pw, po, 0 * LPR * 16, WT);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc.mx), pw, po, 2 * LPR * 16, WT);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc.ws), pw, po, 4 * LPR * 16, WT);
     if constexpr (NEED & NEED_SQ)
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, acc.sq), pw, po, 1 * LPR * 16, WT);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc.sq), pw, po, 1 * LPR * 16, WT);
     if constexpr (NEED & NEED_MN)
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, acc.mn), pw, po, 3 * LPR * 16, WT);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc.mn), pw, po, 3 * LPR * 16, WT);
     if constexpr (NEED & NEED_ARG) {
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, acc.ax), pw, po, 5 * LPR * 16, WT);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc.ax), pw, po, 5 * LPR * 16, WT);
       if constexpr (NEED & NEED_MN)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, acc.an), pw, po, 6 * LPR * 16, WT);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc.an), pw, po, 6 * LPR * 16, WT);
     }
     const __amdgpu_buffer_rsrc_t pn =
         __builtin_amdgcn_make_buffer_rsrc((void*)(a.partial_nself + c), 0, 4u, 0x00020000);

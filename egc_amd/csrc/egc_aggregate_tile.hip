@@ -63,33 +63,6 @@ struct TileArgs {
   int off_bases, off_col, off_rowptr, off_cnt, off_ns, off_dis_raw, off_dis_looped;
 };
 
-// first index i in [0, n) with arr[i] >= key (n if none), by HALF a wavefront (lanes [32 h, 32 h + 32) share `key`): 32-ary
-// narrowing, then one probe per lane -- the two halves of a wavefront run two searches side by side.  On an array that
-// is not sorted the result is still a deterministic function of (arr, key): the tiles' edge ranges therefore always
-// partition [0, E), and the tile kernel's per-edge range check reports what the search got wrong.
-__device__ inline int64_t half_wave_lower_bound(const int64_t* __restrict__ arr, int64_t n, int64_t key, int lane) {
-  const int l32 = lane & 31, sh = lane & 32;
-  int64_t lo = 0, hi = n;   // answer in [lo, hi]; everything before lo is < key, arr[hi] (if hi < n) is >= key
-  while (__ballot(hi - lo > 32) != 0) {            // (the other half may still be narrowing: keep probing in step)
-    const bool live = hi - lo > 32;
-    const int64_t step = live ? (hi - lo + 31) / 32 : 1;
-    const int64_t i = lo + (int64_t)l32 * step;
-    const bool ge = (live && i < hi) ? arr[i] >= key : true;
-    const unsigned m = (unsigned)(__ballot(ge) >> sh);
-    if (!live) continue;
-    const int f = __ffs((int)m) - 1;               // first probe that is >= key
-    if (f < 0) { lo = lo + 31 * step + 1; if (lo > hi) lo = hi; continue; }   // all probes < key: the answer lies behind the last
-    const int64_t nhi = lo + (int64_t)f * step;
-    lo = f > 0 ? lo + (int64_t)(f - 1) * step + 1 : lo;
-    hi = nhi < hi ? nhi : hi;
-  }
-  const int64_t i = lo + l32;
-  const bool ge = i < hi ? arr[i] >= key : true;
-  const unsigned m = (unsigned)(__ballot(ge) >> sh);
-  const int f = __ffs((int)m) - 1;
-  return f < 0 ? hi : (lo + f < hi ? lo + f : hi);
-}
-
 // One wavefront per slot k: lanes 0-31 find where the slot's first graph starts (node n0, edge e0), lanes 32-63 the same
 // for slot k + 1 (n1, e1); a non-empty tile [n0, n1) x [e0, e1) takes the next place of the compacted list.
 __global__ void __launch_bounds__(256) tile_plan_kernel(const int64_t* __restrict__ ptr, int64_t n_graphs,
@@ -246,7 +219,6 @@ __global__ void __launch_bounds__(TILE_THREADS) __attribute__((amdgpu_waves_per_
   const int grp_addr = (g << LPR_LOG2) << 2;
 
   // LDS-only barrier: __syncthreads() would also drain the LDS-DMA in flight (hipcc emits vmcnt(0) in front of it)
-  auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   // the edges of a tile, TILE_EDGE_REGS per thread, checked against the tile (-1 = absent or outside: reported)
   int es[TILE_EDGE_REGS], ed[TILE_EDGE_REGS];
   bool bad = false;

@@ -445,11 +445,7 @@ __device__ inline void records_store(const unsigned* cnt, const unsigned* off, c
       w = uint4{__builtin_amdgcn_alignbyte(d1, d0, sh) & keep(0), __builtin_amdgcn_alignbyte(d2, d1, sh) & keep(4),
                 __builtin_amdgcn_alignbyte(d3, d2, sh) & keep(8), cn <= (unsigned)REC_ITEMS ? cn : REC_OVERFLOW};
     }
-#ifdef EGC_REC_NT_STORE
-    __builtin_nontemporal_store(w, reinterpret_cast<uint4*>(rec0 + (int64_t)e * 16) + v);
-#else
     reinterpret_cast<uint4*>(rec0 + (int64_t)e * 16)[v] = w;
-#endif
   }
 }
 

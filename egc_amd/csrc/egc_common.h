@@ -30,6 +30,23 @@ void set_last_error(const char* what, hipError_t err);
     }                                              \
   } while (0)
 
+// vector types of the kernels (MFMA operands and accumulators, packed fp16 / bf16, 8- and 16-byte LDS pieces)
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16;
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding GLOBAL access of the
+// wavefront (s_waitcnt vmcnt(0)): in a streaming kernel that drains the stores of the tile just finished and the prefetch of
+// the next one at every barrier -- microseconds of HBM latency per tile.  The tiles exchanged between wavefronts live in LDS,
+// so lgkmcnt(0) + s_barrier is all that is needed.
+__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // floats between consecutive bases of a `bases` row (egc_layer.basis_stride; 0 = contiguous)

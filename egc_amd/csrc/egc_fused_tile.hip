@@ -58,7 +58,7 @@ struct FtParamSrc {
   __device__ inline float b(int j) const { return comb_b != nullptr ? comb_b[pack_comb_row(d, j)] : (bcat != nullptr ? bcat[j] : 0.f); }
 };
 template <class S>
-__device__ inline void ft_pack_column(int v, const S& src_of, int K, int F_g, int W, int ldb, ft_u16* __restrict__ packed) {
+__device__ inline void ft_pack_column(int v, const S& src_of, int K, int F_g, int W, int ldb, u16* __restrict__ packed) {
   const int lane = threadIdx.x;
   const int src = (v < F_g) ? v : ((v < ldb || v >= ldb + W) ? -1 : v - ldb + F_g);
   unsigned amax = 0;
@@ -66,27 +66,22 @@ __device__ inline void ft_pack_column(int v, const S& src_of, int K, int F_g, in
     for (int k = lane; k < K; k += 64) amax = max(amax, __float_as_uint(src_of.w(k, src)) & 0x7fffffffu);
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, d));
-  unsigned be = amax >> 23;
-  be = be > 253u ? 253u : be;
-  const float scale = __uint_as_float((254u - be) << 23);
-  const float inv = __uint_as_float(be << 23);
+  const F16x2ColScale col = f16x2_col_scale(amax);
   for (int k = lane; k < FT_KP; k += 64) {
-    const float w = (src >= 0 && k < K) ? src_of.w(k, src) * scale : 0.f;
-    const _Float16 h = (_Float16)w;
-    const _Float16 l = (_Float16)((w - (float)h) * 2048.f);
+    const F16x2Bits b = f16x2_pack_split((src >= 0 && k < K) ? src_of.w(k, src) * col.scale : 0.f);
     const int64_t base = ((((int64_t)(v >> 4) * 4 + (k >> 5)) * 2) * 64 + 16 * ((k & 31) >> 3) + (v & 15)) * 8 + (k & 7);
-    packed[base] = __builtin_bit_cast(ft_u16, h);
-    packed[base + 64 * 8] = __builtin_bit_cast(ft_u16, l);
+    packed[base] = b.h;
+    packed[base + 64 * 8] = b.l;
   }
   if (lane == 0) {
     float* tail = reinterpret_cast<float*>(packed + (int64_t)FT_MFMA_WAVES * 4 * 2 * 64 * 8);
-    tail[v] = inv;
+    tail[v] = col.inv;
     const int wcol = v - ldb;
     tail[FT_NV + v] = (wcol >= 0 && wcol < W) ? src_of.b(wcol) : 0.f;
   }
 }
 __global__ void __launch_bounds__(64) ft_pack_kernel(const float* __restrict__ wcat, const float* __restrict__ bcat, int K,
-                                                      int F_g, int W, int ldb, ft_u16* __restrict__ packed) {
+                                                      int F_g, int W, int ldb, u16* __restrict__ packed) {
   ft_pack_column(blockIdx.x, FtWcatSrc{wcat, bcat, F_g + W}, K, F_g, W, ldb, packed);
 }
 
@@ -96,7 +91,7 @@ __global__ void __launch_bounds__(64) ft_pack_kernel(const float* __restrict__ w
 // weightings ldbp .. ldbp + W).  Tail: float col_inv[384], col_bias[384].
 __global__ void __launch_bounds__(64) ft_pack_wide_kernel(const float* __restrict__ wcat, const float* __restrict__ bcat, int K,
                                                            int F_g, int W, int ldb, int ldbp, int n_ct, int k16,
-                                                           ft_u16* __restrict__ packed) {
+                                                           u16* __restrict__ packed) {
   const int v = blockIdx.x;
   const int lane = threadIdx.x;
   const int ncol = F_g + W;
@@ -106,21 +101,16 @@ __global__ void __launch_bounds__(64) ft_pack_wide_kernel(const float* __restric
     for (int k = lane; k < K; k += 64) amax = max(amax, __float_as_uint(wcat[(int64_t)k * ncol + src]) & 0x7fffffffu);
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, d));
-  unsigned be = amax >> 23;
-  be = be > 253u ? 253u : be;
-  const float scale = __uint_as_float((254u - be) << 23);
-  const float inv = __uint_as_float(be << 23);
+  const F16x2ColScale col = f16x2_col_scale(amax);
   for (int k = lane; k < k16 * 16; k += 64) {
-    const float w = (src >= 0 && k < K) ? wcat[(int64_t)k * ncol + src] * scale : 0.f;
-    const _Float16 h = (_Float16)w;
-    const _Float16 l = (_Float16)((w - (float)h) * 2048.f);
+    const F16x2Bits b = f16x2_pack_split((src >= 0 && k < K) ? wcat[(int64_t)k * ncol + src] * col.scale : 0.f);
     const int64_t base = ((((int64_t)(v >> 5) * k16 + (k >> 4)) * 2) * 64 + 32 * ((k & 15) >> 3) + (v & 31)) * 8 + (k & 7);
-    packed[base] = __builtin_bit_cast(ft_u16, h);
-    packed[base + 64 * 8] = __builtin_bit_cast(ft_u16, l);
+    packed[base] = b.h;
+    packed[base + 64 * 8] = b.l;
   }
   if (lane == 0) {
     float* tail = reinterpret_cast<float*>(packed + (int64_t)n_ct * k16 * 2 * 64 * 8);
-    tail[v] = inv;
+    tail[v] = col.inv;
     const int wcol = v - ldbp;
     tail[FTW_MAX_CT * 32 + v] = (bcat != nullptr && wcol >= 0 && wcol < W) ? bcat[wcol] : 0.f;
   }
@@ -138,22 +128,22 @@ static inline int ftw_k16(int f_in) { return (((f_in + 15) / 16) + 3) & ~3; }   
 static inline int ftw_n_ct(const AggArgs& a) { return (((a.ldb + 31) & ~31) + a.W + 31) / 32; }
 
 size_t fused_tile_pack_bytes(const AggArgs& a, int f_in) {
-  if (ft_narrow_shape(a, f_in)) return (size_t)FT_MFMA_WAVES * 4 * 2 * 64 * 8 * sizeof(ft_u16) + 2 * FT_NV * sizeof(float);
-  if (ft_wide_shape(a, f_in)) return (size_t)ftw_n_ct(a) * ftw_k16(f_in) * 2 * 64 * 8 * sizeof(ft_u16) + 2 * FTW_MAX_CT * 32 * sizeof(float);
+  if (ft_narrow_shape(a, f_in)) return (size_t)FT_MFMA_WAVES * 4 * 2 * 64 * 8 * sizeof(u16) + 2 * FT_NV * sizeof(float);
+  if (ft_wide_shape(a, f_in)) return (size_t)ftw_n_ct(a) * ftw_k16(f_in) * 2 * 64 * 8 * sizeof(u16) + 2 * FTW_MAX_CT * 32 * sizeof(float);
   return 0;
 }
 
 int fused_tile_pack(const AggArgs& a, const float* wcat, const float* bcat, int f_in, int f_g, int w_cols, int ldb, void* packed,
                     hipStream_t stream) {
   if (ft_narrow_shape(a, f_in)) {
-    ft_pack_kernel<<<FT_NV, 64, 0, stream>>>(wcat, bcat, f_in, f_g, w_cols, ldb, (ft_u16*)packed);
+    ft_pack_kernel<<<FT_NV, 64, 0, stream>>>(wcat, bcat, f_in, f_g, w_cols, ldb, (u16*)packed);
     EGC_LAUNCH_CHECK("ft_pack_kernel");
     return EGC_OK;
   }
   if (!ft_wide_shape(a, f_in)) return EGC_ERR_UNSUPPORTED;
   const int n_ct = ftw_n_ct(a);
   ft_pack_wide_kernel<<<n_ct * 32, 64, 0, stream>>>(wcat, bcat, f_in, f_g, w_cols, ldb, (ldb + 31) & ~31, n_ct, ftw_k16(f_in),
-                                                    (ft_u16*)packed);
+                                                    (u16*)packed);
   EGC_LAUNCH_CHECK("ft_pack_wide_kernel");
   return EGC_OK;
 }
@@ -227,40 +217,8 @@ static int launch_ft_one(const AggArgs& a, const FusedTileArgs& t, unsigned grid
     if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(fused_tile_kernel)", e); return EGC_ERR_HIP; }
     attr_set = true;
   }
-#ifdef EGC_FT_STAMPS
-  static unsigned long long* dbuf = nullptr;
-  if (dbuf == nullptr) {
-    hipMalloc(&dbuf, (256 * 9 + 96) * 8);
-    hipMemcpyToSymbol(HIP_SYMBOL(egc_ft_stamp_buf), &dbuf, sizeof(dbuf));
-  }
-  hipMemset(dbuf, 0, (256 * 9 + 96) * 8);
-#endif
   fused_tile_kernel<LPR_LOG2, HPB, NEED, C><<<grid, FT_THREADS, lds, stream>>>(a, t);
   EGC_LAUNCH_CHECK("fused_tile_kernel");
-#ifdef EGC_FT_STAMPS
-  {
-    hipDeviceSynchronize();
-    static int calls = 0;
-    if ((++calls % 40) == 0) {
-      unsigned long long h[256 * 9 + 96];
-      hipMemcpy(h, dbuf, sizeof(h), hipMemcpyDeviceToHost);
-      double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tmax = 0;
-      for (unsigned b = 0; b < grid; ++b) {
-        for (int k = 0; k < 8; ++k) sum[k] += (double)h[b * 8 + k];
-        tmax = std::max(tmax, (double)h[b * 8 + 7]);
-      }
-      for (int i = 0; i < 10; ++i)
-        fprintf(stderr, "[ft tile %d of block 7] start %llu | helpers after the GEMM: plan (wavefront 15) %llu, counts %llu, rows requested %llu, CSR done %llu | GEMM %llu rows %llu end %llu\n", i, h[256 * 9 + i * 8], h[256 * 9 + i * 8 + 7],
-                h[256 * 9 + i * 8 + 1], h[256 * 9 + i * 8 + 2], h[256 * 9 + i * 8 + 3], h[256 * 9 + i * 8 + 4], h[256 * 9 + i * 8 + 5], h[256 * 9 + i * 8 + 6]);
-      double pro = 0;
-      for (unsigned b = 0; b < grid; ++b) pro += (double)h[256 * 8 + b];
-      fprintf(stderr, "[ft stamps] prologue %.0f; ", pro / grid);
-      fprintf(stderr, "[ft stamps] grid %u, n_nodes %d: per workgroup (shader cycles): start %.0f  (-) %.0f  (-) %.0f  "
-              "(-) %.0f  GEMM %.0f  rows %.0f  end barrier %.0f | total avg %.0f max %.0f\n", grid, a.n_nodes,
-              sum[0] / grid, sum[1] / grid, sum[2] / grid, sum[3] / grid, sum[4] / grid, sum[5] / grid, sum[6] / grid, sum[7] / grid, tmax);
-    }
-  }
-#endif
   return EGC_OK;
 }
 
@@ -304,7 +262,7 @@ int launch_fused_tile(AggArgs a, const int64_t* ptr, const int64_t* edge_ptr, in
   a.lds_floats_per_wave = 0;
   FusedTileArgs t = {};
   t.ptr = ptr; t.edge_ptr = edge_ptr; t.n_graphs = n_graphs; t.src = src; t.dst = dst; t.n_edges = n_edges;
-  t.max_index = max_index; t.status = status; t.host_flag = host_flag; t.x = x; t.packed = (const ft_u16*)packed;
+  t.max_index = max_index; t.status = status; t.host_flag = host_flag; t.x = x; t.packed = (const u16*)packed;
   t.F_in = f_in;
   const bool wide = !ft_narrow_shape(a, f_in);
   t.n_ct = wide ? ftw_n_ct(a) : (a.ldb + a.W + 15) / 16;
@@ -319,7 +277,6 @@ int launch_fused_tile(AggArgs a, const int64_t* ptr, const int64_t* edge_ptr, in
   t.p0 = ((a.Ls >> 2) + 1) / 2;
   t.magic0 = (unsigned)(((uint64_t)1 << 32) / (uint64_t)t.p0) + 1u;
   t.magic1 = (unsigned)(((uint64_t)1 << 32) / (uint64_t)std::max(1, (a.Ls >> 2) - t.p0)) + 1u;
-  if (const char* e = getenv("EGC_FT_DBG")) t.dbg = atoi(e);     // (read by diagnostic builds of the kernel only: -DEGC_FT_STAMPS)
   if (tcap < FT_CHUNK || tcap > FT_CHUNK * FT_RING || (tcap % (wide ? FTW_CH : FT_CHUNK)) != 0 || emax < 0 || emax > 65535) return EGC_ERR_INVALID;   // (16-bit cursors of the CSR build)
   const FtLds L = ft_lds(a, t.wl_floats, tcap, emax, a.post_scale != nullptr, wide);
   if (L.total > FT_LDS_BUDGET) return EGC_ERR_UNSUPPORTED;
@@ -374,7 +331,7 @@ int launch_fused_tile(AggArgs a, const int64_t* ptr, const int64_t* edge_ptr, in
 // (a = 0 .. A - 1 real, the rest zero).  Scale per output feature f; tail: float col_inv[128].
 template <class S>
 __device__ inline void ft_pack_t_feature(int f, const S& src_of, int K, int F_g, int W, int A, int ldb, int k2,
-                                         ft_u16* __restrict__ packed) {
+                                         u16* __restrict__ packed) {
   const int lane = threadIdx.x;       // f: output feature (row of wcat), 0 .. 127
   auto src_col = [&](int k) -> int {  // image column k -> column of wcat, or -1
     if (k < ldb) return k < F_g ? k : -1;
@@ -389,36 +346,31 @@ __device__ inline void ft_pack_t_feature(int f, const S& src_of, int K, int F_g,
     }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, d));
-  unsigned be = amax >> 23;
-  be = be > 253u ? 253u : be;
-  const float scale = __uint_as_float((254u - be) << 23);
-  const float inv = __uint_as_float(be << 23);
+  const F16x2ColScale col = f16x2_col_scale(amax);
   for (int k = lane; k < 192; k += 64) {
     const int c = k < k2 ? src_col(k) : -1;
-    const float w = (f < K && c >= 0) ? src_of.w(f, c) * scale : 0.f;
-    const _Float16 h = (_Float16)w;
-    const _Float16 l = (_Float16)((w - (float)h) * 2048.f);
+    const F16x2Bits b = f16x2_pack_split((f < K && c >= 0) ? src_of.w(f, c) * col.scale : 0.f);
     const int64_t base = ((((int64_t)(f >> 4) * 6 + (k >> 5)) * 2) * 64 + 16 * ((k & 31) >> 3) + (f & 15)) * 8 + (k & 7);
-    packed[base] = __builtin_bit_cast(ft_u16, h);
-    packed[base + 64 * 8] = __builtin_bit_cast(ft_u16, l);
+    packed[base] = b.h;
+    packed[base + 64 * 8] = b.l;
   }
-  if (lane == 0) reinterpret_cast<float*>(packed + (int64_t)8 * 6 * 2 * 64 * 8)[f] = inv;
+  if (lane == 0) reinterpret_cast<float*>(packed + (int64_t)8 * 6 * 2 * 64 * 8)[f] = col.inv;
 }
 __global__ void __launch_bounds__(64) ft_pack_t_kernel(const float* __restrict__ wcat, int K, int F_g, int W, int A, int ldb,
-                                                        int k2, ft_u16* __restrict__ packed) {
+                                                        int k2, u16* __restrict__ packed) {
   ft_pack_t_feature(blockIdx.x, FtWcatSrc{wcat, nullptr, F_g + W}, K, F_g, W, A, ldb, k2, packed);
 }
 // both operands of a training step in one launch: blocks 0 .. FT_NV - 1 the forward's columns, the next 128 the backward's features
 __global__ void __launch_bounds__(64) ft_pack_both_kernel(const float* __restrict__ wcat, const float* __restrict__ bcat, int K,
-                                                           int F_g, int W, int A, int ldb, int k2, ft_u16* __restrict__ packed,
-                                                           ft_u16* __restrict__ packed_t) {
+                                                           int F_g, int W, int A, int ldb, int k2, u16* __restrict__ packed,
+                                                           u16* __restrict__ packed_t) {
   const FtWcatSrc src{wcat, bcat, F_g + W};
   if (blockIdx.x < FT_NV) ft_pack_column(blockIdx.x, src, K, F_g, W, ldb, packed);
   else ft_pack_t_feature(blockIdx.x - FT_NV, src, K, F_g, W, A, ldb, k2, packed_t);
 }
 // ... straight from the layer's parameters (no wcat / bcat arrays, no egc_weights_pack_f32 launch in front)
 __global__ void __launch_bounds__(64) ft_pack_both_params_kernel(FtParamSrc src, int K, int F_g, int W, int A, int ldb, int k2,
-                                                                  ft_u16* __restrict__ packed, ft_u16* __restrict__ packed_t) {
+                                                                  u16* __restrict__ packed, u16* __restrict__ packed_t) {
   if (blockIdx.x < FT_NV) ft_pack_column(blockIdx.x, src, K, F_g, W, ldb, packed);
   else ft_pack_t_feature(blockIdx.x - FT_NV, src, K, F_g, W, A, ldb, k2, packed_t);
 }
@@ -431,10 +383,10 @@ bool fused_tile_bwd_shape(const AggArgs& a, int f_in) {
   return true;
 }
 
-size_t fused_tile_bwd_pack_bytes() { return (size_t)8 * 6 * 2 * 64 * 8 * sizeof(ft_u16) + 128 * sizeof(float); }
+size_t fused_tile_bwd_pack_bytes() { return (size_t)8 * 6 * 2 * 64 * 8 * sizeof(u16) + 128 * sizeof(float); }
 
 int fused_tile_bwd_pack(const AggArgs& a, const float* wcat, int f_in, void* packed, hipStream_t stream) {
-  ft_pack_t_kernel<<<128, 64, 0, stream>>>(wcat, f_in, a.B * a.Ls, a.W, a.A, a.ldb, a.ldb + a.H * a.B * 4, (ft_u16*)packed);
+  ft_pack_t_kernel<<<128, 64, 0, stream>>>(wcat, f_in, a.B * a.Ls, a.W, a.A, a.ldb, a.ldb + a.H * a.B * 4, (u16*)packed);
   EGC_LAUNCH_CHECK("ft_pack_t_kernel");
   return EGC_OK;
 }
@@ -442,8 +394,8 @@ int fused_tile_bwd_pack(const AggArgs& a, const float* wcat, int f_in, void* pac
 int fused_tile_train_pack(const AggArgs& a, const float* wcat, const float* bcat, int f_in, int f_g, int w_cols, int ldb, void* packed,
                           void* packed_t, hipStream_t stream) {
   if (!fused_tile_bwd_shape(a, f_in)) return EGC_ERR_UNSUPPORTED;
-  ft_pack_both_kernel<<<FT_NV + 128, 64, 0, stream>>>(wcat, bcat, f_in, f_g, w_cols, a.A, ldb, a.ldb + a.H * a.B * 4, (ft_u16*)packed,
-                                                      (ft_u16*)packed_t);
+  ft_pack_both_kernel<<<FT_NV + 128, 64, 0, stream>>>(wcat, bcat, f_in, f_g, w_cols, a.A, ldb, a.ldb + a.H * a.B * 4, (u16*)packed,
+                                                      (u16*)packed_t);
   EGC_LAUNCH_CHECK("ft_pack_both_kernel");
   return EGC_OK;
 }
@@ -452,8 +404,8 @@ int fused_tile_train_pack_params(const AggArgs& a, const PackPtrs& bases, const 
                                  const PackDims& d, int f_g, int w_cols, int ldb, void* packed, void* packed_t, hipStream_t stream) {
   if (!fused_tile_bwd_shape(a, d.F_in)) return EGC_ERR_UNSUPPORTED;
   FtParamSrc src{bases, comb_w, comb_b, bcat, d};
-  ft_pack_both_params_kernel<<<FT_NV + 128, 64, 0, stream>>>(src, d.F_in, f_g, w_cols, a.A, ldb, a.ldb + a.H * a.B * 4, (ft_u16*)packed,
-                                                             (ft_u16*)packed_t);
+  ft_pack_both_params_kernel<<<FT_NV + 128, 64, 0, stream>>>(src, d.F_in, f_g, w_cols, a.A, ldb, a.ldb + a.H * a.B * 4, (u16*)packed,
+                                                             (u16*)packed_t);
   EGC_LAUNCH_CHECK("ft_pack_both_params_kernel");
   return EGC_OK;
 }
@@ -478,34 +430,8 @@ static int launch_ftb_one(const AggArgs& a, const FusedTileArgs& t, unsigned gri
     if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(fused_tile_kernel, backward)", e); return EGC_ERR_HIP; }
     attr_set = true;
   }
-#ifdef EGC_FT_STAMPS
-  static unsigned long long* dbuf = nullptr;
-  if (dbuf == nullptr) {
-    hipMalloc(&dbuf, (256 * 9 + 96) * 8);
-    hipMemcpyToSymbol(HIP_SYMBOL(egc_ft_stamp_buf), &dbuf, sizeof(dbuf));
-  }
-  hipMemset(dbuf, 0, (256 * 9 + 96) * 8);
-#endif
   fused_tile_kernel<4, 1, 0, C, 0, 1><<<grid, FT_THREADS, lds, stream>>>(a, t);
   EGC_LAUNCH_CHECK("fused_tile_kernel (backward)");
-#ifdef EGC_FT_STAMPS
-  {
-    hipDeviceSynchronize();
-    static int calls = 0;
-    if ((++calls % 40) == 0) {
-      unsigned long long h[256 * 9 + 96];
-      hipMemcpy(h, dbuf, sizeof(h), hipMemcpyDeviceToHost);
-      double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tmax = 0;
-      for (unsigned b = 0; b < grid; ++b) {
-        for (int k = 0; k < 8; ++k) sum[k] += (double)h[b * 8 + k];
-        tmax = std::max(tmax, (double)h[b * 8 + 7]);
-      }
-      fprintf(stderr, "[ft bwd stamps] grid %u, n_nodes %d: per workgroup (shader cycles): start %.0f  GEMM1 %.0f  scale %.0f  "
-              "rows (backward; wavefront 0) %.0f  B1 + GEMM2 %.0f | total avg %.0f max %.0f\n", grid, a.n_nodes,
-              sum[0] / grid, sum[4] / grid, sum[1] / grid, sum[5] / grid, sum[6] / grid, sum[7] / grid, tmax);
-    }
-  }
-#endif
   return EGC_OK;
 }
 
@@ -526,15 +452,14 @@ int launch_fused_tile_bwd(AggArgs a, const int64_t* ptr, const int64_t* edge_ptr
   a.w_aw = 4;
   FusedTileArgs t = {};
   t.ptr = ptr; t.edge_ptr = edge_ptr; t.n_graphs = n_graphs; t.src = src; t.dst = dst; t.n_edges = n_edges;
-  t.max_index = max_index; t.status = status; t.host_flag = host_flag; t.x = x; t.packed = (const ft_u16*)packed;
+  t.max_index = max_index; t.status = status; t.host_flag = host_flag; t.x = x; t.packed = (const u16*)packed;
   t.F_in = f_in;
   t.n_ct = (a.ldb + a.W + 15) / 16;
   t.tcap = tcap; t.emax = emax;
   t.w_aw = 4;
   t.wl_floats = a.H * a.B * 4;
   t.nsets = 1;
-  t.grad_out = grad_out; t.d_x = d_x; t.d_x_add = d_x_add; t.d_cat = d_cat; t.ld_dcat = ld_dcat; t.packed_t = (const ft_u16*)packed_t;
-  if (const char* e = getenv("EGC_FT_DBG")) t.dbg = atoi(e);     // (read by diagnostic builds of the kernel only: -DEGC_FT_STAMPS)
+  t.grad_out = grad_out; t.d_x = d_x; t.d_x_add = d_x_add; t.d_cat = d_cat; t.ld_dcat = ld_dcat; t.packed_t = (const u16*)packed_t;
   if (tcap < FT_CHUNK || tcap > FT_CHUNK * (a.H == 8 ? 6 : 8) || (tcap % FT_CHUNK) != 0 || emax < 0 || emax > 16384) return EGC_ERR_INVALID;
   const FtLds L = ft_lds(a, t.wl_floats, tcap, emax, false, false, true);
   if (L.total > FT_LDS_BUDGET) return EGC_ERR_UNSUPPORTED;

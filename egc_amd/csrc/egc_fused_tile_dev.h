@@ -3,18 +3,11 @@
 // reference's wider batched shapes: weight slabs streamed from L2).  See egc_fused_tile.hip for the description.
 #pragma once
 #include <algorithm>
-#include <cstdio>
 
 #include "egc_aggregate_fast_dev.h"
+#include "egc_gemm_split.h"
 
 namespace egc {
-
-typedef _Float16 ft_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ft_h2 __attribute__((ext_vector_type(2)));
-typedef float ft_f2 __attribute__((ext_vector_type(2)));
-typedef unsigned int ft_u2 __attribute__((ext_vector_type(2)));
-typedef unsigned int ft_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short ft_u16;
 
 constexpr int FT_THREADS = 1024;
 constexpr int FT_WAVES = FT_THREADS / 64;
@@ -55,13 +48,6 @@ constexpr int FTW_MAXCH = FT_CHUNK * FT_RING / FTW_CH;     // chunks of a tile (
 constexpr int FTW_MAX_CT = FT_MFMA_WAVES;                  // 32-column tiles
 constexpr int FT_DBS_POISON = 0x7fffffff;                  // backward: the tile's fixed-point scale when its g or w' holds an Inf / NaN
 
-#ifdef EGC_FT_STAMPS
-__device__ unsigned long long* egc_ft_stamp_buf = nullptr;   // diagnostic build only: [grid][8] accumulated cycles per phase
-#define FT_HSTAMP(k, cond) { if ((cond) && lane == 0 && blockIdx.x == 7 && it < 12 && egc_ft_stamp_buf != nullptr) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); egc_ft_stamp_buf[256 * 9 + it * 8 + k] = _t - ft_h0; } }
-#define FT_STAMP(k) { if (tid == 0) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); ft_acc[k] += _t - ft_t0; if (blockIdx.x == 7 && it < 12 && egc_ft_stamp_buf != nullptr) egc_ft_stamp_buf[256 * 9 + it * 8 + k] = _t - ft_t0; ft_t0 = _t; } }
-#else
-#define FT_STAMP(k)
-#endif
 
 struct FusedTileArgs {
   const int64_t* ptr;        // node offsets of the graphs [G + 1]
@@ -74,13 +60,15 @@ struct FusedTileArgs {
   int32_t* status;
   int32_t* host_flag;
   const float* x;
-  const ft_u16* packed;      // [12][4][2][64][8] fp16 weight fragments, float col_inv[192], float col_bias[192]
+  const u16* packed;      // [12][4][2][64][8] fp16 weight fragments, float col_inv[192], float col_bias[192]
   int F_in;
   int n_ct;                  // column tiles in use = ceil((ldb + W) / 16)
   int tcap, emax;            // LDS image: rows of bases / weightings, entries of the CSR
   int wl_floats;             // floats per weightings row in LDS: H * B * 4
-  int dbg;                   // diagnostic build (EGC_FT_STAMPS) only: bit 0 no split, bit 1 no MFMA, bit 2 no rows
-  int off_rec, off_planes, off_rowinv, off_bases, off_wt;
+  // (8-byte aligned: the argument layout the kernels were scheduled with -- packing the offsets 4 bytes lower changes the
+  //  argument loads, and with them the register allocation: one of the wide instances spills 6 more dwords)
+  alignas(8) int off_rec;
+  int off_planes, off_rowinv, off_bases, off_wt;
   int off_col, off_rowptr, off_cnt, off_dis;   // the CSR areas of an even tile; csr_stride bytes further: those of an odd tile
   int csr_stride;
   // WIDE form only
@@ -96,36 +84,10 @@ struct FusedTileArgs {
   const float* d_x_add;      // [n_nodes, F_in] added to d_x in its store (the gradient reaching x past the layer), or nullptr
   float* d_cat;              // [n_nodes, ld_dcat]: the gradient of [bases | pre-activation weightings] (what x^T d needs), or nullptr
   int ld_dcat;
-  const ft_u16* packed_t;    // [8][6][2][64][8] fp16 fragments of [bases_weight | comb_weight^T]^T, float col_inv[128]
+  const u16* packed_t;    // [8][6][2][64][8] fp16 fragments of [bases_weight | comb_weight^T]^T, float col_inv[128]
   int off_db;                // LDS: d bases image [tcap][ldb]
   int off_rowinv2;           // LDS: row scales of the staged d chunks [2][16]
 };
-
-// first index i in [0, n) with arr[i] >= key (n if none), by HALF a wavefront (lanes [32 h, 32 h + 32) share `key`), as
-// egc_aggregate_tile.hip: the two halves of a wavefront run two searches side by side; deterministic on unsorted input.
-// 32-bit indices (n < 2^31): this runs in the wavefronts whose registers carry a tile of x.
-__device__ inline int ft_half_wave_lower_bound(const int64_t* __restrict__ arr, int n, int64_t key, int lane) {
-  const int l32 = lane & 31, sh = lane & 32;
-  int lo = 0, hi = n;
-  while (__ballot(hi - lo > 32) != 0) {
-    const bool live = hi - lo > 32;
-    const int step = live ? (hi - lo + 31) / 32 : 1;
-    const int i = lo + l32 * step;
-    const bool ge = (live && i < hi) ? arr[i] >= key : true;
-    const unsigned m = (unsigned)(__ballot(ge) >> sh);
-    if (!live) continue;
-    const int f = __ffs((int)m) - 1;
-    if (f < 0) { lo = lo + 31 * step + 1; if (lo > hi) lo = hi; continue; }
-    const int nhi = lo + f * step;
-    lo = f > 0 ? lo + (f - 1) * step + 1 : lo;
-    hi = nhi < hi ? nhi : hi;
-  }
-  const int i = lo + l32;
-  const bool ge = i < hi ? arr[i] >= key : true;
-  const unsigned m = (unsigned)(__ballot(ge) >> sh);
-  const int f = __ffs((int)m) - 1;
-  return f < 0 ? hi : (lo + f < hi ? lo + f : hi);
-}
 
 // The same lower bound with ONE round of loads when the array is close to linear (graph offsets of a batch of similar
 // graphs, the destination row of their edges): each half looks at the 64 entries around guess = key n / top first and
@@ -145,7 +107,7 @@ __device__ inline int ft_guess_lower_bound(const int64_t* __restrict__ arr, int 
   r = r > n ? n : r;
   const bool sure = (first > 0 || w0 == 0) && (first < 64 || w0 + 64 >= n);
   if (__ballot(!sure) != 0) {       // (both halves take part in the full search; each keeps its window result if it was sure)
-    const int full = ft_half_wave_lower_bound(arr, n, key, lane);
+    const int full = half_wave_lower_bound(arr, n, key, lane);
     r = sure ? r : full;
   }
   return r;
@@ -154,18 +116,6 @@ __device__ inline int ft_guess_lower_bound(const int64_t* __restrict__ arr, int 
 __device__ inline void ft_error(const FusedTileArgs& t, int code) {
   atomicOr(t.status, code);
   if (t.host_flag != nullptr) *(volatile int32_t*)t.host_flag = 1;
-}
-
-// largest magnitude of a row = 32 consecutive lanes (bit pattern of a non-negative float), as egc_gemm_f16x2.hip
-__device__ inline unsigned ft_row_amax(const f4 v) {
-  float m;
-  asm("v_max3_f32 %0, |%1|, |%2|, |%3|\n\tv_max_f32 %0, |%4|, %0" : "=&v"(m) : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-  unsigned a = __float_as_uint(m);
-  a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-  a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-  a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x141, 0xf, 0xf, true));  // row_half_mirror
-  a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x140, 0xf, 0xf, true));  // row_mirror
-  return max(a, (unsigned)__builtin_amdgcn_ds_swizzle((int)a, 0x401F));                 // lane ^ 16
 }
 
 // largest magnitude of four floats as a bit pattern, Inf / NaN INCLUDED (integer maximum of the patterns without their sign: a NaN
@@ -178,10 +128,7 @@ __device__ inline unsigned ft_amax_bits(const f4 v) {
 
 // largest of a non-negative bit pattern over the wavefront, uniform (four row maxima by DPP, then four lane reads)
 __device__ inline unsigned ft_wave_umax(unsigned a) {
-  a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-  a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-  a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x141, 0xf, 0xf, true));  // row_half_mirror
-  a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x140, 0xf, 0xf, true));  // row_mirror
+  a = row_group_umax<16>(a);
   return max(max((unsigned)__builtin_amdgcn_readlane((int)a, 0), (unsigned)__builtin_amdgcn_readlane((int)a, 16)),
              max((unsigned)__builtin_amdgcn_readlane((int)a, 32), (unsigned)__builtin_amdgcn_readlane((int)a, 48)));
 }
@@ -207,7 +154,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
   int* lds_rowctr = lds_rec + 24;
   char* lds_planes = base + t.off_planes;                   // [2 buffers][2 planes][16 rows][128 fp16], 16-byte pieces swizzled
   float* lds_rowinv = reinterpret_cast<float*>(base + t.off_rowinv);   // [3][16]
-  auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
   for (int o = tid; o < C::H(a) * C::Ls(a); o += FT_THREADS) {
     const int h = o / C::Ls(a), l = o - h * C::Ls(a);
@@ -222,11 +168,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
     lds_bias[o] = bv;
   }
 
-#ifdef EGC_FT_STAMPS
-  unsigned long long ft_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ft_t0;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ft_t0) :: "memory");
-  const unsigned long long ft_start = ft_t0;
-#endif
 
   // A tile's record -> (n0, T, e0, Et, rows of x to multiply); every wavefront derives the same values from the same record
   struct Tile { int n0, T, e0, Et, nch; bool valid, ok; };
@@ -445,8 +386,8 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
         // (the WIDE form requests every round: under the branches the compiler carried the chunk's registers the edges travel
         // in through copies -- up to 860 spilled registers in its 168 / 224-wide instances)
         if (WIDE != 0 || 64 * j < nw) {
-          const ft_u2 sv = __builtin_bit_cast(ft_u2, __builtin_amdgcn_raw_buffer_load_b64(es, (unsigned)lane * 8u + 512u * j, cw * S * 8, 0));
-          const ft_u2 dv = __builtin_bit_cast(ft_u2, __builtin_amdgcn_raw_buffer_load_b64(ed, (unsigned)lane * 8u + 512u * j, cw * S * 8, 0));
+          const u32x2 sv = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(es, (unsigned)lane * 8u + 512u * j, cw * S * 8, 0));
+          const u32x2 dv = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(ed, (unsigned)lane * 8u + 512u * j, cw * S * 8, 0));
           if (j & 1) { e[j >> 1].z = __uint_as_float(sv.x); e[j >> 1].w = __uint_as_float(sv.y); e[KEEP / 2 + (j >> 1)].z = __uint_as_float(dv.x); e[KEEP / 2 + (j >> 1)].w = __uint_as_float(dv.y); }
           else { e[j >> 1].x = __uint_as_float(sv.x); e[j >> 1].y = __uint_as_float(sv.y); e[KEEP / 2 + (j >> 1)].x = __uint_as_float(dv.x); e[KEEP / 2 + (j >> 1)].y = __uint_as_float(dv.y); }
         }
@@ -658,29 +599,19 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const f4 v = i == 0 ? v0 : v1;
-        unsigned e = ft_row_amax(v) & 0x7f800000u;
-        e = min(max(e, 13u << 23), 253u << 23);
-        const float sc = __uint_as_float(0x7f000000u - e);                  // 2^-e
-        const float sc2k = __uint_as_float(0x7f000000u + (11u << 23) - e);  // 2^(11-e)
-        const ft_h2 h01 = __builtin_convertvector(ft_f2{v.x * sc, v.y * sc}, ft_h2);
-        const ft_h2 h23 = __builtin_convertvector(ft_f2{v.z * sc, v.w * sc}, ft_h2);
-        ft_h2 l01, l23;
-        l01[0] = (_Float16)__builtin_fmaf((float)h01[0], -2048.f, v.x * sc2k);
-        l01[1] = (_Float16)__builtin_fmaf((float)h01[1], -2048.f, v.y * sc2k);
-        l23[0] = (_Float16)__builtin_fmaf((float)h23[0], -2048.f, v.z * sc2k);
-        l23[1] = (_Float16)__builtin_fmaf((float)h23[1], -2048.f, v.w * sc2k);
+        // a row = 32 consecutive lanes
+        const unsigned e = f16x2_row_exp(row_group_umax<32>(__float_as_uint(f16x2_abs_max4(v))));
+        const F16x2RowScale sc = f16x2_row_scale(e);
+        const F16x2Planes p = f16x2_split4(v, sc);
         char* dstp = lds_planes + buf * (2 * FT_PLANE_BYTES) + pdst[i];
-        *reinterpret_cast<ft_u2*>(dstp) = ft_u2{__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23)};
-        *reinterpret_cast<ft_u2*>(dstp + FT_PLANE_BYTES) = ft_u2{__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23)};
+        *reinterpret_cast<u32x2*>(dstp) = p.hi;
+        *reinterpret_cast<u32x2*>(dstp + FT_PLANE_BYTES) = p.lo;
         lds_rowinv[buf * FT_CHUNK + prow[i]] = __uint_as_float(e);          // 2^e (the 32 lanes of a row write the same word)
       }
     };
     // chunks 0 and 1 of a tile -> plane buffers 0 and 1: in front of the tile's first barrier, i.e. at the end of the tile
     // before (the buffers are free from the last GEMM step on, the rows arrived during the CSR build)
     auto stage01 = [&](const Tile& r) {
-#ifdef EGC_FT_STAMPS
-      if (t.dbg & 1) return;
-#endif
       if (0 < r.nch) split(xr[0], xr[1], 0);           // (a tile that is skipped has no chunks: only the barriers remain)
       if (1 < r.nch) split(xr[2], xr[3], 1);
     };
@@ -763,35 +694,17 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
 #pragma unroll
       for (int c = 0; c < RINGN; ++c) {
         if (c < cur.nch) {   // workgroup-uniform
-#ifdef EGC_FT_STAMPS
-          if (!(t.dbg & 1))
-#endif
           // two chunks ahead: the workers take the first half of chunk c + 1 while they are in step c, and chunk c - 1, whose
           // buffer this is, was read in step c - 1 at the latest
           if (c + 2 < RINGN && c + 2 < cur.nch) split(xr[2 * (c + 2)], xr[2 * (c + 2) + 1], (c + 2) % FT_PBUF);
           lds_barrier();
         }
-#ifdef EGC_FT_EARLY_X
-        // The NEXT tile's rows are requested as soon as the registers of a chunk are free -- chunks 0 and 1 at once (they were
-        // staged at the end of the tile before), chunk c + 2 behind its split -- instead of all in the rows phase: the launch's
-        // memory skeleton (no split, no matrix work, no rows: 110 k of a workgroup's 227 k cycles at config 4) is the x stream
-        // running in the rows-phase window only, 40 % of the time.  Unconditional, straight-line (a chunk beyond the next tile
-        // lies outside its descriptor); chunks 5 - 8 stay behind the CSR build's counts: its edges travel in their registers.
-        if (c == 0) { x_load(xr[0], xr[1], rsn, 0); x_load(xr[2], xr[3], rsn, 1); }
-        if (c + 2 < RINGN && (c + 2 < RINGN / 2 || c + 2 == RINGN - 1)) x_load(xr[2 * (c + 2)], xr[2 * (c + 2) + 1], rsn, c + 2);
-#endif
       }
-#ifdef EGC_FT_STAMPS
-      unsigned long long ft_h0;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ft_h0) :: "memory");
-#endif
       // Behind the workgroup's LAST tile there is nothing to plan, build or request: straight to the end-of-tile barrier.  (Same-box
       // A/B under rocprofv3, profiles/r05_last_tile_skip.log: ZINC b128 13.64 -> 13.24 us, config 3 31.5 -> 31.0, config 4 111.9 -> 111.0.)
-#ifndef EGC_FT_NO_LAST_TILE_SKIP
       if constexpr (MODE == 0) {
         if (!nxt.valid) { lds_barrier(); break; }
       }
-#endif
 
       // the tile after the next, while the workers are in their rows phase (its dependent loads -- graph offsets, then edge
       // offsets or the search -- take two to five memory round trips: in front of a barrier they were 15 % of the kernel).
@@ -800,9 +713,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       // reads every dependent step of the CSR build waited its turn at the issue arbiter)
       __builtin_amdgcn_s_setprio(3);
       if (wave == FT_WAVES - 1) plan_tile((it + 2) % 3);
-#ifdef EGC_FT_STAMPS
-      FT_HSTAMP(7, wave == FT_WAVES - 1)
-#endif
       // the next tile's CSR, into the other set of areas (last read during the rows of tile it - 1), interleaved with the
       // requests for its rows: edges | rows of chunks 0-4 | in-degrees | scan | scatter | rows of chunks 5-9.  The
       // vector-memory counter is in order: the edges are requested first, so the wait for them leaves the ten row requests
@@ -811,39 +721,23 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       // then count the requests in flight.  (Requested chunk by chunk inside the loop above, its conservative vmcnt(0) in
       // front of every split made each step wait for the request it had just issued.)
       if (csr_wave) csr_s0(nxt, xr + EREG);
-#ifndef EGC_FT_EARLY_X
 #pragma unroll
       for (int c = 0; c < H1; ++c) x_load(xr[2 * c], xr[2 * c + 1], rsn, c);
-#endif
       if (csr_wave) {
         csr_s1(nxt, nset, xr + EREG, epk);
         csr_s1_rest(nxt, nset);
       }
       __builtin_amdgcn_sched_barrier(0);       // (the second half of the rows into the registers the edges have left)
-#ifdef EGC_FT_STAMPS
-      FT_HSTAMP(1, wave == FT_FIRST_HELPER)
-#endif
       if (csr_wave) {
         csr_sync();
         csr_s2(nxt, nset);
         csr_sync();
         csr_s3(nxt, nset, epk);
       }
-#ifdef EGC_FT_STAMPS
-      FT_HSTAMP(3, wave == FT_FIRST_HELPER)
-#endif
       // (chunks 5-9 are not split before the next tile's fifth step: their requests -- 1,300 cycles of the CU's one
       // vector-memory pipeline -- need not stand between the in-degrees and the scan)
-#ifdef EGC_FT_EARLY_X
-#pragma unroll
-      for (int c = H1; c < RINGN - 1; ++c) x_load(xr[2 * c], xr[2 * c + 1], rsn, c);
-#else
 #pragma unroll
       for (int c = H1; c < RINGN; ++c) x_load(xr[2 * c], xr[2 * c + 1], rsn, c);
-#endif
-#ifdef EGC_FT_STAMPS
-      FT_HSTAMP(2, wave == FT_FIRST_HELPER)
-#endif
       if constexpr (MODE == 1) { if (nxt.valid) g_max(nxt, (it + 1) % 3, std::false_type{}); }
       if constexpr (MODE == 0) {
         stage01(nxt);
@@ -874,9 +768,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
           pc[2] = np2 > 2 ? *reinterpret_cast<const f4*>(base + t.off_wt + (r * t.wl_floats + 64 + 4 * dj) * 4) : f4{0.f, 0.f, 0.f, 0.f};
           // ... and leave for memory as d_cat [n_nodes][ld_dcat] = [d bases (ldb) | d weightings in the layer's column order
           // (h B + b) A + a] on the way (block (h, b) = piece dj / 16 + dj of the w' image)
-#ifdef EGC_FT_STAMPS
-          if (!(t.dbg & 2048))
-#endif
           if (t.d_cat != nullptr && r < cur.T) {
             float* dc = t.d_cat + (int64_t)(cur.n0 + r) * t.ld_dcat;
             __builtin_nontemporal_store(pc[0], reinterpret_cast<f4*>(dc + 4 * dj));
@@ -899,42 +790,24 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
           float m = 0.f;
 #pragma unroll
           for (int i = 0; i < 3; ++i) m = fmaxf(fmaxf(fmaxf(m, fabsf(pc[i].x)), fmaxf(fabsf(pc[i].y), fabsf(pc[i].z))), fabsf(pc[i].w));
-          unsigned am = __float_as_uint(m);
-          am = max(am, (unsigned)__builtin_amdgcn_update_dpp(0, (int)am, 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-          am = max(am, (unsigned)__builtin_amdgcn_update_dpp(0, (int)am, 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-          am = max(am, (unsigned)__builtin_amdgcn_update_dpp(0, (int)am, 0x141, 0xf, 0xf, true));  // row_half_mirror
-          am = max(am, (unsigned)__builtin_amdgcn_update_dpp(0, (int)am, 0x140, 0xf, 0xf, true));  // row_mirror
-          unsigned e = am & 0x7f800000u;
-          e = min(max(e, 13u << 23), 253u << 23);
-          const float sc = __uint_as_float(0x7f000000u - e), sc2k = __uint_as_float(0x7f000000u + (11u << 23) - e);
+          const unsigned e = f16x2_row_exp(row_group_umax<16>(__float_as_uint(m)));
+          const F16x2RowScale sc = f16x2_row_scale(e);
           char* dst0 = lds_planes + buf * FTB_PBUF_BYTES + drow * FTB_ROW_BYTES + 8 * dj;
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
             if (i < np2) {
-              const f4 v = pc[i];
-              const ft_h2 h01 = __builtin_convertvector(ft_f2{v.x * sc, v.y * sc}, ft_h2);
-              const ft_h2 h23 = __builtin_convertvector(ft_f2{v.z * sc, v.w * sc}, ft_h2);
-              ft_h2 l01, l23;
-              l01[0] = (_Float16)__builtin_fmaf((float)h01[0], -2048.f, v.x * sc2k);
-              l01[1] = (_Float16)__builtin_fmaf((float)h01[1], -2048.f, v.y * sc2k);
-              l23[0] = (_Float16)__builtin_fmaf((float)h23[0], -2048.f, v.z * sc2k);
-              l23[1] = (_Float16)__builtin_fmaf((float)h23[1], -2048.f, v.w * sc2k);
+              const F16x2Planes p = f16x2_split4(pc[i], sc);
               char* dstp = dst0 + 128 * i;
-              *reinterpret_cast<ft_u2*>(dstp) = ft_u2{__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23)};
-              *reinterpret_cast<ft_u2*>(dstp + FTB_PLANE_BYTES) = ft_u2{__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23)};
+              *reinterpret_cast<u32x2*>(dstp) = p.hi;
+              *reinterpret_cast<u32x2*>(dstp + FTB_PLANE_BYTES) = p.lo;
             }
           }
           reinterpret_cast<float*>(base + t.off_rowinv2)[buf * FT_CHUNK + drow] = __uint_as_float(e);
         };
-#ifdef EGC_FT_STAMPS
-        const bool do_stage = !(t.dbg & 8192);
-#else
-        constexpr bool do_stage = true;
-#endif
-        if (cur.nch > 0 && do_stage) stage_d(0, 0);
+        if (cur.nch > 0) stage_d(0, 0);
         lds_barrier();                                   // (A: chunk 0 of d staged)
         for (int c = 0; c < cur.nch; ++c) {
-          if (c + 1 < cur.nch && do_stage) stage_d(c + 1, (c + 1) & 1);
+          if (c + 1 < cur.nch) stage_d(c + 1, (c + 1) & 1);
           lds_barrier();
         }
         zero_db(nxt);
@@ -1001,33 +874,20 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
         const f4 v = piece(xs, i);
         m = fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fmaxf(fabsf(v.y), fabsf(v.z))), fabsf(v.w));
       }
-      unsigned am = __float_as_uint(m);
-      am = max(am, (unsigned)__builtin_amdgcn_update_dpp(0, (int)am, 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-      am = max(am, (unsigned)__builtin_amdgcn_update_dpp(0, (int)am, 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-      am = max(am, (unsigned)__builtin_amdgcn_update_dpp(0, (int)am, 0x141, 0xf, 0xf, true));  // row_half_mirror
-      unsigned e = am & 0x7f800000u;
-      return min(max(e, 13u << 23), 253u << 23);
+      return f16x2_row_exp(row_group_umax<8>(__float_as_uint(m)));
     };
     // slab sl of the chunk in xs -> plane buffer buf: pieces 4 sl .. 4 sl + 3 (k = 128 sl + 4 (hj + 8 (i - 4 sl)) ..+3)
     auto split_slab = [&](const f4 (&xs)[PP], int sl, unsigned e, int buf) {
-      const float sc = __uint_as_float(0x7f000000u - e);                  // 2^-e
-      const float sc2k = __uint_as_float(0x7f000000u + (11u << 23) - e);  // 2^(11-e)
+      const F16x2RowScale sc = f16x2_row_scale(e);
       char* dst0 = lds_planes + buf * FTW_PBUF_BYTES + hrow * (FTW_LDX * 2) + 8 * hj;
 #pragma unroll
       for (int ii = 0; ii < 4; ++ii) {
         const int i = 4 * sl + ii;
         if (i < PP) {
-          const f4 v = piece(xs, i);
-          const ft_h2 h01 = __builtin_convertvector(ft_f2{v.x * sc, v.y * sc}, ft_h2);
-          const ft_h2 h23 = __builtin_convertvector(ft_f2{v.z * sc, v.w * sc}, ft_h2);
-          ft_h2 l01, l23;
-          l01[0] = (_Float16)__builtin_fmaf((float)h01[0], -2048.f, v.x * sc2k);
-          l01[1] = (_Float16)__builtin_fmaf((float)h01[1], -2048.f, v.y * sc2k);
-          l23[0] = (_Float16)__builtin_fmaf((float)h23[0], -2048.f, v.z * sc2k);
-          l23[1] = (_Float16)__builtin_fmaf((float)h23[1], -2048.f, v.w * sc2k);
+          const F16x2Planes p = f16x2_split4(piece(xs, i), sc);
           char* dstp = dst0 + 64 * ii;
-          *reinterpret_cast<ft_u2*>(dstp) = ft_u2{__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23)};
-          *reinterpret_cast<ft_u2*>(dstp + FTW_PLANE_BYTES) = ft_u2{__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23)};
+          *reinterpret_cast<u32x2*>(dstp) = p.hi;
+          *reinterpret_cast<u32x2*>(dstp + FTW_PLANE_BYTES) = p.lo;
           // (one piece at a time: interleaved, the four pieces' temporaries were a register too many next to the chunks in
           // flight -- one spilled dword, reloaded inside the GEMM steps with a vmcnt(0) that also waited for the rows just requested)
           __builtin_amdgcn_sched_barrier(0);
@@ -1082,32 +942,17 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       for (int c = 0; c < FTW_MAXCH; ++c) {
 #pragma unroll
         for (int sl = 0; sl < NS; ++sl) {
-#ifdef EGC_FT_STAMPS
-          const bool on = c < cur.nch, work = on && !(t.dbg & 1);       // (diagnostic build: EGC_FT_DBG bit 0 = no split)
-#else
           const bool on = c < cur.nch;                                  // the step exists (workgroup-uniform)
-          const bool work = on;
-#endif
           if (c & 1) {      // chunk c lives in xb, chunk c + 1 in xa
-            if (work && sl + 1 < NS) split_slab(xb, sl + 1, e_cur, qn);                     // the chunk's next slab ...
-            if (work && sl + 1 == NS && c + 1 < cur.nch) start_chunk(xa, c + 1, qn);        // ... or the next chunk's first
-#ifdef EGC_FT_STAMPS
-            if (!(t.dbg & 8))        // (diagnostic build: EGC_FT_DBG bit 3 = no requests inside the GEMM steps)
-#endif
-            {
+            if (on && sl + 1 < NS) split_slab(xb, sl + 1, e_cur, qn);                     // the chunk's next slab ...
+            if (on && sl + 1 == NS && c + 1 < cur.nch) start_chunk(xa, c + 1, qn);        // ... or the next chunk's first
             if (NS >= 2 && sl + 2 == NS) request(xb, rsc, c + 2);                           // the chunk's last slab has left its registers
             if (NS == 1) request(xa, rsc, c + 3);
-            }
           } else {
-            if (work && sl + 1 < NS) split_slab(xa, sl + 1, e_cur, qn);
-            if (work && sl + 1 == NS && c + 1 < cur.nch) start_chunk(xb, c + 1, qn);
-#ifdef EGC_FT_STAMPS
-            if (!(t.dbg & 8))
-#endif
-            {
+            if (on && sl + 1 < NS) split_slab(xa, sl + 1, e_cur, qn);
+            if (on && sl + 1 == NS && c + 1 < cur.nch) start_chunk(xb, c + 1, qn);
             if (NS >= 2 && sl + 2 == NS) request(xa, rsc, c + 2);
             if (NS == 1) request(xb, rsc, c + 3);
-            }
           }
           if (on) {
             lds_barrier();
@@ -1205,10 +1050,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
   const int grp_addr = (g << LPR_LOG2) << 2;
   for (int i = tid; i < ldb4; i += FT_WORKER_THREADS) lds_bases4[zrow * ldb4 + i] = f4{0.f, 0.f, 0.f, 0.f};
   lds_barrier();       // bias strips, the first two tile records
-#ifdef EGC_FT_STAMPS
-  unsigned long long ft_pro = 0;
-  if (tid == 0) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); ft_pro = _t - ft_t0; ft_t0 = _t; }
-#endif
 
   // this wavefront's 16-column tile of the packed weights, from L2, once per tile of graphs (kept across the rows phase its 32
   // registers push that phase's working set out of the register file): requested when the wavefront has left the rows of the
@@ -1253,7 +1094,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
     // the weight tile has landed HERE as far as the compiler is concerned (else it waits for it inside the GEMM loop)
     if constexpr (WIDE == 0) asm volatile("" : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]), "+v"(u[6]), "+v"(u[7]));
     lds_barrier();       // chunk 0 is staged, the tile's CSR complete, the row counter zero
-    FT_STAMP(0)
     unsigned wmx = 0;                      // (backward: largest |w'| of the tile, kept by the GEMM's epilogue below)
 
     // ---- (G) [bases | weightings] of the tile, 16 rows per step.  The A fragments of a chunk are read in two halves: k-steps
@@ -1265,25 +1105,22 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
     int lvm = lane;
     asm volatile("" : "+v"(lvm));
     const int m = lvm & 15, qd = lvm >> 4;
-    auto a_read = [&](int buf, int s, ft_h8& xh, ft_h8& xl) {
+    auto a_read = [&](int buf, int s, f16x8& xh, f16x8& xl) {
       const char* pa = lds_planes + buf * (2 * FT_PLANE_BYTES) + m * (FT_KP * 2) + ((((4 * s + qd) ^ m) & 15) << 4);
-      xh = *reinterpret_cast<const ft_h8*>(pa);
-      xl = *reinterpret_cast<const ft_h8*>(pa + FT_PLANE_BYTES);
+      xh = *reinterpret_cast<const f16x8*>(pa);
+      xl = *reinterpret_cast<const f16x8*>(pa + FT_PLANE_BYTES);
     };
     // (the same two reads, written out: the compiler then does not know of them and puts no wait for them in front of the
     // step's first MFMA -- which would also wait for the step's own four reads, LDS returning in order.  The barrier that
     // always stands between such a request and its use waits for the LDS counter itself.)
     static_assert(FT_PLANE_BYTES == 4096, "offset of the low plane in a_prefetch");
-    auto a_prefetch = [&](int buf, int s, ft_h8& xh, ft_h8& xl) {
+    auto a_prefetch = [&](int buf, int s, f16x8& xh, f16x8& xl) {
       const char* pa = lds_planes + buf * (2 * FT_PLANE_BYTES) + m * (FT_KP * 2) + ((((4 * s + qd) ^ m) & 15) << 4);
       asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:4096"
                    : "=&v"(xh), "=&v"(xl) : "v"((unsigned)(uintptr_t)pa) : "memory");
     };
-    ft_h8 ah[2], al[2];        // k-steps 0, 1 of the chunk of the coming step
-    ah[0] = al[0] = ah[1] = al[1] = ft_h8{0, 0, 0, 0, 0, 0, 0, 0};
-#ifdef EGC_FT_STAMPS
-    if (!(t.dbg & 2))
-#endif
+    f16x8 ah[2], al[2];        // k-steps 0, 1 of the chunk of the coming step
+    ah[0] = al[0] = ah[1] = al[1] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
     if (is_mfma && nch > 0) {
       a_prefetch(0, 0, ah[0], al[0]);
       a_prefetch(0, 1, ah[1], al[1]);
@@ -1291,11 +1128,8 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
     }
     int buf = 0;
     for (int c = 0; c < nch; ++c) {
-#ifdef EGC_FT_STAMPS
-      if (!(t.dbg & 2))
-#endif
       if (is_mfma) {
-        ft_h8 bh[2], bl[2];
+        f16x8 bh[2], bl[2];
         a_read(buf, 2, bh[0], bl[0]);
         a_read(buf, 3, bh[1], bl[1]);
         const f4 ri = *reinterpret_cast<const f4*>(lds_rowinv + buf * FT_CHUNK + 4 * qd);   // (the rows' scales, for the epilogue)
@@ -1303,14 +1137,14 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
         f4 acc0 = f4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          const ft_h8 wh = __builtin_bit_cast(ft_h8, u[2 * s]), wl = __builtin_bit_cast(ft_h8, u[2 * s + 1]);
+          const f16x8 wh = __builtin_bit_cast(f16x8, u[2 * s]), wl = __builtin_bit_cast(f16x8, u[2 * s + 1]);
           acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[s], wh, acc0, 0, 0, 0);
           acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[s], wh, acc1, 0, 0, 0);
           acc2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[s], wl, acc2, 0, 0, 0);
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          const ft_h8 wh = __builtin_bit_cast(ft_h8, u[4 + 2 * s]), wl = __builtin_bit_cast(ft_h8, u[4 + 2 * s + 1]);
+          const f16x8 wh = __builtin_bit_cast(f16x8, u[4 + 2 * s]), wl = __builtin_bit_cast(f16x8, u[4 + 2 * s + 1]);
           acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[s], wh, acc0, 0, 0, 0);
           acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[s], wh, acc1, 0, 0, 0);
           acc2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[s], wl, acc2, 0, 0, 0);
@@ -1324,13 +1158,13 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
         // (on the packed fp32 pipe: the GEMM phase is bound by the SIMD's vector ISSUE -- 36 MFMAs hold it 288 of a step's
         // cycles, the helpers' split 340, this epilogue and the LDS instructions the rest -- so eight instructions instead of
         // sixteen are time; the same operations per component, the same bits)
-        const ft_f2 k2 = ft_f2{1.f / 2048.f, 1.f / 2048.f}, ci2 = ft_f2{col_inv, col_inv}, cb2 = ft_f2{col_bias, col_bias};
-        const ft_f2 a0l = __builtin_shufflevector(acc0, acc0, 0, 1), a0h = __builtin_shufflevector(acc0, acc0, 2, 3);
-        const ft_f2 tl = __builtin_shufflevector(acc1, acc1, 0, 1) + __builtin_shufflevector(acc2, acc2, 0, 1);
-        const ft_f2 th = __builtin_shufflevector(acc1, acc1, 2, 3) + __builtin_shufflevector(acc2, acc2, 2, 3);
-        const ft_f2 ul = __builtin_elementwise_fma(tl, k2, a0l), uh = __builtin_elementwise_fma(th, k2, a0h);
-        const ft_f2 sl = ci2 * __builtin_shufflevector(ri, ri, 0, 1), sh2 = ci2 * __builtin_shufflevector(ri, ri, 2, 3);
-        const ft_f2 ol = __builtin_elementwise_fma(ul, sl, cb2), oh = __builtin_elementwise_fma(uh, sh2, cb2);
+        const f32x2 k2 = f32x2{1.f / 2048.f, 1.f / 2048.f}, ci2 = f32x2{col_inv, col_inv}, cb2 = f32x2{col_bias, col_bias};
+        const f32x2 a0l = __builtin_shufflevector(acc0, acc0, 0, 1), a0h = __builtin_shufflevector(acc0, acc0, 2, 3);
+        const f32x2 tl = __builtin_shufflevector(acc1, acc1, 0, 1) + __builtin_shufflevector(acc2, acc2, 0, 1);
+        const f32x2 th = __builtin_shufflevector(acc1, acc1, 2, 3) + __builtin_shufflevector(acc2, acc2, 2, 3);
+        const f32x2 ul = __builtin_elementwise_fma(tl, k2, a0l), uh = __builtin_elementwise_fma(th, k2, a0h);
+        const f32x2 sl = ci2 * __builtin_shufflevector(ri, ri, 0, 1), sh2 = ci2 * __builtin_shufflevector(ri, ri, 2, 3);
+        const f32x2 ol = __builtin_elementwise_fma(ul, sl, cb2), oh = __builtin_elementwise_fma(uh, sh2, cb2);
         f4 o = __builtin_shufflevector(ol, oh, 0, 1, 2, 3);
         if (dst_act) o = w_act<C>(a, o);
         if constexpr (MODE == 1) {
@@ -1362,19 +1196,18 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
     //      the step every k-step paid the whole L2 latency: 22,000 cycles per chunk against 1,300 of matrix work); three
     //      products, acc0 = xh wh, acc1 = xl wh, acc2 = xh wl.  One barrier per k-slab of 128 the helpers stage; the D tile leaves
     //      behind the chunk's last k-step. ----
-    typedef float ft_f16v __attribute__((ext_vector_type(16)));
     int lvm = lane;
     asm volatile("" : "+v"(lvm));
     const int l31 = lvm & 31, hh = lvm >> 5;
     constexpr int NS = WIDE;
     constexpr int BD = 4;                 // weight fragments in flight per wavefront (k-steps); t.k16 is a multiple of it (zero k-steps)
-    const ft_h8* bsrc = reinterpret_cast<const ft_h8*>(t.packed) + (int64_t)wave * t.k16 * 128 + lvm;   // [tile][k16][plane][64 lanes]
+    const f16x8* bsrc = reinterpret_cast<const f16x8*>(t.packed) + (int64_t)wave * t.k16 * 128 + lvm;   // [tile][k16][plane][64 lanes]
     const int NG = t.k16 / BD;            // groups of BD k-steps per chunk
     // ring of BD fragments, slot = k-step % BD; a k-step's fragment is requested BD steps ahead (the chunk's last BD steps request
     // the next chunk's first), always, so that the compiler counts the requests exactly; every request is 1 KiB per plane
-    ft_h8 wh[BD], wl[BD];
+    f16x8 wh[BD], wl[BD];
 #pragma unroll
-    for (int j = 0; j < BD; ++j) { wh[j] = ft_h8{0, 0, 0, 0, 0, 0, 0, 0}; wl[j] = wh[j]; }
+    for (int j = 0; j < BD; ++j) { wh[j] = f16x8{0, 0, 0, 0, 0, 0, 0, 0}; wl[j] = wh[j]; }
     if (is_mfma && nch > 0) {
 #pragma unroll
       for (int j = 0; j < BD; ++j) { wh[j] = bsrc[j * 128]; wl[j] = bsrc[j * 128 + 64]; }
@@ -1383,26 +1216,20 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
     for (int c = 0; c < nch; ++c) {
       // three accumulators, one per product: a second product on the same accumulator waits for the first (64 cycles of a
       // 32 x 32 x 16 MFMA's latency against 32 of issue) -- 2,300 cycles of matrix work per chunk where 1,150 do
-      ft_f16v acc0, acc1, acc2;
+      f32x16 acc0, acc1, acc2;
 #pragma unroll
       for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; acc2[r] = 0.f; }
       if (is_mfma) {
         const char* pa = lds_planes + qb * FTW_PBUF_BYTES + l31 * (FTW_LDX * 2) + hh * 16;
         for (int g = 0; g < NG; ++g) {
-#ifdef EGC_FT_STAMPS
-          if (t.dbg & 2) {                 // (diagnostic build: EGC_FT_DBG bit 1 = no matrix work, the barriers stay)
-            if ((g & 1) && g + 1 < NG) { qb ^= 1; lds_barrier(); }
-            continue;
-          }
-#endif
-          const ft_h8* bnext = g + 1 < NG ? bsrc + (int64_t)(g + 1) * (BD * 128) : bsrc;
+          const f16x8* bnext = g + 1 < NG ? bsrc + (int64_t)(g + 1) * (BD * 128) : bsrc;
           // the A fragments of the group's four k-steps: requested together (their LDS latency passes once per group)
-          ft_h8 xh[BD], xl[BD];
+          f16x8 xh[BD], xl[BD];
           const char* pg = pa + (g & 1) * (BD * 32);
 #pragma unroll
           for (int j = 0; j < BD; ++j) {
-            xh[j] = *reinterpret_cast<const ft_h8*>(pg + j * 32);
-            xl[j] = *reinterpret_cast<const ft_h8*>(pg + j * 32 + FTW_PLANE_BYTES);
+            xh[j] = *reinterpret_cast<const f16x8*>(pg + j * 32);
+            xl[j] = *reinterpret_cast<const f16x8*>(pg + j * 32 + FTW_PLANE_BYTES);
           }
 #pragma unroll
           for (int j = 0; j < BD; ++j) {
@@ -1418,9 +1245,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
             pa = lds_planes + qb * FTW_PBUF_BYTES + l31 * (FTW_LDX * 2) + hh * 16;
           }
         }
-#ifdef EGC_FT_STAMPS
-        if (!(t.dbg & 16))           // (diagnostic build: EGC_FT_DBG bit 4 = no D-tile epilogue)
-#endif
         {
           // D: lane -> column 32 wave + lane % 32, rows 8 j + 4 (lane / 32) + i.  2^ex 2^ew (acc0 + 2^-11 acc1) + bias
           const float* rinv = lds_rowinv + (c & 1) * FTW_CH + 4 * hh;
@@ -1452,14 +1276,10 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       }
     }
     }
-    FT_STAMP(4)
 
     // ---- (E) rows: one lane group per row, G rows per wavefront and turn (turns handed out by an LDS counter: a wavefront
     //      whose rows are short takes the next ones), everything from LDS ----
     if constexpr (MODE == 0) {
-#ifdef EGC_FT_STAMPS
-    if (!(t.dbg & 4))
-#endif
     for (; cur.ok;) {
       int r0 = 0;
       // (workgroup scope, relaxed: the plain atomicAdd drains the vector-memory counter first, i.e. waits for the `out`
@@ -1593,7 +1413,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       if (tid == 0) lds_rec[28] = nonfinite ? FT_DBS_POISON : dbs;     // (for the helpers, who stage d bases behind barrier B1;
       dbs_tile = nonfinite ? 0 : dbs;                                   //  every wavefront here forms the same number itself)
     }
-    FT_STAMP(1)
     const double db_scale = __builtin_ldexp(1.0, dbs_tile);
     const __amdgpu_buffer_rsrc_t rgo =
         __builtin_amdgcn_make_buffer_rsrc((void*)t.grad_out, 0, (unsigned)a.n_nodes * (unsigned)F_out * 4u, 0x00020000);
@@ -1612,11 +1431,7 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       f4 gv[8];
 #pragma unroll
       for (int h = 0; h < 8; ++h)
-#ifdef EGC_FT_STAMPS
-        gv[h] = load_slot(rgo, (row_ok && h < H && !(t.dbg & 256)) ? ((unsigned)row * (unsigned)F_out + (unsigned)(h * 16 + 4 * l4)) * 4u : OOB);
-#else
         gv[h] = load_slot(rgo, (row_ok && h < H) ? ((unsigned)row * (unsigned)F_out + (unsigned)(h * 16 + 4 * l4)) * 4u : OOB);
-#endif
       const int start = row_ok ? (lds_rowptr[r] & 0xffff) : 0;             // (two adjacent words: one ds_read2_b32)
       const int nd = row_ok ? (lds_rowptr[r + 1] & 0xffff) - start : 0;
       int maxd = nd;
@@ -1638,9 +1453,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       };
       int nself = 0;
       for (int ts = 0; ts < maxd; ts += LPR) {
-#ifdef EGC_FT_STAMPS
-        if (t.dbg & 512) break;
-#endif
         const bool pv = ts + q < nd;
         const int jj = pv ? (int)lds_col[start + ts + q] : 0;
         const bool self_e = pv && jj == r;
@@ -1667,9 +1479,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
           for (int uu = 0; uu < FU; ++uu) {
             sum += v[uu];
             ws = f4_fma(splat(w[uu]), v[uu], ws);
-#ifdef EGC_FT_STAMPS
-            if (!(t.dbg & 32))
-#endif
             if (jn[uu] != zrow) take(v[uu], ts + t0 + uu, jn[uu]);     // (the row's entries are in input order: csr_s3)
           }
         }
@@ -1704,9 +1513,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       float* wrow = lds_wt + (row_ok ? r : 0) * t.wl_floats;
 #pragma unroll
       for (int h = 0; h < 8; ++h) {
-#ifdef EGC_FT_STAMPS
-        if (t.dbg & 64) break;
-#endif
         if (h < H) {
           const f4 wv = *reinterpret_cast<const f4*>(wrow + (h * 4 + bq) * 4);
           dagg[0] = f4_fma(splat(wv.x), gv[h], dagg[0]);
@@ -1749,9 +1555,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
         add_at(p, c.x); add_at(p + 1, c.y); add_at(p + 2, c.z); add_at(p + 3, c.w);
       };
       for (int ts = 0; ts < maxd; ts += LPR) {
-#ifdef EGC_FT_STAMPS
-        if (t.dbg & 128) break;
-#endif
         const bool pv = ts + q < nd;
         const int jj = pv ? (int)lds_col[start + ts + q] : 0;
         const bool self_e = pv && jj == r;
@@ -1766,9 +1569,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
           if (j != zrow) add_row(j, f4_fma(splat(w), d_s, d_t));
         }
       }
-#ifdef EGC_FT_STAMPS
-      if (!(t.dbg & 1024))
-#endif
       if (row_ok) {
         if (C::xl(a)) { if (has_self) add_row(r, f4_fma(splat(dis_i * dis_i), d_s, d_t)); }
         else if (C::yl(a) && has_self) add_row(r, d_s * splat(dis_i * dis_i));
@@ -1781,7 +1581,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       }
     }
     }
-    FT_STAMP(5)
     if constexpr (MODE == 0) {
       request_weights();
       lds_barrier();   // every wavefront is done with the tile's LDS image
@@ -1817,9 +1616,6 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       const int m2 = lvm & 15, qd2 = lvm >> 4;
       int buf2 = 0;
       for (int c = 0; c < nch; ++c) {
-#ifdef EGC_FT_STAMPS
-        if (!(t.dbg & 4096))
-#endif
         if (is_mfma2) {
           const int f = 16 * wave + m2;
           const unsigned off0 = f < t.F_in ? ((unsigned)(FT_CHUNK * c + 4 * qd2) * (unsigned)t.F_in + (unsigned)f) * 4u : OOB;
@@ -1833,9 +1629,9 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
 #pragma unroll
           for (int k2 = 0; k2 < 6; ++k2) {
             if (k2 < K2S) {
-              const ft_h8 xh = *reinterpret_cast<const ft_h8*>(pa + k2 * 64);
-              const ft_h8 xl = *reinterpret_cast<const ft_h8*>(pa + k2 * 64 + FTB_PLANE_BYTES);
-              const ft_h8 wh = __builtin_bit_cast(ft_h8, u2[2 * k2]), wl = __builtin_bit_cast(ft_h8, u2[2 * k2 + 1]);
+              const f16x8 xh = *reinterpret_cast<const f16x8*>(pa + k2 * 64);
+              const f16x8 xl = *reinterpret_cast<const f16x8*>(pa + k2 * 64 + FTB_PLANE_BYTES);
+              const f16x8 wh = __builtin_bit_cast(f16x8, u2[2 * k2]), wl = __builtin_bit_cast(f16x8, u2[2 * k2 + 1]);
               acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wh, acc0, 0, 0, 0);
               acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh, acc1, 0, 0, 0);
               acc2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wl, acc2, 0, 0, 0);
@@ -1855,17 +1651,7 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       }
       request_weights();
     }
-    FT_STAMP(6)
   }
-#ifdef EGC_FT_STAMPS
-  if (tid == 0 && egc_ft_stamp_buf != nullptr) {
-    unsigned long long tend;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tend) :: "memory");
-    ft_acc[7] = tend - ft_start;
-    for (int k = 0; k < 8; ++k) egc_ft_stamp_buf[blockIdx.x * 8 + k] = ft_acc[k];
-    egc_ft_stamp_buf[256 * 8 + blockIdx.x] = ft_pro;
-  }
-#endif
 }
 
 // egc_fused_tile_wide.hip: the WIDE instances (lpr = lanes per row group: 16 / 32 / 64; need = NEED_* mask of the layer)

@@ -22,34 +22,8 @@ static int launch_ftw_one(const AggArgs& a, const FusedTileArgs& t, unsigned gri
     if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(fused_tile_kernel, wide)", e); return EGC_ERR_HIP; }
     attr_set = true;
   }
-#ifdef EGC_FT_STAMPS
-  static unsigned long long* dbuf = nullptr;
-  if (dbuf == nullptr) {
-    hipMalloc(&dbuf, (256 * 9 + 96) * 8);
-    hipMemcpyToSymbol(HIP_SYMBOL(egc_ft_stamp_buf), &dbuf, sizeof(dbuf));
-  }
-  hipMemset(dbuf, 0, (256 * 9 + 96) * 8);
-#endif
   fused_tile_kernel<LPR_LOG2, HPB, NEED, C, EGC_FTW_NS><<<grid, FT_THREADS, lds, stream>>>(a, t);
   EGC_LAUNCH_CHECK("fused_tile_kernel (wide)");
-#ifdef EGC_FT_STAMPS
-  {   // diagnostic build: accumulated shader cycles per phase of the workers' schedule, averaged over the workgroups
-    hipDeviceSynchronize();
-    static int calls = 0;
-    if ((++calls % 40) == 0) {
-      unsigned long long h[256 * 9 + 96];
-      hipMemcpy(h, dbuf, sizeof(h), hipMemcpyDeviceToHost);
-      double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tmax = 0;
-      for (unsigned b = 0; b < grid; ++b) {
-        for (int k = 0; k < 8; ++k) sum[k] += (double)h[b * 8 + k];
-        tmax = std::max(tmax, (double)h[b * 8 + 7]);
-      }
-      fprintf(stderr, "[ftw stamps] grid %u, n_nodes %d, F_in %d, k16 %d: per workgroup (shader cycles): start-of-tile barrier %.0f  GEMM %.0f  "
-              "rows %.0f  end barrier %.0f | total avg %.0f max %.0f\n", grid, a.n_nodes, t.F_in, t.k16,
-              sum[0] / grid, sum[4] / grid, sum[5] / grid, sum[6] / grid, sum[7] / grid, tmax);
-    }
-  }
-#endif
   return EGC_OK;
 }
 

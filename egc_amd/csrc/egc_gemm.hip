@@ -15,8 +15,6 @@
 
 namespace egc {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int BM = 128;
 constexpr int BN = 64;
 constexpr int KT = 32;

@@ -28,31 +28,14 @@
 #include <algorithm>
 
 #include "egc_common.h"
-#include <stdio.h>
-
 #include "egc_gemm_split.h"
 
 namespace egc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 constexpr int XBM = 128;      // rows per block
 constexpr int XBN = 192;      // virtual columns per block (6 MFMA tiles)
 constexpr int XKT = 32;       // k per staging step
 constexpr int XLD = 40;       // LDS row stride in bf16 (80 B: conflict-free ds_read_b128 of 16-byte k-runs)
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding
-// GLOBAL access of the wavefront (s_waitcnt vmcnt(0)): in a streaming kernel that drains the stores of the
-// tile just finished and the prefetch of the next one at every barrier -- microseconds of HBM latency per
-// tile.  The tiles exchanged between wavefronts live in LDS, so lgkmcnt(0) + s_barrier is all that is needed.
-__device__ inline void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 __device__ inline u16 bf16_rn(float f) {
   const unsigned u = __float_as_uint(f);
@@ -61,7 +44,6 @@ __device__ inline u16 bf16_rn(float f) {
 __device__ inline float bf16_f(u16 h) { return __uint_as_float((unsigned)h << 16); }
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Two floats -> three packed bf16 pairs (h, m, l planes) with v_cvt_pk_bf16_f32 (round to nearest even):
 // 9 VALU instructions per pair.  Element 0 sits in the low half of each packed word.
@@ -101,12 +83,6 @@ __global__ void __launch_bounds__(256) pack_bf16x3_kernel(const float* __restric
   packed[base + 2 * (int64_t)NV * XKT] = l;
 }
 
-#ifdef EGC_GEMM3_STAMPS
-__device__ unsigned long long egc_stamp3[8];  // diagnostic build only: cycles per phase, summed over wavefronts
-#define EGC_ST3(k) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); st3[k] += _t - st3_t0; st3_t0 = _t; }
-#else
-#define EGC_ST3(k)
-#endif
 
 // LDS operand read with an immediate offset (one address register for the whole tile loop)
 constexpr unsigned A_PLANE = XBM * XLD * 2, B_TILE = 32 * XLD * 2, SUB = 16 * 2;
@@ -212,17 +188,9 @@ __global__ void __launch_bounds__(256) basis_gemm_bf16x3_kernel(const float* __r
   };
   if (A_VEC4) load_x(0);
   load_w(0);
-#ifdef EGC_GEMM3_STAMPS
-  unsigned long long st3[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st3_t0;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st3_t0) :: "memory");
-#endif
 
   for (int ks = 0; ks < KS; ++ks) {
     const int k0 = ks * XKT;
-#ifdef EGC_GEMM3_STAMPS
-    if (A_VEC4) { asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); }  // x tile landed (the 9 weight pieces may still fly)
-#endif
-    EGC_ST3(0)
     // ---- stage x[m0 .. m0+128, k0 .. k0+32) as three bf16 planes
     if (A_VEC4) {
 #pragma unroll
@@ -252,11 +220,6 @@ __global__ void __launch_bounds__(256) basis_gemm_bf16x3_kernel(const float* __r
         As[2][row][kk] = l;
       }
     }
-    EGC_ST3(1)
-#ifdef EGC_GEMM3_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    EGC_ST3(2)
     // ---- weight planes of this k-step (fetched during the previous step's MFMAs) -> LDS
     {
 #pragma unroll
@@ -267,9 +230,7 @@ __global__ void __launch_bounds__(256) basis_gemm_bf16x3_kernel(const float* __r
           if (i < pieces) *reinterpret_cast<u32x4*>(&Bs[p][i >> 2][(i & 3) * 8]) = wreg[p][j];
         }
     }
-    EGC_ST3(3)
     lds_barrier();
-    EGC_ST3(4)
     if (ks + 1 < KS) {  // next step's operands: in flight during the MFMAs below
       if (A_VEC4) load_x(ks + 1);
       load_w(ks + 1);
@@ -332,14 +293,8 @@ __global__ void __launch_bounds__(256) basis_gemm_bf16x3_kernel(const float* __r
         }
       }
     }
-    EGC_ST3(5)
     lds_barrier();
-    EGC_ST3(6)
   }
-#ifdef EGC_GEMM3_STAMPS
-  if (lane == 0)
-    for (int k = 0; k < 7; ++k) atomicAdd(&egc_stamp3[k], st3[k]);
-#endif
 
   // ---- epilogue.  C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
   const bool wide = (ntile >= 6) && (W % 4 == 0) && (bcat == nullptr || (reinterpret_cast<uintptr_t>(bcat) & 15) == 0);
@@ -702,19 +657,6 @@ int egc_basis_transform_packed_ex(const float* x, const void* packed, const floa
       basis_gemm_bf16x3_kernel<false, 6><<<grid, 256, 0, stream>>>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, KS, 0);
     EGC_LAUNCH_CHECK("basis_gemm_bf16x3_kernel");
   }
-#ifdef EGC_GEMM3_STAMPS
-  {
-    hipDeviceSynchronize();
-    unsigned long long h[8];
-    hipMemcpyFromSymbol(h, HIP_SYMBOL(egc_stamp3), sizeof(h));
-    static int calls = 0;
-    if (++calls % 10 == 0) {
-      const double waves = (double)mblocks * full * 4 * calls;
-      fprintf(stderr, "[gemm3 stamps] K=%d NV=%d per wavefront per k-step (cycles of s_memtime @100MHz x?): xwait %.0f split %.0f wwait %.0f wstage %.0f bar1 %.0f mfma %.0f bar2 %.0f\n",
-              f_in, NV, h[0] / waves / KS, h[1] / waves / KS, h[2] / waves / KS, h[3] / waves / KS, h[4] / waves / KS, h[5] / waves / KS, h[6] / waves / KS);
-    }
-  }
-#endif
   if (NV % XBN != 0) {
     dim3 grid((unsigned)mblocks, 1);
     const bool four = (NV - full * XBN) == 128;  // a 128-column remainder (or a 128-column GEMM): pipelined too

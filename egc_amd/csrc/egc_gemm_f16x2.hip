@@ -24,42 +24,13 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <vector>
 
 #include "egc_common.h"
 #include "egc_gemm_split.h"
 
 namespace egc {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ inline void lds_barrier2() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 constexpr int F16X2_KP = 128;          // k extent of the register-resident weight block (F_in <= 128, zero beyond F_in)
-
-// biased exponent of the scale group's largest magnitude -> (scale, inverse scale), both exact powers of two
-__device__ inline void scales_of(unsigned amax_bits, float& scale, float& inv) {
-  unsigned be = amax_bits >> 23;        // sign already cleared
-  be = be > 253u ? 253u : be;           // huge / inf / nan: keep the scale a normal number (values propagate)
-  scale = __uint_as_float((254u - be) << 23);
-  inv = __uint_as_float(be << 23);      // be == 0 (all-zero or denormal group): result flushes to 0
-}
-
-// two scaled floats -> packed fp16 pairs (h plane, 2^11-scaled l plane); element 0 in the low half
-__device__ inline void split2_pk(f32x2 v, unsigned& h, unsigned& l) {
-  const f16x2 hh = __builtin_convertvector(v, f16x2);
-  h = __builtin_bit_cast(unsigned, hh);
-  const f32x2 r = (v - __builtin_convertvector(hh, f32x2)) * 2048.f;
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-}
 
 // packed[column tile][k-step][plane][lane][8] (fp16 bits, the MFMA B fragments as they are loaded) followed by float inv_scale[NV].  One wavefront per virtual column
 // (runs once per parameter update -- every step when training): lanes stride over k, the column maximum is a
@@ -74,26 +45,20 @@ __global__ void __launch_bounds__(64) pack_f16x2_kernel(const float* __restrict_
     for (int k = lane; k < K; k += 64) amax = max(amax, __float_as_uint(wcat[k * rs + src * cs]) & 0x7fffffffu);
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, d));
-  float scale, inv;
-  scales_of(amax, scale, inv);
+  const F16x2ColScale col = f16x2_col_scale(amax);
   for (int k = lane; k < KS * GEMM_KT; k += 64) {
-    const float w = (src >= 0 && k < K) ? wcat[k * rs + src * cs] * scale : 0.f;
-    const _Float16 h = (_Float16)w;
-    const _Float16 l = (_Float16)((w - (float)h) * 2048.f);
+    const F16x2Bits b = f16x2_pack_split((src >= 0 && k < K) ? wcat[k * rs + src * cs] * col.scale : 0.f);
     // fragment order: the B operand of k-step s (16 k), plane p, column tile ct is 64 lanes x 8 halves, lane
     // 32 (k % 16 / 8) + column % 32 -- a wavefront of the GEMM fetches it as ONE contiguous KiB (with the planes laid
     // out [k-slab][plane][column][32 k] every lane's 16 bytes sat in a line of their own, and the 196 KB of weight
     // loads of a block took ~3 us of its prologue)
     const int64_t base = ((((int64_t)(v >> 5) * (F16X2_KP / 16) + (k >> 4)) * 2) * 64 + 32 * ((k & 15) >> 3) + (v & 31)) * 8 + (k & 7);
-    packed[base] = __builtin_bit_cast(u16, h);
-    packed[base + 64 * 8] = __builtin_bit_cast(u16, l);
+    packed[base] = b.h;
+    packed[base + 64 * 8] = b.l;
   }
-  if (lane == 0) reinterpret_cast<float*>(packed + (int64_t)KS * 2 * NV * GEMM_KT)[v] = inv;
+  if (lane == 0) reinterpret_cast<float*>(packed + (int64_t)KS * 2 * NV * GEMM_KT)[v] = col.inv;
 }
 
-#ifdef EGC_GEMM_STAMPS
-__device__ unsigned long long* egc_stamp_buf2 = nullptr;  // diagnostic build only
-#endif
 
 // What bounds this kernel is each SIMD's vector issue port and its matrix pipe TOGETHER: a VALU instruction
 // holds the port for 4 cycles, a v_mfma_f32_32x32x16_f16 for 8 and the pipe for 32 (MI355X_MICROARCH.md,
@@ -159,10 +124,6 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ct = wave % 6, rt = wave / 6;                       // column tile, 32-row half of the x tile
-#ifdef EGC_GEMM_STAMPS
-  unsigned long long t_entry;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_entry) :: "memory");
-#endif
   const int l31 = lane & 31, hh = lane >> 5;
   const int cb = 32 * ct;
   // A block owns a CONTIGUOUS row range of M / gridDim rows (its last tile is partial: the DMA and the stores of the
@@ -183,22 +144,13 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   const bool to_bases = cb < ldb;
   const int wcol_v = cb - ldb + l31;                  // weightings column of this lane (to_bases == false)
   const int qa = wcol_v & 3;                          // FM >= 0: place in the (h, b) pair's quad
-#ifdef EGC_DIAG_FOLD_W128   // diagnostic build: the fold's arithmetic with the unfolded store pattern (all 128 columns, whole lines;
-  constexpr int FMS = -1;   // results are wrong, times are not) -- what the fold's instructions cost apart from its store layout
-#else
-  constexpr int FMS = FM;   // the store layout's FM
-#endif
-  const int W_out = FMS >= 0 ? W / 4 * 3 : W;         // row length of the weightings written
+  const int W_out = FM >= 0 ? W / 4 * 3 : W;          // row length of the weightings written
   const __amdgpu_buffer_rsrc_t ro =
       to_bases ? __builtin_amdgcn_make_buffer_rsrc((void*)bases, 0, (unsigned)(row_hi * ldb * 4), 0x00020000)
                : __builtin_amdgcn_make_buffer_rsrc((void*)weightings, 0, (unsigned)(row_hi * (int64_t)W_out * 4), 0x00020000);
   const int out_ld = to_bases ? ldb : W_out;
-  const int out_col = to_bases ? cb + l31 : FMS >= 0 ? 3 * (wcol_v >> 2) + qa - (qa > FMS ? 1 : 0) : wcol_v;
-#if defined(EGC_DIAG_GEMM_NO_W_STORE) || defined(EGC_DIAG_GEMM_NO_W)   // diagnostic builds (tools/f3_roundtrip_cost.py): the weightings are
-  const bool col_ok = to_bases && out_col < ldb;                        // not written / not computed at all (wrong results, honest times)
-#else
-  const bool col_ok = to_bases ? out_col < ldb : (wcol_v < W && (FMS < 0 || qa != FMS));
-#endif
+  const int out_col = to_bases ? cb + l31 : FM >= 0 ? 3 * (wcol_v >> 2) + qa - (qa > FM ? 1 : 0) : wcol_v;
+  const bool col_ok = to_bases ? out_col < ldb : (wcol_v < W && (FM < 0 || qa != FM));
   const bool is_sum = FM >= 0 && !to_bases && qa == fold_s;
   const u32x4 rd = {(unsigned)(uintptr_t)dis, (unsigned)((uintptr_t)dis >> 32) & 0xffffu, (unsigned)(M * 4), 0x00020000u};
   const unsigned icnt_lds = (unsigned)(uintptr_t)icnt;
@@ -248,42 +200,19 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
     const float c = __builtin_rintf(__builtin_amdgcn_rcpf(d * d));
     *p = __builtin_amdgcn_rcpf(fmaxf(c, 1.f));
   };
-  // A row is 32 consecutive pieces = one half wavefront: its largest magnitude is an all-reduce over 32 lanes
-  // (4 DPP steps inside the rows of 16, one cross-row exchange).  NaNs drop out of the maxima and propagate
-  // through the products instead.
-  auto row_amax = [&](const float4 v) -> unsigned {
-    // |.| through source modifiers (two instructions for four elements; written as asm because the compiler
-    // canonicalises every fmax operand), then unsigned maxima on the bit patterns of these non-negative floats
-    float m;
-    asm("v_max3_f32 %0, |%1|, |%2|, |%3|\n\tv_max_f32 %0, |%4|, %0" : "=&v"(m) : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-    unsigned a = __float_as_uint(m);
-    a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-    a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-    a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x141, 0xf, 0xf, true));  // row_half_mirror
-    a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x140, 0xf, 0xf, true));  // row_mirror
-    return max(a, (unsigned)__builtin_amdgcn_ds_swizzle((int)a, 0x401F));                 // lane ^ 16
-  };
+  // A row is 32 consecutive pieces = one half wavefront: its largest magnitude is an all-reduce over 32 lanes, on the bit
+  // patterns of the non-negative |maxima|
+  auto row_amax = [&](const float4 v) -> unsigned { return row_group_umax<32>(__float_as_uint(f16x2_abs_max4(v))); };
   auto split_store = [&](int buf, int ri, int i, const float4 v, unsigned amax) {
     const int pc = tid + nthreads * i;
     const int row = pc >> 5;
     const int k4 = (pc & 31) * 4;
-    // exponent field of the row maximum, kept where both 2^-e and 2^(11-e) are normal numbers (rows below
-    // 2^-113 are scaled by 2^114 only and keep fewer bits; rows above 2^126 overflow as they would in fp32)
-    unsigned e = amax & 0x7f800000u;
-    e = min(max(e, 13u << 23), 253u << 23);
-    const float sc = __uint_as_float(0x7f000000u - e);                  // 2^-e
-    const float sc2k = __uint_as_float(0x7f000000u + (11u << 23) - e);  // 2^(11-e)
-    const f16x2 h01 = __builtin_convertvector(f32x2{v.x * sc, v.y * sc}, f16x2);
-    const f16x2 h23 = __builtin_convertvector(f32x2{v.z * sc, v.w * sc}, f16x2);
-    // (xs - h) * 2^11 = fma(h, -2^11, x * 2^(11-e)): one mixed-precision fma, rounded once to fp16
-    f16x2 l01, l23;
-    l01[0] = (_Float16)__builtin_fmaf((float)h01[0], -2048.f, v.x * sc2k);
-    l01[1] = (_Float16)__builtin_fmaf((float)h01[1], -2048.f, v.y * sc2k);
-    l23[0] = (_Float16)__builtin_fmaf((float)h23[0], -2048.f, v.z * sc2k);
-    l23[1] = (_Float16)__builtin_fmaf((float)h23[1], -2048.f, v.w * sc2k);
+    const unsigned e = f16x2_row_exp(amax);
+    const F16x2RowScale sc = f16x2_row_scale(e);
+    const F16x2Planes p = f16x2_split4(v, sc);
     u16* dst = xs + buf * XBUF + row * LDX + k4;
-    *reinterpret_cast<u32x2*>(dst) = u32x2{__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23)};
-    *reinterpret_cast<u32x2*>(dst + ROWS * LDX) = u32x2{__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23)};
+    *reinterpret_cast<u32x2*>(dst) = p.hi;
+    *reinterpret_cast<u32x2*>(dst + ROWS * LDX) = p.lo;
     row_inv[ri * ROWS + row] = __uint_as_float(e);  // 2^e; all 32 lanes of the row write the same word: no branch
   };
   auto raw_piece = [&](int slot, int i) -> float4 {
@@ -301,9 +230,6 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   };
   f32x16 acc0, acc1, t;   // t: previous tile's acc0 + 2^-11 acc1, waiting for its scales
   auto mfma_step = [&](int s, const f16x8 xh, const f16x8 xl) {
-#ifdef EGC_DIAG_GEMM_NO_W
-    if (!to_bases) return;
-#endif
     acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, wf[s][0], acc0, 0, 0, 0);
     acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl, wf[s][0], acc1, 0, 0, 0);
     acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, wf[s][1], acc1, 0, 0, 0);
@@ -319,11 +245,7 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
     float v1 = __builtin_fmaf(t[4 * j + 1], col_inv * ri.y, col_bias);
     float v2 = __builtin_fmaf(t[4 * j + 2], col_inv * ri.z, col_bias);
     float v3 = __builtin_fmaf(t[4 * j + 3], col_inv * ri.w, col_bias);
-#ifdef EGC_DIAG_FOLD_NO_MATH   // diagnostic build: the folded store layout without the fold's arithmetic (wrong results, honest times)
-    if constexpr (false) {
-#else
     if constexpr (FM >= 0) {
-#endif
       if (!to_bases) {  // (wave-uniform) sum lane += mean lane's weighting x 1 / max(cnt, 1); the other lanes add 0 x it
         const float4 ic = *reinterpret_cast<const float4*>(is_sum ? icnt_t + 32 * rt + 8 * j + 4 * hh : zero4);
         constexpr int QP = FM | (FM << 2) | (FM << 4) | (FM << 6);  // quad_perm: every lane reads lane FM of its quad
@@ -350,15 +272,11 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   if (FM >= 0 && tid < 4) zero4[tid] = 0.f;   // (made visible by the barrier before the loop)
   if (K < KP) {  // columns k >= K of a tile are out of range for the DMA and must read as 0
     for (int i = tid; i < 2 * F16X2_RAW_BYTES / 16; i += nthreads) reinterpret_cast<u32x4*>(raw)[i] = u32x4{0, 0, 0, 0};
-    lds_barrier2();
+    lds_barrier();
   }
   // first two tiles on their way before anything else: the weight loads below overlap their latency
   dma_tile(tile, 0);
   dma_tile(tile + stride, 1);
-#ifdef EGC_GEMM_STAMPS
-  unsigned long long t_a, t_b;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_a) :: "memory");
-#endif
   // both planes of this wavefront's 128 x 32 weight block, as B operands of v_mfma_f32_32x32x16_f16:
   // lane -> column cb + l31, k = 16 s + 8 hh .. + 7
 #pragma unroll
@@ -377,14 +295,11 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   asm volatile("" : "+v"(wf[0][0]), "+v"(wf[0][1]), "+v"(wf[1][0]), "+v"(wf[1][1]), "+v"(wf[2][0]), "+v"(wf[2][1]),
                "+v"(wf[3][0]), "+v"(wf[3][1]), "+v"(wf[4][0]), "+v"(wf[4][1]), "+v"(wf[5][0]), "+v"(wf[5][1]),
                "+v"(wf[6][0]), "+v"(wf[6][1]), "+v"(wf[7][0]), "+v"(wf[7][1]), "+v"(col_inv), "+v"(col_bias));
-#ifdef EGC_GEMM_STAMPS
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_b) :: "memory");
-#endif
   stage(0, 0, 0, 0);
   stage(0, 0, 0, 1);
   if (third) stage(0, 0, 0, 2);
   dma_tile(tile + 2 * stride, 0);
-  lds_barrier2();
+  lds_barrier();
   int buf = 0;
   int ri_cur = 0;                 // row_inv slot of the tile being multiplied (tile index mod 3)
   unsigned prev_off = SOOB;       // no previous tile yet: its stores are dropped
@@ -392,14 +307,6 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   const float* prev_ic = icnt;
 #pragma unroll
   for (int r = 0; r < 16; ++r) t[r] = 0.f;
-#ifdef EGC_GEMM_STAMPS
-  unsigned long long tsum[6] = {0, 0, 0, 0, 0, 0}, t0, t1, r0, r1;
-#define EGC_STAMP(k) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1) :: "memory"); tsum[k] += t1 - t0; t0 = t1; }
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r0) :: "memory");
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0) :: "memory");
-#else
-#define EGC_STAMP(k)
-#endif
   // In the loop every wavefront issues, per tile, F16X2_STORES_PER_TILE stores (k-steps 0-3) and then 3
   // (wavefronts 0-7) or 2 (8-11) DMA pieces (k-step 7), always in this order, and the counter retires them in
   // order.  When the pieces of the next tile are read (k-step 4), the operations issued after the DMA of piece
@@ -434,7 +341,6 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
     mfma_step(3, yh, yl);
     epilogue(prev_off, 3, prev_ri, prev_ic);
     EGC_PIN;
-    EGC_STAMP(0)
     // k-steps 4-7: the next tile is split and staged, its ring slot re-armed
     EGC_VMCNT(34);
     if (FM >= 0 && wave == 8) cnt_inverse(tile);   // (this tile's dis arrived with the DMA of three tiles ago)
@@ -453,16 +359,13 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
     mfma_step(7, yh, yl);
     dma_tile(tile + 3 * stride, slot);
     EGC_PIN;
-    EGC_STAMP(1)
 #pragma unroll
     for (int r = 0; r < 16; ++r) t[r] = __builtin_fmaf(acc1[r], 1.f / 2048.f, acc0[r]);
     prev_off = out_offset(tile, true);
     prev_ri = row_inv + ri_cur * ROWS;
     prev_ic = icnt + (tile & (F16X2_CNT_SLOTS - 1)) * ROWS;
     ri_cur = ri_cur == 2 ? 0 : ri_cur + 1;
-    EGC_STAMP(2)
-    lds_barrier2();
-    EGC_STAMP(3)
+    lds_barrier();
     buf ^= 1;
   }
   epilogue(prev_off, 0, prev_ri, prev_ic);
@@ -470,17 +373,6 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   epilogue(prev_off, 2, prev_ri, prev_ic);
   epilogue(prev_off, 3, prev_ri, prev_ic);
   EGC_VMCNT(0);  // no DMA may still be writing this block's LDS when it is handed to the next block
-#ifdef EGC_GEMM_STAMPS
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r1) :: "memory");
-  tsum[5] = r1 - r0;
-  if (lane == 0 && egc_stamp_buf2 != nullptr) {
-    for (int k = 0; k < 6; ++k) egc_stamp_buf2[(blockIdx.x * 16 + wave) * 6 + k] = tsum[k];
-    egc_stamp_buf2[1024 * 16 * 6 + (blockIdx.x * 16 + wave) * 2] = t_entry;
-    egc_stamp_buf2[1024 * 16 * 6 + (blockIdx.x * 16 + wave) * 2 + 1] = r1;
-    egc_stamp_buf2[(blockIdx.x * 16 + wave) * 6 + 4] = r0 - t_entry;
-    egc_stamp_buf2[(blockIdx.x * 16 + wave) * 6 + 3] = ((t_a - t_entry) << 32) | (t_b - t_entry);
-  }
-#endif
 }
 
 size_t f16x2_pack_bytes(int KS, int NV) { return (size_t)KS * 2 * NV * GEMM_KT * sizeof(u16) + (size_t)NV * sizeof(float); }
@@ -523,14 +415,6 @@ static int f16x2_launch_rows(const float* x, const void* packed, const float* bc
   int grid = 256;  // one 12-wavefront block per CU (registers: 3 wavefronts per SIMD)
   if (grid > n_tiles) grid = n_tiles;
   const int rows_per_block = (int)((M + grid - 1) / grid);   // contiguous, equal row ranges
-#ifdef EGC_GEMM_STAMPS
-  static unsigned long long* dbuf = nullptr;
-  if (dbuf == nullptr) {
-    hipMalloc(&dbuf, 1024 * 16 * 8 * 8);
-    hipMemcpyToSymbol(HIP_SYMBOL(egc_stamp_buf2), &dbuf, sizeof(dbuf));
-  }
-  hipMemset(dbuf, 0, 1024 * 16 * 8 * 8);
-#endif
   int st;
   switch (fold_m) {
     case 0: st = f16x2_launch_fm<0>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, dis, fold_s, stream); break;
@@ -540,45 +424,6 @@ static int f16x2_launch_rows(const float* x, const void* packed, const float* bc
     default: st = f16x2_launch_fm<-1>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, nullptr, -1, stream);
   }
   if (st != EGC_OK) return st;
-#ifdef EGC_GEMM_STAMPS
-  {
-    hipDeviceSynchronize();
-    static int calls = 0;
-    if (++calls == 20) {
-      std::vector<unsigned long long> h(1024 * 16 * 8);
-      hipMemcpy(h.data(), dbuf, h.size() * 8, hipMemcpyDeviceToHost);
-      double sum[6] = {0, 0, 0, 0, 0, 0}; int nw = 0;
-      for (int b = 0; b < grid; ++b)
-        for (int w = 0; w < threads / 64; ++w) {
-          for (int k = 0; k < 6; ++k) sum[k] += (double)h[(b * 16 + w) * 6 + k];
-          ++nw;
-        }
-      {
-        unsigned long long lo = ~0ull, hi = 0; int early = 0;
-        for (int b = 0; b < grid; ++b) { unsigned long long e = h[1024 * 16 * 6 + (b * 16) * 2]; if (e && e < lo) lo = e; }
-        for (int b = 0; b < grid; ++b) {
-          unsigned long long e = h[1024 * 16 * 6 + (b * 16) * 2], x = h[1024 * 16 * 6 + (b * 16) * 2 + 1];
-          if (x > hi) hi = x;
-          if (e - lo < 300) ++early;  // entered within 3 us of the first block
-        }
-        double pro = 0, lmin = 1e30, lmax = 0, pa = 0, pb = 0;
-        for (int b = 0; b < grid; ++b) {
-          pro += (double)h[(b * 16) * 6 + 4];
-          pa += (double)(h[(b * 16) * 6 + 3] >> 32); pb += (double)(h[(b * 16) * 6 + 3] & 0xffffffffull);
-          lmin = std::min(lmin, (double)h[(b * 16) * 6 + 5]);
-          lmax = std::max(lmax, (double)h[(b * 16) * 6 + 5]);
-        }
-        fprintf(stderr, "[stamps f16x2] kernel span %.1f us, %d of %d blocks entered within 3 us; prologue avg %.1f us (dma issued %.1f, all landed %.1f); loop min %.1f max %.1f us\n",
-                (hi - lo) * 0.01, early, grid, pro / grid * 0.01, pa / grid * 0.01, pb / grid * 0.01, lmin * 0.01, lmax * 0.01);
-      }
-      const double tpb = (double)n_tiles / grid;
-      const double cyc = sum[0] + sum[1] + sum[2] + sum[3];
-      fprintf(stderr, "[stamps f16x2] per tile per wave (cycles): k0-3+epi %.0f  k4-7+stage %.0f  t-fma %.0f  barrier %.0f  (-) %.0f "
-              "(tiles/block %.1f)  clock %.2f GHz  loop %.1f us\n", sum[0] / nw / tpb, sum[1] / nw / tpb, sum[2] / nw / tpb,
-              sum[3] / nw / tpb, sum[4] / nw / tpb, tpb, cyc / sum[5] * 0.1, sum[5] / nw * 0.01);
-    }
-  }
-#endif
   return EGC_OK;
 }
 

@@ -26,24 +26,13 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <cstdio>
 
 #include "egc_common.h"
 #include "egc_gemm_split.h"
 
 namespace egc {
 
-typedef float f32x4k __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8k __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2k __attribute__((ext_vector_type(2)));
-typedef float f32x2k __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-typedef unsigned int u32x4k __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2k __attribute__((ext_vector_type(2)));
-
 constexpr int KROWS = 16;  // rows of an x tile = one MFMA row block
-
-__device__ inline void lds_barrier_k() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Virtual column space: column tiles of 16; tiles [0, TB) hold the bases columns (ldb of them, the rest of the last
 // tile is padding that is never stored), tiles [TB, NT) the weightings columns.
@@ -70,20 +59,16 @@ __global__ void __launch_bounds__(64) pack_f16x2k_kernel(const float* __restrict
     for (int k = lane; k < K; k += 64) amax = max(amax, __float_as_uint(wcat[k * rs + src * cs]) & 0x7fffffffu);
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, d));
-  unsigned be = amax >> 23;
-  be = be > 253u ? 253u : be;
-  const float scale = __uint_as_float((254u - be) << 23), inv = __uint_as_float(be << 23);
+  const F16x2ColScale col = f16x2_col_scale(amax);
   const int t = v >> 4, i = v & 15;
   for (int k = lane; k < KS * 32; k += 64) {
-    const float w = (src >= 0 && k < K) ? wcat[k * rs + src * cs] * scale : 0.f;
-    const _Float16 h = (_Float16)w;
-    const _Float16 l = (_Float16)((w - (float)h) * 2048.f);
+    const F16x2Bits b = f16x2_pack_split((src >= 0 && k < K) ? wcat[k * rs + src * cs] * col.scale : 0.f);
     const int s = k >> 5, kq = (k >> 3) & 3, e = k & 7;
     const int64_t base = ((((int64_t)t * KS + s) * 2) * 64 + (kq * 16 + i)) * 8 + e;
-    packed[base] = __builtin_bit_cast(u16, h);
-    packed[base + 64 * 8] = __builtin_bit_cast(u16, l);
+    packed[base] = b.h;
+    packed[base + 64 * 8] = b.l;
   }
-  if (lane == 0) reinterpret_cast<float*>(packed + (int64_t)c.NT * KS * 2 * 64 * 8)[v] = inv;
+  if (lane == 0) reinterpret_cast<float*>(packed + (int64_t)c.NT * KS * 2 * 64 * 8)[v] = col.inv;
 }
 
 template <int N>
@@ -106,12 +91,6 @@ __device__ inline void vmwait_rt(int n) {
   }
 }
 
-#ifdef EGC_GEMMK_STAMPS
-__device__ unsigned long long egc_stampk[8];  // diagnostic build only: cycles per phase, summed over wavefronts
-#define KST(k) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); ksum[k] += _t - kt0; kt0 = _t; }
-#else
-#define KST(k)
-#endif
 
 template <int KS, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_kernel(const float* __restrict__ x, const u16* __restrict__ packed,
@@ -133,7 +112,7 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_kernel(const flo
   const int j = lane & 15, quad = lane >> 4;
   const int K4 = K >> 2;                                                 // 16-byte pieces per row
   constexpr unsigned GOOB = 0xFFFFFFF0u;
-  const u32x4k rx = {(unsigned)(uintptr_t)x, (unsigned)((uintptr_t)x >> 32) & 0xffffu, (unsigned)(M * K * 4), 0x00020000u};
+  const u32x4 rx = {(unsigned)(uintptr_t)x, (unsigned)((uintptr_t)x >> 32) & 0xffffu, (unsigned)(M * K * 4), 0x00020000u};
   const unsigned raw_lds = (unsigned)(uintptr_t)raw;
   const unsigned magic_K4 = (unsigned)(((uint64_t)1 << 32) / (uint64_t)K4) + 1u;
 
@@ -160,16 +139,16 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_kernel(const flo
   if (tile >= n_tiles) return;
   for (int r = 0; r < ring; ++r) dma_tile(tile + r * stride, r);    // `ring` tiles of x per CU in flight (two left HBM latency exposed: 3.8 TB/s)
   // zero the planes once: the k range [K, 32 KS) and the row padding are never written again
-  for (int i = tid; i < 4 * KROWS * LDX / 8; i += nthreads) reinterpret_cast<u32x4k*>(xs)[i] = u32x4k{0, 0, 0, 0};
+  for (int i = tid; i < 4 * KROWS * LDX / 8; i += nthreads) reinterpret_cast<u32x4*>(xs)[i] = u32x4{0, 0, 0, 0};
 
   // both planes of this wavefront's F_in x 16 weight block, as A operands
-  f16x8k wf[KS][2];
+  f16x8 wf[KS][2];
   {
     const u16* src = packed + ((int64_t)ct * KS * 2 * 64 + lane) * 8;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      wf[s][0] = *reinterpret_cast<const f16x8k*>(src + (s * 2) * 64 * 8);
-      wf[s][1] = *reinterpret_cast<const f16x8k*>(src + (s * 2 + 1) * 64 * 8);
+      wf[s][0] = *reinterpret_cast<const f16x8*>(src + (s * 2) * 64 * 8);
+      wf[s][1] = *reinterpret_cast<const f16x8*>(src + (s * 2 + 1) * 64 * 8);
     }
   }
   // output addressing: lane (j, quad) holds, per row block, row 16 rb + j and virtual columns 16 ct + 4 quad .. + 3
@@ -192,13 +171,13 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_kernel(const flo
   // the barrier, ahead of the tile's DMA requests, by inline assembly: the compiler, which cannot see the DMAs, would wait for
   // everything)
   const bool add = addend != nullptr && to_bases;    // wave-uniform
-  const u32x4k ra = {(unsigned)(uintptr_t)addend, (unsigned)((uintptr_t)addend >> 32) & 0xffffu, add ? (unsigned)(M * out_ld * 4) : 0u, 0x00020000u};
+  const u32x4 ra = {(unsigned)(uintptr_t)addend, (unsigned)((uintptr_t)addend >> 32) & 0xffffu, add ? (unsigned)(M * out_ld * 4) : 0u, 0x00020000u};
   vmwait_k<0>();
   // the compiler counts only its own loads: let it retire the weight loads HERE
 #pragma unroll
   for (int s = 0; s < KS; ++s) asm volatile("" : "+v"(wf[s][0]), "+v"(wf[s][1]));
   // the first tiles were requested before the weight loads: all have landed by now (vmcnt(0) above)
-  lds_barrier_k();
+  lds_barrier();
 
   const int hw = tid >> 5;                    // half-wavefront index: one row of the tile per half-wavefront and pass
   const int hl = tid & 31;
@@ -215,46 +194,26 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_kernel(const flo
         const int k4 = hl + 32 * i;
         if (k4 < K4) {
           const float4 v = *reinterpret_cast<const float4*>(rs + ((size_t)row * K4 + k4) * 16);
-          float mi;
-          asm("v_max3_f32 %0, |%1|, |%2|, |%3|\n\tv_max_f32 %0, |%4|, %0" : "=&v"(mi) : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-          m = fmaxf(m, mi);
+          m = fmaxf(m, f16x2_abs_max4(v));
         }
       }
-      unsigned a = __float_as_uint(m);
-      a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-      a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-      a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x141, 0xf, 0xf, true));  // row_half_mirror
-      a = max(a, (unsigned)__builtin_amdgcn_update_dpp(0, (int)a, 0x140, 0xf, 0xf, true));  // row_mirror
-      a = max(a, (unsigned)__builtin_amdgcn_ds_swizzle((int)a, 0x401F));                    // lane ^ 16
-      unsigned e = a & 0x7f800000u;
-      e = min(max(e, 13u << 23), 253u << 23);
-      const float sc = __uint_as_float(0x7f000000u - e);                  // 2^-e
-      const float sc2k = __uint_as_float(0x7f000000u + (11u << 23) - e);  // 2^(11-e)
+      const unsigned e = f16x2_row_exp(row_group_umax<32>(__float_as_uint(m)));
+      const F16x2RowScale sc = f16x2_row_scale(e);
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         const int k4 = hl + 32 * i;
         if (k4 < K4) {
           const float4 v = *reinterpret_cast<const float4*>(rs + ((size_t)row * K4 + k4) * 16);   // second read: 12 registers less
-          const f16x2k h01 = __builtin_convertvector(f32x2k{v.x * sc, v.y * sc}, f16x2k);
-          const f16x2k h23 = __builtin_convertvector(f32x2k{v.z * sc, v.w * sc}, f16x2k);
-          f16x2k l01, l23;
-          l01[0] = (_Float16)__builtin_fmaf((float)h01[0], -2048.f, v.x * sc2k);
-          l01[1] = (_Float16)__builtin_fmaf((float)h01[1], -2048.f, v.y * sc2k);
-          l23[0] = (_Float16)__builtin_fmaf((float)h23[0], -2048.f, v.z * sc2k);
-          l23[1] = (_Float16)__builtin_fmaf((float)h23[1], -2048.f, v.w * sc2k);
+          const F16x2Planes p = f16x2_split4(v, sc);
           u16* dst = xp + row * LDX + 4 * k4;
-          *reinterpret_cast<u32x2k*>(dst) = u32x2k{__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23)};
-          *reinterpret_cast<u32x2k*>(dst + KROWS * LDX) = u32x2k{__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23)};
+          *reinterpret_cast<u32x2*>(dst) = p.hi;
+          *reinterpret_cast<u32x2*>(dst + KROWS * LDX) = p.lo;
         }
       }
       if (hl == 0) row_inv[pbuf * KROWS + row] = __uint_as_float(e);  // 2^e
     }
   };
   split(0, 0);
-#ifdef EGC_GEMMK_STAMPS
-  unsigned long long kt0, ksum[6] = {0, 0, 0, 0, 0, 0};
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(kt0) :: "memory");
-#endif
   // One barrier per tile.  At the top of iteration t (tile t of this workgroup): ring slots (t + 1) % ring ... hold or await
   // the raw tiles t + 1 ... t + ring - 1, plane buffer t % 2 the split tile t.  After the barrier the slot t % ring is free
   // (everybody has split tile t) and is re-armed with tile t + ring at once; then the wavefronts split tile t + 1 into the
@@ -265,10 +224,8 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_kernel(const flo
   const int behind = (ring - 2) * (R + (add ? 1 : 0)) + n_stores;
   for (bool first = true; tile < n_tiles; tile += stride, first = false) {
     if (first) vmwait_k<0>(); else vmwait_rt(behind);
-    KST(0)
-    lds_barrier_k();
-    KST(1)
-    f32x4k av;                  // (no initial value: a second definition would be a copy the compiler may place ahead of the wait)
+    lds_barrier();
+    f4 av;                  // (no initial value: a second definition would be a copy the compiler may place ahead of the wait)
     asm volatile("" : "=v"(av));
     if (add) {
       const int64_t arow = (int64_t)tile * KROWS + j;
@@ -277,31 +234,29 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_kernel(const flo
     }
     const int nslot = slot + 1 == ring ? 0 : slot + 1;
     split(nslot, cur ^ 1);
-    KST(3)
     dma_tile(tile + ring * stride, slot);
     slot = nslot;
-    KST(2)
     {
-      f32x4k acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+      f4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
       const u16* xb = xs + cur * 2 * KROWS * LDX + j * LDX + 8 * quad;
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
-        const f16x8k xh = *reinterpret_cast<const f16x8k*>(xb + 32 * s);
-        const f16x8k xl = *reinterpret_cast<const f16x8k*>(xb + KROWS * LDX + 32 * s);
+        const f16x8 xh = *reinterpret_cast<const f16x8*>(xb + 32 * s);
+        const f16x8 xl = *reinterpret_cast<const f16x8*>(xb + KROWS * LDX + 32 * s);
         acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[s][0], xh, acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[s][0], xl, acc1, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[s][1], xh, acc1, 0, 0, 0);
       }
       const float ri = row_inv[cur * KROWS + j];
-      f32x4k cinv, cbias;
+      f4 cinv, cbias;
       {
         const float* ci = colinfo + 2 * (16 * ct + 4 * quad);
-        const f32x4k c01 = *reinterpret_cast<const f32x4k*>(ci), c23 = *reinterpret_cast<const f32x4k*>(ci + 4);
-        cinv = f32x4k{c01[0], c01[2], c23[0], c23[2]};
-        cbias = f32x4k{c01[1], c01[3], c23[1], c23[3]};
+        const f4 c01 = *reinterpret_cast<const f4*>(ci), c23 = *reinterpret_cast<const f4*>(ci + 4);
+        cinv = f4{c01[0], c01[2], c23[0], c23[2]};
+        cbias = f4{c01[1], c01[3], c23[1], c23[3]};
       }
       const int64_t grow = (int64_t)tile * KROWS + j;
-      f32x4k o;
+      f4 o;
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[r] = __builtin_fmaf(__builtin_fmaf(acc1[r], 1.f / 2048.f, acc0[r]), cinv[r] * ri, cbias[r]);
       // Every store instruction is always issued (masked lanes go out of the buffer's range): the counted wait at
@@ -314,21 +269,16 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_kernel(const flo
         o += av;
       }
       if (vec_store) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4k, o), ro, (row_ok && col0 + 3 < lim) ? off : GOOB, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ro, (row_ok && col0 + 3 < lim) ? off : GOOB, 0, 0);
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[r]), ro, (row_ok && col0 + r < lim) ? off + 4u * r : GOOB, 0, 0);
       }
     }
-    KST(5)
     cur ^= 1;
   }
   vmwait_k<0>();  // no DMA may still be writing this block's LDS when it is handed to the next block
-#ifdef EGC_GEMMK_STAMPS
-  if (lane == 0)
-    for (int k = 0; k < 6; ++k) atomicAdd(&egc_stampk[k], ksum[k]);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -368,7 +318,7 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_spec_kernel(cons
   int tile = blockIdx.x;
   if (tile >= n_tiles) return;
   // zero the planes once: the k range [K, 32 KS) and the row padding are never written again
-  for (int i = tid; i < 4 * KROWS * LDX / 8; i += nthreads) reinterpret_cast<u32x4k*>(xs)[i] = u32x4k{0, 0, 0, 0};
+  for (int i = tid; i < 4 * KROWS * LDX / 8; i += nthreads) reinterpret_cast<u32x4*>(xs)[i] = u32x4{0, 0, 0, 0};
   {
     const float* inv_tab = reinterpret_cast<const float*>(packed + (int64_t)c.NT * KS * 2 * 64 * 8);
     for (int v = tid; v < 16 * c.NT; v += nthreads) {
@@ -384,7 +334,7 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_spec_kernel(cons
     const int hthreads = nthreads - nmf * 64;
     const int hwave = wave - nmf;
     constexpr unsigned GOOB = 0xFFFFFFF0u;
-    const u32x4k rx = {(unsigned)(uintptr_t)x, (unsigned)((uintptr_t)x >> 32) & 0xffffu, (unsigned)(M * K * 4), 0x00020000u};
+    const u32x4 rx = {(unsigned)(uintptr_t)x, (unsigned)((uintptr_t)x >> 32) & 0xffffu, (unsigned)(M * K * 4), 0x00020000u};
     const unsigned raw_lds = (unsigned)(uintptr_t)raw;
     const unsigned magic_K4 = (unsigned)(((uint64_t)1 << 32) / (uint64_t)K4) + 1u;
     // this thread's (up to 16) pieces of a tile: byte offset inside the tile, or out of range -- computed once (per tile and
@@ -442,45 +392,25 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_spec_kernel(cons
         float m = 0.f;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          float mi;
-          asm("v_max3_f32 %0, |%1|, |%2|, |%3|\n\tv_max_f32 %0, |%4|, %0" : "=&v"(mi) : "v"(v[r][i].x), "v"(v[r][i].y), "v"(v[r][i].z), "v"(v[r][i].w));
-          m = fmaxf(m, mi);
+          m = fmaxf(m, f16x2_abs_max4(v[r][i]));
         }
         a[r] = __float_as_uint(m);
       }
-#pragma unroll
-      for (int r = 0; r < RPH; ++r) a[r] = max(a[r], (unsigned)__builtin_amdgcn_update_dpp(0, (int)a[r], 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-#pragma unroll
-      for (int r = 0; r < RPH; ++r) a[r] = max(a[r], (unsigned)__builtin_amdgcn_update_dpp(0, (int)a[r], 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-#pragma unroll
-      for (int r = 0; r < RPH; ++r) a[r] = max(a[r], (unsigned)__builtin_amdgcn_update_dpp(0, (int)a[r], 0x141, 0xf, 0xf, true));  // row_half_mirror
-#pragma unroll
-      for (int r = 0; r < RPH; ++r) a[r] = max(a[r], (unsigned)__builtin_amdgcn_update_dpp(0, (int)a[r], 0x140, 0xf, 0xf, true));  // row_mirror
-#pragma unroll
-      for (int r = 0; r < RPH; ++r) a[r] = max(a[r], (unsigned)__builtin_amdgcn_ds_swizzle((int)a[r], 0x401F));                    // lane ^ 16
+      row_group_umax<32>(a);
 #pragma unroll
       for (int r = 0; r < RPH; ++r) {
         const int row = hw + r * n_hw;
         if (row < KROWS) {     // uniform in the half-wavefront
-          unsigned e = a[r] & 0x7f800000u;
-          e = min(max(e, 13u << 23), 253u << 23);
-          const float sc = __uint_as_float(0x7f000000u - e);                  // 2^-e
-          const float sc2k = __uint_as_float(0x7f000000u + (11u << 23) - e);  // 2^(11-e)
+          const unsigned e = f16x2_row_exp(a[r]);
+          const F16x2RowScale sc = f16x2_row_scale(e);
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
             const int k4 = hl + 32 * i;
             if (k4 < K4) {
-              const float4 w = v[r][i];
-              const f16x2k h01 = __builtin_convertvector(f32x2k{w.x * sc, w.y * sc}, f16x2k);
-              const f16x2k h23 = __builtin_convertvector(f32x2k{w.z * sc, w.w * sc}, f16x2k);
-              f16x2k l01, l23;
-              l01[0] = (_Float16)__builtin_fmaf((float)h01[0], -2048.f, w.x * sc2k);
-              l01[1] = (_Float16)__builtin_fmaf((float)h01[1], -2048.f, w.y * sc2k);
-              l23[0] = (_Float16)__builtin_fmaf((float)h23[0], -2048.f, w.z * sc2k);
-              l23[1] = (_Float16)__builtin_fmaf((float)h23[1], -2048.f, w.w * sc2k);
+              const F16x2Planes p = f16x2_split4(v[r][i], sc);
               u16* dst = xp + row * LDX + 4 * k4;
-              *reinterpret_cast<u32x2k*>(dst) = u32x2k{__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23)};
-              *reinterpret_cast<u32x2k*>(dst + KROWS * LDX) = u32x2k{__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23)};
+              *reinterpret_cast<u32x2*>(dst) = p.hi;
+              *reinterpret_cast<u32x2*>(dst + KROWS * LDX) = p.lo;
             }
           }
           if (hl == 0) row_inv[pbuf * KROWS + row] = __uint_as_float(e);  // 2^e
@@ -489,33 +419,22 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_spec_kernel(cons
     };
     for (int r = 0; r < ring; ++r) dma_tile(tile + r * stride, r);
     vmwait_k<0>();
-    lds_barrier_k();           // every helper's pieces of the first tiles have landed; the planes are zeroed, colinfo written
+    lds_barrier();           // every helper's pieces of the first tiles have landed; the planes are zeroed, colinfo written
     split(0, 0);
     // At the top of iteration t: this wavefront's pieces of tile t + 1 must have landed; behind them in the (in-order)
     // counter are only the pieces of tiles t + 2 ... t + ring - 1.
     int cur = 0, slot = 0;
     const int behind = (ring - 2) * R;
-#ifdef EGC_GEMMK_STAMPS
-    unsigned long long kt0, ksum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(kt0) :: "memory");
-#endif
     for (; tile < n_tiles; tile += stride) {
       vmwait_rt(behind);
-      KST(0)
-      lds_barrier_k();         // tile t split (all helpers), tile t + 1 landed, the workers done with plane buffer cur ^ 1
-      KST(1)
+      lds_barrier();         // tile t split (all helpers), tile t + 1 landed, the workers done with plane buffer cur ^ 1
       const int nslot = slot + 1 == ring ? 0 : slot + 1;
       split(nslot, cur ^ 1);
-      KST(2)
       dma_tile(tile + ring * stride, slot);     // (slot held tile t: split in the previous iteration, before this barrier)
-      KST(3)
       slot = nslot;
       cur ^= 1;
     }
     vmwait_k<0>();  // no DMA may still be writing this block's LDS when it is handed to the next block
-#ifdef EGC_GEMMK_STAMPS
-    if (tid == nmf * 64) for (int k = 0; k < 4; ++k) atomicAdd(&egc_stampk[k], ksum[k]);
-#endif
     return;
   }
 
@@ -529,14 +448,14 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_spec_kernel(cons
     live[u] = wave * TPW + u < ntl;                                    // (an odd tile count leaves the last wavefront's second tile idle:
     ct[u] = tile0 + (live[u] ? wave * TPW + u : wave * TPW);           //  it repeats its first tile and stores nothing)
   }
-  f16x8k wf[TPW][KS][2];
+  f16x8 wf[TPW][KS][2];
 #pragma unroll
   for (int u = 0; u < TPW; ++u) {
     const u16* src = packed + ((int64_t)ct[u] * KS * 2 * 64 + lane) * 8;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      wf[u][s][0] = *reinterpret_cast<const f16x8k*>(src + (s * 2) * 64 * 8);
-      wf[u][s][1] = *reinterpret_cast<const f16x8k*>(src + (s * 2 + 1) * 64 * 8);
+      wf[u][s][0] = *reinterpret_cast<const f16x8*>(src + (s * 2) * 64 * 8);
+      wf[u][s][1] = *reinterpret_cast<const f16x8*>(src + (s * 2 + 1) * 64 * 8);
     }
   }
   bool to_bases[TPW], vec_store[TPW], add[TPW];
@@ -560,24 +479,17 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_spec_kernel(cons
   for (int u = 0; u < TPW; ++u)
 #pragma unroll
     for (int s = 0; s < KS; ++s) asm volatile("" : "+v"(wf[u][s][0]), "+v"(wf[u][s][1]));
-  lds_barrier_k();
+  lds_barrier();
   int cur = 0;
-#ifdef EGC_GEMMK_STAMPS
-  unsigned long long kt0, ksum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rt0, rt1, ct0;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(kt0) :: "memory");
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt0) :: "memory");
-  ct0 = kt0;
-#endif
   for (; tile < n_tiles; tile += stride) {
-    lds_barrier_k();
-    KST(4)
-    f32x4k av[TPW], acc0[TPW], acc1[TPW];
+    lds_barrier();
+    f4 av[TPW], acc0[TPW], acc1[TPW];
 #pragma unroll
     for (int u = 0; u < TPW; ++u) {
-      av[u] = acc0[u] = acc1[u] = f32x4k{0.f, 0.f, 0.f, 0.f};
+      av[u] = acc0[u] = acc1[u] = f4{0.f, 0.f, 0.f, 0.f};
       if (add[u]) {
         const int64_t arow = (int64_t)tile * KROWS + j;
-        av[u] = __builtin_bit_cast(f32x4k, __builtin_amdgcn_raw_buffer_load_b128(
+        av[u] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(
                                                ra[u], (arow < M && col0[u] + 3 < lim[u]) ? (unsigned)((arow * out_ld[u] + col0[u]) * 4) : GOOB, 0, 0));
       }
     }
@@ -587,18 +499,18 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_spec_kernel(cons
     // (two tiles: six products per operand pair, and the registers are the weights'; K > 320 at sixteen wavefronts: the third set
     // was paid for in spilled weight registers -- 12 / 20 at KS = 11 / 12 --, 570 -> 540 us at the ogbn-mag shape without it)
     constexpr int PF = (TPW == 1 && KS <= 10) ? 3 : 2;
-    f16x8k xh[PF], xl[PF];
+    f16x8 xh[PF], xl[PF];
 #pragma unroll
     for (int p = 0; p < PF - 1; ++p)
       if (p < KS) {
-        xh[p] = *reinterpret_cast<const f16x8k*>(xb + 32 * p);
-        xl[p] = *reinterpret_cast<const f16x8k*>(xb + KROWS * LDX + 32 * p);
+        xh[p] = *reinterpret_cast<const f16x8*>(xb + 32 * p);
+        xl[p] = *reinterpret_cast<const f16x8*>(xb + KROWS * LDX + 32 * p);
       }
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       if (s + PF - 1 < KS) {
-        xh[(s + PF - 1) % PF] = *reinterpret_cast<const f16x8k*>(xb + 32 * (s + PF - 1));
-        xl[(s + PF - 1) % PF] = *reinterpret_cast<const f16x8k*>(xb + KROWS * LDX + 32 * (s + PF - 1));
+        xh[(s + PF - 1) % PF] = *reinterpret_cast<const f16x8*>(xb + 32 * (s + PF - 1));
+        xl[(s + PF - 1) % PF] = *reinterpret_cast<const f16x8*>(xb + KROWS * LDX + 32 * (s + PF - 1));
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -609,42 +521,33 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_spec_kernel(cons
       for (int u = 0; u < TPW; ++u) acc1[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][s][1], xh[s % PF], acc1[u], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    KST(5)
     const float ri = row_inv[cur * KROWS + j];
     const int64_t grow = (int64_t)tile * KROWS + j;
     const bool row_ok = grow < M;
 #pragma unroll
     for (int u = 0; u < TPW; ++u) {
-      f32x4k cinv, cbias;
+      f4 cinv, cbias;
       {
         const float* ci = colinfo + 2 * (16 * ct[u] + 4 * quad);
-        const f32x4k c01 = *reinterpret_cast<const f32x4k*>(ci), c23 = *reinterpret_cast<const f32x4k*>(ci + 4);
-        cinv = f32x4k{c01[0], c01[2], c23[0], c23[2]};
-        cbias = f32x4k{c01[1], c01[3], c23[1], c23[3]};
+        const f4 c01 = *reinterpret_cast<const f4*>(ci), c23 = *reinterpret_cast<const f4*>(ci + 4);
+        cinv = f4{c01[0], c01[2], c23[0], c23[2]};
+        cbias = f4{c01[1], c01[3], c23[1], c23[3]};
       }
-      f32x4k o;
+      f4 o;
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[r] = __builtin_fmaf(__builtin_fmaf(acc1[u][r], 1.f / 2048.f, acc0[u][r]), cinv[r] * ri, cbias[r]);
       const unsigned off = (unsigned)((grow * out_ld[u] + col0[u]) * 4);
       if (add[u]) o += av[u];
       if (vec_store[u]) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4k, o), ro[u], (row_ok && col0[u] + 3 < lim[u]) ? off : GOOB, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ro[u], (row_ok && col0[u] + 3 < lim[u]) ? off : GOOB, 0, 0);
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[r]), ro[u], (row_ok && col0[u] + r < lim[u]) ? off + 4u * r : GOOB, 0, 0);
       }
     }
-    KST(6)
     cur ^= 1;
   }
-#ifdef EGC_GEMMK_STAMPS
-  if (tid == 0) for (int k = 4; k < 7; ++k) atomicAdd(&egc_stampk[k], ksum[k]);
-  if (tid == 0 && blockIdx.x == 0) {
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt1) :: "memory");
-    egc_stampk[7] = ((kt0 - ct0) << 24) | ((rt1 - rt0) & 0xffffff);     // loop cycles | 100 MHz ticks of block 0
-  }
-#endif
 }
 
 bool f16x2k_shape(int f_in, int f_g, int ldb, int w_cols) {
@@ -720,7 +623,7 @@ static int launch_k(const float* x, const u16* packed, const float* bcat, int64_
       static bool attr_set = false;
       if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2k spec)", e); return EGC_ERR_HIP; }
+        if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2 spec)", e); return EGC_ERR_HIP; }
         attr_set = true;
       }
       int grid = 256;
@@ -728,21 +631,6 @@ static int launch_k(const float* x, const u16* packed, const float* bcat, int64_
       kern<<<grid, (ntl + nh) * 64, lds, stream>>>(x, packed, bcat, M, K, c, bases, weightings, n_tiles, LDX, R, slot_bytes, tile0, ring,
                                                    ntl, addend, ntl);
       EGC_LAUNCH_CHECK("basis_gemm_f16x2k_spec_kernel");
-#ifdef EGC_GEMMK_STAMPS
-      {
-        static int calls = 0;
-        if (++calls == 10) {
-          hipDeviceSynchronize();
-          unsigned long long h[8];
-          hipMemcpyFromSymbol(h, HIP_SYMBOL(egc_stampk), sizeof(h));
-          const double per = (double)calls * n_tiles;   // one helper wavefront and one multiplier per workgroup report
-          fprintf(stderr, "[gemmk spec stamps] K=%d ntl=%d nh=%d R=%d ring=%d per tile (cycles): helper: dma-wait %.0f barrier %.0f split %.0f dma-issue %.0f | multiplier: barrier %.0f products %.0f scale+store %.0f\n",
-                  K, ntl, nh, R, ring, h[0] / per, h[1] / per, h[2] / per, h[3] / per, h[4] / per, h[5] / per, h[6] / per);
-          fprintf(stderr, "[gemmk spec stamps] block 0 loop: %llu shader cycles in %.1f us (s_memrealtime) => %.2f GHz\n", h[7] >> 24, (h[7] & 0xffffff) * 0.01,
-                  (double)(h[7] >> 24) / ((h[7] & 0xffffff) * 10.0));
-        }
-      }
-#endif
       return EGC_OK;
     }
   }
@@ -755,7 +643,7 @@ static int launch_k(const float* x, const u16* packed, const float* bcat, int64_
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2k)", e); return EGC_ERR_HIP; }
+    if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2)", e); return EGC_ERR_HIP; }
     attr_set = true;
   }
   // workgroups per CU: as many as the LDS holds, within about five wavefronts per SIMD (the KS <= 9 kernels use up to
@@ -804,7 +692,7 @@ static int launch_k2(const float* x, const u16* packed, const float* bcat, int64
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2k spec, two tiles)", e); return EGC_ERR_HIP; }
+    if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2 spec, two tiles)", e); return EGC_ERR_HIP; }
     attr_set = true;
   }
   int grid = 256;

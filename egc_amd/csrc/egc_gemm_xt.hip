@@ -33,13 +33,6 @@
 namespace egc {
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt: the global loads that are meant
-// to stay in flight across two tiles would be waited for at every barrier (measured: tile period = compute + HBM
-// latency instead of their maximum).
-__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 constexpr int XT_WM = 2;  // wavefronts along the output rows (F) of a block tile
 
 constexpr int xt_pitch(int cols) { return cols + ((cols % 64) == 0 ? 16 : 48); }  // pitch % 64 == 16: the 4 k-rows of a fragment hit 64 distinct banks
@@ -212,15 +205,12 @@ __global__ void __launch_bounds__(64 * XT_WM * WN) xt_gemm_kernel(const float* _
 // tile behind its own barrier; once per tile inside the MFMA interval (this one) -- all land within 3 us of each
 // other: per 16 rows a CU moves ~180 KB through LDS (stage write, transposing read, plane write, and 96 KB of fragment
 // reads because every B fragment is read by four wavefronts), which is what the three have in common.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 struct Planes3 { bf16x8 h, m, l; };
 
 // eight fp32 values -> three bf16x8 planes (element j of a plane <- v[j]; truncation splits: every step exact)
 __device__ inline Planes3 split3(const float (&v)[8]) {
-  u32x4v ph, pm, pl;
+  u32x4 ph, pm, pl;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const unsigned a0 = __float_as_uint(v[2 * i]), a1 = __float_as_uint(v[2 * i + 1]);
@@ -318,9 +308,6 @@ __global__ void __launch_bounds__(X3_THREADS) xt_gemm_bf16x3_kernel(const float*
     }
   };
   auto put = [&](int sb, const Regs& st) {
-#ifdef EGC_XT_NO_PUT
-    { float sink = st.x.x + st.d[0].x + st.d[LD - 1].x; asm volatile("" :: "v"(sink)); return; }
-#endif
     float* base = stage + sb * X3_STAGE_FLOATS;
     if (has_e) esum += st.e;
     *reinterpret_cast<f4*>(base + lds_x) = st.x;
@@ -333,9 +320,6 @@ __global__ void __launch_bounds__(X3_THREADS) xt_gemm_bf16x3_kernel(const float*
   const int cs_col = wave * 24 + (lane % 24), cs_part = lane / 24;   // lanes 48..63 idle
   float colsum = 0.f;
   auto split = [&](int sb) {   // fp32 stage sb -> planes sb (both indexed by the sub-tile's parity)
-#ifdef EGC_XT_NO_SPLIT
-    return;
-#endif
     const float* src = stage + sb * X3_STAGE_FLOATS;
     unsigned short* pl = planes + sb * 3 * X3_PLANE_HALVES;
     if (sums && cs_part < 2) {
@@ -367,9 +351,6 @@ __global__ void __launch_bounds__(X3_THREADS) xt_gemm_bf16x3_kernel(const float*
     for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
   const int a_row = wm * 32 + c32, b_row = X3_TM + wn * 96 + c32;   // "rows" of the transposed planes = tile columns
   auto multiply = [&](int sb) {
-#ifdef EGC_XT_NO_MFMA
-    return;
-#endif
     const unsigned short* base = planes + sb * 3 * X3_PLANE_HALVES + 8 * g;
     Planes3 a, b[3];
     a.h = *reinterpret_cast<const bf16x8*>(base + a_row * X3_RP);
@@ -414,13 +395,7 @@ __global__ void __launch_bounds__(X3_THREADS) xt_gemm_bf16x3_kernel(const float*
   // The two wavefronts of a SIMD (w and w + 4) take the interval's two halves in OPPOSITE order: a wavefront is held at the
   // issue of its own MFMAs while they run, so in lock step both multiplied (sharing the one matrix pipe) and then both split
   // (sharing the vector pipe) -- the SIMD's two pipes one after the other instead of side by side.
-#ifdef EGC_XT_LOCKSTEP
-  const bool split_first = false;
-#elif defined(EGC_XT_STAGGER_BIT)
-  const bool split_first = ((wave >> EGC_XT_STAGGER_BIT) & 1) != 0;
-#else
   const bool split_first = wave >= 4;
-#endif
 #define X3_INTERVAL(S, SET)                      \
   {                                              \
     if (split_first) {                           \

@@ -17,7 +17,6 @@
 namespace egc {
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 __device__ inline d4 to_d4(f4 v) { return d4{(double)v.x, (double)v.y, (double)v.z, (double)v.w}; }
@@ -143,9 +142,7 @@ __global__ void __launch_bounds__(256) column_moments_kernel(const float* __rest
     __syncthreads();
     if (!last_block) return;
     if (threadIdx.x == 0) __hip_atomic_store(fin.sync, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifndef EGC_BN_NO_ACQ
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
     const double nr = fmax((double)n_rows, 1.0);
     // One thread per column; at most 64 partial blocks (host), added in the finalize kernels' order -- eight runs of eight
     // partials, then the eight run totals: the same bits as the two-launch form.  All loads of a column are independent.

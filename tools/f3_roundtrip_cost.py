@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """What the `weightings` round trip costs at config 2 (SURVEY.md 8f rank 3 on full graphs).
 
-Run once per library (EGC_HIP_LIB selects a diagnostic build, tools/build_variant.sh):
+Run once per library (EGC_HIP_LIB selects a diagnostic build, tools/build_variant.sh; the three -D builds below exist in the
+sources up to efb9f12 and are rebuilt there):
   default                          GEMM (bases + weightings) and the aggregate launch as shipped
   -DEGC_DIAG_GEMM_NO_W_STORE       the GEMM with the weightings' stores dropped         -> what the 86.7 MB write costs
   -DEGC_DIAG_GEMM_NO_W             the GEMM computing and writing `bases` only          -> the most a fused form's GEMM can save

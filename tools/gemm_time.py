@@ -1,6 +1,7 @@
 """Times the basis-transform GEMM alone (egc_basis_transform_packed) with HIP events: config-2 and config-3 row counts
 at the north-star width (F_in 128 -> 64 bases + 128 weightings), the ogbn-mag shape with --mag.  EGC_HIP_LIB selects
-an experiment build (tools/build_variant.sh); a build with -DEGC_GEMM_STAMPS prints its stamps to stderr."""
+an experiment build (tools/build_variant.sh); a build with -DEGC_GEMM_STAMPS (sources up to efb9f12) prints its stamps to
+stderr."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
