@@ -311,6 +311,23 @@ static void save_static(AutogradContext* ctx, const BlockStatic& s);
 static BlockStatic load_static(AutogradContext* ctx);
 
 
+// The operand shapes of a block node, checked before anything is launched: the tail reads gamma / beta / the running
+// statistics as [f_out] vectors and adds x as an [n, f_out] residual, so a module whose widths do not match would be
+// read out of bounds on the device (the Python route raises torch's shape error in the same place).
+static void check_block_operands(const at::Tensor& x, int64_t layer, const c10::optional<at::Tensor>& gamma,
+                                 const c10::optional<at::Tensor>& beta, const c10::optional<at::Tensor>& running_mean,
+                                 const c10::optional<at::Tensor>& running_var, bool residual, bool with_tail) {
+  TORCH_CHECK(layer != 0, "egc_amd: no layer");
+  const auto* l = reinterpret_cast<const egc_layer*>(layer);
+  const int64_t f_in = l->in_channels, f_out = l->out_channels;
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == f_in, "egc_amd: x must be [n, ", f_in, "], got ", x.sizes());
+  if (!with_tail) return;
+  TORCH_CHECK(!residual || f_in == f_out, "egc_amd: a residual block needs in_channels == out_channels, got ", f_in, " and ", f_out);
+  for (const auto* t : {&gamma, &beta, &running_mean, &running_var})
+    TORCH_CHECK(!t->has_value() || (*t)->numel() == f_out, "egc_amd: the BatchNorm's parameters and buffers must hold ", f_out,
+                " elements, got ", (*t)->numel());
+}
+
 static const int64_t* iptr(const at::Tensor& t) { return t.defined() ? t.data_ptr<int64_t>() : nullptr; }
 
 struct BatchBlockTrainFn : public torch::autograd::Function<BatchBlockTrainFn> {
@@ -616,6 +633,7 @@ at::Tensor csr_block_train(const at::Tensor& x, const c10::optional<at::Tensor>&
                            int64_t gemm_flags, double eps, double momentum, bool relu, bool residual, bool with_tail) {
   TORCH_CHECK(dims.size() == 5, "egc_amd: dims = (H, A, B, L, Ls)");
   TORCH_CHECK(parts.size() >= 1, "egc_amd: at least one basis matrix");
+  check_block_operands(x, layer, gamma, beta, running_mean, running_var, residual, with_tail);
   CsrStatic s;
   s.g = *reinterpret_cast<const egc_graph*>(graph);
   s.tg = *reinterpret_cast<const egc_graph*>(t_graph);
@@ -650,6 +668,7 @@ at::Tensor batch_block_train(const at::Tensor& x, const c10::optional<at::Tensor
   i64(ptr, "ptr"); i64(src, "edge_index[0]"); i64(dst, "edge_index[1]");
   TORCH_CHECK(src.numel() == dst.numel() && ptr.numel() >= 1, "egc_amd: malformed batch");
   TORCH_CHECK(status.is_cuda() && status.scalar_type() == at::kInt, "egc_amd: status word");
+  check_block_operands(x, layer, gamma, beta, running_mean, running_var, residual, with_tail);
   BlockStatic s;
   s.ptr = ptr; s.src = src; s.dst = dst; s.status = status;
   if (edge_ptr.has_value()) { i64(*edge_ptr, "edge_ptr"); TORCH_CHECK(edge_ptr->numel() == ptr.numel(), "egc_amd: edge_ptr"); s.edge_ptr = *edge_ptr; }

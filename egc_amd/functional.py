@@ -689,6 +689,13 @@ def _native_train_ops(graph, spec, x, bias, comb_w, comb_b, bcat_direct, bases):
     return nat
 
 
+def _tail_shapes_fit(spec, bn, residual):
+    """The block's tail reads bn.weight / bn.bias as [f_out] and adds x as an [N, f_out] residual: a module of other widths is
+    declined (the Python route then raises torch's own shape error, as the unfused composition does)."""
+    return ((not residual or spec.f_in == spec.f_out) and bn.weight is not None and bn.weight.numel() == spec.f_out
+            and bn.bias is not None and bn.bias.numel() == spec.f_out)
+
+
 def native_block_train(call, bn=None, relu=True, residual=True, with_tail=True):
     """The training call of a layer on a GraphBatch -- with ``with_tail`` the whole block x -> x + relu(bn(conv(x))) of the
     reference's batched nets (zinc/models.py:66-73) -- as ONE autograd node of the compiled binding (egc_torch_ext.cpp:
@@ -719,7 +726,7 @@ def native_block_train(call, bn=None, relu=True, residual=True, with_tail=True):
     gamma = beta = rm = rv = nt = None
     eps, momentum = 1e-5, 0.1
     if with_tail:
-        if not (relu and bn.training and bn.affine and spec.f_out % 4 == 0):
+        if not (relu and bn.training and bn.affine and spec.f_out % 4 == 0) or not _tail_shapes_fit(spec, bn, residual):
             return None
         gamma, beta, eps = bn.weight, bn.bias, float(bn.eps)
         if any(not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in (gamma, beta)):
@@ -766,7 +773,7 @@ def native_csr_block_train(call, bn, relu=True, residual=True):
     cb = comb_b if comb_b is not None else bcat_direct
     if any(not t.requires_grad for t in (bias, comb_w, cb, *bases)):
         return None
-    if not (relu and bn.training and bn.affine and spec.f_out % 4 == 0 and spec.f_out <= 1024):
+    if not (relu and bn.training and bn.affine and spec.f_out % 4 == 0 and spec.f_out <= 1024) or not _tail_shapes_fit(spec, bn, residual):
         return None
     gamma, beta = bn.weight, bn.bias
     if any(not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in (gamma, beta)):

@@ -6,6 +6,7 @@ arxiv/configs.py:52-57).  Run in float64 it is the gradient oracle for the HIP b
 (tests/test_backward_gpu.py).  Max/min gradients go to the FIRST entry (edge order; an appended self loop
 is last) that attains the extremum -- torch_scatter's CPU arg rule (scatter_max/segment_csr update only on
 a strict improvement), which the reference's layers inherit (layers.py:208-219, optimized_layers.py:215-244).
+Runs on the device of its inputs (the graph preparation stays in numpy).
 Parity status: unpinned by reference tests (see oracle/egc_oracle.py header).  Never imported by egc_amd.
 """
 from __future__ import annotations
@@ -17,12 +18,13 @@ from . import egc_oracle as orc
 
 
 def _scatter(src, index, n, reduce):
-    f = src.size(1)
+    f, dev = src.size(1), src.device
+    index = index.to(dev)
     if reduce == "sum":
-        return torch.zeros(n, f, dtype=src.dtype).index_add(0, index, src)
+        return torch.zeros(n, f, dtype=src.dtype, device=dev).index_add(0, index, src)
     if reduce == "mean":
-        out = torch.zeros(n, f, dtype=src.dtype).index_add(0, index, src)
-        cnt = torch.zeros(n, dtype=src.dtype).index_add(0, index, torch.ones(index.numel(), dtype=src.dtype))
+        out = torch.zeros(n, f, dtype=src.dtype, device=dev).index_add(0, index, src)
+        cnt = torch.zeros(n, dtype=src.dtype, device=dev).index_add(0, index, torch.ones(index.numel(), dtype=src.dtype, device=dev))
         return out / cnt.clamp(min=1).view(-1, 1)
     red = "amax" if reduce == "max" else "amin"
     idx = index.view(-1, 1).expand(-1, f)
@@ -31,13 +33,13 @@ def _scatter(src, index, n, reduce):
         # sources with identical features can differ in the last bit of x @ W (the BLAS blocks rows differently),
         # which would break an exact tie at random instead of by edge order.
         s32 = src.float()
-        ext = torch.zeros(n, f, dtype=s32.dtype).scatter_reduce(0, idx, s32, red, include_self=False)
+        ext = torch.zeros(n, f, dtype=s32.dtype, device=dev).scatter_reduce(0, idx, s32, red, include_self=False)
         e = src.size(0)
-        pos = torch.arange(e).view(-1, 1).expand(-1, f)
+        pos = torch.arange(e, device=dev).view(-1, 1).expand(-1, f)
         pos = torch.where(s32 == ext[index], pos, torch.full_like(pos, e))
-        first = torch.full((n, f), e, dtype=torch.int64).scatter_reduce(0, idx, pos, "amin", include_self=True)
+        first = torch.full((n, f), e, dtype=torch.int64, device=dev).scatter_reduce(0, idx, pos, "amin", include_self=True)
         empty = first >= e
-    picked = torch.gather(src, 0, first.clamp(max=max(e - 1, 0))) if e > 0 else torch.zeros(n, f, dtype=src.dtype)
+    picked = torch.gather(src, 0, first.clamp(max=max(e - 1, 0))) if e > 0 else torch.zeros(n, f, dtype=src.dtype, device=dev)
     return torch.where(empty, torch.zeros_like(picked), picked)
 
 
@@ -57,8 +59,8 @@ def egconv_forward(x, edge_index, bases_weight, comb_w, comb_b, bias, H, B, aggr
     """EGConv.forward (optimized_layers.py:124-210), differentiable."""
     n = x.size(0)
     ei, sw = orc.egconv_edge_set(np.asarray(edge_index), n, list(aggrs), add_self_loops)
-    ei = torch.from_numpy(ei)
-    sw = None if sw is None else torch.from_numpy(sw).to(x.dtype)
+    ei = torch.from_numpy(ei).to(x.device)
+    sw = None if sw is None else torch.from_numpy(sw).to(device=x.device, dtype=x.dtype)
     bases = x @ bases_weight
     w = x @ comb_w.t() + comb_b
     if sigmoid:
