@@ -3,7 +3,11 @@
 config 2: N = 169,343, ~2.33 M symmetrised edges + N self loops, d = 128, H = 8, B = 4,
 aggregators sum+mean+max+symnorm, fp32).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+On one GPU a plain run does only what the headline needs: it sets up (untimed steps that bring the chip to steady clocks
+included), warms up, times the K steps and prints the line (with ``roofline`` and ``cpu_baseline`` null).  ``--full`` measures everything else besides it, as listed below; on
+several GPUs or with ``--workload`` the run is the same with or without it.
 
 With ``--dump-outputs DIR`` (one GPU, the default workload) the layer output of the last timed step is written to DIR
 as ``.npy`` files: a fixed, seeded sample of its rows (the full output is 87 MB) and the indices of those rows.  The
@@ -16,7 +20,11 @@ and the line is STRONG scaling of the same config-2 graph, vertex-partitioned ov
 the curve is this file's N = 1 line), with BASELINE config 5 -- the homogeneous ogbn-mag shape and the ~21 M-edge
 typed graph through a partitioned REGConv -- nested under ``strong_scaling`` (bench_multi.py).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line with ``--full`` (one GPU, the default workload):
+  kernels_ms    -- HIP-event times of the basis GEMM (default, exact fp32 and 24-bit forms), the aggregate launch and the
+                   layer, taken before the warm-up (``layer_frac``, ``layer_frac_by_gemm`` follow from them).
+  ms_per_step_median_of_5_regions -- the timed region and four more of its length run after it.
+  std_layer     -- the same layer with `mean` replaced by `std`.
   roofline      -- the dominant kernel (fused aggregate+combine launch): SURVEY.md 8(d) algorithmic bytes of
                    that launch (gather + col + rowptr + deg + out; `weightings` are NOT algorithmic) / its
                    HIP-event time, against the 8 TB/s HBM peak.
@@ -771,8 +779,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU, default workload: also time the kernels one by one (roofline), four more headline regions, "
+                         "the std layer, the other configs and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: leave out the other configs")
     ap.add_argument("--workload", default=None, choices=[None, "all", "arxiv", "mag", "arxiv-weak", "rmag"],
                     help="default: arxiv (config 2) on one GPU; on several GPUs `all` = config 2 strong scaling as the "
                          "headline with config 5 (homogeneous mag, typed rmag through a partitioned REGConv) nested; "
@@ -846,10 +857,6 @@ def main():
                                              spec.w_cols, bases.data_ptr(), ldb, weightings.data_ptr(), stream),
                  "egc_basis_transform_f32")
 
-    nb24 = lib.egc_basis_pack_bytes(F_IN, spec.f_g, spec.w_cols)
-    planes24 = torch.empty(nb24, dtype=torch.uint8, device=dev)
-    _C.check(lib.egc_basis_pack_ex(wcat.data_ptr(), F_IN, spec.f_g, spec.w_cols, 1, planes24.data_ptr(), nb24, stream), "egc_basis_pack_ex")
-
     def gemm_24bit_only():   # the 24-bit-operand form (EGC_GEMM_24BIT: three bf16 planes per operand), for the side field
         _C.check(lib.egc_basis_transform_packed_ex(x.data_ptr(), planes24.data_ptr(), bcat.data_ptr(), n, F_IN, spec.f_g, spec.w_cols, 1,
                                                    bases.data_ptr(), ldb, weightings.data_ptr(), stream), "egc_basis_transform_packed_ex")
@@ -868,18 +875,28 @@ def main():
     def sync_all():
         torch.cuda.synchronize(dev)
 
-    # ---- per-kernel HIP-event timing on the launch stream.  Done BEFORE the contract's warm-up + timed region,
-    # so that region runs at the clocks the chip holds in steady state rather than during the first
-    # milliseconds after idle (the whole region is ~30 ms at the default step count).
     for _ in range(100):  # untimed: bring the chip out of idle clocks before anything is measured
         step()
     reps = max(50, min(args.steps, 200))
-    agg_ms = time_region(agg_only, reps)
-    gemm_ms = time_region(gemm_only, reps)
-    gemm_exact_ms = time_region(gemm_exact_only, 20)
-    gemm_24bit_ms = time_region(gemm_24bit_only, 20)
-    gemm_only()  # leave the split-precision intermediates in place
-    step_ms_events = time_region(step, reps)
+    if not args.full:
+        # untimed: as long on the chip as --full's per-kernel timing below (2 x reps layer forwards of work), so that the headline
+        # is measured from the same clocks either way (without it, a plain run's ms_per_step came out 0.7-0.8% higher)
+        for _ in range(2 * reps):
+            step()
+    else:
+        # ---- per-kernel HIP-event timing on the launch stream.  Done BEFORE the contract's warm-up + timed region,
+        # so that region runs at the clocks the chip holds in steady state rather than during the first
+        # milliseconds after idle (the whole region is ~30 ms at the default step count).
+        nb24 = lib.egc_basis_pack_bytes(F_IN, spec.f_g, spec.w_cols)
+        planes24 = torch.empty(nb24, dtype=torch.uint8, device=dev)
+        _C.check(lib.egc_basis_pack_ex(wcat.data_ptr(), F_IN, spec.f_g, spec.w_cols, 1, planes24.data_ptr(), nb24, stream),
+                 "egc_basis_pack_ex")
+        agg_ms = time_region(agg_only, reps)
+        gemm_ms = time_region(gemm_only, reps)
+        gemm_exact_ms = time_region(gemm_exact_only, 20)
+        gemm_24bit_ms = time_region(gemm_24bit_only, 20)
+        gemm_only()  # leave the split-precision intermediates in place
+        step_ms_events = time_region(step, reps)
 
     # ---- warm-up, then EXACTLY --steps timed steps bracketed by synchronize ----
     for _ in range(args.warmup):
@@ -895,29 +912,6 @@ def main():
     if args.dump_outputs:   # the last timed step's output, before anything below overwrites `out`
         dump_rows = dump_sample_rows(n)
         dump_out = out.index_select(0, torch.from_numpy(dump_rows).to(dev)).cpu().numpy()
-    # robustness of the headline (not part of its definition): four more regions of the same length, the median of the five
-    regions = [ms_per_step]
-    for _ in range(4):
-        sync_all()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        sync_all()
-        regions.append((time.perf_counter() - t0) / args.steps * 1e3)
-
-    terms = roofline_terms(n, e_eff, F_IN, spec.f_g, F_OUT, spec.w_cols, symnorm=True)
-    agg_bytes = terms["aggregate_launch"]
-    agg_gbs = agg_bytes / (agg_ms * 1e-3) / 1e9
-    traffic, traffic_src = None, None
-    pmc_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc_file):
-        try:
-            pj = json.load(open(pmc_file))
-            traffic = pj.get("aggregate_kernel_hbm_bytes_per_launch")
-            traffic_src = "profiles/pmc_traffic.json (" + pj.get("collected", "rocprofv3 --pmc passes, not this run") + ")"
-        except Exception:
-            traffic = None
-
     result = {
         "metric": METRIC,
         "value": value, "unit": "edges/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -930,89 +924,116 @@ def main():
                                f"E_in={e_in} (+N self loops => E_eff={e_eff}), EGC-M d=128 H=8 B=4 "
                                "aggrs=sum+mean+max+symnorm, CSR cached",
                    "n_nodes": n, "e_in": e_in, "e_eff": e_eff, "layer": "EGConv", "parallelism": "single GPU"},
-        "roofline": {"bound": "hbm", "kernel": "egc::agg_fast_kernel (fused aggregate+combine, one launch)",
-                     "achieved": agg_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": agg_gbs / HBM_PEAK_GBS,
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     "algorithmic_bytes_per_launch": agg_bytes, "launch_ms": agg_ms,
-                     "frac_vs_measured_copy_ceiling": agg_gbs / HBM_COPY_CEILING_GBS,
-                     "frac_incl_materialised_weightings": (agg_bytes + terms["weightings"]) / (agg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "note": "SURVEY.md 8(d): gather + col + rowptr + deg + out of the launch; the materialised "
-                             "weightings it also reads are waste, not algorithmic bytes"},
-        "kernels_ms": {"basis_gemm": gemm_ms, "aggregate_combine": agg_ms, "layer_forward": step_ms_events,
-                       "basis_gemm_exact_fp32": gemm_exact_ms, "layer_forward_gemm_exact_fp32": gemm_exact_ms + agg_ms,
-                       "basis_gemm_24bit": gemm_24bit_ms, "layer_forward_gemm_24bit": gemm_24bit_ms + agg_ms},
-        "layer_algorithmic_bytes": terms["layer"],
-        "layer_achieved_gbs": terms["layer"] / (step_ms_events * 1e-3) / 1e9,
-        "layer_frac": terms["layer"] / (step_ms_events * 1e-3) / 1e9 / HBM_PEAK_GBS,
-        # the precision / speed trade of the GEMM, on the line: the default (fp16x2: 22-bit operands, componentwise error 1.3e-7
-        # against float64 -- below the fp32-MFMA kernel's 3.2e-7, tests/test_gemm_gpu.py), the 24-bit-operand form (bf16x3: what
-        # std / var layers ran in rounds 2-3, on request since), the plain fp32-MFMA kernel
-        "layer_frac_by_gemm": {"fp16x2_default": terms["layer"] / (step_ms_events * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                               "bf16x3_24bit": terms["layer"] / ((gemm_24bit_ms + agg_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                               "exact_fp32_mfma": terms["layer"] / ((gemm_exact_ms + agg_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS},
-        "ms_per_step_regions": regions, "ms_per_step_median_of_5_regions": sorted(regions)[2],
+        "roofline": None, "cpu_baseline": None,   # measured with --full
     }
+    if args.full:
+        # robustness of the headline (not part of its definition): four more regions of the same length, the median of the five
+        regions = [ms_per_step]
+        for _ in range(4):
+            sync_all()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            sync_all()
+            regions.append((time.perf_counter() - t0) / args.steps * 1e3)
 
-    # ---- a std layer at this size (VERDICT r3 #4c): the same layer with `mean` replaced by `std` -- the same algorithmic bytes.
-    # Since round 4 such layers run the default GEMM (the variance is accumulated about the row's first entry: no cancellation
-    # left to amplify the 22-bit operand split, profiles/r04_stdvar_shift.md); timed through the module on the cached graph.
-    try:
-        torch.manual_seed(args.seed + 7)
-        conv_std = egc_amd.EGConv(F_IN, F_OUT, aggrs=["sum", "std", "max", "symnorm"], num_heads=HEADS, num_bases=BASES,
-                                  cached=True).to(dev).eval()
+        terms = roofline_terms(n, e_eff, F_IN, spec.f_g, F_OUT, spec.w_cols, symnorm=True)
+        agg_bytes = terms["aggregate_launch"]
+        agg_gbs = agg_bytes / (agg_ms * 1e-3) / 1e9
+        traffic, traffic_src = None, None
+        pmc_file = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(pmc_file):
+            try:
+                pj = json.load(open(pmc_file))
+                traffic = pj.get("aggregate_kernel_hbm_bytes_per_launch")
+                traffic_src = "profiles/pmc_traffic.json (" + pj.get("collected", "rocprofv3 --pmc passes, not this run") + ")"
+            except Exception:
+                traffic = None
 
-        spec_s = conv_std._spec_coo
-        wcat_s, bcat_s = conv_std._packed_weights()
-        planes_s = pack_weights(spec_s, wcat_s)
-        bias_s = conv_std.bias.detach()
-        ws_s = torch.zeros(max(lib.egc_aggregate_workspace_bytes(C.byref(spec_s.c), n, e_in), 1), dtype=torch.uint8, device=dev)
+        result.update({
+            "roofline": {"bound": "hbm", "kernel": "egc::agg_fast_kernel (fused aggregate+combine, one launch)",
+                         "achieved": agg_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": agg_gbs / HBM_PEAK_GBS,
+                         "traffic": traffic, "traffic_source": traffic_src,
+                         "algorithmic_bytes_per_launch": agg_bytes, "launch_ms": agg_ms,
+                         "frac_vs_measured_copy_ceiling": agg_gbs / HBM_COPY_CEILING_GBS,
+                         "frac_incl_materialised_weightings": (agg_bytes + terms["weightings"]) / (agg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                         "note": "SURVEY.md 8(d): gather + col + rowptr + deg + out of the launch; the materialised "
+                                 "weightings it also reads are waste, not algorithmic bytes"},
+            "kernels_ms": {"basis_gemm": gemm_ms, "aggregate_combine": agg_ms, "layer_forward": step_ms_events,
+                           "basis_gemm_exact_fp32": gemm_exact_ms, "layer_forward_gemm_exact_fp32": gemm_exact_ms + agg_ms,
+                           "basis_gemm_24bit": gemm_24bit_ms, "layer_forward_gemm_24bit": gemm_24bit_ms + agg_ms},
+            "layer_algorithmic_bytes": terms["layer"],
+            "layer_achieved_gbs": terms["layer"] / (step_ms_events * 1e-3) / 1e9,
+            "layer_frac": terms["layer"] / (step_ms_events * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            # the precision / speed trade of the GEMM, on the line: the default (fp16x2: 22-bit operands, componentwise error 1.3e-7
+            # against float64 -- below the fp32-MFMA kernel's 3.2e-7, tests/test_gemm_gpu.py), the 24-bit-operand form (bf16x3: what
+            # std / var layers ran in rounds 2-3, on request since), the plain fp32-MFMA kernel
+            "layer_frac_by_gemm": {"fp16x2_default": terms["layer"] / (step_ms_events * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                   "bf16x3_24bit": terms["layer"] / ((gemm_24bit_ms + agg_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                   "exact_fp32_mfma": terms["layer"] / ((gemm_exact_ms + agg_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS},
+            "ms_per_step_regions": regions, "ms_per_step_median_of_5_regions": sorted(regions)[2],
+        })
 
-        def std_step():   # the same C-ABI call as the headline's step (same shapes: the intermediates are shared)
-            _C.check(lib.egc_layer_forward_packed(C.byref(g), C.byref(spec_s.c), x.data_ptr(), planes_s.data_ptr(),
-                                                  bcat_s.data_ptr(), bias_s.data_ptr(), bases.data_ptr(), ldb,
-                                                  weightings.data_ptr(), out.data_ptr(), ws_s.data_ptr(), ws_s.numel(),
-                                                  stream), "egc_layer_forward_packed")
-        for _ in range(20):
-            std_step()
-        std_ms = time_region_median(std_step, reps)
-        result["std_layer"] = {"aggregators": "sum+std+max+symnorm", "gemm_flags": int(spec_s.gemm_flags),
-                               "layer_ms": std_ms, "layer_frac": terms["layer"] / (std_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                               "formula": "variance evaluated as E[(x-s)^2] - (E[x]-s)^2 about the row's first entry s -- a DELIBERATE "
-                                          "departure from the reference's float32 E[x^2] - E[x]^2 (layers.py:203-216): same number in exact "
-                                          "arithmetic, no cancellation; such layers are held to 1e-4 against the reference-generated float32 "
-                                          "fixtures and to 1e-5 against float64 (DESIGN.md section 4, profiles/r04_stdvar_shift.md)",
-                               "note": "egc_layer_forward_packed on the cached CSR graph; same byte model as the headline layer"}
-        gemm_only()
-        agg_only()   # `out` and the intermediates back to the headline layer's
-    except Exception as exc:   # (a side field must not take the line down)
-        result["std_layer"] = {"error": repr(exc)}
-
-    log("algorithmic bytes (SURVEY.md 8d), per forward:")
-    for k, v in terms.items():
-        log(f"  {k:18s} {v / 1e6:10.2f} MB")
-    log(f"kernel ms: gemm {gemm_ms:.4f} (exact fp32: {gemm_exact_ms:.4f})  aggregate+combine {agg_ms:.4f}  layer {step_ms_events:.4f}")
-    out_main = out.clone()
-    measure_layer_config.no_cpu = bool(args.no_cpu_baseline)
-    if not args.no_other_configs:
-        log("other configs:")
-        result["other_configs"] = other_configs(dev, args.seed)
-    if not args.no_cpu_baseline:
+        # ---- a std layer at this size (VERDICT r3 #4c): the same layer with `mean` replaced by `std` -- the same algorithmic bytes.
+        # Since round 4 such layers run the default GEMM (the variance is accumulated about the row's first entry: no cancellation
+        # left to amplify the 22-bit operand split, profiles/r04_stdvar_shift.md); timed through the module on the cached graph.
         try:
-            ref_out, cpu_s, threads, e_cached = cpu_baseline(ei_cpu, n, x_cpu, state_cpu)
-            err = float((out_main.cpu() - ref_out).abs().max() / max(1.0, float(ref_out.abs().max())))
-            log(f"cpu port: {cpu_s * 1e3:.1f} ms/forward on {threads} threads; HIP vs CPU port rel err {err:.2e}")
-            result["cpu_baseline"] = {
-                "value": e_eff / cpu_s, "unit": "edges/s", "cores": threads, "threads": threads,
-                "host_cores": os.cpu_count(), "kind": "port",   # `cores` = the threads actually used (the contract's field)
-                "sample": f"full config-2 layer forward (E_eff={e_cached}), gcn_norm cached; best of 8/16/32/64 "
-                          f"torch threads, median of 5 runs each after a warm-up; {cpu_s * 1e3:.1f} ms per forward "
-                          f"on a {os.cpu_count()}-core host (torch's scatter / index kernels stop scaling at 8-32 threads: in "
-                          f"plain words, the host is used as an {threads}-core machine)",
-                "hip_vs_port_rel_err": err}
-        except Exception as ex:   # noqa: BLE001 -- the measured line is printed either way, with the failure in it
-            log(f"cpu baseline failed: {ex!r}")
-            result["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": 0, "kind": "port", "sample": "failed",
-                                      "error": repr(ex)[:500]}
+            torch.manual_seed(args.seed + 7)
+            conv_std = egc_amd.EGConv(F_IN, F_OUT, aggrs=["sum", "std", "max", "symnorm"], num_heads=HEADS, num_bases=BASES,
+                                      cached=True).to(dev).eval()
+
+            spec_s = conv_std._spec_coo
+            wcat_s, bcat_s = conv_std._packed_weights()
+            planes_s = pack_weights(spec_s, wcat_s)
+            bias_s = conv_std.bias.detach()
+            ws_s = torch.zeros(max(lib.egc_aggregate_workspace_bytes(C.byref(spec_s.c), n, e_in), 1), dtype=torch.uint8, device=dev)
+
+            def std_step():   # the same C-ABI call as the headline's step (same shapes: the intermediates are shared)
+                _C.check(lib.egc_layer_forward_packed(C.byref(g), C.byref(spec_s.c), x.data_ptr(), planes_s.data_ptr(),
+                                                      bcat_s.data_ptr(), bias_s.data_ptr(), bases.data_ptr(), ldb,
+                                                      weightings.data_ptr(), out.data_ptr(), ws_s.data_ptr(), ws_s.numel(),
+                                                      stream), "egc_layer_forward_packed")
+            for _ in range(20):
+                std_step()
+            std_ms = time_region_median(std_step, reps)
+            result["std_layer"] = {"aggregators": "sum+std+max+symnorm", "gemm_flags": int(spec_s.gemm_flags),
+                                   "layer_ms": std_ms, "layer_frac": terms["layer"] / (std_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                   "formula": "variance evaluated as E[(x-s)^2] - (E[x]-s)^2 about the row's first entry s -- a DELIBERATE "
+                                              "departure from the reference's float32 E[x^2] - E[x]^2 (layers.py:203-216): same number in exact "
+                                              "arithmetic, no cancellation; such layers are held to 1e-4 against the reference-generated float32 "
+                                              "fixtures and to 1e-5 against float64 (DESIGN.md section 4, profiles/r04_stdvar_shift.md)",
+                                   "note": "egc_layer_forward_packed on the cached CSR graph; same byte model as the headline layer"}
+            gemm_only()
+            agg_only()   # `out` and the intermediates back to the headline layer's
+        except Exception as exc:   # (a side field must not take the line down)
+            result["std_layer"] = {"error": repr(exc)}
+
+        log("algorithmic bytes (SURVEY.md 8d), per forward:")
+        for k, v in terms.items():
+            log(f"  {k:18s} {v / 1e6:10.2f} MB")
+        log(f"kernel ms: gemm {gemm_ms:.4f} (exact fp32: {gemm_exact_ms:.4f})  aggregate+combine {agg_ms:.4f}  layer {step_ms_events:.4f}")
+        out_main = out.clone()
+        measure_layer_config.no_cpu = bool(args.no_cpu_baseline)
+        if not args.no_other_configs:
+            log("other configs:")
+            result["other_configs"] = other_configs(dev, args.seed)
+        if not args.no_cpu_baseline:
+            try:
+                ref_out, cpu_s, threads, e_cached = cpu_baseline(ei_cpu, n, x_cpu, state_cpu)
+                err = float((out_main.cpu() - ref_out).abs().max() / max(1.0, float(ref_out.abs().max())))
+                log(f"cpu port: {cpu_s * 1e3:.1f} ms/forward on {threads} threads; HIP vs CPU port rel err {err:.2e}")
+                result["cpu_baseline"] = {
+                    "value": e_eff / cpu_s, "unit": "edges/s", "cores": threads, "threads": threads,
+                    "host_cores": os.cpu_count(), "kind": "port",   # `cores` = the threads actually used (the contract's field)
+                    "sample": f"full config-2 layer forward (E_eff={e_cached}), gcn_norm cached; best of 8/16/32/64 "
+                              f"torch threads, median of 5 runs each after a warm-up; {cpu_s * 1e3:.1f} ms per forward "
+                              f"on a {os.cpu_count()}-core host (torch's scatter / index kernels stop scaling at 8-32 threads: in "
+                              f"plain words, the host is used as an {threads}-core machine)",
+                    "hip_vs_port_rel_err": err}
+            except Exception as ex:   # noqa: BLE001 -- the measured line is printed either way, with the failure in it
+                log(f"cpu baseline failed: {ex!r}")
+                result["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": 0, "kind": "port", "sample": "failed",
+                                          "error": repr(ex)[:500]}
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, {"layer_out_rows_sample": dump_out, "layer_out_row_ids": dump_rows.astype(np.float64)})
     emit(result)

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-B="python3 $R/bench.py --no-cpu-baseline"
+B="python3 $R/bench.py --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats -d $O/kt2 -o kt --output-format csv -- $B --no-other-configs > $O/bench_config2_under_rocprof.json 2> $O/kt2.log
 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- $B > $O/bench_under_rocprof.json 2> $O/kt.log
 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o pmc --output-format csv -- $B --no-other-configs --steps 20 --warmup 5 > /dev/null 2> $O/pmc_fetch.log
@@ -48,7 +48,7 @@ python3 tools/host_overhead_time.py > $O/host_overhead.log 2>&1
 python3 tools/reference_shapes_time.py > $O/reference_shapes.log 2>&1   # every trained layer shape of the reference, arxiv-shaped graph
 python3 tools/gemm_time.py > $O/gemm_time.log 2>&1
 python3 bench.py --workload rmag --steps 10 --warmup 3 > $O/rmag_bench.json 2> $O/rmag.err
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 tail -3 $O/bench.err
 # the raw per-dispatch traces are large: keep the statistics and the counter collections only
 find $O -name "*kernel_trace.csv" -delete

@@ -5,8 +5,8 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r05c
 mkdir -p $O
 cd $R
-timeout 900 python3 bench.py > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
-EGC_HIP_LIB=$R/egc_amd/lib/var_agg6.so timeout 600 python3 bench.py --no-other-configs --no-cpu-baseline > $O/bench_agg6.json 2> $O/bench_agg6.err
+timeout 900 python3 bench.py --full > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err
+EGC_HIP_LIB=$R/egc_amd/lib/var_agg6.so timeout 600 python3 bench.py --full --no-other-configs --no-cpu-baseline > $O/bench_agg6.json 2> $O/bench_agg6.err
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt_shapes -o kt --output-format csv -- python3 $R/tools/batch_shapes_time.py > $O/batch_shapes_under_rocprof.log 2>&1
 for w in molhiv cifar; do

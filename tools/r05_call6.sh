@@ -6,9 +6,9 @@ O=$R/gpurun_out/r05i
 mkdir -p $O
 cd $R
 timeout 2400 python3 -m pytest tests -q -m gpu --timeout 1200 -x > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
-timeout 1200 python3 bench.py > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
+timeout 1200 python3 bench.py --full > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/kt_bench -o kt --output-format csv -- python3 $R/bench.py --no-other-configs --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/kt_bench -o kt --output-format csv -- python3 $R/bench.py --full --no-other-configs --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt_step -o kt --output-format csv -- python3 $R/tools/batch_train_step_time.py > $O/step_under_rocprof.log 2>&1
 find $O -name "*kernel_trace.csv" -delete
 cd $R

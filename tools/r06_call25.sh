@@ -14,6 +14,6 @@ for r in csv.DictReader(open('$f')):
 done; done
 # config 2 forward (headline kernel) and config 3 CSR path
 for q in 1 2 4; do
-  EGC_AGG_Q=$q python3 $R/bench.py --no-cpu-baseline --no-other-configs --steps 100 --warmup 10 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('config2 Q=$q', d['ms_per_step'], d['roofline']['launch_ms'])"
+  EGC_AGG_Q=$q python3 $R/bench.py --full --no-cpu-baseline --no-other-configs --steps 100 --warmup 10 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('config2 Q=$q', d['ms_per_step'], d['roofline']['launch_ms'])"
 done
 rm -rf $O/kt_v

@@ -1,7 +1,7 @@
 # round 6: the profile collection kept under profiles/r06_* (run on the GPU box: gpurun -- 'bash tools/r06_final.sh')
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06_final; rm -rf $O; mkdir -p $O
-B="python3 $R/bench.py --no-cpu-baseline --no-other-configs --steps 200 --warmup 20"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-other-configs --steps 200 --warmup 20"
 # (1) the headline under the kernel trace: the dominant kernel's average duration (must agree with roofline.launch_ms of the bench line)
 rocprofv3 --kernel-trace --stats -d $O/kt2 -o kt --output-format csv -- $B > $O/bench_config2_under_rocprof.json 2> $O/kt2.log
 # (2) its HBM-side traffic: FETCH_SIZE and WRITE_SIZE in separate passes
@@ -39,5 +39,5 @@ EGC_NO_NATIVE_TRAIN=1 TOP=25 python3 tools/eager_batch_step_profile.py > $O/eage
 python3 tools/eager_step_variants.py > $O/eager_step_variants.log 2>&1
 hipcc -O2 --offload-arch=gfx950 tools/src/lds_atomic_order.hip -o /tmp/lao 2>/dev/null && /tmp/lao > $O/lds_atomic_order.log 2>&1
 # (5) the bench in the driver's form, last (what BENCH_r06.json should look like)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; wc -c $O/bench_line.json; cp bench_detail.json $O/
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"; wc -c $O/bench_line.json; cp bench_detail.json $O/
 du -sh $O
