@@ -6,17 +6,17 @@
 // caching allocator and issues the library's launches on the caller's stream.  No device code here; nothing of the
 // hot path is computed by torch.
 //
-// The graph and the layer description are the library's own structs (egc_graph, egc_layer), kept alive by their Python
-// owners (CSRGraph.c_struct(), LayerSpec.c); they travel as integer addresses, the stream as the raw hipStream_t the
-// ctypes path uses as well (torch._C._cuda_getCurrentRawStream).
+// The graph and the layer description are the library's own structs (egc_graph, egc_layer) owned by Python objects
+// (CSRGraph.c_struct(), LayerSpec.c); they travel as integer addresses, read only for the length of the op call: the block
+// nodes, whose backward may run after those owners are gone, copy them into their own state.  The stream travels as the
+// raw hipStream_t the ctypes path uses as well (torch._C._cuda_getCurrentRawStream).
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <torch/csrc/autograd/custom_function.h>
 #include <torch/library.h>
 
 #include <algorithm>
-#include <cstring>
-#include <string>
+#include <tuple>
 #include <vector>
 
 #include "egc_hip.h"
@@ -33,6 +33,9 @@ void check_f32(const at::Tensor& t, const char* name) {
 void check_status(int st, const char* what) {
   TORCH_CHECK(st == EGC_OK, "egc_amd: ", what, " failed with status ", st, " (", egc_last_error(), ")");
 }
+
+// the partial sums of the column-sum kernels: one per 128 rows, at most 1024
+int64_t n_partials(int64_t n) { return std::max<int64_t>(1, std::min<int64_t>(1024, (n + 127) / 128)); }
 
 // Shapes of the optional operands and the workspace (the ctypes path checks them in Python; here a wrong-sized scale or
 // residual would be read out of bounds on the device), and the device the pointers live on.
@@ -116,13 +119,11 @@ at::Tensor layer_forward_post(const at::Tensor& x, const at::Tensor& packed, con
 // -> [out, wcat, bcat (or empty), bases, weightings, stats, cnt, arg_max (or empty), arg_min (or empty)]
 std::vector<at::Tensor> train_forward(const at::Tensor& x, const at::Tensor& comb_w, const c10::optional<at::Tensor>& comb_b,
                                       const c10::optional<at::Tensor>& bcat_direct, at::TensorList basis_parts,
-                                      const c10::optional<at::Tensor>& bias, int64_t graph, int64_t layer,
+                                      const c10::optional<at::Tensor>& bias, const egc_graph* g, const egc_layer* l,
                                       const at::Tensor& workspace, int64_t stream, int64_t H, int64_t A, int64_t B, int64_t L,
                                       int64_t Ls, bool permute_hab, int64_t gemm_flags) {
   check_f32(x, "x");
   check_f32(comb_w, "comb weight");
-  const auto* g = reinterpret_cast<const egc_graph*>(graph);
-  const auto* l = reinterpret_cast<const egc_layer*>(layer);
   auto st = reinterpret_cast<egc_stream_t>(stream);
   const int64_t n = x.size(0), f_in = x.size(1);
   TORCH_CHECK(x.dim() == 2 && n == g->n_nodes && f_in == l->in_channels, "egc_amd: x has the wrong shape");
@@ -170,6 +171,15 @@ std::vector<at::Tensor> train_forward(const at::Tensor& x, const at::Tensor& com
   return {out, wcat, bcat, bases, weightings, stats, cnt, arg_max, arg_min};
 }
 
+std::vector<at::Tensor> train_forward_op(const at::Tensor& x, const at::Tensor& comb_w, const c10::optional<at::Tensor>& comb_b,
+                                         const c10::optional<at::Tensor>& bcat_direct, at::TensorList basis_parts,
+                                         const c10::optional<at::Tensor>& bias, int64_t graph, int64_t layer,
+                                         const at::Tensor& workspace, int64_t stream, int64_t H, int64_t A, int64_t B, int64_t L,
+                                         int64_t Ls, bool permute_hab, int64_t gemm_flags) {
+  return train_forward(x, comb_w, comb_b, bcat_direct, basis_parts, bias, reinterpret_cast<const egc_graph*>(graph),
+                       reinterpret_cast<const egc_layer*>(layer), workspace, stream, H, A, B, L, Ls, permute_hab, gemm_flags);
+}
+
 // -> [dx (or empty), d comb_w, d comb_b or d bcat_direct (or empty), d bias (or empty), d basis matrices ...]
 // Requires (checked by the caller): ldb == B Ls, (ldb + W) % 4 == 0, f_in % 4 == 0, f_out % 4 == 0; a bias and a combination bias
 // present.  The one-pass dense-gradient kernel inside its envelope (f_in <= 128, ldb + W <= 192, f_out <= 128), the general
@@ -179,14 +189,11 @@ std::vector<at::Tensor> train_forward(const at::Tensor& x, const at::Tensor& com
 // when the caller holds them already (the BatchNorm tail's backward: egc_bn_backward_stats_sums_f32) -- no pass over grad_out.
 static std::vector<at::Tensor> train_backward_impl(const at::Tensor& grad_out, const at::Tensor& x, const at::Tensor& wcat,
                                                    const at::Tensor& bases, const at::Tensor& weightings, const at::Tensor& stats,
-                                                   const at::Tensor& cnt, const at::Tensor& arg_max, const at::Tensor& arg_min, int64_t graph,
-                                                   int64_t t_graph, int64_t layer, int64_t stream, int64_t H, int64_t A, int64_t B, int64_t L,
-                                                   int64_t Ls, bool permute_hab, bool packed_bias, bool need_x, at::IntArrayRef comb_w_shape,
-                                                   at::IntArrayRef comb_b_shape, int64_t n_parts, at::IntArrayRef part_shape,
-                                                   const at::Tensor* dx_addend, const at::Tensor* bias_grad) {
-  const auto* g = reinterpret_cast<const egc_graph*>(graph);
-  const auto* tg = reinterpret_cast<const egc_graph*>(t_graph);
-  const auto* l = reinterpret_cast<const egc_layer*>(layer);
+                                                   const at::Tensor& cnt, const at::Tensor& arg_max, const at::Tensor& arg_min,
+                                                   const egc_graph* g, const egc_graph* tg, const egc_layer* l, int64_t stream, int64_t H,
+                                                   int64_t A, int64_t B, int64_t L, int64_t Ls, bool permute_hab, bool packed_bias, bool need_x,
+                                                   at::IntArrayRef comb_w_shape, at::IntArrayRef comb_b_shape, int64_t n_parts,
+                                                   at::IntArrayRef part_shape, const at::Tensor* dx_addend, const at::Tensor* bias_grad) {
   auto st = reinterpret_cast<egc_stream_t>(stream);
   at::Tensor go = grad_out.contiguous();
   check_f32(go, "grad_out");
@@ -254,7 +261,7 @@ static std::vector<at::Tensor> train_backward_impl(const at::Tensor& grad_out, c
                  "egc_weight_grad_params_f32");
   }
   if (!have_es && !ride) {      // the layer's bias gradient on its own: the column sums of grad_out
-    const int64_t parts = std::max<int64_t>(1, std::min<int64_t>(1024, (n + 127) / 128));
+    const int64_t parts = n_partials(n);
     at::Tensor psum = at::empty({parts, f_out}, opts);
     check_status(egc_column_sums_f32(go.data_ptr<float>(), n, (int32_t)f_out, (int32_t)f_out, psum.data_ptr<float>(), (int32_t)parts, st),
                  "egc_column_sums_f32");
@@ -266,14 +273,15 @@ static std::vector<at::Tensor> train_backward_impl(const at::Tensor& grad_out, c
   return out;
 }
 
-std::vector<at::Tensor> train_backward(const at::Tensor& grad_out, const at::Tensor& x, const at::Tensor& wcat,
-                                       const at::Tensor& bases, const at::Tensor& weightings, const at::Tensor& stats,
-                                       const at::Tensor& cnt, const at::Tensor& arg_max, const at::Tensor& arg_min, int64_t graph,
-                                       int64_t t_graph, int64_t layer, int64_t stream, int64_t H, int64_t A, int64_t B, int64_t L,
-                                       int64_t Ls, bool permute_hab, bool packed_bias, bool need_x, at::IntArrayRef comb_w_shape,
-                                       at::IntArrayRef comb_b_shape, int64_t n_parts, at::IntArrayRef part_shape) {
-  return train_backward_impl(grad_out, x, wcat, bases, weightings, stats, cnt, arg_max, arg_min, graph, t_graph, layer, stream, H, A, B, L, Ls,
-                             permute_hab, packed_bias, need_x, comb_w_shape, comb_b_shape, n_parts, part_shape, nullptr, nullptr);
+std::vector<at::Tensor> train_backward_op(const at::Tensor& grad_out, const at::Tensor& x, const at::Tensor& wcat,
+                                          const at::Tensor& bases, const at::Tensor& weightings, const at::Tensor& stats,
+                                          const at::Tensor& cnt, const at::Tensor& arg_max, const at::Tensor& arg_min, int64_t graph,
+                                          int64_t t_graph, int64_t layer, int64_t stream, int64_t H, int64_t A, int64_t B, int64_t L,
+                                          int64_t Ls, bool permute_hab, bool packed_bias, bool need_x, at::IntArrayRef comb_w_shape,
+                                          at::IntArrayRef comb_b_shape, int64_t n_parts, at::IntArrayRef part_shape) {
+  return train_backward_impl(grad_out, x, wcat, bases, weightings, stats, cnt, arg_max, arg_min, reinterpret_cast<const egc_graph*>(graph),
+                             reinterpret_cast<const egc_graph*>(t_graph), reinterpret_cast<const egc_layer*>(layer), stream, H, A, B, L,
+                             Ls, permute_hab, packed_bias, need_x, comb_w_shape, comb_b_shape, n_parts, part_shape, nullptr, nullptr);
 }
 
 
@@ -290,42 +298,115 @@ std::vector<at::Tensor> train_backward(const at::Tensor& grad_out, const at::Ten
 // _BatchNormActResidualFunction + ResidualLink, without their ctypes marshalling, the two Python autograd Functions and the
 // hand-over between them (the eager ZINC step was ~1 ms of host time for 0.37 ms of kernels: profiles/r06_eager_step.md).
 // `with_tail` false: the layer alone (a conv called outside a FusedEGCBlock).  Envelope: checked by the Python caller
-// (functional._native_block_train); everything outside it stays on the Python path, same kernels.
+// (functional.native_block_train); everything outside it stays on the Python path, same kernels.
 // ---------------------------------------------------------------------------------------------------------------------
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
-struct BlockStatic {
-  at::Tensor ptr, edge_ptr, src, dst, max_index, status;      // the batch (kept alive for the backward): edge_ptr / max_index may be undefined
-  at::Tensor running_mean, running_var, n_tracked;            // BatchNorm's buffers, updated in place by the forward (may be undefined)
-  int64_t host_flag, layer, stream;
-  int64_t f_in, H, A, B, L, Ls;
-  bool permute_hab;
-  int64_t tile_f, emax_f, tile_b, emax_b;
-  double eps, momentum;                                        // momentum < 0: cumulative average over n_tracked
-  bool relu, residual, with_tail;
+// What a block node needs besides its tensor operands: built at op entry (block_state), owned by the node (a capsule in
+// ctx->saved_data -- which compiled autograd cannot collect from a C++ node; no caller uses it).  The layer and graph structs
+// are copies, so the backward reads nothing a Python object owns.
+struct BlockState : torch::CustomClassHolder {
+  egc_layer layer{};
+  egc_graph g{}, tg{};                                        // CsrBlockTrainFn: the graph and its transpose,
+  std::vector<at::Tensor> keep;                               //   the device tensors they point into
+  at::Tensor ptr, edge_ptr, src, dst, max_index, status;      // BatchBlockTrainFn: the batch; edge_ptr / max_index may be undefined
+  int64_t host_flag = 0, tile_f = 0, emax_f = 0, tile_b = 0, emax_b = 0;
+  // the forward's alone -- the CSR aggregate's workspace, BatchNorm's buffers (updated in place; may be undefined) -- released
+  // once it has run, so that the node does not hold them until its backward
+  at::Tensor workspace, running_mean, running_var, n_tracked;
+  void release_forward_operands() { workspace.reset(); running_mean.reset(); running_var.reset(); n_tracked.reset(); }
+  int64_t stream = 0, H = 0, A = 0, B = 0, L = 0, Ls = 0, gemm_flags = 0;
+  bool permute_hab = false, residual = false, with_tail = true;
+  double eps = 0, momentum = 0;                               // momentum < 0: cumulative average over n_tracked
+  bool has_bias = false, has_comb_b = false, has_bcat = false, has_gamma = false, has_beta = false;
+  std::vector<int64_t> comb_w_shape, comb_b_shape;            // the shapes of the parameters' gradients
+  std::vector<std::vector<int64_t>> part_shapes;
 };
 
-// BlockStatic <-> AutogradContext::saved_data (plain IValues: tensor list with presence flags, ints, doubles)
-static void save_static(AutogradContext* ctx, const BlockStatic& s);
-static BlockStatic load_static(AutogradContext* ctx);
-
-
-// The operand shapes of a block node, checked before anything is launched: the tail reads gamma / beta / the running
-// statistics as [f_out] vectors and adds x as an [n, f_out] residual, so a module whose widths do not match would be
-// read out of bounds on the device (the Python route raises torch's shape error in the same place).
-static void check_block_operands(const at::Tensor& x, int64_t layer, const c10::optional<at::Tensor>& gamma,
-                                 const c10::optional<at::Tensor>& beta, const c10::optional<at::Tensor>& running_mean,
-                                 const c10::optional<at::Tensor>& running_var, bool residual, bool with_tail) {
-  TORCH_CHECK(layer != 0, "egc_amd: no layer");
-  const auto* l = reinterpret_cast<const egc_layer*>(layer);
+// The op entry's state of a block node, after the checks that come before anything is launched: the tail reads gamma / beta / the
+// running statistics as [f_out] vectors and adds x as an [n, f_out] residual, so a module whose widths do not match would be read
+// out of bounds on the device (the Python route raises torch's shape error in the same place).
+static c10::intrusive_ptr<BlockState> block_state(const at::Tensor& x, const c10::optional<at::Tensor>& bias, const at::Tensor& comb_w,
+                                                  const c10::optional<at::Tensor>& comb_b, const c10::optional<at::Tensor>& bcat_direct,
+                                                  const c10::optional<at::Tensor>& gamma, const c10::optional<at::Tensor>& beta,
+                                                  at::TensorList parts, const c10::optional<at::Tensor>& running_mean,
+                                                  const c10::optional<at::Tensor>& running_var, const c10::optional<at::Tensor>& n_tracked,
+                                                  const egc_layer* l, int64_t stream, bool permute_hab, double eps, double momentum,
+                                                  bool residual, bool with_tail) {
+  TORCH_CHECK(l != nullptr, "egc_amd: no layer");
   const int64_t f_in = l->in_channels, f_out = l->out_channels;
   TORCH_CHECK(x.dim() == 2 && x.size(1) == f_in, "egc_amd: x must be [n, ", f_in, "], got ", x.sizes());
-  if (!with_tail) return;
-  TORCH_CHECK(!residual || f_in == f_out, "egc_amd: a residual block needs in_channels == out_channels, got ", f_in, " and ", f_out);
-  for (const auto* t : {&gamma, &beta, &running_mean, &running_var})
-    TORCH_CHECK(!t->has_value() || (*t)->numel() == f_out, "egc_amd: the BatchNorm's parameters and buffers must hold ", f_out,
-                " elements, got ", (*t)->numel());
+  if (with_tail) {
+    TORCH_CHECK(!residual || f_in == f_out, "egc_amd: a residual block needs in_channels == out_channels, got ", f_in, " and ", f_out);
+    for (const auto* t : {&gamma, &beta, &running_mean, &running_var})
+      TORCH_CHECK(!t->has_value() || (*t)->numel() == f_out, "egc_amd: the BatchNorm's parameters and buffers must hold ", f_out,
+                  " elements, got ", (*t)->numel());
+  }
+  auto s = c10::make_intrusive<BlockState>();
+  if (running_mean.has_value()) {
+    TORCH_CHECK(running_var.has_value(), "egc_amd: running_mean and running_var come together");
+    check_f32(*running_mean, "running_mean"); check_f32(*running_var, "running_var");
+    s->running_mean = *running_mean; s->running_var = *running_var;
+  }
+  if (n_tracked.has_value()) { TORCH_CHECK(n_tracked->is_cuda() && n_tracked->scalar_type() == at::kLong && n_tracked->numel() == 1, "egc_amd: num_batches_tracked"); s->n_tracked = *n_tracked; }
+  TORCH_CHECK(momentum >= 0 || !s->running_mean.defined() || s->n_tracked.defined(), "egc_amd: a cumulative average needs num_batches_tracked");
+  s->layer = *l;
+  s->stream = stream; s->permute_hab = permute_hab; s->eps = eps; s->momentum = momentum; s->residual = residual; s->with_tail = with_tail;
+  s->has_bias = bias.has_value(); s->has_comb_b = comb_b.has_value(); s->has_bcat = bcat_direct.has_value();
+  s->has_gamma = gamma.has_value(); s->has_beta = beta.has_value();
+  s->comb_w_shape = comb_w.sizes().vec();
+  if (comb_b.has_value()) s->comb_b_shape = comb_b->sizes().vec();
+  for (const auto& t : parts) s->part_shapes.push_back(t.sizes().vec());
+  return s;
+}
+
+// The block's tail: BatchNorm on batch statistics (running statistics updated as nn.BatchNorm1d does), then normalise -> ReLU -> + x.
+// -> [out, affine (scale, shift), stats]
+static std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_tail_forward(const at::Tensor& h, const at::Tensor& x, const c10::optional<at::Tensor>& gamma,
+                                                                      const c10::optional<at::Tensor>& beta, const BlockState& s) {
+  auto st = reinterpret_cast<egc_stream_t>(s.stream);
+  const int64_t n = h.size(0), c = h.size(1), n_parts = n_partials(n);
+  const auto opts = h.options();
+  at::Tensor partials = at::empty({n_parts, 2, c}, opts.dtype(at::kDouble)), stats = at::empty({3, c}, opts.dtype(at::kDouble));
+  at::Tensor affine = at::empty({2, c}, opts), out = at::empty({n, c}, opts);
+  if (gamma.has_value()) check_f32(*gamma, "BatchNorm weight");
+  if (beta.has_value()) check_f32(*beta, "BatchNorm bias");
+  const bool track = s.running_mean.defined();
+  int64_t* cnt = s.n_tracked.defined() ? s.n_tracked.data_ptr<int64_t>() : nullptr;
+  check_status(egc_bn_forward_stats_f32(h.data_ptr<float>(), n, (int32_t)c, partials.data_ptr<double>(), (int32_t)n_parts,
+                                        track ? cnt : nullptr, nullptr, fptr(gamma), fptr(beta), s.eps, stats.data_ptr<double>(),
+                                        affine.data_ptr<float>(), track ? s.running_mean.data_ptr<float>() : nullptr,
+                                        track ? s.running_var.data_ptr<float>() : nullptr, s.momentum, cnt, nullptr, st),
+               "egc_bn_forward_stats_f32");
+  check_status(egc_affine_act_residual_f32(h.data_ptr<float>(), affine.data_ptr<float>(), affine.data_ptr<float>() + c,
+                                           s.residual ? x.data_ptr<float>() : nullptr, 1, nullptr, 1.0f, n, (int32_t)c,
+                                           out.data_ptr<float>(), nullptr, st), "egc_affine_act_residual_f32");
+  return {out, affine, stats};
+}
+
+// Its backward (go: the gradient of out) -> [dh, d gamma, d beta, the column sums of dh (with_sums) or undefined].  The column sums of
+// dh are the layer's bias gradient: they come from this step's own sums.
+static std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_tail_backward(const at::Tensor& go, const at::Tensor& h, const at::Tensor& affine,
+                                                                                   const at::Tensor& stats, const at::Tensor& gamma, bool with_sums,
+                                                                                   const BlockState& s) {
+  auto st = reinterpret_cast<egc_stream_t>(s.stream);
+  const int64_t n = h.size(0), c = h.size(1), n_parts = n_partials(n);
+  const auto opts = h.options();
+  at::Tensor partials = at::empty({n_parts, 2, c}, opts.dtype(at::kDouble)), out5 = at::empty({5, c}, opts);
+  at::Tensor dh_sums = with_sums ? at::empty({c}, opts) : at::Tensor();
+  const float* a0 = affine.data_ptr<float>();
+  check_status(egc_bn_backward_stats_sums_f32(go.data_ptr<float>(), h.data_ptr<float>(), a0, a0 + c, 1, nullptr, 1.0f, n, (int32_t)c,
+                                              partials.data_ptr<double>(), (int32_t)n_parts, nullptr, stats.data_ptr<double>(),
+                                              gamma.defined() ? gamma.data_ptr<float>() : nullptr, out5.data_ptr<float>(),
+                                              with_sums ? dh_sums.data_ptr<float>() : nullptr, nullptr, st),
+               "egc_bn_backward_stats_sums_f32");
+  at::Tensor dh = at::empty({n, c}, opts);
+  const float* o5 = out5.data_ptr<float>();
+  check_status(egc_affine_act_backward_f32(go.data_ptr<float>(), h.data_ptr<float>(), a0, a0 + c, 1, nullptr, 1.0f, o5 + 2 * c,
+                                           o5 + 3 * c, o5 + 4 * c, n, (int32_t)c, dh.data_ptr<float>(), nullptr, st),
+               "egc_affine_act_backward_f32");
+  return {dh, out5[0], out5[1], dh_sums};
 }
 
 static const int64_t* iptr(const at::Tensor& t) { return t.defined() ? t.data_ptr<int64_t>() : nullptr; }
@@ -334,13 +415,13 @@ struct BatchBlockTrainFn : public torch::autograd::Function<BatchBlockTrainFn> {
   static at::Tensor forward(AutogradContext* ctx, const at::Tensor& x, const c10::optional<at::Tensor>& bias, const at::Tensor& comb_w,
                             const c10::optional<at::Tensor>& comb_b, const c10::optional<at::Tensor>& bcat_direct,
                             const c10::optional<at::Tensor>& gamma, const c10::optional<at::Tensor>& beta, at::TensorList parts,
-                            const BlockStatic& s) {
+                            const c10::intrusive_ptr<BlockState>& state) {
+    const BlockState& s = *state;
     check_f32(x, "x");
     check_f32(comb_w, "comb weight");
-    const auto* l = reinterpret_cast<const egc_layer*>(s.layer);
+    const egc_layer* l = &s.layer;
     auto st = reinterpret_cast<egc_stream_t>(s.stream);
     const int64_t n = x.size(0), f_out = l->out_channels;
-    TORCH_CHECK(x.dim() == 2 && x.size(1) == s.f_in && s.f_in == l->in_channels, "egc_amd: x has the wrong shape");
     TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "egc_amd: x must be 16-byte aligned");
     TORCH_CHECK(!(comb_b.has_value() && bcat_direct.has_value()), "egc_amd: one combination bias, not two");
     const c10::OptionalDeviceGuard device_guard(x.device());
@@ -365,77 +446,40 @@ struct BatchBlockTrainFn : public torch::autograd::Function<BatchBlockTrainFn> {
                                                    packed.data_ptr(), fptr(bias), nullptr, h.data_ptr<float>(), (int32_t)s.tile_f, (int32_t)s.emax_f,
                                                    s.status.data_ptr<int32_t>(), reinterpret_cast<int32_t*>(s.host_flag), st),
                  "egc_layer_forward_batch_fused_f32");
-    save_static(ctx, s);
-    ctx->saved_data["has"] = std::vector<bool>{bias.has_value(), comb_b.has_value(), bcat_direct.has_value(), gamma.has_value(), beta.has_value()};
-    std::vector<std::vector<int64_t>> shapes;
-    shapes.push_back(comb_w.sizes().vec());
-    shapes.push_back(comb_b.has_value() ? comb_b->sizes().vec() : std::vector<int64_t>{});
-    for (const auto& t : parts) shapes.push_back(t.sizes().vec());
-    ctx->saved_data["shapes"] = shapes;
+    ctx->saved_data["state"] = c10::IValue::make_capsule(state);
     if (!s.with_tail) {
+      state->release_forward_operands();
       ctx->save_for_backward({x, packed, packed_t});
       return h;
     }
-    // (3) BatchNorm on batch statistics (running statistics updated as nn.BatchNorm1d does), (4) normalise -> ReLU -> + x
-    const int64_t c = f_out;
-    const int64_t n_parts = std::max<int64_t>(1, std::min<int64_t>(1024, (n + 127) / 128));
-    at::Tensor partials = at::empty({n_parts, 2, c}, opts.dtype(at::kDouble)), stats = at::empty({3, c}, opts.dtype(at::kDouble));
-    at::Tensor affine = at::empty({2, c}, opts), out = at::empty({n, c}, opts);
-    at::Tensor gamma_c = gamma.has_value() ? gamma->detach() : at::Tensor();
-    if (gamma.has_value()) check_f32(*gamma, "BatchNorm weight");
-    if (beta.has_value()) check_f32(*beta, "BatchNorm bias");
-    const bool track = s.running_mean.defined();
-    int64_t* cnt = s.n_tracked.defined() ? s.n_tracked.data_ptr<int64_t>() : nullptr;
-    check_status(egc_bn_forward_stats_f32(h.data_ptr<float>(), n, (int32_t)c, partials.data_ptr<double>(), (int32_t)n_parts,
-                                          track ? cnt : nullptr, nullptr, fptr(gamma), fptr(beta), s.eps, stats.data_ptr<double>(),
-                                          affine.data_ptr<float>(), track ? s.running_mean.data_ptr<float>() : nullptr,
-                                          track ? s.running_var.data_ptr<float>() : nullptr, s.momentum, cnt, nullptr, st),
-                 "egc_bn_forward_stats_f32");
-    check_status(egc_affine_act_residual_f32(h.data_ptr<float>(), affine.data_ptr<float>(), affine.data_ptr<float>() + c,
-                                             s.residual ? x.data_ptr<float>() : nullptr, s.relu ? 1 : 0, nullptr, 1.0f, n, (int32_t)c,
-                                             out.data_ptr<float>(), nullptr, st), "egc_affine_act_residual_f32");
-    ctx->save_for_backward({x, packed, packed_t, h, affine, stats, gamma_c});
+    // (3) BatchNorm -> ReLU -> + x
+    auto [out, affine, stats] = bn_tail_forward(h, x, gamma, beta, s);
+    state->release_forward_operands();
+    ctx->save_for_backward({x, packed, packed_t, h, affine, stats, gamma.has_value() ? gamma->detach() : at::Tensor()});
     return out;
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     const auto saved = ctx->get_saved_variables();
-    const BlockStatic s = load_static(ctx);
-    const auto has = ctx->saved_data["has"].toBoolList();
-    const auto shapes = ctx->saved_data["shapes"].to<std::vector<std::vector<int64_t>>>();
-    const int64_t n_parts_w = (int64_t)shapes.size() - 2;
-    variable_list out(8 + n_parts_w);            // x, bias, comb_w, comb_b, bcat_direct, gamma, beta, parts..., static
+    const BlockState& s = *static_cast<const BlockState*>(ctx->saved_data["state"].toCapsule().get());   // (held by ctx)
+    const int64_t n_parts_w = (int64_t)s.part_shapes.size();
+    variable_list out(8 + n_parts_w);            // x, bias, comb_w, comb_b, bcat_direct, gamma, beta, parts..., state
     if (!grads[0].defined()) return out;
     const at::Tensor& x = saved[0];
     const at::Tensor &packed = saved[1], &packed_t = saved[2];
-    const auto* l = reinterpret_cast<const egc_layer*>(s.layer);
+    const egc_layer* l = &s.layer;
     auto st = reinterpret_cast<egc_stream_t>(s.stream);
     const c10::OptionalDeviceGuard device_guard(x.device());
     const auto opts = x.options();
-    const int64_t n = x.size(0), f_in = s.f_in, f_out = l->out_channels, W = s.H * s.B * s.A, ldb = egc_bases_ld(l), k = ldb + W;
+    const int64_t n = x.size(0), f_in = l->in_channels, f_out = l->out_channels, W = s.H * s.B * s.A, ldb = egc_bases_ld(l), k = ldb + W;
     at::Tensor go = grads[0].contiguous();
     check_f32(go, "grad_out");
     at::Tensor g_conv = go, dh_sums;
     if (s.with_tail) {
-      const at::Tensor &h = saved[3], &affine = saved[4], &stats = saved[5], &gamma_c = saved[6];
-      const int64_t c = f_out;
-      const int64_t n_parts = std::max<int64_t>(1, std::min<int64_t>(1024, (n + 127) / 128));
-      at::Tensor partials = at::empty({n_parts, 2, c}, opts.dtype(at::kDouble)), out5 = at::empty({5, c}, opts);
-      const float* a0 = affine.data_ptr<float>();
-      if (has[0]) dh_sums = at::empty({c}, opts);      // the layer's bias gradient = the column sums of dh: from this step's own sums
-      check_status(egc_bn_backward_stats_sums_f32(go.data_ptr<float>(), h.data_ptr<float>(), a0, a0 + c, s.relu ? 1 : 0, nullptr, 1.0f, n, (int32_t)c,
-                                                  partials.data_ptr<double>(), (int32_t)n_parts, nullptr, stats.data_ptr<double>(),
-                                                  gamma_c.defined() ? gamma_c.data_ptr<float>() : nullptr, out5.data_ptr<float>(),
-                                                  dh_sums.defined() ? dh_sums.data_ptr<float>() : nullptr, nullptr, st),
-                   "egc_bn_backward_stats_sums_f32");
-      at::Tensor dh = at::empty({n, c}, opts);
-      const float* o5 = out5.data_ptr<float>();
-      check_status(egc_affine_act_backward_f32(go.data_ptr<float>(), h.data_ptr<float>(), a0, a0 + c, s.relu ? 1 : 0, nullptr, 1.0f, o5 + 2 * c,
-                                               o5 + 3 * c, o5 + 4 * c, n, (int32_t)c, dh.data_ptr<float>(), nullptr, st),
-                   "egc_affine_act_backward_f32");
-      if (has[3]) out[5] = out5[0];
-      if (has[4]) out[6] = out5[1];
-      g_conv = dh;
+      at::Tensor dgamma, dbeta;
+      std::tie(g_conv, dgamma, dbeta, dh_sums) = bn_tail_backward(go, saved[3], saved[4], saved[5], saved[6], s.has_bias, s);
+      if (s.has_gamma) out[5] = dgamma;
+      if (s.has_beta) out[6] = dbeta;
     }
     // the layer's backward, one launch; the residual branch's gradient (x = x + ...) joins d x in its store
     at::Tensor dx = at::empty({n, f_in}, opts), d_cat = at::empty({n, k}, opts);
@@ -448,177 +492,77 @@ struct BatchBlockTrainFn : public torch::autograd::Function<BatchBlockTrainFn> {
                                                     reinterpret_cast<int32_t*>(s.host_flag), st), "egc_layer_backward_batch_fused_f32");
     out[0] = dx;
     // x^T d_cat + the column sums of d_cat's weightings part (combination bias) and of the layer's incoming gradient (its bias)
-    at::Tensor es = at::empty({f_out}, opts), dcw = at::empty(shapes[0], opts);
-    at::Tensor dcb = has[1] ? at::empty(shapes[1], opts) : at::empty({W}, opts);
+    at::Tensor es = at::empty({f_out}, opts), dcw = at::empty(s.comb_w_shape, opts);
+    at::Tensor dcb = s.has_comb_b ? at::empty(s.comb_b_shape, opts) : at::empty({W}, opts);
     std::vector<at::Tensor> dparts;
     std::vector<float*> ptrs;
     for (int64_t i = 0; i < n_parts_w; ++i) {
-      dparts.push_back(at::empty(shapes[2 + i], opts));
+      dparts.push_back(at::empty(s.part_shapes[i], opts));
       ptrs.push_back(dparts.back().data_ptr<float>());
     }
     // (the layer's bias gradient: from the BatchNorm step above where there is one, else -- and when nobody asks -- no third stream)
-    const bool ride = has[0] && !dh_sums.defined();
+    const bool ride = s.has_bias && !dh_sums.defined();
     const int64_t gbytes = egc_weight_grad_ex_workspace_bytes(n, (int32_t)f_in, (int32_t)k, ride ? (int32_t)f_out : 0);
     at::Tensor gws = at::empty({std::max<int64_t>(gbytes, 16)}, opts.dtype(at::kByte));
     check_status(egc_weight_grad_params_f32(x.data_ptr<float>(), f_in, d_cat.data_ptr<float>(), k, n, (int32_t)f_in, (int32_t)s.H, (int32_t)s.A,
                                             (int32_t)s.B, (int32_t)s.L, (int32_t)s.Ls, s.permute_hab ? 1 : 0, ptrs.data(), (int32_t)n_parts_w,
-                                            dcw.data_ptr<float>(), has[1] ? dcb.data_ptr<float>() : nullptr, has[1] ? nullptr : dcb.data_ptr<float>(),
-                                            ride ? g_conv.data_ptr<float>() : nullptr, f_out, ride ? (int32_t)f_out : 0,
-                                            ride ? es.data_ptr<float>() : nullptr, gws.data_ptr(), gws.numel(),
-                                            reinterpret_cast<void*>(s.stream)), "egc_weight_grad_params_f32");
-    if (has[0]) out[1] = dh_sums.defined() ? dh_sums : es;
+                                            dcw.data_ptr<float>(), s.has_comb_b ? dcb.data_ptr<float>() : nullptr,
+                                            s.has_comb_b ? nullptr : dcb.data_ptr<float>(), ride ? g_conv.data_ptr<float>() : nullptr, f_out,
+                                            ride ? (int32_t)f_out : 0, ride ? es.data_ptr<float>() : nullptr, gws.data_ptr(), gws.numel(), st),
+                 "egc_weight_grad_params_f32");
+    if (s.has_bias) out[1] = dh_sums.defined() ? dh_sums : es;
     out[2] = dcw;
-    if (has[1]) out[3] = dcb;
-    if (has[2]) out[4] = dcb;
+    if (s.has_comb_b) out[3] = dcb;
+    if (s.has_bcat) out[4] = dcb;
     for (int64_t i = 0; i < n_parts_w; ++i) out[7 + i] = dparts[i];
     return out;
   }
 };
 
-static void save_static(AutogradContext* ctx, const BlockStatic& s) {
-  // (the batch's tensors are kept alive for the backward; BatchNorm's buffers are not needed there)
-  std::vector<at::Tensor> ts;
-  std::vector<int64_t> present;
-  for (const at::Tensor* t : {&s.ptr, &s.edge_ptr, &s.src, &s.dst, &s.max_index, &s.status}) {
-    present.push_back(t->defined() ? 1 : 0);
-    ts.push_back(t->defined() ? *t : s.ptr);
-  }
-  ctx->saved_data["batch"] = ts;
-  ctx->saved_data["present"] = present;
-  ctx->saved_data["ints"] = std::vector<int64_t>{s.host_flag, s.layer, s.stream, s.f_in, s.H, s.A, s.B, s.L, s.Ls, s.permute_hab ? 1 : 0, s.tile_f,
-                                                s.emax_f, s.tile_b, s.emax_b, s.relu ? 1 : 0, s.residual ? 1 : 0, s.with_tail ? 1 : 0};
-}
-static BlockStatic load_static(AutogradContext* ctx) {
-  BlockStatic s;
-  const auto ts = ctx->saved_data["batch"].toTensorVector();
-  const auto pr = ctx->saved_data["present"].toIntVector();
-  at::Tensor* dst[6] = {&s.ptr, &s.edge_ptr, &s.src, &s.dst, &s.max_index, &s.status};
-  for (int i = 0; i < 6; ++i) if (pr[i]) *dst[i] = ts[i];
-  const auto v = ctx->saved_data["ints"].toIntVector();
-  s.host_flag = v[0]; s.layer = v[1]; s.stream = v[2]; s.f_in = v[3]; s.H = v[4]; s.A = v[5]; s.B = v[6]; s.L = v[7]; s.Ls = v[8];
-  s.permute_hab = v[9] != 0; s.tile_f = v[10]; s.emax_f = v[11]; s.tile_b = v[12]; s.emax_b = v[13];
-  s.relu = v[14] != 0; s.residual = v[15] != 0; s.with_tail = v[16] != 0;
-  s.eps = 0; s.momentum = 0;
-  return s;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // The same block on the CSR path (round 6): x -> x + relu(bn(conv(x))) for layers and batches outside the one-launch training
 // envelope -- the reference's own batched nets (168 / 224 / 296 / 300 / 304 wide: run_pretrained.sh:7-48), full graphs -- as ONE
 // autograd node: train_forward (pack, planes, GEMM, training aggregate) + the BatchNorm tail forward; the tail's backward +
-// train_backward (sparse backward, d x GEMM, dense gradients into the parameters) + the residual branch's gradient backward.
-// The graph structs are COPIED into the node (their Python owners may be gone when the backward runs); `keep` holds the device
-// tensors they point into.
+// train_backward_impl (sparse backward, d x GEMM, dense gradients into the parameters) + the residual branch's gradient backward.
 // ---------------------------------------------------------------------------------------------------------------------
-struct CsrStatic {
-  egc_graph g, tg;
-  at::Tensor workspace, running_mean, running_var, n_tracked;
-  std::vector<at::Tensor> keep;
-  int64_t layer, stream, H, A, B, L, Ls, gemm_flags;
-  bool permute_hab;
-  double eps, momentum;
-  bool relu, residual, with_tail;
-};
-
 struct CsrBlockTrainFn : public torch::autograd::Function<CsrBlockTrainFn> {
   static at::Tensor forward(AutogradContext* ctx, const at::Tensor& x, const c10::optional<at::Tensor>& bias, const at::Tensor& comb_w,
                             const c10::optional<at::Tensor>& comb_b, const c10::optional<at::Tensor>& bcat_direct,
                             const c10::optional<at::Tensor>& gamma, const c10::optional<at::Tensor>& beta, at::TensorList parts,
-                            const CsrStatic& s) {
+                            const c10::intrusive_ptr<BlockState>& state) {
+    const BlockState& s = *state;
     const c10::OptionalDeviceGuard device_guard(x.device());
-    auto r = train_forward(x, comb_w, comb_b, bcat_direct, parts, bias, reinterpret_cast<int64_t>(&s.g), s.layer, s.workspace, s.stream,
-                           s.H, s.A, s.B, s.L, s.Ls, s.permute_hab, s.gemm_flags);
+    auto r = train_forward(x, comb_w, comb_b, bcat_direct, parts, bias, &s.g, &s.layer, s.workspace, s.stream, s.H, s.A, s.B, s.L, s.Ls,
+                           s.permute_hab, s.gemm_flags);
     const at::Tensor& h = r[0];
-    const auto* l = reinterpret_cast<const egc_layer*>(s.layer);
-    auto st = reinterpret_cast<egc_stream_t>(s.stream);
-    const int64_t n = x.size(0), c = l->out_channels;
-    const auto opts = x.options();
-    ctx->saved_data["graphs"] = std::string(reinterpret_cast<const char*>(&s.g), sizeof(egc_graph)) +
-                                std::string(reinterpret_cast<const char*>(&s.tg), sizeof(egc_graph));
-    ctx->saved_data["keep"] = s.keep;
-    ctx->saved_data["ints"] = std::vector<int64_t>{s.layer, s.stream, s.H, s.A, s.B, s.L, s.Ls, s.permute_hab ? 1 : 0, s.relu ? 1 : 0,
-                                                  s.residual ? 1 : 0, s.with_tail ? 1 : 0, comb_b.has_value() ? 1 : 0,
-                                                  bias.has_value() ? 1 : 0, gamma.has_value() ? 1 : 0, beta.has_value() ? 1 : 0,
-                                                  (int64_t)parts.size()};
-    ctx->saved_data["comb_w_shape"] = comb_w.sizes().vec();
-    ctx->saved_data["comb_b_shape"] = comb_b.has_value() ? comb_b->sizes().vec() : std::vector<int64_t>{0};
-    ctx->saved_data["part_shape"] = parts[0].sizes().vec();
-    if (!s.with_tail) {
-      ctx->save_for_backward({x, r[1], r[3], r[4], r[5], r[6], r[7], r[8]});
-      return h;
-    }
-    const int64_t n_parts = std::max<int64_t>(1, std::min<int64_t>(1024, (n + 127) / 128));
-    at::Tensor partials = at::empty({n_parts, 2, c}, opts.dtype(at::kDouble)), stats = at::empty({3, c}, opts.dtype(at::kDouble));
-    at::Tensor affine = at::empty({2, c}, opts), out = at::empty({n, c}, opts);
-    at::Tensor gamma_c = gamma.has_value() ? gamma->detach() : at::Tensor();
-    if (gamma.has_value()) check_f32(*gamma, "BatchNorm weight");
-    if (beta.has_value()) check_f32(*beta, "BatchNorm bias");
-    const bool track = s.running_mean.defined();
-    int64_t* cnt = s.n_tracked.defined() ? s.n_tracked.data_ptr<int64_t>() : nullptr;
-    check_status(egc_bn_forward_stats_f32(h.data_ptr<float>(), n, (int32_t)c, partials.data_ptr<double>(), (int32_t)n_parts,
-                                          track ? cnt : nullptr, nullptr, fptr(gamma), fptr(beta), s.eps, stats.data_ptr<double>(),
-                                          affine.data_ptr<float>(), track ? s.running_mean.data_ptr<float>() : nullptr,
-                                          track ? s.running_var.data_ptr<float>() : nullptr, s.momentum, cnt, nullptr, st),
-                 "egc_bn_forward_stats_f32");
-    check_status(egc_affine_act_residual_f32(h.data_ptr<float>(), affine.data_ptr<float>(), affine.data_ptr<float>() + c,
-                                             s.residual ? x.data_ptr<float>() : nullptr, s.relu ? 1 : 0, nullptr, 1.0f, n, (int32_t)c,
-                                             out.data_ptr<float>(), nullptr, st), "egc_affine_act_residual_f32");
-    ctx->save_for_backward({x, r[1], r[3], r[4], r[5], r[6], r[7], r[8], h, affine, stats, gamma_c});
+    ctx->saved_data["state"] = c10::IValue::make_capsule(state);
+    auto [out, affine, stats] = bn_tail_forward(h, x, gamma, beta, s);
+    state->release_forward_operands();
+    ctx->save_for_backward({x, r[1], r[3], r[4], r[5], r[6], r[7], r[8], h, affine, stats, gamma.has_value() ? gamma->detach() : at::Tensor()});
     return out;
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     const auto saved = ctx->get_saved_variables();
-    const auto v = ctx->saved_data["ints"].toIntVector();
-    const int64_t layer = v[0], stream = v[1], H = v[2], A = v[3], B = v[4], L = v[5], Ls = v[6], n_parts_w = v[15];
-    const bool permute = v[7] != 0, relu = v[8] != 0, residual = v[9] != 0, with_tail = v[10] != 0, packed_bias = v[11] != 0;
-    const bool has_bias = v[12] != 0, has_gamma = v[13] != 0, has_beta = v[14] != 0;
-    variable_list out(8 + n_parts_w);            // x, bias, comb_w, comb_b, bcat_direct, gamma, beta, parts..., static
+    const BlockState& s = *static_cast<const BlockState*>(ctx->saved_data["state"].toCapsule().get());   // (held by ctx)
+    const int64_t n_parts_w = (int64_t)s.part_shapes.size();
+    variable_list out(8 + n_parts_w);            // x, bias, comb_w, comb_b, bcat_direct, gamma, beta, parts..., state
     if (!grads[0].defined()) return out;
-    const std::string gs = ctx->saved_data["graphs"].toStringRef();
-    egc_graph g, tg;
-    std::memcpy(&g, gs.data(), sizeof(egc_graph));
-    std::memcpy(&tg, gs.data() + sizeof(egc_graph), sizeof(egc_graph));
     const at::Tensor& x = saved[0];
     const c10::OptionalDeviceGuard device_guard(x.device());
-    const auto opts = x.options();
-    auto st = reinterpret_cast<egc_stream_t>(stream);
-    const auto* l = reinterpret_cast<const egc_layer*>(layer);
-    const int64_t n = x.size(0), c = l->out_channels;
     at::Tensor go = grads[0].contiguous();
     check_f32(go, "grad_out");
-    at::Tensor g_conv = go, dh_sums;
-    if (with_tail) {
-      const at::Tensor &h = saved[8], &affine = saved[9], &stats = saved[10], &gamma_c = saved[11];
-      const int64_t n_parts = std::max<int64_t>(1, std::min<int64_t>(1024, (n + 127) / 128));
-      at::Tensor partials = at::empty({n_parts, 2, c}, opts.dtype(at::kDouble)), out5 = at::empty({5, c}, opts);
-      const float* a0 = affine.data_ptr<float>();
-      dh_sums = at::empty({c}, opts);                   // the layer's bias gradient = the column sums of dh: from this step's own sums
-      check_status(egc_bn_backward_stats_sums_f32(go.data_ptr<float>(), h.data_ptr<float>(), a0, a0 + c, relu ? 1 : 0, nullptr, 1.0f, n, (int32_t)c,
-                                                  partials.data_ptr<double>(), (int32_t)n_parts, nullptr, stats.data_ptr<double>(),
-                                                  gamma_c.defined() ? gamma_c.data_ptr<float>() : nullptr, out5.data_ptr<float>(),
-                                                  dh_sums.data_ptr<float>(), nullptr, st),
-                   "egc_bn_backward_stats_sums_f32");
-      at::Tensor dh = at::empty({n, c}, opts);
-      const float* o5 = out5.data_ptr<float>();
-      check_status(egc_affine_act_backward_f32(go.data_ptr<float>(), h.data_ptr<float>(), a0, a0 + c, relu ? 1 : 0, nullptr, 1.0f, o5 + 2 * c,
-                                               o5 + 3 * c, o5 + 4 * c, n, (int32_t)c, dh.data_ptr<float>(), nullptr, st),
-                   "egc_affine_act_backward_f32");
-      if (has_gamma) out[5] = out5[0];
-      if (has_beta) out[6] = out5[1];
-      g_conv = dh;
-    }
-    const auto cws = ctx->saved_data["comb_w_shape"].toIntVector(), cbs = ctx->saved_data["comb_b_shape"].toIntVector();
-    const auto ps = ctx->saved_data["part_shape"].toIntVector();
+    auto [dh, dgamma, dbeta, dh_sums] = bn_tail_backward(go, saved[8], saved[9], saved[10], saved[11], true, s);
+    if (s.has_gamma) out[5] = dgamma;
+    if (s.has_beta) out[6] = dbeta;
     // the residual branch's gradient (x = x + ...) joins d x in the d x GEMM's store where that kernel takes an addend
-    auto r = train_backward_impl(g_conv, x, saved[1], saved[2], saved[3], saved[4], saved[5], saved[6], saved[7], reinterpret_cast<int64_t>(&g),
-                                 reinterpret_cast<int64_t>(&tg), layer, stream, H, A, B, L, Ls, permute, packed_bias, true, cws, cbs, n_parts_w, ps,
-                                 (with_tail && residual) ? &go : nullptr, dh_sums.defined() ? &dh_sums : nullptr);
-    at::Tensor dx = r[0];
-    out[0] = dx;
-    if (has_bias) out[1] = r[3];
+    auto r = train_backward_impl(dh, x, saved[1], saved[2], saved[3], saved[4], saved[5], saved[6], saved[7], &s.g, &s.tg, &s.layer,
+                                 s.stream, s.H, s.A, s.B, s.L, s.Ls, s.permute_hab, s.has_comb_b, true, s.comb_w_shape, s.comb_b_shape,
+                                 n_parts_w, s.part_shapes[0], s.residual ? &go : nullptr, &dh_sums);
+    out[0] = r[0];
+    if (s.has_bias) out[1] = r[3];
     out[2] = r[1];
-    if (packed_bias) out[3] = r[2]; else out[4] = r[2];
+    if (s.has_comb_b) out[3] = r[2]; else out[4] = r[2];
     for (int64_t i = 0; i < n_parts_w; ++i) out[7 + i] = r[4 + i];
     return out;
   }
@@ -630,26 +574,17 @@ at::Tensor csr_block_train(const at::Tensor& x, const c10::optional<at::Tensor>&
                            const c10::optional<at::Tensor>& running_mean, const c10::optional<at::Tensor>& running_var,
                            const c10::optional<at::Tensor>& n_tracked, int64_t graph, int64_t t_graph, at::TensorList keep,
                            const at::Tensor& workspace, int64_t layer, int64_t stream, at::IntArrayRef dims, bool permute_hab,
-                           int64_t gemm_flags, double eps, double momentum, bool relu, bool residual, bool with_tail) {
+                           int64_t gemm_flags, double eps, double momentum, bool residual) {
   TORCH_CHECK(dims.size() == 5, "egc_amd: dims = (H, A, B, L, Ls)");
   TORCH_CHECK(parts.size() >= 1, "egc_amd: at least one basis matrix");
-  check_block_operands(x, layer, gamma, beta, running_mean, running_var, residual, with_tail);
-  CsrStatic s;
-  s.g = *reinterpret_cast<const egc_graph*>(graph);
-  s.tg = *reinterpret_cast<const egc_graph*>(t_graph);
-  s.keep = keep.vec();
-  s.workspace = workspace;
-  if (running_mean.has_value()) {
-    TORCH_CHECK(running_var.has_value(), "egc_amd: running_mean and running_var come together");
-    check_f32(*running_mean, "running_mean"); check_f32(*running_var, "running_var");
-    s.running_mean = *running_mean; s.running_var = *running_var;
-  }
-  if (n_tracked.has_value()) { TORCH_CHECK(n_tracked->is_cuda() && n_tracked->scalar_type() == at::kLong && n_tracked->numel() == 1, "egc_amd: num_batches_tracked"); s.n_tracked = *n_tracked; }
-  TORCH_CHECK(momentum >= 0 || !s.running_mean.defined() || s.n_tracked.defined(), "egc_amd: a cumulative average needs num_batches_tracked");
-  s.layer = layer; s.stream = stream;
-  s.H = dims[0]; s.A = dims[1]; s.B = dims[2]; s.L = dims[3]; s.Ls = dims[4];
-  s.gemm_flags = gemm_flags; s.permute_hab = permute_hab;
-  s.eps = eps; s.momentum = momentum; s.relu = relu; s.residual = residual; s.with_tail = with_tail;
+  auto s = block_state(x, bias, comb_w, comb_b, bcat_direct, gamma, beta, parts, running_mean, running_var, n_tracked,
+                       reinterpret_cast<const egc_layer*>(layer), stream, permute_hab, eps, momentum, residual, /*with_tail=*/true);
+  s->g = *reinterpret_cast<const egc_graph*>(graph);
+  s->tg = *reinterpret_cast<const egc_graph*>(t_graph);
+  s->keep = keep.vec();
+  s->workspace = workspace;
+  s->H = dims[0]; s->A = dims[1]; s->B = dims[2]; s->L = dims[3]; s->Ls = dims[4];
+  s->gemm_flags = gemm_flags;
   return CsrBlockTrainFn::apply(x, bias, comb_w, comb_b, bcat_direct, gamma, beta, parts, s);
 }
 
@@ -660,7 +595,7 @@ at::Tensor batch_block_train(const at::Tensor& x, const c10::optional<at::Tensor
                              const c10::optional<at::Tensor>& n_tracked, const at::Tensor& ptr, const c10::optional<at::Tensor>& edge_ptr,
                              const at::Tensor& src, const at::Tensor& dst, const c10::optional<at::Tensor>& max_index, const at::Tensor& status,
                              int64_t host_flag, int64_t layer, int64_t stream, at::IntArrayRef dims, bool permute_hab, at::IntArrayRef setups,
-                             double eps, double momentum, bool relu, bool residual, bool with_tail) {
+                             double eps, double momentum, bool residual, bool with_tail) {
   TORCH_CHECK(dims.size() == 6 && setups.size() == 4, "egc_amd: dims = (f_in, H, A, B, L, Ls), setups = (tile_f, emax_f, tile_b, emax_b)");
   auto i64 = [](const at::Tensor& t, const char* name) {
     TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(), "egc_amd: ", name, " must be a dense int64 tensor on the device");
@@ -668,23 +603,15 @@ at::Tensor batch_block_train(const at::Tensor& x, const c10::optional<at::Tensor
   i64(ptr, "ptr"); i64(src, "edge_index[0]"); i64(dst, "edge_index[1]");
   TORCH_CHECK(src.numel() == dst.numel() && ptr.numel() >= 1, "egc_amd: malformed batch");
   TORCH_CHECK(status.is_cuda() && status.scalar_type() == at::kInt, "egc_amd: status word");
-  check_block_operands(x, layer, gamma, beta, running_mean, running_var, residual, with_tail);
-  BlockStatic s;
-  s.ptr = ptr; s.src = src; s.dst = dst; s.status = status;
-  if (edge_ptr.has_value()) { i64(*edge_ptr, "edge_ptr"); TORCH_CHECK(edge_ptr->numel() == ptr.numel(), "egc_amd: edge_ptr"); s.edge_ptr = *edge_ptr; }
-  if (max_index.has_value()) { TORCH_CHECK(max_index->is_cuda() && max_index->scalar_type() == at::kInt, "egc_amd: max_index"); s.max_index = *max_index; }
-  if (running_mean.has_value()) {
-    TORCH_CHECK(running_var.has_value(), "egc_amd: running_mean and running_var come together");
-    check_f32(*running_mean, "running_mean"); check_f32(*running_var, "running_var");
-    s.running_mean = *running_mean; s.running_var = *running_var;
-  }
-  if (n_tracked.has_value()) { TORCH_CHECK(n_tracked->is_cuda() && n_tracked->scalar_type() == at::kLong && n_tracked->numel() == 1, "egc_amd: num_batches_tracked"); s.n_tracked = *n_tracked; }
-  TORCH_CHECK(momentum >= 0 || !s.running_mean.defined() || s.n_tracked.defined(), "egc_amd: a cumulative average needs num_batches_tracked");
-  s.host_flag = host_flag; s.layer = layer; s.stream = stream;
-  s.f_in = dims[0]; s.H = dims[1]; s.A = dims[2]; s.B = dims[3]; s.L = dims[4]; s.Ls = dims[5];
-  s.permute_hab = permute_hab;
-  s.tile_f = setups[0]; s.emax_f = setups[1]; s.tile_b = setups[2]; s.emax_b = setups[3];
-  s.eps = eps; s.momentum = momentum; s.relu = relu; s.residual = residual; s.with_tail = with_tail;
+  auto s = block_state(x, bias, comb_w, comb_b, bcat_direct, gamma, beta, parts, running_mean, running_var, n_tracked,
+                       reinterpret_cast<const egc_layer*>(layer), stream, permute_hab, eps, momentum, residual, with_tail);
+  TORCH_CHECK(dims[0] == s->layer.in_channels, "egc_amd: dims[0] is not the layer's in_channels");
+  s->ptr = ptr; s->src = src; s->dst = dst; s->status = status;
+  if (edge_ptr.has_value()) { i64(*edge_ptr, "edge_ptr"); TORCH_CHECK(edge_ptr->numel() == ptr.numel(), "egc_amd: edge_ptr"); s->edge_ptr = *edge_ptr; }
+  if (max_index.has_value()) { TORCH_CHECK(max_index->is_cuda() && max_index->scalar_type() == at::kInt, "egc_amd: max_index"); s->max_index = *max_index; }
+  s->host_flag = host_flag;
+  s->H = dims[1]; s->A = dims[2]; s->B = dims[3]; s->L = dims[4]; s->Ls = dims[5];
+  s->tile_f = setups[0]; s->emax_f = setups[1]; s->tile_b = setups[2]; s->emax_b = setups[3];
   return BatchBlockTrainFn::apply(x, bias, comb_w, comb_b, bcat_direct, gamma, beta, parts, s);
 }
 
@@ -705,23 +632,23 @@ TORCH_LIBRARY(egc_amd_native, m) {
   m.def("batch_block_train(Tensor x, Tensor? bias, Tensor comb_w, Tensor? comb_b, Tensor? bcat_direct, Tensor? gamma, Tensor? beta, "
         "Tensor[] parts, Tensor(a!)? running_mean, Tensor(b!)? running_var, Tensor(c!)? n_tracked, Tensor ptr, Tensor? edge_ptr, Tensor src, "
         "Tensor dst, Tensor? max_index, Tensor status, int host_flag, int layer, int stream, int[] dims, bool permute_hab, int[] setups, "
-        "float eps, float momentum, bool relu, bool residual, bool with_tail) -> Tensor");
+        "float eps, float momentum, bool residual, bool with_tail) -> Tensor");
   m.def("csr_block_train(Tensor x, Tensor? bias, Tensor comb_w, Tensor? comb_b, Tensor? bcat_direct, Tensor? gamma, Tensor? beta, "
         "Tensor[] parts, Tensor(a!)? running_mean, Tensor(b!)? running_var, Tensor(c!)? n_tracked, int graph, int t_graph, Tensor[] keep, "
-        "Tensor workspace, int layer, int stream, int[] dims, bool permute_hab, int gemm_flags, float eps, float momentum, bool relu, "
-        "bool residual, bool with_tail) -> Tensor");
+        "Tensor workspace, int layer, int stream, int[] dims, bool permute_hab, int gemm_flags, float eps, float momentum, "
+        "bool residual) -> Tensor");
 }
 
 // HIP devices only (PyTorch-ROCm dispatches them under the CUDA key): a CPU tensor finds no kernel and the dispatcher raises
 TORCH_LIBRARY_IMPL(egc_amd_native, CUDA, m) {
   m.impl("layer_forward", &layer_forward);
   m.impl("layer_forward_post", &layer_forward_post);
-  m.impl("train_forward", &train_forward);
-  m.impl("train_backward", &train_backward);
+  m.impl("train_forward", &train_forward_op);
+  m.impl("train_backward", &train_backward_op);
 }
 
-// the batch training block carries its own autograd node (BatchBlockTrainFn): registered at the Autograd key, which is where a call
-// with parameters that require gradients enters; the node's forward issues the library's launches itself (no dispatcher re-entry)
+// the block ops carry their own autograd nodes (BatchBlockTrainFn, CsrBlockTrainFn): registered at the Autograd key, which is where a
+// call with parameters that require gradients enters; the node's forward issues the library's launches itself (no dispatcher re-entry)
 TORCH_LIBRARY_IMPL(egc_amd_native, Autograd, m) {
   m.impl("batch_block_train", &batch_block_train);
   m.impl("csr_block_train", &csr_block_train);

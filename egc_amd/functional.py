@@ -689,14 +689,27 @@ def _native_train_ops(graph, spec, x, bias, comb_w, comb_b, bcat_direct, bases):
     return nat
 
 
-def _tail_shapes_fit(spec, bn, residual):
-    """The block's tail reads bn.weight / bn.bias as [f_out] and adds x as an [N, f_out] residual: a module of other widths is
-    declined (the Python route then raises torch's own shape error, as the unfused composition does)."""
-    return ((not residual or spec.f_in == spec.f_out) and bn.weight is not None and bn.weight.numel() == spec.f_out
-            and bn.bias is not None and bn.bias.numel() == spec.f_out)
+def _bn_tail_operands(spec, bn, residual):
+    """The BatchNorm operands of a block node's tail -- (gamma, beta, running_mean, running_var, num_batches_tracked, eps,
+    momentum) -- or None when the BatchNorm is outside the node's envelope.  The tail reads bn.weight / bn.bias as [f_out] and
+    adds x as an [N, f_out] residual: a module of other widths is declined (the Python route then raises torch's own shape
+    error, as the unfused composition does)."""
+    if not (bn.training and bn.affine and spec.f_out % 4 == 0 and spec.f_out <= 1024) or (residual and spec.f_in != spec.f_out):
+        return None
+    gamma, beta = bn.weight, bn.bias
+    if any(t is None or t.numel() != spec.f_out or not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous())
+           for t in (gamma, beta)):
+        return None
+    rm = rv = nt = None
+    if bn.track_running_stats:
+        rm, rv, nt = bn.running_mean, bn.running_var, bn.num_batches_tracked
+        if not (_f32_vec(rm, spec.f_out) and _f32_vec(rv, spec.f_out) and rm.is_cuda and nt is not None and nt.dtype == torch.int64
+                and nt.is_cuda):
+            return None
+    return gamma, beta, rm, rv, nt, float(bn.eps), -1.0 if bn.momentum is None else float(bn.momentum)
 
 
-def native_block_train(call, bn=None, relu=True, residual=True, with_tail=True):
+def native_block_train(call, bn=None, residual=True, with_tail=True):
     """The training call of a layer on a GraphBatch -- with ``with_tail`` the whole block x -> x + relu(bn(conv(x))) of the
     reference's batched nets (zinc/models.py:66-73) -- as ONE autograd node of the compiled binding (egc_torch_ext.cpp:
     batch_block_train), or None when the call is outside its envelope (the Python Functions below then, same kernels).
@@ -726,17 +739,10 @@ def native_block_train(call, bn=None, relu=True, residual=True, with_tail=True):
     gamma = beta = rm = rv = nt = None
     eps, momentum = 1e-5, 0.1
     if with_tail:
-        if not (relu and bn.training and bn.affine and spec.f_out % 4 == 0) or not _tail_shapes_fit(spec, bn, residual):
+        tail = _bn_tail_operands(spec, bn, residual)
+        if tail is None:
             return None
-        gamma, beta, eps = bn.weight, bn.bias, float(bn.eps)
-        if any(not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in (gamma, beta)):
-            return None
-        if bn.track_running_stats:
-            rm, rv, nt = bn.running_mean, bn.running_var, bn.num_batches_tracked
-            if not (_f32_vec(rm, spec.f_out) and _f32_vec(rv, spec.f_out) and rm.is_cuda and nt is not None and nt.dtype == torch.int64
-                    and nt.is_cuda):
-                return None
-        momentum = -1.0 if bn.momentum is None else float(bn.momentum)
+        gamma, beta, rm, rv, nt, eps, momentum = tail
     setups = _batch_fused_train_setup(graph, spec, x)
     if setups is None:
         return None
@@ -746,11 +752,10 @@ def native_block_train(call, bn=None, relu=True, residual=True, with_tail=True):
     return nat.batch_block_train(x, bias, comb_w, comb_b, bcat_direct, gamma, beta, list(bases), rm, rv, nt, graph.ptr, graph.edge_ptr,
                                  src, dst, graph.max_index() if needs_max else None, graph.status(), _IndexFlag.ptr() or 0, spec.c_addr,
                                  _stream_ptr(x.device), (int(f_in), int(H), int(A), int(B), int(L), int(Ls)), bool(permute),
-                                 (setups[0][0], setups[0][1], setups[1][0], setups[1][1]), eps, momentum, bool(relu), bool(residual),
-                                 bool(with_tail))
+                                 (setups[0][0], setups[0][1], setups[1][0], setups[1][1]), eps, momentum, bool(residual), bool(with_tail))
 
 
-def native_csr_block_train(call, bn, relu=True, residual=True):
+def native_csr_block_train(call, bn, residual=True):
     """The block x -> x + relu(bn(conv(x))) in training on the CSR path -- layers and batches outside the one-launch training
     envelope: the reference's own 168 - 304-wide batched nets, full graphs -- as ONE autograd node of the compiled binding
     (egc_torch_ext.cpp: csr_block_train = train_forward + the BatchNorm tail / its backward + train_backward + the residual
@@ -773,22 +778,15 @@ def native_csr_block_train(call, bn, relu=True, residual=True):
     cb = comb_b if comb_b is not None else bcat_direct
     if any(not t.requires_grad for t in (bias, comb_w, cb, *bases)):
         return None
-    if not (relu and bn.training and bn.affine and spec.f_out % 4 == 0 and spec.f_out <= 1024) or not _tail_shapes_fit(spec, bn, residual):
+    tail = _bn_tail_operands(spec, bn, residual)
+    if tail is None:
         return None
-    gamma, beta = bn.weight, bn.bias
-    if any(not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in (gamma, beta)):
-        return None
-    rm = rv = nt = None
-    if bn.track_running_stats:
-        rm, rv, nt = bn.running_mean, bn.running_var, bn.num_batches_tracked
-        if not (_f32_vec(rm, spec.f_out) and _f32_vec(rv, spec.f_out) and rm.is_cuda and nt is not None and nt.dtype == torch.int64
-                and nt.is_cuda):
-            return None
+    gamma, beta, rm, rv, nt, eps, momentum = tail
     tg = graph.transposed()
     return nat.csr_block_train(x, bias, comb_w, comb_b, bcat_direct, gamma, beta, list(bases), rm, rv, nt, graph.c_addr(), tg.c_addr(),
                                graph.tensors() + tg.tensors(), graph.workspace_for(spec), spec.c_addr, _stream_ptr(x.device),
-                               (int(H), int(A), int(B), int(L), int(Ls)), bool(permute), spec.gemm_flags, float(bn.eps),
-                               -1.0 if bn.momentum is None else float(bn.momentum), True, bool(residual), True)
+                               (int(H), int(A), int(B), int(L), int(Ls)), bool(permute), spec.gemm_flags, eps, momentum,
+                               bool(residual))
 
 
 def _layer_forward_one_call(graph: CSRGraph, spec: LayerSpec, x, packed, bcat, bias):

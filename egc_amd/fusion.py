@@ -68,9 +68,9 @@ class FusedEGCBlock(nn.Module):
                 and not (self.residual and _C.env_flag("EGC_NO_RESIDUAL_LINK"))):
             call = self.conv._train_call(x, edge_index)
             if call is not None:
-                out = native_block_train(call, bn, relu=True, residual=bool(self.residual), with_tail=True)
+                out = native_block_train(call, bn, residual=bool(self.residual))
                 if out is None:      # outside the one-launch envelope (the reference's wide nets, full graphs): the CSR path's node
-                    out = native_csr_block_train(call, bn, relu=True, residual=bool(self.residual))
+                    out = native_csr_block_train(call, bn, residual=bool(self.residual))
                 if out is not None:
                     return out
         # the residual branch's gradient may join d x inside the conv's backward launch (functional.ResidualLink): offered when

@@ -215,3 +215,36 @@ def test_csr_block_train_node_equals_the_python_functions(hidden, H, B, aggrs, a
         _same_gradient(k, a, b, go)
     for a, b in zip(res["native"][3], res["python"][3]):
         assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hidden,node", [(128, "BatchBlockTrainFn"), (224, "CsrBlockTrainFn")])
+def test_block_node_backward_after_its_module_is_freed(hidden, node):
+    """A block node's backward reads the layer and graph descriptions from its own state: run after the block, its conv and their
+    LayerSpec are freed, it gives the x gradient of the same step run with the module alive, bit for bit."""
+    import gc
+    from test_batch_tile_gpu import _messy_batch
+    dev = torch.device("cuda:0")
+    ei, n, ptr = _messy_batch(hidden + 2, n_graphs=150, max_size=60)
+    x0, go = torch.randn(n, hidden, device=dev), torch.randn(n, hidden, device=dev)
+
+    def step():
+        torch.manual_seed(13)
+        if hidden == 128:
+            conv = egc_amd.EGConv(128, 128, aggrs=["sum", "mean", "max", "symnorm"], num_heads=8, num_bases=4)
+        else:
+            conv = egc_amd.EfficientGraphConv(hidden, hidden, 4, 4, False, aggrs=["add", "mean", "max"])
+        block = egc_amd.FusedEGCBlock(conv, torch.nn.BatchNorm1d(hidden)).to(dev).train()
+        x = x0.clone().requires_grad_(True)
+        out = block(x, egc_amd.GraphBatch(ei.to(dev), ptr=ptr.to(dev), max_nodes=60))
+        assert node in out.grad_fn.name(), out.grad_fn.name()
+        return x, out, block
+
+    x, out, block = step()
+    out.backward(go)
+    alive = x.grad.clone()
+    x, out, block = step()
+    del block
+    gc.collect()
+    out.backward(go)
+    assert torch.equal(x.grad, alive)
