@@ -5,7 +5,9 @@ Public surface (mirrors the reference's layer API):
   EGConv               drop-in for experiments/optimized_layers.py:EGConv
   REGConv              drop-in for experiments/rmag/models.py:REGConv (relational EGC)
   FusedEGCBlock        conv -> BatchNorm1d -> ReLU (-> dropout) -> + identity: eval mode in the kernel's store, training
-                       mode in two passes each way; global_mean_pool (differentiable segmented mean)
+                       mode in two passes each way
+  global_mean_pool / global_add_pool / global_max_pool, readout(name)
+                       the graph-level readouts of the reference's nets (differentiable segmented mean / sum / max)
   SparseTensor         minimal adj_t container (torch_sparse is not required)
   CSRGraph             device CSR + degree statistics + long-row plan
   GraphBatch           a PyG-style batch of small graphs (edge_index + graph offsets) for the tile kernels: the CSR of
@@ -19,7 +21,7 @@ from .functional import egc_layer_forward, make_spec, LayerSpec  # noqa: F401
 from .layers import EfficientGraphConv  # noqa: F401
 from .optimized_layers import EGConv  # noqa: F401
 from .relational import REGConv  # noqa: F401
-from .fusion import FusedEGCBlock, global_mean_pool  # noqa: F401
+from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean_pool, readout  # noqa: F401
 from .hipgraph import GraphedStep  # noqa: F401
 from . import ops  # noqa: F401  (registers torch.ops.egc_amd.*)
 

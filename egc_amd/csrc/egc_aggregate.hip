@@ -437,20 +437,6 @@ __global__ void __launch_bounds__(256) column_sums_kernel(const float* __restric
   }
 }
 
-__global__ void __launch_bounds__(256) segment_mean_kernel(const float* __restrict__ x, const int64_t* __restrict__ seg_ptr,
-                                                           int64_t n_segments, int width, float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= n_segments) return;
-  const int64_t r0 = seg_ptr[g], r1 = seg_ptr[g + 1];
-  const float cnt = (float)(r1 > r0 ? r1 - r0 : 1);  // scatter-mean divides the sum by the count
-  for (int c = lane; c < width; c += 64) {
-    float s = 0.f;
-    for (int64_t r = r0; r < r1; ++r) s += x[r * width + c];
-    out[g * width + c] = s / cnt;
-  }
-}
-
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static int validate_layer(const egc_layer* L) {
@@ -568,9 +554,9 @@ int egc_segment_mean_f32(const float* x, const int64_t* seg_ptr, int64_t n_segme
   if (n_segments == 0) return EGC_OK;
   // x may be NULL when every segment is empty (a zero-row tensor has no storage); the kernel then reads nothing
   if (seg_ptr == nullptr || out == nullptr) return EGC_ERR_INVALID;
-  segment_mean_kernel<<<(unsigned)ceil_div(n_segments, 4), 256, 0, stream>>>(x, seg_ptr, n_segments, width, out);
-  EGC_LAUNCH_CHECK("segment_mean_kernel");
-  return EGC_OK;
+  // the mean form of the readout kernel (egc_readout.hip): same sum order, same division, same bits; this entry has no
+  // row count, so the kernel's clamp of seg_ptr to the rows is off
+  return launch_segment_reduce(x, seg_ptr, n_segments, INT64_MAX, width, EGC_READOUT_MEAN, out, nullptr, stream);
 }
 
 int64_t egc_train_stats_floats(const egc_layer* layer) {

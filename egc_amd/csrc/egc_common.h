@@ -84,4 +84,8 @@ int arg_extrema(const egc_graph* graph, const egc_layer* layer, const float* bas
                 const int32_t* cnt, int32_t* arg_max, int32_t* arg_min, unsigned* arg8_max, unsigned* arg8_min,
                 hipStream_t stream);
 
+// egc_readout.hip: the segmented readout's forward launch (op = EGC_READOUT_*; arguments already validated)
+int launch_segment_reduce(const float* x, const int64_t* seg_ptr, int64_t n_segments, int64_t n_rows, int32_t width,
+                          int32_t op, float* out, int32_t* arg, hipStream_t stream);
+
 }  // namespace egc

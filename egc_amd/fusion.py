@@ -18,7 +18,7 @@ from . import _C
 import torch.nn as nn
 
 from .functional import (PostOp, ResidualLink, native_block_train, native_csr_block_train, batch_norm_act_residual, batch_norm_act_residual_supported, egc_layer_forward,
-                         segment_mean)
+                         segment_mean, segment_reduce, segment_reduce_backward)
 from .graph import GraphBatch, graph_from_input
 
 
@@ -161,19 +161,32 @@ class FusedEGCBlock(nn.Module):
         return egc_layer_forward(graph, spec, x, wcat, bcat, conv.bias, packed=conv._weight_planes(spec, wcat), post=post)
 
 
-class _SegmentMeanFunction(torch.autograd.Function):
-    """out[g] = mean of the rows of graph g (a sorted batch vector's segments); d x[r] = d out[batch[r]] / count."""
+class _SegmentReduceFunction(torch.autograd.Function):
+    """out[g] = sum / mean / max of the rows of graph g (a sorted batch vector's segments); the backward is one kernel
+    driven by the segment offsets: d x[r] = d out[g], d out[g] / count, or d out[g] on the winning row of each column."""
 
     @staticmethod
-    def forward(ctx, x, seg, batch):
-        ctx.save_for_backward(seg, batch)
-        return segment_mean(x, seg)
+    def forward(ctx, x, seg, op):
+        ctx.op, ctx.n_rows = op, x.size(0)
+        if op == "max":
+            out, arg = segment_reduce(x, seg, op, want_arg=True)
+            ctx.save_for_backward(seg, arg)
+            return out
+        ctx.save_for_backward(seg)
+        return segment_mean(x, seg) if op == "mean" else segment_reduce(x, seg, op)
 
     @staticmethod
     def backward(ctx, dout):
-        seg, batch = ctx.saved_tensors
-        counts = (seg[1:] - seg[:-1]).clamp_(min=1).to(dout.dtype)
-        return (dout / counts[:, None]).index_select(0, batch), None, None
+        seg, *arg = ctx.saved_tensors
+        return segment_reduce_backward(dout, seg, ctx.op, ctx.n_rows, arg[0] if arg else None), None, None
+
+
+def _global_pool(x: torch.Tensor, batch: torch.Tensor, size: int | None, op: str) -> torch.Tensor:
+    n_graphs = int(batch.max()) + 1 if size is None else int(size)
+    seg = torch.searchsorted(batch, torch.arange(n_graphs + 1, device=batch.device, dtype=batch.dtype))
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _SegmentReduceFunction.apply(x, seg, op)
+    return segment_mean(x, seg) if op == "mean" else segment_reduce(x, seg, op)
 
 
 def global_mean_pool(x: torch.Tensor, batch: torch.Tensor, size: int | None = None) -> torch.Tensor:
@@ -181,8 +194,35 @@ def global_mean_pool(x: torch.Tensor, batch: torch.Tensor, size: int | None = No
     readout of the reference's batched nets, zinc/models.py:73): a segmented mean on the device
     (``egc_segment_mean_f32``), differentiable.  Pass ``size`` (the number of graphs) where nothing may be read back
     to the host -- inside a hipGraph recording; without it the number of graphs comes from ``batch.max()``."""
-    n_graphs = int(batch.max()) + 1 if size is None else int(size)
-    seg = torch.searchsorted(batch, torch.arange(n_graphs + 1, device=batch.device, dtype=batch.dtype))
-    if torch.is_grad_enabled() and x.requires_grad:
-        return _SegmentMeanFunction.apply(x, seg, batch)
-    return segment_mean(x, seg)
+    return _global_pool(x, batch, size, "mean")
+
+
+def global_add_pool(x: torch.Tensor, batch: torch.Tensor, size: int | None = None) -> torch.Tensor:
+    """torch_geometric.nn.global_add_pool for a SORTED batch vector (graphs are contiguous in a PyG batch; the
+    ``readout="sum"`` of the reference's batched nets, zinc/models.py:49): a segmented sum on the device
+    (``egc_segment_reduce_f32``, float32 adds in input order), differentiable.  Pass ``size`` (the number of graphs)
+    where nothing may be read back to the host -- inside a hipGraph recording; without it the number of graphs comes
+    from ``batch.max()``.  Trailing graphs without rows give zero rows."""
+    return _global_pool(x, batch, size, "sum")
+
+
+def global_max_pool(x: torch.Tensor, batch: torch.Tensor, size: int | None = None) -> torch.Tensor:
+    """torch_geometric.nn.global_max_pool for a SORTED batch vector (graphs are contiguous in a PyG batch; the
+    ``readout="max"`` of the reference's batched nets, zinc/models.py:51): a segmented maximum on the device
+    (``egc_segment_reduce_f32``), differentiable: the gradient goes to the FIRST row in input order that attains the
+    maximum of its column.  Pass ``size`` (the number of graphs) where nothing may be read back to the host -- inside a
+    hipGraph recording; without it the number of graphs comes from ``batch.max()``.  Graphs without rows give zero
+    rows (and no gradient)."""
+    return _global_pool(x, batch, size, "max")
+
+
+def readout(name: str):
+    """The pooling function of the reference's ``readout`` constructor argument (zinc/models.py:45-52):
+    "mean" | "sum" | "max" -> global_mean_pool | global_add_pool | global_max_pool."""
+    if name == "mean":
+        return global_mean_pool
+    if name == "sum":
+        return global_add_pool
+    if name == "max":
+        return global_max_pool
+    raise ValueError(f"egc_amd: unknown readout {name!r} (expected 'mean', 'sum' or 'max')")

@@ -478,6 +478,32 @@ int egc_sum_partials_f32(const float* partials, int32_t n_partials, int32_t cols
 int egc_segment_mean_f32(const float* x, const int64_t* seg_ptr, int64_t n_segments, int32_t width, float* out,
                          egc_stream_t stream);
 
+/* The readout family of the reference's graph-level nets, `x = self.pool(x, batch.batch)` with pool =
+ * global_add_pool | global_mean_pool | global_max_pool by the constructor's `readout` (zinc/models.py:45-52,73,
+ * mol/pna_style_models.py:52-59,79, cifar/models.py:47-52,75, code/models.py:86-91), over consecutive row segments
+ * of x [n_rows, width] (seg_ptr int64 [n_segments + 1], as in egc_segment_mean_f32; clamped to [0, n_rows]).
+ * out [n_segments, width].  SUM: ((x[r0] + x[r0+1]) + x[r0+2]) + ..., rows ascending, one float32 add each -- the
+ * order of a sequential scatter loop, a pure function of the input.  MEAN: that sum divided by float(max(count, 1)),
+ * the bits of egc_segment_mean_f32.  MAX: the first row, then every later row that is strictly greater: the first row in
+ * input order wins a tie; arg (int32 [n_segments, width], MAX only, may be NULL) receives the winner's absolute row
+ * index, -1 for an empty segment; NaN / Inf follow the strict compare and nothing else.  An empty segment gives 0 for
+ * every op.  n_segments == 0 and n_rows == 0 are fine; x may be NULL when there are no rows.  One group of
+ * ceil(width / 4) lanes walks a segment: a single very long segment is correct and slow.
+ * EGC_ERR_INVALID: unknown op, width <= 0, a missing pointer; EGC_ERR_UNSUPPORTED: MAX with n_rows >= 2^31. */
+#define EGC_READOUT_SUM 0
+#define EGC_READOUT_MEAN 1
+#define EGC_READOUT_MAX 2
+int egc_segment_reduce_f32(const float* x, const int64_t* seg_ptr, int64_t n_segments, int64_t n_rows, int32_t width,
+                           int32_t op, float* out, int32_t* arg, egc_stream_t stream);
+
+/* Backward of egc_segment_reduce_f32 (what autograd derives from torch_scatter's scatter in the reference's pools):
+ * d_x [n_rows, width] from d_out [n_segments, width], every element written exactly once, driven by seg_ptr alone
+ * (no batch vector, no zero-fill, no atomics).  SUM: d_x[r] = d_out[g]; MEAN: d_x[r] = d_out[g] / float(max(count, 1));
+ * MAX: d_x[r, c] = arg[g, c] == r ? d_out[g, c] : 0 with the forward's arg (required for MAX, ignored otherwise).
+ * Rows in no segment (r < seg_ptr[0] or r >= seg_ptr[n_segments]) receive 0. */
+int egc_segment_reduce_backward_f32(const float* d_out, const int64_t* seg_ptr, const int32_t* arg, int64_t n_segments,
+                                    int64_t n_rows, int32_t width, int32_t op, float* d_x, egc_stream_t stream);
+
 /* Training form of egc_aggregate_combine_f32: same `out`, plus what the backward needs instead of a second
  * gather.  stats (n_nodes * egc_train_stats_floats(layer) floats, opaque to the caller, handed to the backward
  * as it is) receives every row's raw running aggregates after the self-loop term (those of sum / variance -- as the

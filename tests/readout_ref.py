@@ -1,0 +1,53 @@
+"""The sequential CPU reference of the graph-level readouts (egc_amd.global_add_pool / global_mean_pool / global_max_pool):
+what a scatter loop over the rows in input order computes, vectorised over the segments.  torch's CPU float32 add, divide and
+compare are single correctly rounded IEEE operations, so these ARE the order rule of egc_amd/csrc/egc_readout.hip restated;
+nothing here calls the code under test."""
+import torch
+
+
+def seg_ptr_of(batch: torch.Tensor, n_graphs: int) -> torch.Tensor:
+    """Offsets of the graphs of a sorted batch vector: int64 [n_graphs + 1]."""
+    return torch.searchsorted(batch.contiguous(), torch.arange(n_graphs + 1, dtype=batch.dtype))
+
+
+def forward(x: torch.Tensor, seg: torch.Tensor, op: str):
+    """(out float32 [G, C], arg int32 [G, C] or None): acc = 0; for k in range(longest segment):
+    acc[live] = acc[live] + x[r0[live] + k] (sum, mean), or take = x_k > cur (first step: take all) with arg updated where
+    take (max).  Mean divides by clamp(count, 1).  Empty segments give 0 and arg -1."""
+    assert x.dtype == torch.float32 and x.device.type == "cpu"
+    G, C = seg.numel() - 1, x.size(1)
+    r0, cnt = seg[:-1], seg[1:] - seg[:-1]
+    acc = torch.zeros(G, C, dtype=torch.float32)
+    arg = torch.full((G, C), -1, dtype=torch.int32) if op == "max" else None
+    for k in range(int(cnt.max()) if G else 0):
+        live = torch.nonzero(cnt > k).view(-1)
+        rows = r0[live] + k
+        xk = x[rows]
+        if op == "max":
+            cur = acc[live]
+            take = torch.ones_like(xk, dtype=torch.bool) if k == 0 else xk > cur
+            acc[live] = torch.where(take, xk, cur)
+            arg[live] = torch.where(take, rows.to(torch.int32)[:, None].expand_as(xk), arg[live])
+        else:
+            acc[live] = acc[live] + xk
+    if op == "mean":
+        acc = acc / cnt.clamp(min=1).to(torch.float32)[:, None]
+    return acc, arg
+
+
+def backward(d_out: torch.Tensor, seg: torch.Tensor, op: str, n_rows: int, arg=None) -> torch.Tensor:
+    """d x [n_rows, C]: sum d_out[batch]; mean (d_out / clamp(count, 1))[batch]; max a zero tensor with d_out[g, c] placed at
+    (arg[g, c], c).  Rows outside every segment stay 0."""
+    assert d_out.dtype == torch.float32 and d_out.device.type == "cpu"
+    G, C = d_out.shape
+    cnt = seg[1:] - seg[:-1]
+    d_x = torch.zeros(n_rows, C, dtype=torch.float32)
+    if op == "max":
+        g, c = torch.nonzero(arg >= 0, as_tuple=True)
+        d_x[arg[g, c].long(), c] = d_out[g, c]
+        return d_x
+    rows = torch.arange(int(seg[0]), int(seg[-1])) if G else torch.zeros(0, dtype=torch.int64)
+    owner = torch.repeat_interleave(torch.arange(G), cnt)
+    src = d_out / cnt.clamp(min=1).to(torch.float32)[:, None] if op == "mean" else d_out
+    d_x[rows] = src[owner]
+    return d_x
