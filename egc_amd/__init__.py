@@ -8,6 +8,9 @@ Public surface (mirrors the reference's layer API):
                        mode in two passes each way
   global_mean_pool / global_add_pool / global_max_pool, readout(name)
                        the graph-level readouts of the reference's nets (differentiable segmented mean / sum / max)
+  Embedding / AtomEncoder / ASTNodeEncoder, NodeEncoder(table_rows, emb_dim)
+                       the node encoders at the head of the reference's batched nets (state-dict compatible): a sum of
+                       embedding rows (+ input dropout) in one forward launch and two atomic-free backward launches
   SparseTensor         minimal adj_t container (torch_sparse is not required)
   CSRGraph             device CSR + degree statistics + long-row plan
   GraphBatch           a PyG-style batch of small graphs (edge_index + graph offsets) for the tile kernels: the CSR of
@@ -22,6 +25,7 @@ from .layers import EfficientGraphConv  # noqa: F401
 from .optimized_layers import EGConv  # noqa: F401
 from .relational import REGConv  # noqa: F401
 from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean_pool, readout  # noqa: F401
+from .encoders import ASTNodeEncoder, AtomEncoder, Embedding, NodeEncoder  # noqa: F401
 from .hipgraph import GraphedStep  # noqa: F401
 from . import ops  # noqa: F401  (registers torch.ops.egc_amd.*)
 

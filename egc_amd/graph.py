@@ -70,7 +70,8 @@ class _IndexFlag:
             raise RuntimeError("egc_amd: an earlier call reported malformed graph input: an edge_index with node ids outside "
                                "[0, num_nodes): index out of range (those edges were dropped) -- or, for a GraphBatch, edges that "
                                "leave their graph / a graph larger than max_nodes (its rows were written as zeros; "
-                               "GraphBatch.check() tells which)")
+                               "GraphBatch.check() tells which) -- or, for a node encoder, an index outside its embedding table (that "
+                               "table contributed a zero row)")
 
 
 def _require_cuda(t: torch.Tensor, what: str):

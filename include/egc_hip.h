@@ -504,6 +504,46 @@ int egc_segment_reduce_f32(const float* x, const int64_t* seg_ptr, int64_t n_seg
 int egc_segment_reduce_backward_f32(const float* d_out, const int64_t* seg_ptr, const int32_t* arg, int64_t n_segments,
                                     int64_t n_rows, int32_t width, int32_t op, float* d_x, egc_stream_t stream);
 
+/* The node encoders at the head of the reference's batched nets, `x = self.embedding(batch.x)` followed by
+ * `x = self.in_feat_dropout(x)`: nn.Embedding (zinc/models.py:28-30,62-63), ogb's AtomEncoder, nine tables summed
+ * (mol/pna_style_models.py:33-34,66-69; table sizes output/pretrained.txt:460-470), ASTNodeEncoder, three tables and
+ * `depth[depth > max_depth] = max_depth` (code/models.py:27-45,104-112).  One definition: n_tables tables
+ * tables[t] [table_rows[t], width] float32 (device pointers in a HOST array, as are table_rows and clamp: they are read
+ * during the call and travel in the kernel arguments), idx int64 [n_rows, n_tables], clamp[t] >= 0: the index of table t
+ * is replaced by min(idx, clamp[t]) (-1 or clamp == NULL: none; the caller's idx is never written).
+ *   out[n, :] = ((W_0[idx[n,0]] + W_1[idx[n,1]]) + W_2[idx[n,2]]) + ...     tables ascending, one float32 add each
+ * -- the order of AtomEncoder.forward (its leading `0 +` is exact) and of ASTNodeEncoder.forward: a pure function of the
+ * inputs.  keep (uint8 [n_rows, width], may be NULL) and keep_scale = 1 / (1 - p) are the dropout behind the encoder:
+ * out = keep ? sum * keep_scale : 0.  An index outside [0, table_rows[t]) after the clamp is never used as an address:
+ * that table contributes a zero row for the node and *host_flag = 1 is stored (may be NULL; the sticky host-visible word
+ * of egc_coo_to_csr_checked).  One launch.  n_rows == 0 is fine.
+ * EGC_ERR_INVALID: a missing pointer, n_rows < 0, n_tables <= 0, width <= 0, a table without rows;
+ * EGC_ERR_UNSUPPORTED: n_tables > EGC_ENCODER_MAX_TABLES, more than EGC_ENCODER_MAX_TABLE_ROWS rows in all tables
+ * together, width > EGC_ENCODER_MAX_WIDTH, n_rows >= 2^31 - 256, ceil(n_rows / 256) * total rows >= 2^31.  Any width inside
+ * the limit is handled; 16-byte accesses need width % 4 == 0 and 16-byte aligned pointers. */
+#define EGC_ENCODER_MAX_TABLES 16
+#define EGC_ENCODER_MAX_TABLE_ROWS (1 << 20)
+#define EGC_ENCODER_MAX_WIDTH 1024
+int egc_encoder_forward_f32(const float* const* tables, const int32_t* table_rows, const int32_t* clamp, int32_t n_tables,
+                            const int64_t* idx, int64_t n_rows, int32_t width, const uint8_t* keep, float keep_scale,
+                            float* out, int32_t* host_flag, egc_stream_t stream);
+
+/* Backward of egc_encoder_forward_f32 (what autograd derives for the same lines: one embedding_dense_backward per
+ * table, each a sort and a segmented sum): d_tables[t] [table_rows[t], width] (device pointers in a host array -- e.g.
+ * where the tables' .grad tensors are),
+ *   d W_t[v, :] = sum over { n : min(idx[n,t], clamp[t]) == v } of (keep ? d_out[n, :] * keep_scale : 0),
+ * rows that nobody indexes receive 0, EVERY element of every d W_t is written exactly once (no zero fill by the caller).
+ * No gradient for idx.  Indices outside their table are skipped (the forward reports them).  Two launches, no atomics:
+ * nodes are cut into chunks of 256; inside a chunk the rows of one destination are added in ascending n, then a
+ * destination's chunk sums are added in ascending chunk order -- the summation order is a function of idx and the shapes
+ * alone, the result is bit-reproducible.  workspace: egc_encoder_workspace_bytes(n_rows, n_tables, total rows of all
+ * tables, width) bytes, 16-byte aligned, any content (EGC_ERR_WORKSPACE if smaller; 0 bytes for n_rows == 0); the size depends on
+ * host-known numbers only.  Errors and limits as the forward. */
+size_t egc_encoder_workspace_bytes(int64_t n_rows, int32_t n_tables, int64_t total_table_rows, int32_t width);
+int egc_encoder_backward_f32(const float* d_out, const uint8_t* keep, float keep_scale, const int64_t* idx, int64_t n_rows,
+                             int32_t width, const int32_t* table_rows, const int32_t* clamp, int32_t n_tables,
+                             float* const* d_tables, void* workspace, size_t workspace_bytes, egc_stream_t stream);
+
 /* Training form of egc_aggregate_combine_f32: same `out`, plus what the backward needs instead of a second
  * gather.  stats (n_nodes * egc_train_stats_floats(layer) floats, opaque to the caller, handed to the backward
  * as it is) receives every row's raw running aggregates after the self-loop term (those of sum / variance -- as the
