@@ -20,8 +20,8 @@ import torch.nn as nn
 
 from . import _C
 from . import ops
-from .functional import (egc_layer_apply, egc_layer_apply_params, gemm_exact, make_spec, pack_layer_weights, pack_weights,
-                         pad_bases_columns, padded_basis_stride)
+from .functional import (TrainCall, egc_layer_apply, egc_layer_apply_params, gemm_exact, make_spec, pack_layer_weights,
+                         pack_weights, pad_bases_columns, padded_basis_stride)
 from .graph import CSRGraph, GraphBatch, SparseTensor, graph_from_input
 
 _AGGR_CODE = {"add": _C.AGGR_SUM, "mean": _C.AGGR_MEAN, "max": _C.AGGR_MAX, "min": _C.AGGR_MIN,
@@ -139,8 +139,16 @@ class EfficientGraphConv(nn.Module):
             self._planes = pack_weights(self._spec, wcat)
         return self._planes
 
+    def _train_record(self, graph, x):
+        """The layer's training call on `graph` (functional.TrainCall): one basis matrix per base, the combination bias already
+        in the operand's order."""
+        sp, w = self._spec, self.comb_weights.weight
+        A = w.size(0) // (self.num_heads * self.num_bases)
+        return TrainCall(graph, sp, x, self.bias, w, None, self.comb_weights.bias, list(self.bases_weight._parameters.values()),
+                         self.in_channels, self.num_heads, A, self.num_bases, sp.basis_len, sp.basis_stride, False)
+
     def _train_call(self, x, edge_index):
-        """The arguments of functional.egc_layer_apply_params for a training call on a GraphBatch, or None (see EGConv._train_call)."""
+        """The TrainCall of functional.egc_layer_apply_params for a training call on a GraphBatch, or None (see EGConv._train_call)."""
         w = self.comb_weights.weight
         if not (w.is_cuda and w.dtype == torch.float32 and self.num_bases <= 32 and x.is_cuda) or ops.use_torch_op():
             return None
@@ -154,10 +162,7 @@ class EfficientGraphConv(nn.Module):
             if self.cache:
                 return None          # (forward() builds and caches the graph first)
             graph = graph_from_input(edge_index, x.size(0))
-        sp = self._spec
-        A = w.size(0) // (self.num_heads * self.num_bases)
-        return (graph, sp, x, self.bias, w, None, self.comb_weights.bias, list(self.bases_weight._parameters.values()),
-                self.in_channels, self.num_heads, A, self.num_bases, sp.basis_len, sp.basis_stride, False)
+        return self._train_record(graph, x)
 
     def forward(self, x, edge_index):
         if _is_adj_t(edge_index) and any(a.aggr_fun in ("var", "std") for a in self.aggs):      # (also a real torch_sparse.SparseTensor)
@@ -173,11 +178,7 @@ class EfficientGraphConv(nn.Module):
         if (torch.is_grad_enabled() and w.is_cuda and w.dtype == torch.float32 and self.num_bases <= 32
                 and x.is_cuda and (w.requires_grad or any(p.requires_grad for p in params)) and not ops.use_torch_op()):
             # training: parameters in, parameter gradients out, one autograd node (pack + layer + unpack)
-            sp = self._spec
-            A = w.size(0) // (self.num_heads * self.num_bases)
-            return egc_layer_apply_params(graph, sp, x, self.bias, w, None, self.comb_weights.bias, params,
-                                          self.in_channels, self.num_heads, A, self.num_bases, sp.basis_len,
-                                          sp.basis_stride, False)
+            return egc_layer_apply_params(self._train_record(graph, x))
         wcat = self._packed_weights()
         return egc_layer_apply(graph, self._spec, x, wcat, self.comb_weights.bias, self.bias,
                                packed=self._weight_planes(wcat))

@@ -23,8 +23,8 @@ import torch.nn as nn
 
 from . import _C
 from . import ops
-from .functional import (egc_layer_apply, egc_layer_apply_params, gemm_exact, make_spec, pack_egconv_weights, pack_weights,
-                         pad_bases_columns, padded_basis_stride)
+from .functional import (TrainCall, egc_layer_apply, egc_layer_apply_params, gemm_exact, make_spec, pack_layer_weights,
+                         pack_weights, pad_bases_columns, padded_basis_stride)
 from .graph import GraphBatch, graph_from_input
 from .layers import glorot_
 
@@ -92,8 +92,9 @@ class EGConv(nn.Module):
         if (torch.is_grad_enabled() and self.bases_weight.is_cuda and self.bases_weight.dtype == torch.float32
                 and self.comb_weight.bias is not None):
             # training: one launch each way instead of the differentiable torch chain below
-            return pack_egconv_weights(self.bases_weight, self.comb_weight.weight, self.comb_weight.bias, F, H, A, B,
-                                       sp.basis_len, sp.basis_stride)
+            # (comb rows [h][a][b] permuted to [h][b][a]: optimized_layers.py:195-202)
+            return pack_layer_weights([self.bases_weight], self.comb_weight.weight, self.comb_weight.bias, F, H, A, B,
+                                      sp.basis_len, sp.basis_stride, True)
         w = self.comb_weight.weight.view(H, A, B, F).permute(0, 2, 1, 3).reshape(H * B * A, F)
         b = self.comb_weight.bias.view(H, A, B).permute(0, 2, 1).reshape(H * B * A)
         sp = self._spec_coo
@@ -122,10 +123,16 @@ class EGConv(nn.Module):
             self._planes = pack_weights(spec, wcat)
         return self._planes
 
+    def _train_record(self, graph, spec, x):
+        """The layer's training call on `graph` (functional.TrainCall): the parameters as they are, comb rows to be permuted."""
+        return TrainCall(graph, spec, x, self.bias, self.comb_weight.weight, self.comb_weight.bias, None, [self.bases_weight],
+                         self.in_channels, self.num_heads, len(self.aggregators), self.num_bases, spec.basis_len,
+                         spec.basis_stride, True)
+
     def _train_call(self, x, edge_index):
-        """The arguments of functional.egc_layer_apply_params for a training call, or None (what forward() below passes on its
-        training path; egc_amd.FusedEGCBlock hands them to the compiled binding's block nodes)."""
-        bw, cw, cb = self.bases_weight, self.comb_weight.weight, self.comb_weight.bias
+        """The TrainCall of functional.egc_layer_apply_params for a training call, or None (what forward() below passes on its
+        training path; egc_amd.FusedEGCBlock hands it to the compiled binding's block nodes)."""
+        bw, cb = self.bases_weight, self.comb_weight.bias
         if not (bw.is_cuda and bw.dtype == torch.float32 and cb is not None and x.is_cuda) or ops.use_torch_op():
             return None
         if self.cached and self._cached_graph is not None:
@@ -137,8 +144,7 @@ class EGConv(nn.Module):
                 return None          # (forward() builds and caches the graph first)
             graph = graph_from_input(edge_index, x.size(self.node_dim))
             spec = self._spec_coo if (isinstance(edge_index, torch.Tensor) and edge_index.layout == torch.strided) else self._spec_adj
-        return (graph, spec, x, self.bias, cw, cb, None, [bw], self.in_channels, self.num_heads, len(self.aggregators),
-                self.num_bases, spec.basis_len, spec.basis_stride, True)
+        return self._train_record(graph, spec, x)
 
     def forward(self, x, edge_index):
         if self.cached and self._cached_graph is not None:
@@ -153,8 +159,7 @@ class EGConv(nn.Module):
         if (torch.is_grad_enabled() and bw.is_cuda and bw.dtype == torch.float32 and cb is not None and x.is_cuda
                 and (bw.requires_grad or cw.requires_grad or cb.requires_grad) and not ops.use_torch_op()):
             # training: parameters in, parameter gradients out, one autograd node (pack + layer + unpack)
-            return egc_layer_apply_params(graph, spec, x, self.bias, cw, cb, None, [bw], self.in_channels, self.num_heads,
-                                          len(self.aggregators), self.num_bases, spec.basis_len, spec.basis_stride, True)
+            return egc_layer_apply_params(self._train_record(graph, spec, x))
         wcat, bcat = self._packed_weights()
         return egc_layer_apply(graph, spec, x, wcat, bcat, self.bias, packed=self._weight_planes(spec, wcat))
 
