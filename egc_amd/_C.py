@@ -26,6 +26,7 @@ LAYOUT_HBA, LAYOUT_HAB = 0, 1
 ACT_NONE, ACT_SOFTMAX, ACT_SIGMOID, ACT_HARDTANH = range(4)
 # EGC_READOUT_*
 READOUT_SUM, READOUT_MEAN, READOUT_MAX = range(3)
+SOFTMAX_MAX_CLASSES = 1024   # EGC_SOFTMAX_MAX_CLASSES
 
 _STATUS = {1: "EGC_ERR_INVALID", 2: "EGC_ERR_WORKSPACE", 3: "EGC_ERR_HIP", 4: "EGC_ERR_UNSUPPORTED"}
 
@@ -169,6 +170,16 @@ SYMBOLS = {
     "egc_encoder_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int64, C.c_int32]),
     "egc_encoder_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egc_log_softmax_forward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    "egc_log_softmax_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "egc_row_selection_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egc_nll_log_softmax_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "egc_nll_log_softmax_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                  C.c_void_p]),
+    "egc_nll_log_softmax_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "egc_train_stats_floats": (C.c_int64, [C.POINTER(EgcLayer)]),
     "egc_aggregate_combine_train_f32": (C.c_int, [C.POINTER(EgcGraph), C.POINTER(EgcLayer), C.c_void_p, C.c_int32,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

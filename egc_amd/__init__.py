@@ -11,6 +11,10 @@ Public surface (mirrors the reference's layer API):
   Embedding / AtomEncoder / ASTNodeEncoder, NodeEncoder(table_rows, emb_dim)
                        the node encoders at the head of the reference's batched nets (state-dict compatible): a sum of
                        embedding rows (+ input dropout) in one forward launch and two atomic-free backward launches
+  log_softmax / nll_log_softmax / cross_entropy, RowSelection(index, n_rows)
+                       the output head and loss of the classification nets on the full-width logits: the row
+                       log-softmax (+ arg-max) in one read, and ``F.nll_loss(x[:, :C].log_softmax(-1)[idx], y[idx])`` as
+                       one read of the selected rows forward and one read plus one write of the gradient backward
   SparseTensor         minimal adj_t container (torch_sparse is not required)
   CSRGraph             device CSR + degree statistics + long-row plan
   GraphBatch           a PyG-style batch of small graphs (edge_index + graph offsets) for the tile kernels: the CSR of
@@ -26,6 +30,7 @@ from .optimized_layers import EGConv  # noqa: F401
 from .relational import REGConv  # noqa: F401
 from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean_pool, readout  # noqa: F401
 from .encoders import ASTNodeEncoder, AtomEncoder, Embedding, NodeEncoder  # noqa: F401
+from ._softmax import RowSelection, cross_entropy, log_softmax, nll_log_softmax  # noqa: F401
 from .hipgraph import GraphedStep  # noqa: F401
 from . import ops  # noqa: F401  (registers torch.ops.egc_amd.*)
 

@@ -24,6 +24,8 @@ from .graph import CSRGraph, GraphBatch, _IndexFlag, _stream_ptr, _device_guard
 from ._args import _check_f32, _check_keep, _ptr  # noqa: F401
 from ._readout import READOUT_OPS, _readout_code, segment_mean, segment_reduce, segment_reduce_backward  # noqa: F401
 from ._encoder import _encoder_args, encoder_backward, encoder_forward, encoder_supported  # noqa: F401
+from ._softmax import (log_softmax_backward, log_softmax_forward, nll_backward, nll_forward,  # noqa: F401
+                       softmax_supported)
 from ._bn_tail import (_BatchNormActResidualFunction, _bn_tail_operands, _f32_vec, batch_norm_act_residual,  # noqa: F401
                        batch_norm_act_residual_supported)
 from ._dense import (_PackWeightsFunction, _column_sums, _dense_param_grads, _dims, _dx_matmul, _pack_params,  # noqa: F401

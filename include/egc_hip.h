@@ -544,6 +544,62 @@ int egc_encoder_backward_f32(const float* d_out, const uint8_t* keep, float keep
                              int32_t width, const int32_t* table_rows, const int32_t* clamp, int32_t n_tables,
                              float* const* d_tables, void* workspace, size_t workspace_bytes, egc_stream_t stream);
 
+/* The output head and loss of the reference's classification nets (egc_softmax.hip): `conv(x)[:, :349].log_softmax(-1)`,
+ * `out[train_idx]`, `F.nll_loss(out, y[train_idx])` (mag/models.py:68-69 + mag/configs.py:34-35, arxiv/norm_models.py:42-43 +
+ * arxiv/configs.py:53-54, rmag/configs.py:35-36) and F.cross_entropy (cifar/configs.py:57).  float32 rows of n_classes columns
+ * inside a row stride ld >= n_classes (in floats); columns n_classes .. ld-1 are never read, and the backward forms write
+ * them as zeros.  ignore_index and class weights are NOT supported (the reference uses neither).
+ * Order of every row sum (sum of exp, sum of grad_out): a group of G lanes owns a row, G the power of two >=
+ * ceil(n_classes / 4), at most 64; a lane adds its columns ascending, then the lanes combine over the xor distances
+ * G/2, .., 1 -- a function of n_classes alone, so every call gives the same bits.
+ * EGC_ERR_INVALID: a missing pointer, n_rows < 0, n_classes <= 0, ld < n_classes; EGC_ERR_UNSUPPORTED: n_classes >
+ * EGC_SOFTMAX_MAX_CLASSES (the 5,002-wide token heads of ogbg-code stay with the caller), n_rows >= 2^38.  n_rows == 0 is
+ * fine.  16-byte accesses need the row strides % 4 == 0 and 16-byte aligned pointers; any other shape takes 4-byte ones.
+ *
+ * egc_log_softmax_forward_f32    out [n_rows, n_classes] dense: out[r, c] = x[r, c] - lse[r], lse[r] = m_r + log(sum_c
+ *                                exp(x[r, c] - m_r)), m_r the row maximum.  lse [n_rows] and argmax [n_rows] (int32) may be
+ *                                NULL.  argmax: the FIRST maximal column (ties go to the smaller column).  One launch.
+ * egc_log_softmax_backward_f32   d_x [n_rows, ld]: d_x[r, c] = grad_out[r, c] - exp(out[r, c]) * sum_c grad_out[r, c] for
+ *                                c < n_classes, 0 for the padding; grad_out and out dense [n_rows, n_classes].  Every
+ *                                element of d_x is written exactly once.  One launch. */
+#define EGC_SOFTMAX_MAX_CLASSES 1024
+int egc_log_softmax_forward_f32(const float* x, int64_t n_rows, int32_t n_classes, int32_t ld, float* out, float* lse,
+                                int32_t* argmax, egc_stream_t stream);
+int egc_log_softmax_backward_f32(const float* grad_out, const float* out, int64_t n_rows, int32_t n_classes, int32_t ld,
+                                 float* d_x, egc_stream_t stream);
+
+/* Selection counts of an index vector (the `[train_idx]` of the lines above): cnt[r] = how often r occurs in index
+ * [n_index] (int64), *total = the number of indices inside [0, n_rows) -- the M of the mean.  cnt [n_rows] int32 and total
+ * (one int64) are device memory, zeroed and filled here (integer atomics: the result does not depend on their order).  An
+ * index outside [0, n_rows) is never used as an address: it is not counted and *host_flag = 1 is stored (may be NULL; the
+ * sticky host-visible word of egc_coo_to_csr_checked).  EGC_ERR_UNSUPPORTED: n_index >= 2^31. */
+int egc_row_selection_count(const int64_t* index, int64_t n_index, int64_t n_rows, int32_t* cnt, int64_t* total,
+                            int32_t* host_flag, egc_stream_t stream);
+
+/* Fused selected-row NLL of the row log-softmax, forward: with logp[r, c] = x[r, c] - lse[r],
+ *   *loss = -(1 / M) sum_r cnt[r] * logp[r, y[r]]    (mean != 0),    -sum_r cnt[r] * logp[r, y[r]]    (mean == 0)
+ * y [n_rows] int64 labels; cnt / total from egc_row_selection_count, or cnt == NULL: every row once, M = n_rows (total is
+ * then ignored).  lse [n_rows] is written for the backward (0 on rows with cnt[r] <= 0, which are not read).  A label outside
+ * [0, n_classes) on a selected row is never used as an address: the row adds 0 to the loss, receives a zero gradient row,
+ * and *host_flag = 1 is stored (may be NULL).  M == 0 with mean gives NaN, as torch does.
+ * Summation order (no float atomics, bit-reproducible): rows are cut into chunks of 128; group s of a chunk's 256 / G lane
+ * groups adds its rows chunk0 + s, chunk0 + s + 256 / G, ... ascending; the chunk's group sums are added four adjacent ones
+ * at a time, ascending, then over the xor distances 32, .., 1; the second launch adds chunk sums t, t + 256, ... ascending in
+ * thread t and the 256 thread sums in the same way.  The longest chain of adds is 128 G / 256 + 9 + ceil(chunks / 256) + 9.
+ * workspace: egc_nll_log_softmax_workspace_bytes(n_rows, n_classes) bytes (0 outside the limits), 4-byte aligned, any
+ * content; EGC_ERR_WORKSPACE if smaller.  Two launches.
+ * Backward: d_x [n_rows, ld] from the forward's lse and *grad_loss (device scalar),
+ *   d_x[r, c] = w_r * (exp(x[r, c] - lse[r]) - [c == y[r]]),   w_r = (grad_loss * cnt[r]) / M  (mean) or grad_loss * cnt[r],
+ * for c < n_classes on selected rows with a label inside the classes, 0 in the padding columns and on every other row.
+ * Every element of d_x is written exactly once: no zero fill in front, no atomics.  One launch. */
+size_t egc_nll_log_softmax_workspace_bytes(int64_t n_rows, int32_t n_classes);
+int egc_nll_log_softmax_forward_f32(const float* x, const int64_t* y, const int32_t* cnt, const int64_t* total, int64_t n_rows,
+                                    int32_t n_classes, int32_t ld, int32_t mean, float* loss, float* lse, void* workspace,
+                                    size_t workspace_bytes, int32_t* host_flag, egc_stream_t stream);
+int egc_nll_log_softmax_backward_f32(const float* x, const int64_t* y, const int32_t* cnt, const int64_t* total,
+                                     const float* lse, const float* grad_loss, int64_t n_rows, int32_t n_classes, int32_t ld,
+                                     int32_t mean, float* d_x, egc_stream_t stream);
+
 /* Training form of egc_aggregate_combine_f32: same `out`, plus what the backward needs instead of a second
  * gather.  stats (n_nodes * egc_train_stats_floats(layer) floats, opaque to the caller, handed to the backward
  * as it is) receives every row's raw running aggregates after the self-loop term (those of sum / variance -- as the
