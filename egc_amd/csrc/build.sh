@@ -11,7 +11,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="-O3 --offload-arch=gfx950 -fPIC -std=c++17 -ffp-contract=off -I$ROOT/include -I$HERE -Wall -Wno-unused-function -Wno-pass-failed ${EGC_EXTRA_FLAGS:-}"
 pids=()
 for src in egc_graph egc_gemm egc_gemm_bf16x3 egc_gemm_f16x2 egc_gemm_f16x2k egc_gemm_xt egc_aggregate egc_aggregate_fast egc_aggregate_tile egc_fused_tile egc_fused_tile_wide1 egc_fused_tile_wide2 egc_fused_tile_wide3 egc_backward egc_tail egc_readout egc_encoder egc_softmax; do
-  if [ ! -f "$OBJ/$src.o" ] || [ "$HERE/$src.hip" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_common.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_gemm_split.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_aggregate_dev.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_aggregate_fast_dev.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_fused_tile_dev.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_fused_tile_wide.inc" -nt "$OBJ/$src.o" ] || [ "$ROOT/include/egc_hip.h" -nt "$OBJ/$src.o" ]; then
+  if [ ! -f "$OBJ/$src.o" ] || [ "$HERE/$src.hip" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_common.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_gemm_split.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_aggregate_dev.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_aggregate_fast_dev.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_aggregate_host.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_fused_tile_dev.h" -nt "$OBJ/$src.o" ] || [ "$HERE/egc_fused_tile_wide.inc" -nt "$OBJ/$src.o" ] || [ "$ROOT/include/egc_hip.h" -nt "$OBJ/$src.o" ]; then
     extra=""
     # packed-f32 VALU next to MFMAs costs more issue cycles than two scalar operations (egc_gemm_f16x2.hip header)
     { [ "$src" = egc_gemm_f16x2 ] || [ "$src" = egc_gemm_f16x2k ]; } && extra="-fno-slp-vectorize"

@@ -24,7 +24,7 @@
 
 #include <algorithm>
 
-#include "egc_aggregate_dev.h"
+#include "egc_aggregate_host.h"
 #include "egc_gemm_split.h"
 #include "egc_pack_map.h"
 
@@ -679,9 +679,8 @@ static int aggregate_combine_impl(const egc_graph* graph, const egc_layer* layer
     a.edis = layer->sym_set == EGC_SET_LOOPED ? graph->edge_dis_looped : graph->edge_dis_raw;
     if (a.dis == nullptr) return EGC_ERR_INVALID;
   }
-  a.loops_all = layer->loops_all_nodes != 0;
   a.max_index = graph->max_index;
-  if (!a.loops_all && graph->max_index == nullptr) return EGC_ERR_INVALID;
+  if (layer->loops_all_nodes == 0 && graph->max_index == nullptr) return EGC_ERR_INVALID;
   a.plan = graph->plan;
   a.bases = bases;
   a.weightings = weightings;
@@ -694,29 +693,13 @@ static int aggregate_combine_impl(const egc_graph* graph, const egc_layer* layer
   a.row_end = row_end < 0 ? (int)n : (int)row_end;
   if (a.row_begin < 0 || a.row_end > (int)n) return EGC_ERR_INVALID;
   if (a.row_begin >= a.row_end) return EGC_OK;
-  a.ldb = ldb;
-  a.slots = ldb / 4;
-  a.F_out = layer->out_channels;
-  a.H = layer->num_heads;
-  a.B = layer->num_bases;
-  a.A = layer->num_aggrs;
-  a.L = layer->out_channels / layer->num_heads;
-  a.Ls = layer_basis_stride(layer);
-  a.W = a.H * a.B * a.A;
-  a.ldw = ldw > 0 ? ldw : a.W;  // row stride of `weightings` (a column block of a wider array when > W)
+  agg_layer_fields(layer, a);   // (ldb == egc_bases_ld(layer): checked above)
+  if (ldw > 0) a.ldw = ldw;     // row stride of `weightings` (a column block of a wider array when > W)
   if (a.ldw != a.W && (a.ldw < a.W || (a.ldw & 3) != 0 || (reinterpret_cast<uintptr_t>(weightings) & 15) != 0))
     return EGC_ERR_INVALID;
-  for (int t = 0; t < EGC_MAX_AGGRS; ++t) a.aggr[t] = t < a.A ? layer->aggrs[t] : 0;
-  a.x_looped = layer->agg_set == EGC_SET_LOOPED;
-  a.y_looped = layer->sym_set == EGC_SET_LOOPED;
-  if (layer->weight_layout == EGC_LAYOUT_HAB) { a.sa = a.B; a.sb = 1; } else { a.sa = 1; a.sb = a.A; }
-  a.act = layer->weight_act;
-  a.magic_L = a.L > 1 ? (unsigned)(((uint64_t)1 << 32) / (uint64_t)a.L) + 1u : 0u;  // L == 1: h = o in-kernel
+  a.magic_L = a.L > 1 ? agg_magic(a.L) : 0u;  // L == 1: h = o in-kernel
   a.bases_bytes = (unsigned)((uint64_t)n_src * ldb * 4ull);
-  a.post_scale = post != nullptr ? post->scale : nullptr;
-  a.post_shift = post != nullptr ? post->shift : nullptr;
-  a.residual = post != nullptr ? post->residual : nullptr;
-  a.post_relu = post != nullptr && post->relu != 0;
+  agg_set_post(a, post);
   a.stats = stats;
   a.cnt_out = cnt_out;
   a.stat_k = stat_layout(a.aggr, a.A, a.stat_slot);
@@ -847,22 +830,7 @@ static int tile_layer_args(const egc_layer* layer, AggArgs& a, bool two_sets_ok 
   int st = validate_layer(layer);
   if (st != EGC_OK) return st;
   a = AggArgs{};
-  a.ldb = egc_bases_ld(layer);
-  a.slots = a.ldb / 4;
-  a.F_out = layer->out_channels;
-  a.H = layer->num_heads;
-  a.B = layer->num_bases;
-  a.A = layer->num_aggrs;
-  a.L = layer->out_channels / layer->num_heads;
-  a.Ls = layer_basis_stride(layer);
-  a.W = a.H * a.B * a.A;
-  a.ldw = a.W;
-  for (int t = 0; t < EGC_MAX_AGGRS; ++t) a.aggr[t] = t < a.A ? layer->aggrs[t] : 0;
-  a.x_looped = layer->agg_set == EGC_SET_LOOPED;
-  a.y_looped = layer->sym_set == EGC_SET_LOOPED;
-  a.loops_all = layer->loops_all_nodes != 0;
-  if (layer->weight_layout == EGC_LAYOUT_HAB) { a.sa = a.B; a.sb = 1; } else { a.sa = 1; a.sb = a.A; }
-  a.act = layer->weight_act;
+  agg_layer_fields(layer, a);
   a.lpr_log2 = 4;
   int chunks = a.slots <= 64 ? 1 : (a.slots + 63) / 64;
   a.n_nodes = 1;
@@ -871,14 +839,43 @@ static int tile_layer_args(const egc_layer* layer, AggArgs& a, bool two_sets_ok 
   return EGC_OK;
 }
 
+// every node of the batch is a row of the launch; a.dis is only a flag here (`any`: some non-null device pointer): the deg^-1/2
+// tables are built per tile, in LDS
+static void batch_rows(AggArgs& a, const egc_layer* layer, int64_t n_nodes, const float* any) {
+  a.n_nodes = (int)n_nodes;
+  a.row_begin = 0;
+  a.row_end = (int)n_nodes;
+  a.dis = layer_uses_symnorm(layer) ? any : nullptr;
+  a.self_pos = 0;
+}
+
+// The argument checks both directions of the one-launch batch kernel share, and the AggArgs of a launch whose bases and
+// weightings never exist in memory.  `own_ok`: the caller's own pointer / alignment checks (EGC_ERR_INVALID like the ones
+// here, so their order does not show).  *go = false with EGC_OK: an empty batch, nothing to launch.
+static int fused_batch_args(AggArgs& a, const egc_layer* layer, const int64_t* graph_ptr, int64_t n_graphs, const int64_t* src,
+                            const int64_t* dst, int64_t n_edges, int64_t n_nodes, const int32_t* max_index, const float* x,
+                            const void* packed, const int32_t* status, bool own_ok, bool* go) {
+  *go = false;
+  if (n_nodes < 0 || n_graphs < 0 || n_edges < 0 || n_nodes >= ((int64_t)1 << 31) - 1 || n_edges >= ((int64_t)1 << 31) - 1)
+    return EGC_ERR_INVALID;
+  if (n_nodes == 0 || n_graphs == 0) return EGC_OK;
+  if (graph_ptr == nullptr || x == nullptr || packed == nullptr || status == nullptr || !own_ok) return EGC_ERR_INVALID;
+  if (n_edges > 0 && (src == nullptr || dst == nullptr)) return EGC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(packed) & 15) != 0) return EGC_ERR_INVALID;
+  if (!a.loops_all && max_index == nullptr) return EGC_ERR_INVALID;
+  if ((uint64_t)n_nodes * (uint64_t)a.F_out * 4ull > (uint64_t)OOB) return EGC_ERR_UNSUPPORTED;
+  batch_rows(a, layer, n_nodes, x);
+  a.bases = nullptr;          // never in memory
+  a.weightings = nullptr;
+  a.bases_bytes = 0;
+  *go = true;
+  return EGC_OK;
+}
+
 int32_t egc_batch_tile_nodes(const egc_layer* layer, int32_t max_tile_nodes, int32_t max_tile_edges, int32_t with_post) {
   AggArgs a;
   if (tile_layer_args(layer, a) != EGC_OK || max_tile_nodes < 1 || max_tile_edges < 0) return 0;
-  const int lpr = a.slots <= 16 ? 16 : a.slots <= 32 ? 32 : 64;
-  a.w_lds_stride = (a.W + 3) & ~3;
-  a.bias_lds_floats = (a.H * a.Ls + 3) & ~3;
-  a.lds_floats_per_wave = (with_post ? 2 : 1) * a.bias_lds_floats + (64 / lpr) * a.w_lds_stride;
-  return tile_capacity(a, max_tile_nodes, max_tile_edges);
+  return tile_capacity(a, max_tile_nodes, max_tile_edges, with_post != 0);
 }
 
 int egc_batch_plan(const int64_t* graph_ptr, const int64_t* edge_ptr, int64_t n_graphs, const int64_t* dst, int64_t n_edges,
@@ -912,20 +909,13 @@ int egc_aggregate_combine_batch_f32(const int32_t* tiles, const int32_t* n_tiles
   if ((uint64_t)n_nodes * (uint64_t)a.F_out * 4ull > (uint64_t)OOB) return EGC_ERR_UNSUPPORTED;   // out / residual descriptors
   a.ldw = ldw > 0 ? ldw : a.W;
   if (a.ldw != a.W && (a.ldw < a.W || (a.ldw & 3) != 0 || (reinterpret_cast<uintptr_t>(weightings) & 15) != 0)) return EGC_ERR_INVALID;
-  a.n_nodes = (int)n_nodes;
-  a.row_begin = 0;
-  a.row_end = (int)n_nodes;
+  batch_rows(a, layer, n_nodes, bases);
   a.bases = bases;
   a.weightings = weightings;
   a.bias = bias;
   a.out = out;
-  a.dis = layer_uses_symnorm(layer) ? bases : nullptr;   // (a flag here: the deg^-1/2 tables are built per tile, in LDS)
   a.bases_bytes = (unsigned)((uint64_t)n_nodes * ldb * 4ull);
-  a.post_scale = post != nullptr ? post->scale : nullptr;
-  a.post_shift = post != nullptr ? post->shift : nullptr;
-  a.residual = post != nullptr ? post->residual : nullptr;
-  a.post_relu = post != nullptr && post->relu != 0;
-  a.self_pos = 0;
+  agg_set_post(a, post);
   return launch_tile_simple(a, reinterpret_cast<const int4*>(tiles), n_tiles, n_tiles_bound, lds_nodes, max_tile_nodes,
                             max_tile_edges, src, dst, max_index, status, host_flag, (hipStream_t)stream);
 }
@@ -967,29 +957,13 @@ int egc_layer_forward_batch_fused_f32(const int64_t* graph_ptr, const int64_t* e
   AggArgs a;
   int st = tile_layer_args(layer, a, true);
   if (st != EGC_OK) return st;
-  if (n_nodes < 0 || n_graphs < 0 || n_edges < 0 || n_nodes >= ((int64_t)1 << 31) - 1 || n_edges >= ((int64_t)1 << 31) - 1)
-    return EGC_ERR_INVALID;
-  if (n_nodes == 0 || n_graphs == 0) return EGC_OK;
-  if (graph_ptr == nullptr || x == nullptr || packed == nullptr || out == nullptr || status == nullptr) return EGC_ERR_INVALID;
-  if (n_edges > 0 && (src == nullptr || dst == nullptr)) return EGC_ERR_INVALID;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(packed) & 15) != 0) return EGC_ERR_INVALID;
-  if (post != nullptr && ((post->scale == nullptr) != (post->shift == nullptr))) return EGC_ERR_INVALID;
-  if (!a.loops_all && max_index == nullptr) return EGC_ERR_INVALID;
-  if ((uint64_t)n_nodes * (uint64_t)a.F_out * 4ull > (uint64_t)OOB) return EGC_ERR_UNSUPPORTED;
-  a.n_nodes = (int)n_nodes;
-  a.row_begin = 0;
-  a.row_end = (int)n_nodes;
-  a.bases = nullptr;          // never in memory
-  a.weightings = nullptr;
-  a.bases_bytes = 0;
+  const bool own_ok = out != nullptr && (post == nullptr || (post->scale == nullptr) == (post->shift == nullptr));
+  bool go;
+  st = fused_batch_args(a, layer, graph_ptr, n_graphs, src, dst, n_edges, n_nodes, max_index, x, packed, status, own_ok, &go);
+  if (!go) return st;
   a.bias = bias;
   a.out = out;
-  a.dis = layer_uses_symnorm(layer) ? x : nullptr;   // (a flag: the deg^-1/2 tables are built per tile, in LDS)
-  a.post_scale = post != nullptr ? post->scale : nullptr;
-  a.post_shift = post != nullptr ? post->shift : nullptr;
-  a.residual = post != nullptr ? post->residual : nullptr;
-  a.post_relu = post != nullptr && post->relu != 0;
-  a.self_pos = 0;
+  agg_set_post(a, post);
   return launch_fused_tile(a, graph_ptr, edge_ptr, n_graphs, src, dst, n_edges, max_index, x, layer->in_channels, packed,
                            tile_nodes, max_tile_edges, status, host_flag, (hipStream_t)stream);
 }
@@ -1064,28 +1038,13 @@ int egc_layer_backward_batch_fused_f32(const int64_t* graph_ptr, const int64_t* 
   AggArgs a;
   int st = tile_layer_args(layer, a);
   if (st != EGC_OK) return st;
-  if (n_nodes < 0 || n_graphs < 0 || n_edges < 0 || n_nodes >= ((int64_t)1 << 31) - 1 || n_edges >= ((int64_t)1 << 31) - 1)
-    return EGC_ERR_INVALID;
-  if (n_nodes == 0 || n_graphs == 0) return EGC_OK;
-  if (graph_ptr == nullptr || x == nullptr || packed == nullptr || packed_t == nullptr || grad_out == nullptr || d_x == nullptr ||
-      status == nullptr)
-    return EGC_ERR_INVALID;
-  if (n_edges > 0 && (src == nullptr || dst == nullptr)) return EGC_ERR_INVALID;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(packed) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(packed_t) & 15) != 0 || (reinterpret_cast<uintptr_t>(grad_out) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_x_add) & 3) != 0)
-    return EGC_ERR_INVALID;
-  if (d_cat != nullptr && (ld_dcat < a.ldb + a.W || (ld_dcat & 3) != 0 || (reinterpret_cast<uintptr_t>(d_cat) & 15) != 0)) return EGC_ERR_INVALID;
-  if (!a.loops_all && max_index == nullptr) return EGC_ERR_INVALID;
-  if ((uint64_t)n_nodes * (uint64_t)a.F_out * 4ull > (uint64_t)OOB) return EGC_ERR_UNSUPPORTED;
-  a.n_nodes = (int)n_nodes;
-  a.row_begin = 0;
-  a.row_end = (int)n_nodes;
-  a.bases = nullptr;
-  a.weightings = nullptr;
-  a.bases_bytes = 0;
-  a.dis = layer_uses_symnorm(layer) ? x : nullptr;   // (a flag: the deg^-1/2 tables are built per tile, in LDS)
-  a.self_pos = 0;
+  const bool own_ok =
+      packed_t != nullptr && grad_out != nullptr && d_x != nullptr && (reinterpret_cast<uintptr_t>(packed_t) & 15) == 0 &&
+      (reinterpret_cast<uintptr_t>(grad_out) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_x_add) & 3) == 0 &&
+      (d_cat == nullptr || (ld_dcat >= a.ldb + a.W && (ld_dcat & 3) == 0 && (reinterpret_cast<uintptr_t>(d_cat) & 15) == 0));
+  bool go;
+  st = fused_batch_args(a, layer, graph_ptr, n_graphs, src, dst, n_edges, n_nodes, max_index, x, packed, status, own_ok, &go);
+  if (!go) return st;
   return launch_fused_tile_bwd(a, graph_ptr, edge_ptr, n_graphs, src, dst, n_edges, max_index, x, layer->in_channels, packed, packed_t,
                                grad_out, d_x, d_x_add, d_cat, ld_dcat, tile_nodes, max_tile_edges, status, host_flag, (hipStream_t)stream);
 }

@@ -133,6 +133,14 @@ struct AggArgs {
   int* queue;                // [FUSEDW_QUEUES + 1] work counters + exit counter (zero on entry, zero on exit)
 };
 
+// an aggregator list as one word: 3 bits per code, first aggregator in the low bits (what the compiled-in configurations of
+// the forward -- StCfg's AGG, agg_pack -- and of the backward -- bwd_agg_pack -- are matched against)
+static inline unsigned pack_aggr_codes(const int* aggr, int A) {
+  unsigned pk = 0;
+  for (int t = 0; t < A; ++t) pk |= (unsigned)aggr[t] << (3 * t);
+  return pk;
+}
+
 enum { STAT_SUM = 0, STAT_SQ = 1, STAT_MX = 2, STAT_MN = 3, STAT_WS = 4 };
 
 // Which raw statistics a layer's aggregator list needs (shared by the forward store and the backward load).
@@ -226,7 +234,7 @@ int launch_wide_rows(AggArgs a, const PlanCaps& caps, hipStream_t stream);   // 
 constexpr int FUSEDW_QUEUE_INTS = 16;  // (reserved words of the aggregate workspace: layout of rounds 2-4)
 
 // egc_aggregate_tile.hip: batches of small graphs, tiles of whole graphs with the CSR built in LDS
-int tile_capacity(const AggArgs& a, int tmax, int emax);
+int tile_capacity(AggArgs a, int tmax, int emax, bool with_post);
 int launch_tile_plan(const int64_t* ptr, int64_t n_graphs, const int64_t* dst, int64_t n_edges, int64_t n_nodes, int slot,
                      int n_slots, int4* tiles, int* count, const int64_t* edge_ptr, hipStream_t stream);
 int launch_tile_simple(AggArgs a, const int4* tiles, const int* n_tiles_dev, int n_tiles_bound, int tlds, int tmax, int emax,

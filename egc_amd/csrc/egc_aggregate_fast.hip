@@ -35,7 +35,7 @@
 //     arguments and serves every other qualifying layer with the same code.
 #include <stdlib.h>
 
-#include "egc_aggregate_fast_dev.h"
+#include "egc_aggregate_host.h"
 
 namespace egc {
 
@@ -436,15 +436,14 @@ bool wide_path_supported(const AggArgs& a, int layout) {
   if ((a.Ls & 3) != 0 || a.ldb != a.B * a.Ls) return false;          // every 16-byte slot belongs to one basis (padded bases)
   if ((a.B & (a.B - 1)) != 0) return false;
   if (a.A < 1 || a.A > AMAX) return false;
-  if ((a.H + a.B - 1) / a.B > HPB_MAX) return false;
+  if (agg_hpb(a) > HPB_MAX) return false;
   if (a.W > 512) return false;                                        // weightings row: 2 x 16 bytes per lane
   const int P = a.Ls / 4, P0 = (P + 1) / 2;
   if (a.B * P0 > 64) return false;
   if (a.stats != nullptr || a.arg_max != nullptr || a.arg_min != nullptr) return false;   // inference form
   if ((uint64_t)a.n_nodes * (uint64_t)a.F_out * 4ull > (uint64_t)OOB) return false;
   // LDS of launch_wide_rows (bias strip [+ scale strip] + one weightings row per wavefront, four wavefronts)
-  const size_t strips = (size_t)(a.post_scale != nullptr ? 2 : 1) * ((a.H * a.Ls + 3) & ~3) + ((a.W + 3) & ~3);
-  if (4 * strips * sizeof(float) > 64 * 1024) return false;
+  if ((size_t)4 * agg_strip_floats(a, 1, a.post_scale != nullptr) * sizeof(float) > 64 * 1024) return false;
   return true;
 }
 
@@ -455,56 +454,43 @@ static int launch_wide_one(const AggArgs& a, unsigned grid, size_t lds, hipStrea
   return EGC_OK;
 }
 
-template <int HPB>
-static int launch_wide_need(const AggArgs& a, int need, unsigned grid, size_t lds, hipStream_t stream) {
-  using R0 = WideSet<RtCfg, 0>;
-  using R1 = WideSet<RtCfg, 1>;
-  if (need == 0) return launch_wide_one<HPB, 0, R0, R1>(a, grid, lds, stream);
-  return launch_wide_one<HPB, NEED_SQ | NEED_MN, R0, R1>(a, grid, lds, stream);
+// a compiled-in layer of the two-slots-per-lane kernel: P0 + P1 slots of every basis in the first / second set
+template <class St, int HPB, int NEED, int P0, int P1>
+static bool try_wide_static(const AggArgs& a, unsigned grid, size_t lds, hipStream_t stream, int* status) {
+  if (!cfg_matches<St>(a)) return false;
+  *status = launch_wide_one<HPB, NEED, WideSet<St, 0, P0, 0>, WideSet<St, 1, P1, P0>>(a, grid, lds, stream);
+  return true;
 }
 
 int launch_wide_rows(AggArgs a, const PlanCaps& caps, hipStream_t stream) {
   const int P = a.Ls / 4;
   a.wide_p0 = (P + 1) / 2;
   a.wide_p1 = P - a.wide_p0;
-  a.magic_P = (unsigned)(((uint64_t)1 << 32) / (uint64_t)a.wide_p0) + 1u;
-  a.magic_P1 = (unsigned)(((uint64_t)1 << 32) / (uint64_t)a.wide_p1) + 1u;
-  a.lanes_pb = a.wide_p0;
-  a.lpb_log2 = -1;
+  agg_lane_geometry(a, a.wide_p0);
+  a.lpb_log2 = -1;                  // (WideSet answers pow2 / lpb_log2 itself)
+  a.magic_P1 = agg_magic(a.wide_p1);
   a.l4_off = 0;
   a.rows_per_wave = 8;
   a.chunk_blocks = (int)ceil_div(a.n_chunks_hint >= 0 ? a.n_chunks_hint : caps.cap_chunks, 4);
-  a.need_mean = a.need_var = 0;
-  int need = 0;
-  unsigned packed = 0;
-  for (int t = 0; t < a.A; ++t) {
-    if (a.aggr[t] == EGC_AGGR_MEAN || a.aggr[t] == EGC_AGGR_VAR || a.aggr[t] == EGC_AGGR_STD) a.need_mean = 1;
-    if (a.aggr[t] == EGC_AGGR_VAR || a.aggr[t] == EGC_AGGR_STD) { a.need_var = 1; need |= NEED_SQ; }
-    if (a.aggr[t] == EGC_AGGR_MIN) need |= NEED_MN;
-    packed |= (unsigned)a.aggr[t] << (3 * t);
-  }
-  a.w_lds_stride = (a.W + 3) & ~3;
-  a.bias_lds_floats = (a.H * a.Ls + 3) & ~3;
-  a.lds_floats_per_wave = (a.post_scale != nullptr ? 2 : 1) * a.bias_lds_floats + a.w_lds_stride;   // G = 1
+  const int need = agg_need(a);
+  agg_lds_strips(a, 1, a.post_scale != nullptr);   // G = 1
   const size_t lds = (size_t)4 * a.lds_floats_per_wave * sizeof(float);
   if (lds > 64 * 1024) return EGC_ERR_UNSUPPORTED;
   const unsigned grid = (unsigned)(a.chunk_blocks + ceil_div((int64_t)a.row_end - a.row_begin, (int64_t)4 * a.rows_per_wave));
-  if (getenv("EGC_NO_STATIC_CFG") == nullptr && a.act == EGC_ACT_NONE && !a.x_looped && a.y_looped && a.loops_all) {
+  if (getenv("EGC_NO_STATIC_CFG") == nullptr) {
+    int status = EGC_OK;
     constexpr int X = EGC_AGGR_MAX, N = EGC_AGGR_MIN, Y = EGC_AGGR_SYMNORM;
     // the reference's ogbg-code nets (run_pretrained.sh:47-48): EGC-M 300/H4/B4 symadd,min,max and EGC-S 304/H8/B8 symadd
-    if (a.H == 4 && a.B == 4 && a.L == 75 && a.Ls == 76 && a.A == 3 && packed == agg_pack(Y, N, X)) {
-      using St = StCfg<4, 4, 75, 3, agg_pack(Y, N, X), EGC_ACT_NONE, false, true, true, 76>;
-      return launch_wide_one<1, NEED_MN, WideSet<St, 0, 10, 0>, WideSet<St, 1, 9, 10>>(a, grid, lds, stream);
-    }
-    if (a.H == 8 && a.B == 8 && a.L == 38 && a.Ls == 40 && a.A == 1 && packed == agg_pack(Y)) {
-      using St = StCfg<8, 8, 38, 1, agg_pack(Y), EGC_ACT_NONE, false, true, true, 40>;
-      return launch_wide_one<1, 0, WideSet<St, 0, 5, 0>, WideSet<St, 1, 5, 5>>(a, grid, lds, stream);
-    }
+    if (try_wide_static<StCfg<4, 4, 75, 3, agg_pack(Y, N, X), EGC_ACT_NONE, false, true, true, 76>, 1, NEED_MN, 10, 9>(
+            a, grid, lds, stream, &status)) return status;
+    if (try_wide_static<StCfg<8, 8, 38, 1, agg_pack(Y), EGC_ACT_NONE, false, true, true, 40>, 1, 0, 5, 5>(
+            a, grid, lds, stream, &status)) return status;
   }
-  const int hpb = (a.H + a.B - 1) / a.B;
-  if (hpb <= 1) return launch_wide_need<1>(a, need, grid, lds, stream);
-  if (hpb <= 2) return launch_wide_need<2>(a, need, grid, lds, stream);
-  return launch_wide_need<4>(a, need, grid, lds, stream);
+  using R0 = WideSet<RtCfg, 0>;
+  using R1 = WideSet<RtCfg, 1>;
+  return agg_dispatch_rows<NeedCoarse>(a, need, [&](auto hpb, auto nd) {
+    return launch_wide_one<decltype(hpb)::value, decltype(nd)::value, R0, R1>(a, grid, lds, stream);
+  });
 }
 
 bool fast_path_supported(const AggArgs& a, int layout, int chunks) {
@@ -514,8 +500,8 @@ bool fast_path_supported(const AggArgs& a, int layout, int chunks) {
   if ((a.Ls & 3) != 0 || a.ldb != a.B * a.Ls) return false;  // every 16-byte slot belongs to one basis
   if ((a.B & (a.B - 1)) != 0) return false;
   if (a.A < 1 || a.A > AMAX) return false;
-  if ((a.H + a.B - 1) / a.B > HPB_MAX) return false;
-  if (a.W > 8 * (a.slots <= 16 ? 16 : a.slots <= 32 ? 32 : 64)) return false;  // weightings row: 2 x 16 bytes per lane of a group
+  if (agg_hpb(a) > HPB_MAX) return false;
+  if (a.W > 8 * agg_lpr(a.slots)) return false;  // weightings row: 2 x 16 bytes per lane of a group
   // the buffer descriptor addresses `out` with 32-bit byte offsets
   if ((uint64_t)a.n_nodes * (uint64_t)a.F_out * 4ull > (uint64_t)OOB) return false;
   return true;
@@ -528,40 +514,13 @@ static int launch_one(const AggArgs& a, unsigned grid, size_t lds, hipStream_t s
   return EGC_OK;
 }
 
-template <int LPR_LOG2, int HPB>
-static int launch_need(const AggArgs& a, int need, unsigned grid, size_t lds, hipStream_t stream) {
-  if (a.arg_max != nullptr || a.arg_min != nullptr) {  // training forward of a layer with max / min
-    if (need == 0) return launch_one<LPR_LOG2, HPB, NEED_ARG, RtCfg>(a, grid, lds, stream);
-    return launch_one<LPR_LOG2, HPB, NEED_SQ | NEED_MN | NEED_ARG, RtCfg>(a, grid, lds, stream);
-  }
-  if (need == 0) return launch_one<LPR_LOG2, HPB, 0, RtCfg>(a, grid, lds, stream);
-  // (squares without min and min without squares are kernels of their own: either accumulator alone leaves room for a fifth
-  // wavefront per SIMD -- a std layer's aggregate at ogbn-arxiv size 137 -> see DESIGN.md 3.1)
-  if (need == NEED_SQ) return launch_one<LPR_LOG2, HPB, NEED_SQ, RtCfg>(a, grid, lds, stream);
-  if (need == NEED_MN) return launch_one<LPR_LOG2, HPB, NEED_MN, RtCfg>(a, grid, lds, stream);
-  return launch_one<LPR_LOG2, HPB, NEED_SQ | NEED_MN, RtCfg>(a, grid, lds, stream);
-}
-
-template <int LPR_LOG2>
-static int launch_rt(const AggArgs& a, int need, unsigned grid, size_t lds, hipStream_t stream) {
-  const int hpb = (a.H + a.B - 1) / a.B;
-  if (hpb <= 1) return launch_need<LPR_LOG2, 1>(a, need, grid, lds, stream);
-  if (hpb <= 2) return launch_need<LPR_LOG2, 2>(a, need, grid, lds, stream);
-  return launch_need<LPR_LOG2, 4>(a, need, grid, lds, stream);
-}
-
-
 // Statically specialised configurations (H, B, L, aggregator list, nonlinearity, edge sets).  Adding a
 // line to launch_fast() buys the constant-folded kernel for that layer; everything else runs RtCfg.
-template <class C, int LPR_LOG2, int HPB, int NEED>
-static bool try_static(const AggArgs& a, int h, int b, int l, int ls, int na, unsigned agg, int act, bool xl, bool yl,
-                       bool loops_all, unsigned grid, size_t lds, hipStream_t stream, int* status) {
-  unsigned packed = 0;
-  for (int t = 0; t < a.A; ++t) packed |= (unsigned)a.aggr[t] << (3 * t);
-  if (a.H != h || a.B != b || a.L != l || a.A != na || packed != agg || a.act != act ||
-      (a.x_looped != 0) != xl || (a.y_looped != 0) != yl || (a.loops_all != 0) != loops_all ||
-      a.Ls != ls || a.slots > (1 << LPR_LOG2) || 2 * a.slots <= (1 << LPR_LOG2))
-    return false;
+// The lane-group size and the heads per lane follow from the configuration; NEED is the entry's own.
+template <class C, int NEED>
+static bool try_static(const AggArgs& a, unsigned grid, size_t lds, hipStream_t stream, int* status) {
+  constexpr int LPR_LOG2 = agg_lpr_log2(C::kB * C::P_), HPB = (C::kH + C::kB - 1) / C::kB;
+  if (!cfg_matches<C>(a) || a.slots > (1 << LPR_LOG2) || 2 * a.slots <= (1 << LPR_LOG2)) return false;
   if constexpr (C::has(EGC_AGGR_MAX)) {
     if (a.arg_max != nullptr) {  // training forward: the variant that also tracks the arg positions
       *status = launch_one<LPR_LOG2, HPB, NEED | NEED_ARG, C>(a, grid, lds, stream);
@@ -572,26 +531,14 @@ static bool try_static(const AggArgs& a, int h, int b, int l, int ls, int na, un
   return true;
 }
 
-constexpr int lpr_log2_of(int slots) { return slots <= 16 ? 4 : slots <= 32 ? 5 : 6; }
+// (bases whose length is no multiple of 4 are padded to the next one: StCfg's LS)
 #define EGC_STATIC_CFG(H, B, L, A, AGG, ACT, XL, YL, LA, NEED)                                                      \
-  if (try_static<StCfg<H, B, L, A, AGG, ACT, XL, YL, LA, ((L) + 3) / 4 * 4>,                                        \
-                 lpr_log2_of((B) * (((L) + 3) / 4)), ((H) + (B)-1) / (B), NEED>(                                   \
-          a, H, B, L, ((L) + 3) / 4 * 4, A, AGG, ACT, XL, YL, LA, grid, lds, stream, &status))                      \
+  if (try_static<StCfg<H, B, L, A, AGG, ACT, XL, YL, LA, ((L) + 3) / 4 * 4>, NEED>(a, grid, lds, stream, &status)) \
     return status;
 
 int launch_fast(AggArgs a, int64_t n_nodes, const PlanCaps& caps, hipStream_t stream) {
-  const int lpr = a.slots <= 16 ? 16 : a.slots <= 32 ? 32 : 64;
-  const int G = 64 / lpr;
-  // lanes per basis: shifts and an xor butterfly when L / 4 is a power of two, else division + rotation butterfly
-  a.lanes_pb = a.Ls / 4;
-  a.magic_P = (unsigned)(((uint64_t)1 << 32) / (uint64_t)a.lanes_pb) + 1u;  // q / lanes_pb == umulhi(q, magic_P), q < 64
-  if ((a.lanes_pb & (a.lanes_pb - 1)) == 0) {
-    int lg = 0;
-    while ((4 << lg) < a.Ls) ++lg;
-    a.lpb_log2 = lg;
-  } else {
-    a.lpb_log2 = -1;
-  }
+  const int G = 64 / agg_lpr(a.slots);
+  agg_lane_geometry(a);
   // Row groups per wavefront (the kernel requests group k + 1's bounds and first column indices under group k's gathers, and
   // stages its bias strip once).  One-row groups (33 - 64 slots: the 136 - 352-wide layers) on graphs that leave every CU
   // thousands of wavefronts take four: row pointers -> indices -> gathers are three dependent round trips per row otherwise --
@@ -602,16 +549,8 @@ int launch_fast(AggArgs a, int64_t n_nodes, const PlanCaps& caps, hipStream_t st
   if (a.rows_per_wave <= 0) a.rows_per_wave = (G == 1 && (int64_t)a.row_end - a.row_begin >= 32768) ? 4 : 1;
   if (a.rows_per_wave * G > 60) a.rows_per_wave = 60 / G;
   a.chunk_blocks = (int)ceil_div(a.n_chunks_hint >= 0 ? a.n_chunks_hint : caps.cap_chunks, 4);
-  a.need_mean = a.need_var = 0;
-  int need = 0;
-  for (int t = 0; t < a.A; ++t) {
-    if (a.aggr[t] == EGC_AGGR_MEAN || a.aggr[t] == EGC_AGGR_VAR || a.aggr[t] == EGC_AGGR_STD) a.need_mean = 1;
-    if (a.aggr[t] == EGC_AGGR_VAR || a.aggr[t] == EGC_AGGR_STD) { a.need_var = 1; need |= NEED_SQ; }
-    if (a.aggr[t] == EGC_AGGR_MIN) need |= NEED_MN;
-  }
-  a.w_lds_stride = (a.W + 3) & ~3;
-  a.bias_lds_floats = (a.H * a.Ls + 3) & ~3;  // >= F_out: the bias strip follows the (padded) head layout
-  a.lds_floats_per_wave = (a.post_scale != nullptr ? 2 : 1) * a.bias_lds_floats + G * a.w_lds_stride;
+  const int need = agg_need(a);
+  agg_lds_strips(a, G, a.post_scale != nullptr);
   size_t lds = (size_t)4 * a.lds_floats_per_wave * sizeof(float);
   if (lds > 64 * 1024) return EGC_ERR_UNSUPPORTED;
   const int64_t row_blocks = ceil_div((int64_t)a.row_end - a.row_begin, (int64_t)4 * a.rows_per_wave * G);
@@ -649,11 +588,9 @@ int launch_fast(AggArgs a, int64_t n_nodes, const PlanCaps& caps, hipStream_t st
     EGC_STATIC_CFG(4, 4, 16, 2, agg_pack(M, X), EGC_ACT_NONE, false, false, true, 0)
     EGC_STATIC_CFG(4, 4, 16, 1, agg_pack(S), EGC_ACT_NONE, false, false, true, 0)
   }
-  switch (lpr) {
-    case 16: return launch_rt<4>(a, need, grid, lds, stream);
-    case 32: return launch_rt<5>(a, need, grid, lds, stream);
-    default: return launch_rt<6>(a, need, grid, lds, stream);
-  }
+  return agg_dispatch<NeedFine>(a, need, [&](auto lpr, auto hpb, auto nd) {
+    return launch_one<decltype(lpr)::value, decltype(hpb)::value, decltype(nd)::value, RtCfg>(a, grid, lds, stream);
+  });
 }
 
 }  // namespace egc

@@ -64,7 +64,10 @@ constexpr unsigned agg_pack(int a0, int a1 = 0, int a2 = 0, int a3 = 0) {
 // LS_ = floats between consecutive bases in a row (L_ rounded up to 4 when the layer pads them).
 template <int H_, int B_, int L_, int A_, unsigned AGG, int ACT_, bool XL_, bool YL_, bool LOOPS_ALL_, int LS_ = L_>
 struct StCfg {
-  static constexpr int kH = H_;
+  // what the host matches a layer against (cfg_matches, egc_aggregate_host.h): each constant is stated here and nowhere else
+  static constexpr int kH = H_, kB = B_, kL = L_, kLs = LS_, kA = A_, kAct = ACT_;
+  static constexpr unsigned kAgg = AGG;
+  static constexpr bool kXl = XL_, kYl = YL_, kLoopsAll = LOOPS_ALL_;
   static constexpr int P_ = LS_ / 4;                       // lanes per basis
   static constexpr bool POW2_ = (P_ & (P_ - 1)) == 0;
   static constexpr int agg_at(int t) { return (int)((AGG >> (3 * t)) & 7u); }

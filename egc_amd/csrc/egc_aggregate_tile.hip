@@ -32,7 +32,7 @@
 // give the same bits.
 #include <algorithm>
 
-#include "egc_aggregate_fast_dev.h"
+#include "egc_aggregate_host.h"
 
 namespace egc {
 
@@ -473,47 +473,16 @@ constexpr size_t TILE_LDS_BUDGET = (160 * 1024) / TILE_WGS_PER_CU - 512;   // pe
 
 template <int LPR_LOG2, int HPB, int NEED, class C>
 static int launch_tile_one(const AggArgs& a, const TileArgs& t, unsigned grid, size_t lds, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&agg_tile_kernel<LPR_LOG2, HPB, NEED, C>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)TILE_LDS_BUDGET);
-    if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(agg_tile_kernel)", e); return EGC_ERR_HIP; }
-    attr_set = true;
-  }
-  agg_tile_kernel<LPR_LOG2, HPB, NEED, C><<<grid, TILE_THREADS, lds, stream>>>(a, t);
+  const auto kern = &agg_tile_kernel<LPR_LOG2, HPB, NEED, C>;
+  EGC_ALLOW_DYNAMIC_LDS(kern, TILE_LDS_BUDGET, "agg_tile_kernel");
+  kern<<<grid, TILE_THREADS, lds, stream>>>(a, t);
   EGC_LAUNCH_CHECK("agg_tile_kernel");
   return EGC_OK;
 }
 
-template <int LPR_LOG2>
-static int launch_tile_rt(const AggArgs& a, const TileArgs& t, int need, unsigned grid, size_t lds, hipStream_t stream) {
-  const int hpb = (a.H + a.B - 1) / a.B;
-  if (need == 0) {
-    if (hpb <= 1) return launch_tile_one<LPR_LOG2, 1, 0, RtCfg>(a, t, grid, lds, stream);
-    if (hpb <= 2) return launch_tile_one<LPR_LOG2, 2, 0, RtCfg>(a, t, grid, lds, stream);
-    return launch_tile_one<LPR_LOG2, 4, 0, RtCfg>(a, t, grid, lds, stream);
-  }
-  if (hpb <= 1) return launch_tile_one<LPR_LOG2, 1, NEED_SQ | NEED_MN, RtCfg>(a, t, grid, lds, stream);
-  if (hpb <= 2) return launch_tile_one<LPR_LOG2, 2, NEED_SQ | NEED_MN, RtCfg>(a, t, grid, lds, stream);
-  return launch_tile_one<LPR_LOG2, 4, NEED_SQ | NEED_MN, RtCfg>(a, t, grid, lds, stream);
-}
-
-// the layer configurations with their constants compiled in (the same idea as EGC_STATIC_CFG of the fast kernel)
-template <class C, int LPR_LOG2, int HPB, int NEED>
-static bool try_tile_static(const AggArgs& a, const TileArgs& t, int h, int b, int l, int na, unsigned agg, bool xl, bool yl,
-                            bool loops_all, unsigned grid, size_t lds, hipStream_t stream, int* status) {
-  unsigned packed = 0;
-  for (int k = 0; k < a.A; ++k) packed |= (unsigned)a.aggr[k] << (3 * k);
-  if (a.H != h || a.B != b || a.L != l || a.Ls != l || a.A != na || packed != agg || a.act != EGC_ACT_NONE ||
-      (a.x_looped != 0) != xl || (a.y_looped != 0) != yl || (a.loops_all != 0) != loops_all)
-    return false;
-  *status = launch_tile_one<LPR_LOG2, HPB, NEED, C>(a, t, grid, lds, stream);
-  return true;
-}
-
 // nodes whose basis rows fit the LDS area of one workgroup, next to CSR areas for (tmax nodes, emax edges)
-int tile_capacity(const AggArgs& a_in, int tmax, int emax) {
-  AggArgs a = a_in;
+int tile_capacity(AggArgs a, int tmax, int emax, bool with_post) {
+  agg_lds_strips(a, 64 / agg_lpr(a.slots), with_post);     // as launch_tile: the query and the launch agree about LDS
   int best = 0;
   for (int tlds = 16; tlds <= tmax; tlds += 16) {
     if (tile_lds(a, tlds, tmax, emax).total <= TILE_LDS_BUDGET) best = tlds; else break;
@@ -522,49 +491,24 @@ int tile_capacity(const AggArgs& a_in, int tmax, int emax) {
 }
 
 int launch_tile(AggArgs a, TileArgs t, int n_tiles, hipStream_t stream) {
-  const int lpr = a.slots <= 16 ? 16 : a.slots <= 32 ? 32 : 64;
-  const int G = 64 / lpr;
-  a.lanes_pb = a.Ls / 4;
-  a.magic_P = (unsigned)(((uint64_t)1 << 32) / (uint64_t)a.lanes_pb) + 1u;
-  if ((a.lanes_pb & (a.lanes_pb - 1)) == 0) {
-    int lg = 0;
-    while ((4 << lg) < a.Ls) ++lg;
-    a.lpb_log2 = lg;
-  } else {
-    a.lpb_log2 = -1;
-  }
-  a.need_mean = a.need_var = 0;
-  int need = 0;
-  for (int k = 0; k < a.A; ++k) {
-    if (a.aggr[k] == EGC_AGGR_MEAN || a.aggr[k] == EGC_AGGR_VAR || a.aggr[k] == EGC_AGGR_STD) a.need_mean = 1;
-    if (a.aggr[k] == EGC_AGGR_VAR || a.aggr[k] == EGC_AGGR_STD) { a.need_var = 1; need |= NEED_SQ; }
-    if (a.aggr[k] == EGC_AGGR_MIN) need |= NEED_MN;
-  }
-  a.w_lds_stride = (a.W + 3) & ~3;
-  a.bias_lds_floats = (a.H * a.Ls + 3) & ~3;
-  a.lds_floats_per_wave = (a.post_scale != nullptr ? 2 : 1) * a.bias_lds_floats + G * a.w_lds_stride;
+  agg_lane_geometry(a);
+  const int need = agg_need(a);
+  agg_lds_strips(a, 64 / agg_lpr(a.slots), a.post_scale != nullptr);
   const TileLds L = tile_lds(a, t.tlds, t.tmax, t.emax);
   if (L.total > TILE_LDS_BUDGET || t.tmax > TILE_MAX_NODES || t.tlds > t.tmax || t.tlds < 1 || t.emax > 65535) return EGC_ERR_UNSUPPORTED;   // (16-bit cursors)
   t.off_bases = L.off_bases; t.off_col = L.off_col; t.off_rowptr = L.off_rowptr; t.off_cnt = L.off_cnt; t.off_ns = L.off_ns;
   t.off_dis_raw = L.off_dis_raw; t.off_dis_looped = L.off_dis_looped;
   const unsigned grid = (unsigned)std::min(n_tiles, 256 * TILE_WGS_PER_CU);   // persistent: n_tiles = upper bound of the tile count
+  // the d = 128 layer configurations with their constants compiled in (the same idea as EGC_STATIC_CFG of the fast kernel):
+  // 16-lane groups, two heads per lane, no optional aggregate
   if (getenv("EGC_NO_STATIC_CFG") == nullptr) {
-    int status = EGC_OK;
-    constexpr int S = EGC_AGGR_SUM, M = EGC_AGGR_MEAN, X = EGC_AGGR_MAX, Y = EGC_AGGR_SYMNORM;
-    // EGConv EGC-M north star (configs 3 / 4 of BASELINE.json): d=128, H=8, B=4, sum+mean+max+symnorm, loops on every node
-    if (try_tile_static<StCfg<8, 4, 16, 4, agg_pack(S, M, X, Y), EGC_ACT_NONE, true, true, true>, 4, 2, 0>(
-            a, t, 8, 4, 16, 4, agg_pack(S, M, X, Y), true, true, true, grid, L.total, stream, &status)) return status;
-    // EfficientGraphConv EGC-M / EGC-S at d=128 (symadd looped, the others raw)
-    if (try_tile_static<StCfg<8, 4, 16, 3, agg_pack(Y, X, M), EGC_ACT_NONE, false, true, true>, 4, 2, 0>(
-            a, t, 8, 4, 16, 3, agg_pack(Y, X, M), false, true, true, grid, L.total, stream, &status)) return status;
-    if (try_tile_static<StCfg<8, 4, 16, 1, agg_pack(Y), EGC_ACT_NONE, false, true, true>, 4, 2, 0>(
-            a, t, 8, 4, 16, 1, agg_pack(Y), false, true, true, grid, L.total, stream, &status)) return status;
+    if (cfg_matches<cfg::EGConvM128>(a)) return launch_tile_one<4, 2, 0, cfg::EGConvM128>(a, t, grid, L.total, stream);
+    if (cfg_matches<cfg::EgcM128>(a)) return launch_tile_one<4, 2, 0, cfg::EgcM128>(a, t, grid, L.total, stream);
+    if (cfg_matches<cfg::EgcS128>(a)) return launch_tile_one<4, 2, 0, cfg::EgcS128>(a, t, grid, L.total, stream);
   }
-  switch (lpr) {
-    case 16: return launch_tile_rt<4>(a, t, need, grid, L.total, stream);
-    case 32: return launch_tile_rt<5>(a, t, need, grid, L.total, stream);
-    default: return launch_tile_rt<6>(a, t, need, grid, L.total, stream);
-  }
+  return agg_dispatch<NeedCoarse>(a, need, [&](auto lpr, auto hpb, auto nd) {
+    return launch_tile_one<decltype(lpr)::value, decltype(hpb)::value, decltype(nd)::value, RtCfg>(a, t, grid, L.total, stream);
+  });
 }
 
 int launch_tile_simple(AggArgs a, const int4* tiles, const int* n_tiles_dev, int n_tiles_bound, int tlds, int tmax, int emax,

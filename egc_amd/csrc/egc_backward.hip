@@ -1388,8 +1388,7 @@ int egc_aggregate_combine_backward_f32(const egc_graph* graph, const egc_graph* 
       }
       const unsigned fgrid = (unsigned)(a.dst_row_blocks + rec_chunk_blocks);
       if (flds > 64 * 1024) return EGC_ERR_UNSUPPORTED;
-      unsigned packed = BWD_STATIC;
-      for (int t = 0; t < a.A; ++t) packed |= (unsigned)a.aggr[t] << (3 * t);
+      const unsigned packed = BWD_STATIC | pack_aggr_codes(a.aggr, a.A);
       constexpr int S = EGC_AGGR_SUM, M = EGC_AGGR_MEAN, X = EGC_AGGR_MAX, Y = EGC_AGGR_SYMNORM;
       // the reference's own batched nets with their aggregator lists compiled in (round 6: these layers train on this path --
       // DESIGN.md section 3.7 -- and the run-time form's per-aggregator switches are most of its instructions): molhiv EGC-M

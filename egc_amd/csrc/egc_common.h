@@ -30,6 +30,22 @@ void set_last_error(const char* what, hipError_t err);
     }                                              \
   } while (0)
 
+// Allow `bytes` of dynamic LDS (beyond the default 64 KiB) for one kernel instance, once per process: the flag is a static of
+// the expansion, so inside a launcher template there is one per kernel instance.  Returns EGC_ERR_HIP from the caller on failure.
+#define EGC_ALLOW_DYNAMIC_LDS(kernel, bytes, what)                                                              \
+  do {                                                                                                          \
+    static bool _allowed = false;                                                                               \
+    if (!_allowed) {                                                                                            \
+      hipError_t _e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),                                \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes));            \
+      if (_e != hipSuccess) {                                                                                   \
+        ::egc::set_last_error("hipFuncSetAttribute(" what ")", _e);                                             \
+        return EGC_ERR_HIP;                                                                                     \
+      }                                                                                                         \
+      _allowed = true;                                                                                          \
+    }                                                                                                           \
+  } while (0)
+
 // vector types of the kernels (MFMA operands and accumulators, packed fp16 / bf16, 8- and 16-byte LDS pieces)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));

@@ -30,6 +30,7 @@
 // their tile raise *status and the sticky host flag; the host routes batches whose declared largest graph exceeds the
 // capacity to the two-launch path.
 #include "egc_pack_map.h"
+#include "egc_aggregate_host.h"
 #include "egc_fused_tile_dev.h"
 
 namespace egc {
@@ -164,8 +165,7 @@ struct FtLds {
 static FtLds ft_lds(const AggArgs& a, int wl_floats, int tcap, int emax, bool with_post, bool wide = false, bool bwd = false) {
   FtLds L = {};
   auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const int bias_floats = (a.H * a.Ls + 3) & ~3;
-  size_t at = up16((size_t)(with_post ? 2 : 1) * bias_floats * sizeof(float));
+  size_t at = up16((size_t)(with_post ? 2 : 1) * agg_bias_floats(a) * sizeof(float));
   L.off_rec = (int)at; at += 128;
   L.off_planes = (int)at; at += wide ? FTW_PLANES_BYTES : (bwd ? std::max(FT_PLANES_BYTES, FTB_PLANES_BYTES) : FT_PLANES_BYTES);
   L.off_rowinv = (int)at; at += wide ? up16(2 * FTW_CH * sizeof(float)) : up16(FT_PBUF * FT_CHUNK * sizeof(float));
@@ -208,110 +208,87 @@ int fused_tile_capacity(const AggArgs& a, int f_in, int max_tile_edges, bool wit
   return best;
 }
 
-template <int LPR_LOG2, int HPB, int NEED, class C>
-static int launch_ft_one(const AggArgs& a, const FusedTileArgs& t, unsigned grid, size_t lds, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_tile_kernel<LPR_LOG2, HPB, NEED, C>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(fused_tile_kernel)", e); return EGC_ERR_HIP; }
-    attr_set = true;
-  }
-  fused_tile_kernel<LPR_LOG2, HPB, NEED, C><<<grid, FT_THREADS, lds, stream>>>(a, t);
-  EGC_LAUNCH_CHECK("fused_tile_kernel");
-  return EGC_OK;
+// What both directions of the one-launch kernel hand it: AggArgs' share (the lane geometry of a row, the bias strip; the
+// weight strip of a lane group IS the row of the LDS image it is handed -- finish_group<W_READY> -- so there is none per
+// wavefront) ...
+static int ft_row_args(AggArgs& a, bool with_post) {
+  agg_lane_geometry(a);
+  const int need = agg_need(a);
+  agg_lds_strips(a, 0, with_post);
+  a.w_lds_stride = 0;
+  a.lds_floats_per_wave = 0;
+  return need;
 }
 
-template <int LPR_LOG2>
-static int launch_ft_rt(const AggArgs& a, const FusedTileArgs& t, int need, unsigned grid, size_t lds, hipStream_t stream) {
-  const int hpb = (a.H + a.B - 1) / a.B;
-  if (need == 0) {
-    if (hpb <= 1) return launch_ft_one<LPR_LOG2, 1, 0, RtCfg>(a, t, grid, lds, stream);
-    if (hpb <= 2) return launch_ft_one<LPR_LOG2, 2, 0, RtCfg>(a, t, grid, lds, stream);
-    return launch_ft_one<LPR_LOG2, 4, 0, RtCfg>(a, t, grid, lds, stream);
-  }
-  if (hpb <= 1) return launch_ft_one<LPR_LOG2, 1, NEED_SQ | NEED_MN, RtCfg>(a, t, grid, lds, stream);
-  if (hpb <= 2) return launch_ft_one<LPR_LOG2, 2, NEED_SQ | NEED_MN, RtCfg>(a, t, grid, lds, stream);
-  return launch_ft_one<LPR_LOG2, 4, NEED_SQ | NEED_MN, RtCfg>(a, t, grid, lds, stream);
+// ... and FusedTileArgs': the batch, the LDS image (`L`: ft_lds of a.H * a.B * a.w_aw floats per weightings row), the virtual
+// column tiles.  Returns the grid: one workgroup per CU at most; fewer when the batch is small (a workgroup's share: at least
+// ~16 nodes, at least one graph).
+static unsigned ft_tile_args(FusedTileArgs& t, const AggArgs& a, const FtLds& L, bool wide, const int64_t* ptr, const int64_t* edge_ptr,
+                             int64_t n_graphs, const int64_t* src, const int64_t* dst, int64_t n_edges, const int* max_index,
+                             const float* x, int f_in, const void* packed, int tcap, int emax, int32_t* status, int32_t* host_flag) {
+  t = FusedTileArgs{};
+  t.ptr = ptr; t.edge_ptr = edge_ptr; t.n_graphs = n_graphs; t.src = src; t.dst = dst; t.n_edges = n_edges;
+  t.max_index = max_index; t.status = status; t.host_flag = host_flag; t.x = x; t.packed = (const u16*)packed;
+  t.F_in = f_in;
+  t.n_ct = wide ? ftw_n_ct(a) : (a.ldb + a.W + 15) / 16;
+  t.tcap = tcap; t.emax = emax;
+  t.w_aw = a.w_aw;
+  t.wl_floats = a.H * a.B * a.w_aw;
+  t.nsets = a.slots > 64 ? 2 : 1;
+  t.off_rec = L.off_rec; t.off_planes = L.off_planes; t.off_rowinv = L.off_rowinv; t.off_bases = L.off_bases; t.off_wt = L.off_wt;
+  t.off_col = L.off_col; t.off_rowptr = L.off_rowptr; t.off_cnt = L.off_cnt; t.off_dis = L.off_dis; t.csr_stride = L.csr_stride;
+  t.off_db = L.off_db; t.off_rowinv2 = L.off_rowinv2;     // (backward form; 0 in the forward's image)
+  int64_t grid = 256;
+  if (const char* e = getenv("EGC_FT_GRID")) grid = std::max(1, atoi(e));
+  grid = std::min<int64_t>(grid, std::max<int64_t>(1, n_graphs));
+  grid = std::min<int64_t>(grid, std::max<int64_t>(1, (int64_t)a.n_nodes / 16));
+  return (unsigned)grid;
+}
+
+template <int LPR_LOG2, int HPB, int NEED, class C>
+static int launch_ft_one(const AggArgs& a, const FusedTileArgs& t, unsigned grid, size_t lds, hipStream_t stream) {
+  const auto kern = &fused_tile_kernel<LPR_LOG2, HPB, NEED, C>;
+  EGC_ALLOW_DYNAMIC_LDS(kern, 160 * 1024, "fused_tile_kernel");
+  kern<<<grid, FT_THREADS, lds, stream>>>(a, t);
+  EGC_LAUNCH_CHECK("fused_tile_kernel");
+  return EGC_OK;
 }
 
 int launch_fused_tile(AggArgs a, const int64_t* ptr, const int64_t* edge_ptr, int64_t n_graphs, const int64_t* src,
                       const int64_t* dst, int64_t n_edges, const int* max_index, const float* x, int f_in, const void* packed,
                       int tcap, int emax, int32_t* status, int32_t* host_flag, hipStream_t stream) {
   if (!fused_tile_shape(a, f_in)) return EGC_ERR_UNSUPPORTED;
-  const int lpr = a.slots <= 16 ? 16 : a.slots <= 32 ? 32 : 64;
-  const bool two_sets = a.slots > 64;
-  a.lanes_pb = a.Ls / 4;
-  a.magic_P = (unsigned)(((uint64_t)1 << 32) / (uint64_t)a.lanes_pb) + 1u;
-  if ((a.lanes_pb & (a.lanes_pb - 1)) == 0) {
-    int lg = 0;
-    while ((4 << lg) < a.Ls) ++lg;
-    a.lpb_log2 = lg;
-  } else {
-    a.lpb_log2 = -1;
-  }
-  a.need_mean = a.need_var = 0;
-  int need = 0;
-  for (int k = 0; k < a.A; ++k) {
-    if (a.aggr[k] == EGC_AGGR_MEAN || a.aggr[k] == EGC_AGGR_VAR || a.aggr[k] == EGC_AGGR_STD) a.need_mean = 1;
-    if (a.aggr[k] == EGC_AGGR_VAR || a.aggr[k] == EGC_AGGR_STD) { a.need_var = 1; need |= NEED_SQ; }
-    if (a.aggr[k] == EGC_AGGR_MIN) need |= NEED_MN;
-  }
-  a.w_lds_stride = 0;     // finish_group<W_READY>: the weight strip of a lane group IS the row of the LDS image it is handed
-  a.bias_lds_floats = (a.H * a.Ls + 3) & ~3;
-  a.lds_floats_per_wave = 0;
-  FusedTileArgs t = {};
-  t.ptr = ptr; t.edge_ptr = edge_ptr; t.n_graphs = n_graphs; t.src = src; t.dst = dst; t.n_edges = n_edges;
-  t.max_index = max_index; t.status = status; t.host_flag = host_flag; t.x = x; t.packed = (const u16*)packed;
-  t.F_in = f_in;
+  const int need = ft_row_args(a, a.post_scale != nullptr);
   const bool wide = !ft_narrow_shape(a, f_in);
-  t.n_ct = wide ? ftw_n_ct(a) : (a.ldb + a.W + 15) / 16;
-  t.tcap = tcap; t.emax = emax;
   a.w_aw = wide ? ftw_aw(a) : 4;
-  t.w_aw = a.w_aw;
-  t.wl_floats = a.H * a.B * a.w_aw;
+  if (tcap < FT_CHUNK || tcap > FT_CHUNK * FT_RING || (tcap % (wide ? FTW_CH : FT_CHUNK)) != 0 || emax < 0 || emax > 65535) return EGC_ERR_INVALID;   // (16-bit cursors of the CSR build)
+  const FtLds L = ft_lds(a, a.H * a.B * a.w_aw, tcap, emax, a.post_scale != nullptr, wide);
+  if (L.total > FT_LDS_BUDGET) return EGC_ERR_UNSUPPORTED;
+  FusedTileArgs t;
+  const unsigned grid = ft_tile_args(t, a, L, wide, ptr, edge_ptr, n_graphs, src, dst, n_edges, max_index, x, f_in, packed, tcap, emax,
+                                     status, host_flag);
+  // WIDE form: the k-slabs of x and the streamed weight fragments; rows of more than 64 slots: the first pass's share of a basis
   t.n_slabs = (f_in + FTW_SLAB - 1) / FTW_SLAB;
   t.k16 = ftw_k16(f_in);
   t.ldbp = (a.ldb + 31) & ~31;
-  t.nsets = two_sets ? 2 : 1;
   t.p0 = ((a.Ls >> 2) + 1) / 2;
-  t.magic0 = (unsigned)(((uint64_t)1 << 32) / (uint64_t)t.p0) + 1u;
-  t.magic1 = (unsigned)(((uint64_t)1 << 32) / (uint64_t)std::max(1, (a.Ls >> 2) - t.p0)) + 1u;
-  if (tcap < FT_CHUNK || tcap > FT_CHUNK * FT_RING || (tcap % (wide ? FTW_CH : FT_CHUNK)) != 0 || emax < 0 || emax > 65535) return EGC_ERR_INVALID;   // (16-bit cursors of the CSR build)
-  const FtLds L = ft_lds(a, t.wl_floats, tcap, emax, a.post_scale != nullptr, wide);
-  if (L.total > FT_LDS_BUDGET) return EGC_ERR_UNSUPPORTED;
-  t.off_rec = L.off_rec; t.off_planes = L.off_planes; t.off_rowinv = L.off_rowinv; t.off_bases = L.off_bases; t.off_wt = L.off_wt;
-  t.off_col = L.off_col; t.off_rowptr = L.off_rowptr; t.off_cnt = L.off_cnt; t.off_dis = L.off_dis; t.csr_stride = L.csr_stride;
-  // one workgroup per CU at most; fewer when the batch is small (a workgroup's share: at least ~16 nodes, at least one graph)
-  int64_t grid = 256;
-  if (const char* e = getenv("EGC_FT_GRID")) grid = std::max(1, atoi(e));
-  grid = std::min<int64_t>(grid, std::max<int64_t>(1, n_graphs));
-  grid = std::min<int64_t>(grid, std::max<int64_t>(1, (int64_t)a.n_nodes / 16));
+  t.magic0 = agg_magic(t.p0);
+  t.magic1 = agg_magic(std::max(1, (a.Ls >> 2) - t.p0));
   if (wide) {
     switch (t.n_slabs) {
-      case 1: return launch_fused_tile_wide1(a, t, lpr, need, (unsigned)grid, L.total, stream);
-      case 2: return launch_fused_tile_wide2(a, t, lpr, need, (unsigned)grid, L.total, stream);
-      default: return launch_fused_tile_wide3(a, t, lpr, need, (unsigned)grid, L.total, stream);
+      case 1: return launch_fused_tile_wide1(a, t, need, grid, L.total, stream);
+      case 2: return launch_fused_tile_wide2(a, t, need, grid, L.total, stream);
+      default: return launch_fused_tile_wide3(a, t, need, grid, L.total, stream);
     }
   }
-  if (getenv("EGC_NO_STATIC_CFG") == nullptr && a.act == EGC_ACT_NONE && a.Ls == a.L) {
-    constexpr int S = EGC_AGGR_SUM, M = EGC_AGGR_MEAN, X = EGC_AGGR_MAX, Y = EGC_AGGR_SYMNORM;
-    unsigned pk = 0;
-    for (int k = 0; k < a.A; ++k) pk |= (unsigned)a.aggr[k] << (3 * k);
-    // EGConv EGC-M north star (configs 3 / 4 of BASELINE.json): d=128, H=8, B=4, sum+mean+max+symnorm, loops on every node
-    if (a.H == 8 && a.B == 4 && a.L == 16 && a.A == 4 && pk == agg_pack(S, M, X, Y) && a.x_looped && a.y_looped && a.loops_all)
-      return launch_ft_one<4, 2, 0, StCfg<8, 4, 16, 4, agg_pack(S, M, X, Y), EGC_ACT_NONE, true, true, true>>(a, t, (unsigned)grid,
-                                                                                                              L.total, stream);
-    // EfficientGraphConv EGC-M at d=128 (symadd looped, the others raw)
-    if (a.H == 8 && a.B == 4 && a.L == 16 && a.A == 3 && pk == agg_pack(Y, X, M) && !a.x_looped && a.y_looped && a.loops_all)
-      return launch_ft_one<4, 2, 0, StCfg<8, 4, 16, 3, agg_pack(Y, X, M), EGC_ACT_NONE, false, true, true>>(a, t, (unsigned)grid,
-                                                                                                            L.total, stream);
+  // the d = 128 layers with their constants compiled in (contiguous bases): 16-lane groups, two heads per lane
+  if (getenv("EGC_NO_STATIC_CFG") == nullptr && a.Ls == a.L) {
+    if (cfg_matches<cfg::EGConvM128>(a)) return launch_ft_one<4, 2, 0, cfg::EGConvM128>(a, t, grid, L.total, stream);
+    if (cfg_matches<cfg::EgcM128>(a)) return launch_ft_one<4, 2, 0, cfg::EgcM128>(a, t, grid, L.total, stream);
   }
-  switch (lpr) {
-    case 16: return launch_ft_rt<4>(a, t, need, (unsigned)grid, L.total, stream);
-    case 32: return launch_ft_rt<5>(a, t, need, (unsigned)grid, L.total, stream);
-    default: return launch_ft_rt<6>(a, t, need, (unsigned)grid, L.total, stream);
-  }
+  return agg_dispatch<NeedCoarse>(a, need, [&](auto lpr, auto hpb, auto nd) {
+    return launch_ft_one<decltype(lpr)::value, decltype(hpb)::value, decltype(nd)::value, RtCfg>(a, t, grid, L.total, stream);
+  });
 }
 
 
@@ -423,14 +400,9 @@ int fused_tile_bwd_capacity(const AggArgs& a, int f_in, int max_tile_edges) {
 
 template <class C>
 static int launch_ftb_one(const AggArgs& a, const FusedTileArgs& t, unsigned grid, size_t lds, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_tile_kernel<4, 1, 0, C, 0, 1>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(fused_tile_kernel, backward)", e); return EGC_ERR_HIP; }
-    attr_set = true;
-  }
-  fused_tile_kernel<4, 1, 0, C, 0, 1><<<grid, FT_THREADS, lds, stream>>>(a, t);
+  const auto kern = &fused_tile_kernel<4, 1, 0, C, 0, 1>;
+  EGC_ALLOW_DYNAMIC_LDS(kern, 160 * 1024, "fused_tile_kernel, backward");
+  kern<<<grid, FT_THREADS, lds, stream>>>(a, t);
   EGC_LAUNCH_CHECK("fused_tile_kernel (backward)");
   return EGC_OK;
 }
@@ -440,48 +412,24 @@ int launch_fused_tile_bwd(AggArgs a, const int64_t* ptr, const int64_t* edge_ptr
                           const void* packed_t, const float* grad_out, float* d_x, const float* d_x_add, float* d_cat, int ld_dcat, int tcap, int emax,
                           int32_t* status, int32_t* host_flag, hipStream_t stream) {
   if (!fused_tile_bwd_shape(a, f_in)) return EGC_ERR_UNSUPPORTED;
-  a.lanes_pb = a.Ls / 4;
-  a.magic_P = (unsigned)(((uint64_t)1 << 32) / (uint64_t)a.lanes_pb) + 1u;
-  a.lpb_log2 = 2;
-  a.need_mean = a.need_var = 0;
-  for (int k = 0; k < a.A; ++k)
-    if (a.aggr[k] == EGC_AGGR_MEAN) a.need_mean = 1;
-  a.w_lds_stride = 0;
-  a.bias_lds_floats = (a.H * a.Ls + 3) & ~3;
-  a.lds_floats_per_wave = 0;
+  // (the envelope -- Ls == 16, no var / std / min -- makes the shared derivations give lpb_log2 == 2, need_var == 0 and an
+  // empty need mask: the one instance family the backward has)
+  ft_row_args(a, false);
   a.w_aw = 4;
-  FusedTileArgs t = {};
-  t.ptr = ptr; t.edge_ptr = edge_ptr; t.n_graphs = n_graphs; t.src = src; t.dst = dst; t.n_edges = n_edges;
-  t.max_index = max_index; t.status = status; t.host_flag = host_flag; t.x = x; t.packed = (const u16*)packed;
-  t.F_in = f_in;
-  t.n_ct = (a.ldb + a.W + 15) / 16;
-  t.tcap = tcap; t.emax = emax;
-  t.w_aw = 4;
-  t.wl_floats = a.H * a.B * 4;
-  t.nsets = 1;
-  t.grad_out = grad_out; t.d_x = d_x; t.d_x_add = d_x_add; t.d_cat = d_cat; t.ld_dcat = ld_dcat; t.packed_t = (const u16*)packed_t;
   if (tcap < FT_CHUNK || tcap > FT_CHUNK * (a.H == 8 ? 6 : 8) || (tcap % FT_CHUNK) != 0 || emax < 0 || emax > 16384) return EGC_ERR_INVALID;
-  const FtLds L = ft_lds(a, t.wl_floats, tcap, emax, false, false, true);
+  const FtLds L = ft_lds(a, a.H * a.B * a.w_aw, tcap, emax, false, false, true);
   if (L.total > FT_LDS_BUDGET) return EGC_ERR_UNSUPPORTED;
-  t.off_rec = L.off_rec; t.off_planes = L.off_planes; t.off_rowinv = L.off_rowinv; t.off_bases = L.off_bases; t.off_wt = L.off_wt;
-  t.off_col = L.off_col; t.off_rowptr = L.off_rowptr; t.off_cnt = L.off_cnt; t.off_dis = L.off_dis; t.csr_stride = L.csr_stride;
-  t.off_db = L.off_db; t.off_rowinv2 = L.off_rowinv2;
-  int64_t grid = 256;
-  if (const char* e = getenv("EGC_FT_GRID")) grid = std::max(1, atoi(e));
-  grid = std::min<int64_t>(grid, std::max<int64_t>(1, n_graphs));
-  grid = std::min<int64_t>(grid, std::max<int64_t>(1, (int64_t)a.n_nodes / 16));
+  FusedTileArgs t;
+  const unsigned grid = ft_tile_args(t, a, L, false, ptr, edge_ptr, n_graphs, src, dst, n_edges, max_index, x, f_in, packed, tcap, emax,
+                                     status, host_flag);
+  t.grad_out = grad_out; t.d_x = d_x; t.d_x_add = d_x_add; t.d_cat = d_cat; t.ld_dcat = ld_dcat; t.packed_t = (const u16*)packed_t;
   if (getenv("EGC_NO_STATIC_CFG") == nullptr && a.Ls == a.L) {
     // the row pass is bound by its vector instructions: with the layer's constants compiled in the aggregator switches, the
     // head count and the edge-set tests fold away (the run-time form is 2,000 instructions per turn, a quarter of them moves)
-    constexpr int S = EGC_AGGR_SUM, M = EGC_AGGR_MEAN, X = EGC_AGGR_MAX, Y = EGC_AGGR_SYMNORM;
-    unsigned pk = 0;
-    for (int k = 0; k < a.A; ++k) pk |= (unsigned)a.aggr[k] << (3 * k);
-    if (a.H == 8 && a.A == 4 && pk == agg_pack(S, M, X, Y) && a.x_looped && a.y_looped && a.loops_all)       // EGConv EGC-M north star
-      return launch_ftb_one<StCfg<8, 4, 16, 4, agg_pack(S, M, X, Y), EGC_ACT_NONE, true, true, true>>(a, t, (unsigned)grid, L.total, stream);
-    if (a.H == 8 && a.A == 3 && pk == agg_pack(Y, X, M) && !a.x_looped && a.y_looped && a.loops_all)          // EfficientGraphConv EGC-M at d = 128
-      return launch_ftb_one<StCfg<8, 4, 16, 3, agg_pack(Y, X, M), EGC_ACT_NONE, false, true, true>>(a, t, (unsigned)grid, L.total, stream);
+    if (cfg_matches<cfg::EGConvM128>(a)) return launch_ftb_one<cfg::EGConvM128>(a, t, grid, L.total, stream);
+    if (cfg_matches<cfg::EgcM128>(a)) return launch_ftb_one<cfg::EgcM128>(a, t, grid, L.total, stream);
   }
-  return launch_ftb_one<RtCfg>(a, t, (unsigned)grid, L.total, stream);
+  return launch_ftb_one<RtCfg>(a, t, grid, L.total, stream);
 }
 
 }  // namespace egc

@@ -1655,8 +1655,8 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
 }
 
 // egc_fused_tile_wide.hip: the WIDE instances (lpr = lanes per row group: 16 / 32 / 64; need = NEED_* mask of the layer)
-int launch_fused_tile_wide1(const AggArgs& a, const FusedTileArgs& t, int lpr, int need, unsigned grid, size_t lds, hipStream_t stream);
-int launch_fused_tile_wide2(const AggArgs& a, const FusedTileArgs& t, int lpr, int need, unsigned grid, size_t lds, hipStream_t stream);
-int launch_fused_tile_wide3(const AggArgs& a, const FusedTileArgs& t, int lpr, int need, unsigned grid, size_t lds, hipStream_t stream);
+int launch_fused_tile_wide1(const AggArgs& a, const FusedTileArgs& t, int need, unsigned grid, size_t lds, hipStream_t stream);
+int launch_fused_tile_wide2(const AggArgs& a, const FusedTileArgs& t, int need, unsigned grid, size_t lds, hipStream_t stream);
+int launch_fused_tile_wide3(const AggArgs& a, const FusedTileArgs& t, int need, unsigned grid, size_t lds, hipStream_t stream);
 
 }  // namespace egc

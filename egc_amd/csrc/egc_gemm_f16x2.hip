@@ -389,13 +389,7 @@ template <int FM>
 static int f16x2_launch_fm(int grid, size_t lds, const float* x, const void* packed, const float* bcat, int64_t M, int K, int W,
                            float* bases, int ldb, float* weightings, int NV, int rows_per_block, const float* dis, int fold_s,
                            hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&basis_gemm_f16x2_kernel<FM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2)", e); return EGC_ERR_HIP; }
-    attr_set = true;
-  }
+  EGC_ALLOW_DYNAMIC_LDS(&basis_gemm_f16x2_kernel<FM>, 160 * 1024, "f16x2");
   basis_gemm_f16x2_kernel<FM><<<grid, F16X2_THREADS, lds, stream>>>(x, (const u16*)packed, bcat, M, K, W, bases, ldb, weightings,
                                                                     NV, rows_per_block, dis, fold_s);
   EGC_LAUNCH_CHECK("basis_gemm_f16x2_kernel");

@@ -620,12 +620,7 @@ static int launch_k(const float* x, const u16* packed, const float* bcat, int64_
     if (ring >= 2 && R <= 16) {
       const size_t lds = (size_t)ring * slot_bytes + fixed;
       auto kern = &basis_gemm_f16x2k_spec_kernel<KS, WAVES>;
-      static bool attr_set = false;
-      if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2 spec)", e); return EGC_ERR_HIP; }
-        attr_set = true;
-      }
+      EGC_ALLOW_DYNAMIC_LDS(kern, 160 * 1024, "f16x2 spec");
       int grid = 256;
       if (grid > n_tiles) grid = n_tiles;
       kern<<<grid, (ntl + nh) * 64, lds, stream>>>(x, packed, bcat, M, K, c, bases, weightings, n_tiles, LDX, R, slot_bytes, tile0, ring,
@@ -640,12 +635,7 @@ static int launch_k(const float* x, const u16* packed, const float* bcat, int64_
   size_t lds = (size_t)2 * slot_bytes + fixed;
   if (lds > 160 * 1024 || R > 16) return EGC_ERR_UNSUPPORTED;
   auto kern = &basis_gemm_f16x2k_kernel<KS, WAVES>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2)", e); return EGC_ERR_HIP; }
-    attr_set = true;
-  }
+  EGC_ALLOW_DYNAMIC_LDS(kern, 160 * 1024, "f16x2");
   // workgroups per CU: as many as the LDS holds, within about five wavefronts per SIMD (the KS <= 9 kernels use up to
   // 102 registers).  Short k leaves room for two (F_in = 192, 8 column tiles: 59 KB of LDS each), and the second one's
   // matrix work covers the first one's barrier and split: 66.9 -> 50.1 us for the 192 -> 128 gradient GEMM at
@@ -689,12 +679,7 @@ static int launch_k2(const float* x, const u16* packed, const float* bcat, int64
   if (ring < 2 || R > 16) return EGC_ERR_UNSUPPORTED;
   const size_t lds = (size_t)ring * slot_bytes + fixed;
   auto kern = &basis_gemm_f16x2k_spec_kernel<KS, WAVES, 2>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { set_last_error("hipFuncSetAttribute(f16x2 spec, two tiles)", e); return EGC_ERR_HIP; }
-    attr_set = true;
-  }
+  EGC_ALLOW_DYNAMIC_LDS(kern, 160 * 1024, "f16x2 spec, two tiles");
   int grid = 256;
   if (grid > n_tiles) grid = n_tiles;
   kern<<<grid, WAVES * 64, lds, stream>>>(x, packed, bcat, M, K, c, bases, weightings, n_tiles, LDX, R, slot_bytes, 0, ring, nmf, addend, c.NT);

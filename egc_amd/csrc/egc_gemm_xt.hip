@@ -591,12 +591,8 @@ template <int MT, int NT, int WN, int ROWS>
 int launch_xt(const XtPlan& p, const float* x, int64_t ldx, int F, const float* d, int64_t ldd, int K, int64_t n_rows,
               float* partial, int want_sums, hipStream_t stream) {
   constexpr int lds_bytes = 2 * ROWS * xt_pitch(16 * XT_WM * MT + 16 * WN * NT) * 4;
-  static bool configured = false;
-  if (!configured) {
-    EGC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&xt_gemm_kernel<MT, NT, WN, ROWS>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    configured = true;
-  }
+  const auto kern = &xt_gemm_kernel<MT, NT, WN, ROWS>;
+  EGC_ALLOW_DYNAMIC_LDS(kern, lds_bytes, "xt_gemm_kernel");
   const unsigned grid = (unsigned)(ceil_div(p.chunks, 8) * 8 * p.m_tiles * p.n_tiles);
   xt_gemm_kernel<MT, NT, WN, ROWS><<<grid, 64 * XT_WM * WN, lds_bytes, stream>>>(
       x, ldx, F, d, ldd, K, n_rows, p.rows_per_chunk, p.chunks, p.m_tiles, p.n_tiles, partial, want_sums);
@@ -659,12 +655,7 @@ static int weight_grad_impl(const float* x, int64_t ldx, const float* d, int64_t
   int rc = EGC_ERR_UNSUPPORTED;
   if (one_tile) {   // one accumulator tile: the bf16x3 kernel
     constexpr int lds_bytes = X3_LDS_BYTES;
-    static bool configured = false;
-    if (!configured) {
-      EGC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&xt_gemm_bf16x3_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-      configured = true;
-    }
+    EGC_ALLOW_DYNAMIC_LDS(&xt_gemm_bf16x3_kernel, lds_bytes, "xt_gemm_bf16x3_kernel");
     xt_gemm_bf16x3_kernel<<<(unsigned)p.chunks, X3_THREADS, lds_bytes, stream>>>(
         x, ldx, f_in, d, ldd, k_cols, n_rows, p.rows_per_chunk, p.chunks, partial, want_sums, e, lde, e_cols);
     EGC_LAUNCH_CHECK("xt_gemm_bf16x3_kernel");
