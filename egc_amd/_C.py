@@ -27,6 +27,7 @@ ACT_NONE, ACT_SOFTMAX, ACT_SIGMOID, ACT_HARDTANH = range(4)
 # EGC_READOUT_*
 READOUT_SUM, READOUT_MEAN, READOUT_MAX = range(3)
 SOFTMAX_MAX_CLASSES = 1024   # EGC_SOFTMAX_MAX_CLASSES
+TYPED_MAX_RELATIONS = 8      # EGC_TYPED_MAX_RELATIONS
 
 _STATUS = {1: "EGC_ERR_INVALID", 2: "EGC_ERR_WORKSPACE", 3: "EGC_ERR_HIP", 4: "EGC_ERR_UNSUPPORTED"}
 
@@ -65,6 +66,12 @@ def env_flag(name: str) -> bool:
 
 class EgcPost(C.Structure):
     _fields_ = [("scale", C.c_void_p), ("shift", C.c_void_p), ("residual", C.c_void_p), ("relu", C.c_int32)]
+
+
+class EgcTypedRel(C.Structure):
+    _fields_ = [("rowptr", C.c_void_p), ("col", C.c_void_p), ("pre_rowptr", C.c_void_p), ("in_", C.c_void_p),
+                ("n_edges", C.c_int64), ("n_in_rows", C.c_int64), ("ld_in", C.c_int32), ("out_col", C.c_int32),
+                ("post_mean", C.c_int32), ("reserved", C.c_int32)]
 
 
 # name -> (restype, argtypes): exactly the symbols include/egc_hip.h declares
@@ -180,6 +187,10 @@ SYMBOLS = {
                                                   C.c_void_p]),
     "egc_nll_log_softmax_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "egc_typed_mean_chunk": (C.c_int32, []),
+    "egc_typed_mean_workspace_bytes": (C.c_size_t, [C.POINTER(EgcTypedRel), C.c_int32, C.c_int32]),
+    "egc_typed_mean_f32": (C.c_int, [C.POINTER(EgcTypedRel), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "egc_train_stats_floats": (C.c_int64, [C.POINTER(EgcLayer)]),
     "egc_aggregate_combine_train_f32": (C.c_int, [C.POINTER(EgcGraph), C.POINTER(EgcLayer), C.c_void_p, C.c_int32,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

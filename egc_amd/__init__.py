@@ -4,6 +4,8 @@ Public surface (mirrors the reference's layer API):
   EfficientGraphConv   drop-in for experiments/layers.py:EfficientGraphConv
   EGConv               drop-in for experiments/optimized_layers.py:EGConv
   REGConv              drop-in for experiments/rmag/models.py:REGConv (relational EGC)
+  RGCNConv / REGC      the R-GCN baseline layer of the same file (state-dict compatible; its per-relation mean is one
+                       typed-mean launch per node type, forward and backward) and the relational net over both layers
   FusedEGCBlock        conv -> BatchNorm1d -> ReLU (-> dropout) -> + identity: eval mode in the kernel's store, training
                        mode in two passes each way
   global_mean_pool / global_add_pool / global_max_pool, readout(name)
@@ -27,7 +29,7 @@ from .graph import CSRGraph, GraphBatch, SparseTensor, GLOBAL_GRAPH_CACHE  # noq
 from .functional import egc_layer_forward, make_spec, LayerSpec  # noqa: F401
 from .layers import EfficientGraphConv  # noqa: F401
 from .optimized_layers import EGConv  # noqa: F401
-from .relational import REGConv  # noqa: F401
+from .relational import REGC, REGConv, RGCNConv  # noqa: F401
 from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean_pool, readout  # noqa: F401
 from .encoders import ASTNodeEncoder, AtomEncoder, Embedding, NodeEncoder  # noqa: F401
 from ._softmax import RowSelection, cross_entropy, log_softmax, nll_log_softmax  # noqa: F401

@@ -1,4 +1,7 @@
-"""Relational EGC on the gfx950 kernels: ``REGConv`` (reference experiments/rmag/models.py:75-148).
+"""Relational nets on the gfx950 kernels: ``REGConv`` (reference experiments/rmag/models.py:75-148), the R-GCN baseline
+layer ``RGCNConv`` (rmag/models.py:32-72) and the net over both, ``REGC`` (rmag/models.py:151-212).
+
+REGConv.
 
 One shared basis matrix for every node type; per node type a "root" combination of the node's own bases;
 per relation (source type, name, target type) the ``mean`` and ``max`` of the source type's bases over the
@@ -14,15 +17,27 @@ Interface = the reference's: ``REGConv(in_channels, out_channels, num_heads, num
 (here ``egc_amd.SparseTensor`` / ``CSRGraph`` / ``torch.sparse_csr``); parameter names ``bases_weight``,
 ``rel_combs.<src>_<rel>_<dst>.{weight,bias}``, ``root_combs.<type>.{weight,bias}`` (state dicts interchange).
 The node / edge type lists are the reference's module constants (rmag/models.py:10-26) and may be overridden.
+
+RGCNConv.  out[t] = root_lins[t](x[t]) + sum over relations (s, r, t) of rel_lins[s_r_t](mean of x[s] over the relation's
+in-neighbours).  Per target type ONE typed-mean launch (``egc_typed_mean_f32``, _typed.py) writes the operand
+A_t = [x_t | mean_1 | mean_2 ...] and ONE dense product A_t [W_root | W_1 | W_2 ...]^T + b (torch: rocBLAS) gives out[t];
+the backward is that product's two gradient GEMMs and one typed-mean launch per SOURCE type over the transposed CSRs.
+x_t is the operand's first block rather than a second product accumulated into out[t]: the copy moves 2 N F_in floats
+inside a launch that runs anyway, a second product reads and rewrites out[t] (2 N F_out floats, F_out = 349 in the last
+layer) and needs two more GEMMs backward.
 """
 from __future__ import annotations
 
 from types import SimpleNamespace
 
+import copy
+
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _C
+from ._typed import TypedMeanPlan, typed_mean_cat
 from .functional import (PostOp, egc_aggregate_combine, egc_aggregate_combine_apply, egc_basis_transform,
                          egc_dense_transform_apply, gemm_exact, make_spec, pack_weights)
 from .graph import CSRGraph, SparseTensor
@@ -38,9 +53,12 @@ EDGE_TYPES = [                                                             # rma
     ("paper", "has_topic", "field_of_study"),
     ("field_of_study", "to", "paper"),
 ]
+NUM_NODES_DICT = {"author": 1134649, "field_of_study": 59965, "institution": 8740, "paper": 736389}   # rmag/models.py:10-15
+X_TYPES = ["paper"]                                                        # rmag/models.py:16
+IN_FEATURES, NUM_CLASSES = 128, 349                                        # rmag/models.py:28-29
 
 
-def _as_graph(adj_t, n_dst: int, n_src: int) -> CSRGraph:
+def _as_graph(adj_t, n_dst: int, n_src: int, who: str = "REGConv") -> CSRGraph:
     if isinstance(adj_t, CSRGraph):
         g = adj_t
     elif isinstance(adj_t, SparseTensor):
@@ -48,9 +66,9 @@ def _as_graph(adj_t, n_dst: int, n_src: int) -> CSRGraph:
     elif isinstance(adj_t, torch.Tensor) and adj_t.layout == torch.sparse_csr:
         g = CSRGraph.from_csr(adj_t.crow_indices(), adj_t.col_indices(), n_dst, n_src)
     else:
-        raise RuntimeError(f"egc_amd.REGConv: unsupported adjacency type {type(adj_t)}")
+        raise RuntimeError(f"egc_amd.{who}: unsupported adjacency type {type(adj_t)}")
     if g.n_nodes != n_dst or g.n_src_rows != n_src:
-        raise RuntimeError(f"egc_amd.REGConv: adjacency is [{g.n_nodes}, {g.n_src_rows}], features say [{n_dst}, {n_src}]")
+        raise RuntimeError(f"egc_amd.{who}: adjacency is [{g.n_nodes}, {g.n_src_rows}], features say [{n_dst}, {n_src}]")
     return g
 
 
@@ -232,3 +250,91 @@ class REGConv(nn.Module):
     def __repr__(self):
         return (f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, num_heads={self.num_heads}, "
                 f"num_bases={self.num_bases})")
+
+
+class RGCNConv(nn.Module):
+    def __init__(self, in_channels: int, out_channels: int, node_types=None, edge_types=None):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.node_types = list(NODE_TYPES if node_types is None else node_types)
+        self.edge_types = [tuple(k) for k in (EDGE_TYPES if edge_types is None else edge_types)]
+        self.rel_lins = nn.ModuleDict({f"{k[0]}_{k[1]}_{k[2]}": nn.Linear(in_channels, out_channels, bias=False)
+                                       for k in self.edge_types})
+        self.root_lins = nn.ModuleDict({k: nn.Linear(in_channels, out_channels, bias=True) for k in self.node_types})
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in self.rel_lins.values():
+            lin.reset_parameters()
+        for lin in self.root_lins.values():
+            lin.reset_parameters()
+
+    def forward(self, x_dict, adj_t_dict):
+        adj = {tuple(k): v for k, v in adj_t_dict.items()}
+        for k in adj:
+            if k not in self.edge_types:
+                raise RuntimeError(f"egc_amd.RGCNConv: relation {k} is not one of the layer's edge types {self.edge_types}")
+        for t, x in x_dict.items():
+            if t not in self.root_lins:
+                raise RuntimeError(f"egc_amd.RGCNConv: node type {t!r} is not one of the layer's node types {self.node_types}")
+            if x.dim() != 2 or x.size(1) != self.in_channels:
+                raise RuntimeError(f"egc_amd.RGCNConv: x[{t}] has shape {tuple(x.shape)}, expected (rows, {self.in_channels})")
+        types = list(x_dict)
+        rels = {t: [] for t in types}
+        for k in self.edge_types:          # the blocks of a type's operand: the layer's relation order, whatever the dict's
+            if k in adj:
+                src, _, dst = k
+                if src not in x_dict or dst not in x_dict:
+                    raise RuntimeError(f"egc_amd.RGCNConv: relation {k} needs the features of {src!r} and {dst!r}")
+                rels[dst].append((k, _as_graph(adj[k], x_dict[dst].size(0), x_dict[src].size(0), "RGCNConv")))
+        plan = TypedMeanPlan(types, {t: [(k[0], g) for k, g in lst] for t, lst in rels.items()})
+        operands = typed_mean_cat(plan, [x_dict[t] for t in types])                       # rmag/models.py:69, the sparse part
+        out = {}
+        for t, a in zip(types, operands):
+            root = self.root_lins[t]
+            lins = [root] + [self.rel_lins[f"{k[0]}_{k[1]}_{k[2]}"] for k, _ in rels[t]]
+            wcat = torch.cat([lin.weight for lin in lins], dim=1) if len(lins) > 1 else root.weight
+            out[t] = F.linear(a, wcat, root.bias)                                         # rmag/models.py:64,69-70
+        return out
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({self.in_channels}, {self.out_channels})"
+
+
+class REGC(nn.Module):
+    """The reference's relational net (rmag/models.py:151-212): learned features for every node type but ``paper``,
+    ``num_layers - 1`` REGConv (``use_egc``) or RGCNConv layers with ReLU and dropout behind each, and a final
+    RGCNConv onto the classes.  The sizes the reference keeps as module constants are arguments here."""
+
+    def __init__(self, hidden_channels, num_layers, dropout, use_egc=True, egc_heads=8, egc_bases=4,
+                 num_nodes_dict=None, in_features=IN_FEATURES, num_classes=NUM_CLASSES):
+        super().__init__()
+        num_nodes_dict = dict(NUM_NODES_DICT if num_nodes_dict is None else num_nodes_dict)
+        self.embs = nn.ParameterDict({k: nn.Parameter(torch.empty(num_nodes_dict[k], in_features))
+                                      for k in num_nodes_dict if k not in X_TYPES})
+
+        def layer(f_in):
+            return REGConv(f_in, hidden_channels, egc_heads, egc_bases) if use_egc else RGCNConv(f_in, hidden_channels)
+
+        self.convs = nn.ModuleList([layer(in_features)])
+        for _ in range(num_layers - 2):
+            self.convs.append(layer(hidden_channels))
+        self.convs.append(RGCNConv(hidden_channels, num_classes))
+        self.dropout = dropout
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for emb in self.embs.values():
+            nn.init.xavier_uniform_(emb)
+        for conv in self.convs:
+            conv.reset_parameters()
+
+    def forward(self, x_dict, adj_t_dict):
+        x_dict = copy.copy(x_dict)
+        for key, emb in self.embs.items():
+            x_dict[key] = emb
+        for conv in self.convs[:-1]:
+            x_dict = conv(x_dict, adj_t_dict)
+            for key, x in x_dict.items():
+                x_dict[key] = F.dropout(F.relu(x), p=self.dropout, training=self.training)
+        return self.convs[-1](x_dict, adj_t_dict)

@@ -600,6 +600,53 @@ int egc_nll_log_softmax_backward_f32(const float* x, const int64_t* y, const int
                                      const float* lse, const float* grad_loss, int64_t n_rows, int32_t n_classes, int32_t ld,
                                      int32_t mean, float* d_x, egc_stream_t stream);
 
+/* Typed mean aggregation (egc_typed_mean.hip): the sparse part of the reference's R-GCN baseline layer,
+ * `self.rel_lins[key](adj_t.matmul(x_dict[src], reduce="mean"))` per relation (rmag/models.py:61-72), and of what autograd
+ * derives from it, over a LIST of relations in one call:
+ *   out[row, block(r)] (+)= post(row, r) * sum over p in rowptr_r[row] .. rowptr_r[row+1] of pre_r(col_r[p]) * in_r[col_r[p], 0:width]
+ * One descriptor per relation (a HOST array: it is read during the call and travels in the kernel arguments):
+ *   rowptr / col   int32 CSR whose rows are the rows of `out` (n_rows + 1 offsets, n_edges entries); rowptr == NULL is the
+ *                  identity relation: row i has the one entry i (col and n_edges are then ignored)
+ *   pre_rowptr     NULL: pre = 1; else int32 [n_in_rows + 1] and pre(j) = 1 / float(max(pre_rowptr[j+1] - pre_rowptr[j], 1)),
+ *                  one float32 multiply per entry (the forward graph's rowptr when the CSR is its transpose)
+ *   in, ld_in      float32 rows the entries name: n_in_rows rows of stride ld_in floats, `in` pointing at the relation's
+ *                  first column (a column block of a wider array is fine)
+ *   post_mean      != 0: the row's sum is divided by float(entry count); a row without entries gives 0
+ *   out_col        first column of the relation's block of `out` (accumulate == 0)
+ * accumulate == 0: every relation writes its own block out[:, out_col : out_col + width] (the forward: one launch per target
+ * type fills the operand [x_t | mean_1 | mean_2 ...] of ONE dense product; blocks the descriptors do not name are not
+ * touched).  accumulate != 0: the relations' terms are added in table order, ((0 + term_0) + term_1) + ..., into
+ * out[:, 0:width] (the backward: one launch per source type over the transposed CSRs); n_rels == 0 then writes zeros.
+ * Every element named is written exactly once: no zero fill in front, no atomics.
+ * Order of a row's float32 sum: the entries are cut into consecutive chunks of EGC_TYPED_MEAN_CHUNK counted from the row's
+ * first entry; a chunk's sum is ((0 + v0) + v1) + ... in entry order; the row's sum is chunk 0's with those of chunks 1, 2, ..
+ * added in ascending order -- a function of the CSR and the inputs alone.  Chunks 1.. of long rows are summed by a first
+ * launch, one group of lanes per chunk, into `workspace` (egc_typed_mean_workspace_bytes: depends on the descriptors' n_edges
+ * and width only; 16-byte aligned, any content; 0 when no relation has more than one chunk's entries; EGC_ERR_WORKSPACE if
+ * smaller), which finds them on the device from rowptr; nothing is read back.  Column indices are clamped to the input's
+ * rows, offsets to [0, n_edges].  n_rows == 0 is fine.  16-byte accesses need width, ld_in, ld_out, out_col % 4 == 0 and
+ * 16-byte aligned pointers; anything else takes 4-byte ones.
+ * EGC_ERR_INVALID: a missing pointer, a negative count, ld_in < width, ld_out smaller than the columns named;
+ * EGC_ERR_UNSUPPORTED: n_rels > EGC_TYPED_MAX_RELATIONS, n_edges or n_in_rows >= 2^31. */
+#define EGC_TYPED_MEAN_CHUNK 256
+#define EGC_TYPED_MAX_RELATIONS 8
+typedef struct egc_typed_rel {
+  const int32_t* rowptr;
+  const int32_t* col;
+  const int32_t* pre_rowptr;
+  const float* in;
+  int64_t n_edges;
+  int64_t n_in_rows;
+  int32_t ld_in;
+  int32_t out_col;
+  int32_t post_mean;
+  int32_t reserved;
+} egc_typed_rel;
+int32_t egc_typed_mean_chunk(void);
+size_t egc_typed_mean_workspace_bytes(const egc_typed_rel* rels, int32_t n_rels, int32_t width);
+int egc_typed_mean_f32(const egc_typed_rel* rels, int32_t n_rels, int64_t n_rows, int32_t width, int32_t accumulate,
+                       float* out, int32_t ld_out, void* workspace, size_t workspace_bytes, egc_stream_t stream);
+
 /* Training form of egc_aggregate_combine_f32: same `out`, plus what the backward needs instead of a second
  * gather.  stats (n_nodes * egc_train_stats_floats(layer) floats, opaque to the caller, handed to the backward
  * as it is) receives every row's raw running aggregates after the self-loop term (those of sum / variance -- as the
