@@ -28,6 +28,8 @@ ACT_NONE, ACT_SOFTMAX, ACT_SIGMOID, ACT_HARDTANH = range(4)
 READOUT_SUM, READOUT_MEAN, READOUT_MAX = range(3)
 SOFTMAX_MAX_CLASSES = 1024   # EGC_SOFTMAX_MAX_CLASSES
 TYPED_MAX_RELATIONS = 8      # EGC_TYPED_MAX_RELATIONS
+# EGC_MPNN_*
+MPNN_ADD, MPNN_MEAN, MPNN_MAX = range(3)
 
 _STATUS = {1: "EGC_ERR_INVALID", 2: "EGC_ERR_WORKSPACE", 3: "EGC_ERR_HIP", 4: "EGC_ERR_UNSUPPORTED"}
 
@@ -191,6 +193,14 @@ SYMBOLS = {
     "egc_typed_mean_workspace_bytes": (C.c_size_t, [C.POINTER(EgcTypedRel), C.c_int32, C.c_int32]),
     "egc_typed_mean_f32": (C.c_int, [C.POINTER(EgcTypedRel), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egc_mpnn_message_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "egc_mpnn_message_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    "egc_mpnn_message_backward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "egc_mpnn_message_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "egc_train_stats_floats": (C.c_int64, [C.POINTER(EgcLayer)]),
     "egc_aggregate_combine_train_f32": (C.c_int, [C.POINTER(EgcGraph), C.POINTER(EgcLayer), C.c_void_p, C.c_int32,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -6,6 +6,9 @@ Public surface (mirrors the reference's layer API):
   REGConv              drop-in for experiments/rmag/models.py:REGConv (relational EGC)
   RGCNConv / REGC      the R-GCN baseline layer of the same file (state-dict compatible; its per-relation mean is one
                        typed-mean launch per node type, forward and backward) and the relational net over both layers
+  Mpnn                 drop-in for experiments/layers.py:Mpnn, the baseline MPNN-Sum / -Mean / -Max layer (state-dict compatible):
+                       the per-edge message Linear split into two [N, d] projections, aggregated by one gather launch that
+                       writes the update's operand; no [E, d] array forward or backward
   FusedEGCBlock        conv -> BatchNorm1d -> ReLU (-> dropout) -> + identity: eval mode in the kernel's store, training
                        mode in two passes each way
   global_mean_pool / global_add_pool / global_max_pool, readout(name)
@@ -30,6 +33,7 @@ from .functional import egc_layer_forward, make_spec, LayerSpec  # noqa: F401
 from .layers import EfficientGraphConv  # noqa: F401
 from .optimized_layers import EGConv  # noqa: F401
 from .relational import REGC, REGConv, RGCNConv  # noqa: F401
+from ._mpnn import Mpnn  # noqa: F401
 from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean_pool, readout  # noqa: F401
 from .encoders import ASTNodeEncoder, AtomEncoder, Embedding, NodeEncoder  # noqa: F401
 from ._softmax import RowSelection, cross_entropy, log_softmax, nll_log_softmax  # noqa: F401

@@ -95,6 +95,31 @@ static inline PlanCaps plan_caps(int64_t n_nodes, int64_t n_edges) {
   return c;
 }
 
+// A lane's four adjacent columns c .. c + 3 of a row of `width` floats (egc_typed_mean.hip, egc_mpnn.hip): one 16-byte access
+// (VEC: width, strides and pointers are multiples of 16 bytes) or 4-byte ones of the columns that exist.
+template <bool VEC>
+__device__ inline f4 tm_load(const float* __restrict__ p, int c, int width) {
+  if (VEC) return *reinterpret_cast<const f4*>(p);
+  f4 v = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (c + j < width) v[j] = p[j];
+  return v;
+}
+
+template <bool VEC>
+__device__ inline void tm_store(float* __restrict__ p, int c, int width, f4 v) {
+  if (VEC) {
+    *reinterpret_cast<f4*>(p) = v;
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (c + j < width) p[j] = v[j];
+}
+
+static inline bool tm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // egc_backward.hip: CSR positions of the first entries attaining each row's max / min (training forward)
 int arg_extrema(const egc_graph* graph, const egc_layer* layer, const float* bases, int32_t ldb, const float* stats,
                 const int32_t* cnt, int32_t* arg_max, int32_t* arg_min, unsigned* arg8_max, unsigned* arg8_min,

@@ -1,0 +1,363 @@
+// Message aggregation of the baseline MPNN layer (reference experiments/layers.py:231-267) without its [E, 2 d] and [E, d] edge
+// arrays.  A tower's message Linear acts on [x_i | x_j], so it splits into a target half and a source half: with
+// P = x BD(Ws)^T and Q = x BD(Wd)^T + b (two dense [N, d] arrays, one product on the host side) the aggregated message of row i is
+//
+//   add   m_i = (sum over the row's entries of P[col]) + float(deg_i) * Q_i
+//   mean  m_i = (that sum) / float(deg_i) + Q_i
+//   max   m_i = (max over the row's entries of P[col]) + Q_i          per column; arg = the FIRST entry attaining the max
+//
+// and 0 (arg -1) for a row without entries.  gfx950 only.  Forward: one gather pass over P, the self term fused in, m stored
+// into a column block of the caller's [m | x] operand.  Backward: d Q_i = s_i d m_i (s_i = deg_i / 1 / 1, 0 for an empty row) and
+// d P_j = sum over j's entries of the TRANSPOSED CSR of d m_i (add), d m_i / float(deg_i) (mean), or d m_i[c] where arg[i, c]
+// names that edge and 0 elsewhere (max: the transposed entry q is forward CSR position t_edge_id[q], edge edge_id[that]).
+// Every output element is written exactly once: no zero fill, no atomics, nothing read back.
+//
+// Order rule = egc_typed_mean.hip's: a row's entries are cut into consecutive chunks of EGC_TYPED_MEAN_CHUNK counted from the
+// row's first entry; a chunk's sum is ((0 + v0) + v1) + ... in entry order, the row's sum is chunk 0's with the sums of chunks
+// 1, 2, ... added in ascending order; then the division (mean), then the self term -- each one IEEE operation
+// (-ffp-contract=off).  The max is exact in any order; its argument follows the same walk with a strict `>`, so the first
+// entry wins a tie inside a chunk and the first chunk wins between chunks (a NaN is never selected).  Two launches: the CHUNK
+// kernel reduces chunks 1.. of the rows longer than one chunk into the workspace (one group of lanes per chunk; the group of
+// slot b looks at CSR position b * CHUNK, finds its row by bisection and owns the one chunk k >= 1 of that row that starts in
+// [b * CHUNK, (b + 1) * CHUNK)), the ROW kernel reduces every row's chunk 0, folds the row's partials in, finishes and stores.
+//
+// Mapping (egc_typed_mean.hip's): a lane owns four adjacent columns (16-byte accesses; 4-byte ones of the same columns when a
+// width, stride or pointer is not a multiple of 16 bytes), ceil(width / 4) lanes form a group, one group per row, groups laid back
+// to back over the grid.  MP_AHEAD entries' indices, then their rows, are requested before the first operation that consumes
+// them; a partial batch issues all its loads too (index clamped, surplus not taken).  Column indices are clamped to the
+// input's rows, offsets and edge positions to the entry count: malformed input gives garbage, never an access outside.
+#include "egc_common.h"
+
+namespace egc {
+
+constexpr int MP_CHUNK = EGC_TYPED_MEAN_CHUNK;
+constexpr int MP_AHEAD = 8;
+
+typedef int i4 __attribute__((ext_vector_type(4)));
+
+// what an entry contributes: the row it names; that row over the named row's forward degree; that row where arg names the edge
+enum { MP_PLAIN = 0, MP_DIV_DEG = 1, MP_MATCH = 2 };
+
+struct MpWalk {
+  const int32_t* rowptr;     // the CSR walked: n_rows + 1 offsets
+  const int32_t* col;        // n_edges entries: rows of `in`
+  const int32_t* eid;        // MP_MATCH: forward CSR position of each entry (NULL: the entry's own position)
+  const int32_t* f_rowptr;   // MP_DIV_DEG: forward rowptr, n_in_rows + 1 offsets
+  const int32_t* f_eid;      // MP_MATCH: edge id of each forward CSR position (NULL: the position)
+  const int32_t* arg;        // MP_MATCH: [n_in_rows, width] edge ids, dense
+  const float* in;           // n_in_rows rows of ld_in floats
+  int64_t n_rows, n_edges, n_in_rows;
+  int32_t ld_in, width, lanes;
+};
+
+template <bool VEC>
+__device__ inline i4 mp_load_i(const int32_t* __restrict__ p, int c, int width) {
+  if (VEC) return *reinterpret_cast<const i4*>(p);
+  i4 v = i4{-1, -1, -1, -1};
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (c + j < width) v[j] = p[j];
+  return v;
+}
+
+template <bool VEC>
+__device__ inline void mp_store_i(int32_t* __restrict__ p, int c, int width, i4 v) {
+  if (VEC) {
+    *reinterpret_cast<i4*>(p) = v;
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (c + j < width) p[j] = v[j];
+}
+
+// MP_AHEAD consecutive entries from p on (FULL: all of them exist; else those before p1, the others load entry p1 - 1 again
+// and are not taken) folded into acc (and pos: the entry of the running max) in entry order
+template <bool VEC, bool MAX, int KIND, bool FULL>
+__device__ inline void mp_take_batch(f4& acc, i4& pos, const MpWalk& W, int64_t p, int64_t p1, int c) {
+  constexpr int N = FULL ? MP_AHEAD : MP_AHEAD - 1;
+  const int last_in = (int)W.n_in_rows - 1, last_e = (int)W.n_edges - 1;   // (both < 2^31: the entries are int32)
+  int j[N], e[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
+    j[k] = min(max(W.col[q], 0), last_in);
+    if (KIND == MP_MATCH) e[k] = W.eid != nullptr ? min(max(W.eid[q], 0), last_e) : (int)q;
+  }
+  if (KIND == MP_MATCH && W.f_eid != nullptr) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) e[k] = W.f_eid[e[k]];
+  }
+  float deg[N];
+  if (KIND == MP_DIV_DEG) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) deg[k] = (float)max(W.f_rowptr[j[k] + 1] - W.f_rowptr[j[k]], 1);
+  }
+  f4 v[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = tm_load<VEC>(W.in + (int64_t)j[k] * W.ld_in + c, c, W.width);
+  if (KIND == MP_MATCH) {
+    i4 a[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) a[k] = mp_load_i<VEC>(W.arg + (int64_t)j[k] * W.width + c, c, W.width);
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[k][i] = a[k][i] == e[k] ? v[k][i] : 0.f;
+  }
+  if (KIND == MP_DIV_DEG) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] /= deg[k];
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const bool live = FULL || p + k < p1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (MAX) {
+        const bool better = live && v[k][i] > acc[i];
+        acc[i] = better ? v[k][i] : acc[i];
+        pos[i] = better ? (int)(p + k) : pos[i];
+      } else {
+        acc[i] = live ? acc[i] + v[k][i] : acc[i];
+      }
+    }
+  }
+}
+
+// the entries [p0, p1), p0 < p1, in order: ((0 + v[p0]) + v[p0 + 1]) + ..., or the running max from (-inf, p0) on
+template <bool VEC, bool MAX, int KIND>
+__device__ inline void mp_reduce_entries(f4& acc, i4& pos, const MpWalk& W, int64_t p0, int64_t p1, int c) {
+  const float start = MAX ? -__builtin_inff() : 0.f;
+  acc = f4{start, start, start, start};
+  pos = i4{(int)p0, (int)p0, (int)p0, (int)p0};
+  int64_t p = p0;
+#pragma unroll 1
+  for (; p + MP_AHEAD <= p1; p += MP_AHEAD) mp_take_batch<VEC, MAX, KIND, true>(acc, pos, W, p, p1, c);
+  if (p < p1) mp_take_batch<VEC, MAX, KIND, false>(acc, pos, W, p, p1, c);
+}
+
+__device__ inline void mp_row_range(const MpWalk& W, int64_t row, int64_t& p0, int64_t& p1) {
+  p0 = min(max((int64_t)W.rowptr[row], (int64_t)0), W.n_edges);
+  p1 = min(max((int64_t)W.rowptr[row + 1], p0), W.n_edges);
+}
+
+// workspace: [slots][lanes] f4 partial values, then (MAX) [slots][lanes] i4 CSR positions of the partial maxima
+template <bool VEC, bool MAX, int KIND>
+__global__ void __launch_bounds__(256) mpnn_chunks_kernel(const MpWalk W, int64_t slots, float* __restrict__ ws) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t g = t / W.lanes;
+  if (g >= slots) return;
+  const int c = (int)(t - g * W.lanes) * 4;
+  const int64_t at = g * MP_CHUNK;
+  int64_t lo = 0, hi = W.n_rows;   // the last row that starts at or before `at`
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)W.rowptr[mid] <= at) lo = mid;
+    else hi = mid;
+  }
+  int64_t p0, p1;
+  mp_row_range(W, lo, p0, p1);
+  if (p1 - p0 <= MP_CHUNK || at <= p0) return;   // a short row; or chunk 0, which the row kernel reduces
+  const int64_t s = p0 + (at - p0 + MP_CHUNK - 1) / MP_CHUNK * MP_CHUNK;   // the row's chunk that starts in this window
+  if (s >= p1) return;
+  f4 acc;
+  i4 pos;
+  mp_reduce_entries<VEC, MAX, KIND>(acc, pos, W, s, min(s + MP_CHUNK, p1), c);
+  *reinterpret_cast<f4*>(ws + (g * W.lanes) * 4 + c) = acc;
+  if (MAX) *reinterpret_cast<i4*>(ws + ((slots + g) * W.lanes) * 4 + c) = pos;
+}
+
+// a row's reduction: chunk 0 here, chunks 1, 2, ... from the workspace in ascending order
+template <bool VEC, bool MAX, int KIND>
+__device__ inline void mp_reduce_row(f4& acc, i4& pos, const MpWalk& W, int64_t p0, int64_t p1, int c, int64_t slots,
+                                  const float* __restrict__ ws) {
+  mp_reduce_entries<VEC, MAX, KIND>(acc, pos, W, p0, min(p0 + MP_CHUNK, p1), c);
+  if (p1 - p0 <= MP_CHUNK) return;
+  const int64_t first = (p0 + MP_CHUNK) / MP_CHUNK, n_part = (p1 - p0 - 1) / MP_CHUNK;
+#pragma unroll 4
+  for (int64_t k = 0; k < n_part; ++k) {
+    const f4 v = *reinterpret_cast<const f4*>(ws + ((first + k) * W.lanes) * 4 + c);
+    if (MAX) {
+      const i4 q = *reinterpret_cast<const i4*>(ws + ((slots + first + k) * W.lanes) * 4 + c);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool better = v[i] > acc[i];
+        acc[i] = better ? v[i] : acc[i];
+        pos[i] = better ? q[i] : pos[i];
+      }
+    } else {
+      acc += v;
+    }
+  }
+}
+
+template <bool VEC, int OP>
+__global__ void __launch_bounds__(256) mpnn_message_rows_kernel(const MpWalk W, const int32_t* __restrict__ edge_id,
+                                                                const float* __restrict__ Q, int ld_q, float* __restrict__ out,
+                                                                int ld_out, int32_t* __restrict__ arg, int64_t slots,
+                                                                const float* __restrict__ ws) {
+  constexpr bool MAX = OP == EGC_MPNN_MAX;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = t / W.lanes;
+  if (row >= W.n_rows) return;
+  const int c = (int)(t - row * W.lanes) * 4;
+  int64_t p0, p1;
+  mp_row_range(W, row, p0, p1);
+  f4 m = f4{0.f, 0.f, 0.f, 0.f};
+  i4 e = i4{-1, -1, -1, -1};
+  if (p1 > p0) {
+    const f4 q = tm_load<VEC>(Q + row * ld_q + c, c, W.width);
+    f4 acc;
+    i4 pos;
+    mp_reduce_row<VEC, MAX, MP_PLAIN>(acc, pos, W, p0, p1, c, slots, ws);
+    const float deg = (float)(p1 - p0);
+    if (OP == EGC_MPNN_ADD) m = acc + deg * q;
+    else if (OP == EGC_MPNN_MEAN) m = acc / deg + q;
+    else m = acc + q;
+    if (MAX && arg != nullptr) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) e[i] = edge_id != nullptr ? edge_id[pos[i]] : pos[i];
+    }
+  }
+  tm_store<VEC>(out + row * ld_out + c, c, W.width, m);
+  if (MAX && arg != nullptr) mp_store_i<VEC>(arg + row * W.width + c, c, W.width, e);
+}
+
+// group g: d P of transposed row g (g < W.n_rows) and d Q of forward row g (g < W.n_in_rows)
+template <bool VEC, int KIND>
+__global__ void __launch_bounds__(256) mpnn_backward_rows_kernel(const MpWalk W, const int32_t* __restrict__ f_rowptr, int op,
+                                                                 float* __restrict__ dP, int ld_dp, float* __restrict__ dQ,
+                                                                 int ld_dq, int64_t slots, const float* __restrict__ ws) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t g = t / W.lanes;
+  const int c = (int)(t - g * W.lanes) * 4;
+  if (dP != nullptr && g < W.n_rows) {
+    int64_t p0, p1;
+    mp_row_range(W, g, p0, p1);
+    f4 acc = f4{0.f, 0.f, 0.f, 0.f};
+    i4 pos;
+    if (p1 > p0) mp_reduce_row<VEC, false, KIND>(acc, pos, W, p0, p1, c, slots, ws);
+    tm_store<VEC>(dP + g * ld_dp + c, c, W.width, acc);
+  }
+  if (dQ != nullptr && g < W.n_in_rows) {
+    const int deg = max(f_rowptr[g + 1] - f_rowptr[g], 0);
+    f4 d = f4{0.f, 0.f, 0.f, 0.f};
+    if (deg > 0) {
+      d = tm_load<VEC>(W.in + g * W.ld_in + c, c, W.width);
+      if (op == EGC_MPNN_ADD) d = (float)deg * d;
+    }
+    tm_store<VEC>(dQ + g * ld_dq + c, c, W.width, d);
+  }
+}
+
+static inline int64_t mp_slots(int64_t n_edges) { return n_edges > MP_CHUNK ? ceil_div(n_edges, MP_CHUNK) : 0; }
+
+static inline size_t mp_workspace_bytes(int64_t n_edges, int32_t width, bool with_pos) {
+  if (n_edges <= 0 || width <= 0) return 0;
+  return (size_t)mp_slots(n_edges) * (size_t)((width + 3) / 4) * 16 * (with_pos ? 2 : 1);
+}
+
+template <bool MAX, int KIND>
+static int launch_chunks(const MpWalk& W, bool vec, int64_t slots, float* ws, hipStream_t stream) {
+  const int64_t blocks = ceil_div(slots * W.lanes, 256);
+  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  if (vec) mpnn_chunks_kernel<true, MAX, KIND><<<(unsigned)blocks, 256, 0, stream>>>(W, slots, ws);
+  else mpnn_chunks_kernel<false, MAX, KIND><<<(unsigned)blocks, 256, 0, stream>>>(W, slots, ws);
+  EGC_LAUNCH_CHECK("mpnn_chunks_kernel");
+  return EGC_OK;
+}
+
+}  // namespace egc
+
+using namespace egc;
+
+size_t egc_mpnn_message_workspace_bytes(int64_t n_edges, int32_t width, int32_t op) {
+  return mp_workspace_bytes(n_edges, width, op == EGC_MPNN_MAX);
+}
+
+size_t egc_mpnn_message_backward_workspace_bytes(int64_t n_edges, int32_t width) {
+  return mp_workspace_bytes(n_edges, width, false);
+}
+
+int egc_mpnn_message_f32(const int32_t* rowptr, const int32_t* col, const int32_t* edge_id, int64_t n_rows, int64_t n_edges,
+                         int64_t n_src_rows, const float* P, int32_t ld_p, const float* Q, int32_t ld_q, int32_t width,
+                         int32_t op, float* out, int32_t ld_out, int32_t* arg, void* workspace, size_t workspace_bytes,
+                         egc_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (width <= 0 || n_rows < 0 || n_edges < 0 || n_src_rows < 0) return EGC_ERR_INVALID;
+  if (op != EGC_MPNN_ADD && op != EGC_MPNN_MEAN && op != EGC_MPNN_MAX) return EGC_ERR_INVALID;
+  if (ld_p < width || ld_q < width || ld_out < width) return EGC_ERR_INVALID;
+  if (n_rows == 0) return EGC_OK;
+  if (rowptr == nullptr || Q == nullptr || out == nullptr) return EGC_ERR_INVALID;
+  if (n_edges > 0 && (col == nullptr || P == nullptr || n_src_rows == 0)) return EGC_ERR_INVALID;
+  if (n_rows >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31) || n_src_rows >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  MpWalk W = {};
+  W.rowptr = rowptr, W.col = col, W.in = P;
+  W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_src_rows;
+  W.ld_in = ld_p, W.width = width, W.lanes = (width + 3) / 4;
+  const bool vec = (width & 3) == 0 && (ld_p & 3) == 0 && (ld_q & 3) == 0 && (ld_out & 3) == 0 && tm_aligned16(P) &&
+                   tm_aligned16(Q) && tm_aligned16(out) && tm_aligned16(arg);
+  const int64_t slots = mp_slots(n_edges);
+  float* ws = static_cast<float*>(workspace);
+  if (slots > 0) {
+    if (ws == nullptr || !tm_aligned16(ws) || workspace_bytes < mp_workspace_bytes(n_edges, width, op == EGC_MPNN_MAX))
+      return EGC_ERR_WORKSPACE;
+    const int st = op == EGC_MPNN_MAX ? launch_chunks<true, MP_PLAIN>(W, vec, slots, ws, stream)
+                                      : launch_chunks<false, MP_PLAIN>(W, vec, slots, ws, stream);
+    if (st != EGC_OK) return st;
+  }
+  const int64_t blocks = ceil_div(n_rows * W.lanes, 256);
+  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+#define EGC_MPNN_ROWS(V, O) \
+  mpnn_message_rows_kernel<V, O><<<(unsigned)blocks, 256, 0, stream>>>(W, edge_id, Q, ld_q, out, ld_out, arg, slots, ws)
+  if (op == EGC_MPNN_ADD) { if (vec) EGC_MPNN_ROWS(true, EGC_MPNN_ADD); else EGC_MPNN_ROWS(false, EGC_MPNN_ADD); }
+  else if (op == EGC_MPNN_MEAN) { if (vec) EGC_MPNN_ROWS(true, EGC_MPNN_MEAN); else EGC_MPNN_ROWS(false, EGC_MPNN_MEAN); }
+  else { if (vec) EGC_MPNN_ROWS(true, EGC_MPNN_MAX); else EGC_MPNN_ROWS(false, EGC_MPNN_MAX); }
+#undef EGC_MPNN_ROWS
+  EGC_LAUNCH_CHECK("mpnn_message_rows_kernel");
+  return EGC_OK;
+}
+
+int egc_mpnn_message_backward_f32(const int32_t* rowptr, const int32_t* edge_id, int64_t n_rows, const int32_t* t_rowptr,
+                                  const int32_t* t_col, const int32_t* t_edge_id, int64_t n_src_rows, int64_t n_edges,
+                                  const float* dm, int32_t ld_dm, const int32_t* arg, int32_t width, int32_t op, float* dP,
+                                  int32_t ld_dp, float* dQ, int32_t ld_dq, void* workspace, size_t workspace_bytes,
+                                  egc_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (width <= 0 || n_rows < 0 || n_edges < 0 || n_src_rows < 0) return EGC_ERR_INVALID;
+  if (op != EGC_MPNN_ADD && op != EGC_MPNN_MEAN && op != EGC_MPNN_MAX) return EGC_ERR_INVALID;
+  if (ld_dm < width || (dP != nullptr && ld_dp < width) || (dQ != nullptr && ld_dq < width)) return EGC_ERR_INVALID;
+  const int64_t p_rows = dP != nullptr ? n_src_rows : 0, q_rows = dQ != nullptr ? n_rows : 0;
+  const int64_t groups = p_rows > q_rows ? p_rows : q_rows;
+  if (groups == 0) return EGC_OK;
+  if (rowptr == nullptr || (n_rows > 0 && dm == nullptr)) return EGC_ERR_INVALID;
+  if (dP != nullptr && (t_rowptr == nullptr || (n_edges > 0 && (t_col == nullptr || n_rows == 0)))) return EGC_ERR_INVALID;
+  if (dP != nullptr && op == EGC_MPNN_MAX && n_edges > 0 && arg == nullptr) return EGC_ERR_INVALID;
+  if (n_rows >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31) || n_src_rows >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  MpWalk W = {};
+  W.rowptr = t_rowptr, W.col = t_col, W.eid = t_edge_id, W.f_rowptr = rowptr, W.f_eid = edge_id, W.arg = arg, W.in = dm;
+  W.n_rows = n_src_rows, W.n_edges = n_edges, W.n_in_rows = n_rows;
+  W.ld_in = ld_dm, W.width = width, W.lanes = (width + 3) / 4;
+  const bool vec = (width & 3) == 0 && (ld_dm & 3) == 0 && (ld_dp & 3) == 0 && (ld_dq & 3) == 0 && tm_aligned16(dm) &&
+                   tm_aligned16(dP) && tm_aligned16(dQ) && tm_aligned16(arg);
+  const int64_t slots = dP != nullptr ? mp_slots(n_edges) : 0;
+  float* ws = static_cast<float*>(workspace);
+  if (slots > 0) {
+    if (ws == nullptr || !tm_aligned16(ws) || workspace_bytes < mp_workspace_bytes(n_edges, width, false)) return EGC_ERR_WORKSPACE;
+    const int st = op == EGC_MPNN_ADD    ? launch_chunks<false, MP_PLAIN>(W, vec, slots, ws, stream)
+                   : op == EGC_MPNN_MEAN ? launch_chunks<false, MP_DIV_DEG>(W, vec, slots, ws, stream)
+                                         : launch_chunks<false, MP_MATCH>(W, vec, slots, ws, stream);
+    if (st != EGC_OK) return st;
+  }
+  const int64_t blocks = ceil_div(groups * W.lanes, 256);
+  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+#define EGC_MPNN_BWD(V, K) \
+  mpnn_backward_rows_kernel<V, K><<<(unsigned)blocks, 256, 0, stream>>>(W, rowptr, op, dP, ld_dp, dQ, ld_dq, slots, ws)
+  if (op == EGC_MPNN_ADD) { if (vec) EGC_MPNN_BWD(true, MP_PLAIN); else EGC_MPNN_BWD(false, MP_PLAIN); }
+  else if (op == EGC_MPNN_MEAN) { if (vec) EGC_MPNN_BWD(true, MP_DIV_DEG); else EGC_MPNN_BWD(false, MP_DIV_DEG); }
+  else { if (vec) EGC_MPNN_BWD(true, MP_MATCH); else EGC_MPNN_BWD(false, MP_MATCH); }
+#undef EGC_MPNN_BWD
+  EGC_LAUNCH_CHECK("mpnn_backward_rows_kernel");
+  return EGC_OK;
+}

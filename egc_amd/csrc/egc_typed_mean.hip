@@ -42,27 +42,6 @@ struct TypedTable {
   int32_t n_rels;
 };
 
-template <bool VEC>
-__device__ inline f4 tm_load(const float* __restrict__ p, int c, int width) {
-  if (VEC) return *reinterpret_cast<const f4*>(p);
-  f4 v = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (c + j < width) v[j] = p[j];
-  return v;
-}
-
-template <bool VEC>
-__device__ inline void tm_store(float* __restrict__ p, int c, int width, f4 v) {
-  if (VEC) {
-    *reinterpret_cast<f4*>(p) = v;
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (c + j < width) p[j] = v[j];
-}
-
 // TM_AHEAD consecutive entries from p on (FULL: all of them exist; else those before p1, the others load entry p1 - 1 again
 // and are not taken) added to acc in entry order
 template <bool VEC, bool FULL>
@@ -177,8 +156,6 @@ __global__ void __launch_bounds__(256) typed_mean_rows_kernel(const TypedTable T
   }
   tm_store<VEC>(out + row * ld_out + out_col + c, c, width, total);
 }
-
-static inline bool tm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static inline int64_t tm_slots(const egc_typed_rel& R) {
   return (R.rowptr != nullptr && R.n_edges > TM_CHUNK) ? ceil_div(R.n_edges, TM_CHUNK) : 0;

@@ -647,6 +647,58 @@ size_t egc_typed_mean_workspace_bytes(const egc_typed_rel* rels, int32_t n_rels,
 int egc_typed_mean_f32(const egc_typed_rel* rels, int32_t n_rels, int64_t n_rows, int32_t width, int32_t accumulate,
                        float* out, int32_t ld_out, void* workspace, size_t workspace_bytes, egc_stream_t stream);
 
+/* Message aggregation of the baseline MPNN layer (egc_mpnn.hip): the reference's Mpnn.message + aggregate
+ * (experiments/layers.py:251-258 under MessagePassing.propagate) without the [E, 2 d] concatenated endpoint features and the
+ * [E, d] messages.  A tower's message Linear acts on [x_i | x_j] and so splits into a target half and a source half: with
+ * P = x BD(Ws)^T and Q = x BD(Wd)^T + b_msg, both [N, d], the aggregated message of row i over its entries (no self loops added) is
+ *   EGC_MPNN_ADD    m_i = (sum of P[col[p]]) + float(deg_i) * Q_i
+ *   EGC_MPNN_MEAN   m_i = (sum of P[col[p]]) / float(deg_i) + Q_i
+ *   EGC_MPNN_MAX    m_i = (max of P[col[p]]) + Q_i     per column
+ * and 0 for a row without entries.
+ *   rowptr / col / edge_id   int32 CSR by destination, stable inside a row (n_rows + 1 offsets, n_edges entries); edge_id[p] is
+ *                  the position of entry p in the edge list (read for EGC_MPNN_MAX with `arg` only; NULL: edge_id[p] = p)
+ *   P, ld_p        n_src_rows rows of stride ld_p floats; Q, ld_q: n_rows rows of stride ld_q (column blocks of one wider array
+ *                  are fine: the pointers name the blocks' first columns)
+ *   out, ld_out    m, n_rows rows of stride ld_out, `out` pointing at the first column of the block to write (the left half of
+ *                  the [m | x] operand of the layer's second dense product); columns outside the block are not touched
+ *   arg            NULL, or (EGC_MPNN_MAX, the training form) int32 [n_rows, width], dense: the edge_id of the FIRST entry of the
+ *                  row, in entry order, that attains the column's maximum (duplicate edges are separate entries; a NaN is never
+ *                  selected); -1 for a row without entries
+ * Every element named is written exactly once: no zero fill in front, no atomics, nothing read back.
+ * Order of a row's float32 sum: egc_typed_mean_f32's -- consecutive chunks of EGC_TYPED_MEAN_CHUNK entries counted from the row's
+ * first entry, a chunk's sum ((0 + v0) + v1) + ... in entry order, the chunk sums added in ascending order; then the division
+ * (mean); the self term last, agg + s * Q, each one IEEE operation.  Chunks 1.. of the rows longer than one chunk are reduced by
+ * a first launch into `workspace` (egc_mpnn_message_workspace_bytes: a function of n_edges, width and op only; 16-byte aligned,
+ * any content; 0 when n_edges <= one chunk; EGC_ERR_WORKSPACE if smaller).  Column indices are clamped to [0, n_src_rows),
+ * offsets to [0, n_edges].  Any width >= 1: 16-byte accesses when width and the strides are multiples of 4 and the pointers
+ * 16-byte aligned, 4-byte ones otherwise.
+ *
+ * egc_mpnn_message_backward_f32: from d m (n_rows rows of stride ld_dm)
+ *   d Q_i = s_i * d m_i,  s_i = float(deg_i) (add), 1 (mean, max), and d Q_i = 0 for a row without entries
+ *   d P_j = sum over j's entries q of the TRANSPOSED CSR (t_rowptr [n_src_rows + 1], t_col = the destination i, t_edge_id = the
+ *           forward CSR position of the entry; stable, so a row's entries ascend in forward position), in the chunked order
+ *           above, of   d m_i (add),   d m_i / float(deg_i) (mean, one division per entry),   d m_i[c] where
+ *           arg[i, c] == edge_id[t_edge_id[q]] and 0 elsewhere (max: with duplicate edges only the first one receives)
+ * rowptr / edge_id are the forward graph's (degrees; NULL edge_id or t_edge_id: the identity).  d P (n_src_rows rows) or d Q
+ * (n_rows rows) may be NULL and is then not computed.  Atomic-free, every element written once, bit-reproducible; workspace as
+ * above (egc_mpnn_message_backward_workspace_bytes).
+ * EGC_ERR_INVALID: width <= 0, an unknown op, a missing pointer, a negative count, a stride smaller than width;
+ * EGC_ERR_UNSUPPORTED: n_rows, n_src_rows or n_edges >= 2^31. */
+#define EGC_MPNN_ADD 0
+#define EGC_MPNN_MEAN 1
+#define EGC_MPNN_MAX 2
+size_t egc_mpnn_message_workspace_bytes(int64_t n_edges, int32_t width, int32_t op);
+int egc_mpnn_message_f32(const int32_t* rowptr, const int32_t* col, const int32_t* edge_id, int64_t n_rows, int64_t n_edges,
+                         int64_t n_src_rows, const float* P, int32_t ld_p, const float* Q, int32_t ld_q, int32_t width,
+                         int32_t op, float* out, int32_t ld_out, int32_t* arg, void* workspace, size_t workspace_bytes,
+                         egc_stream_t stream);
+size_t egc_mpnn_message_backward_workspace_bytes(int64_t n_edges, int32_t width);
+int egc_mpnn_message_backward_f32(const int32_t* rowptr, const int32_t* edge_id, int64_t n_rows, const int32_t* t_rowptr,
+                                  const int32_t* t_col, const int32_t* t_edge_id, int64_t n_src_rows, int64_t n_edges,
+                                  const float* dm, int32_t ld_dm, const int32_t* arg, int32_t width, int32_t op, float* dP,
+                                  int32_t ld_dp, float* dQ, int32_t ld_dq, void* workspace, size_t workspace_bytes,
+                                  egc_stream_t stream);
+
 /* Training form of egc_aggregate_combine_f32: same `out`, plus what the backward needs instead of a second
  * gather.  stats (n_nodes * egc_train_stats_floats(layer) floats, opaque to the caller, handed to the backward
  * as it is) receives every row's raw running aggregates after the self-loop term (those of sum / variance -- as the
