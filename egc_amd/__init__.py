@@ -9,6 +9,9 @@ Public surface (mirrors the reference's layer API):
   Mpnn                 drop-in for experiments/layers.py:Mpnn, the baseline MPNN-Sum / -Mean / -Max layer (state-dict compatible):
                        the per-edge message Linear split into two [N, d] projections, aggregated by one gather launch that
                        writes the update's operand; no [E, d] array forward or backward
+  GATv2Conv            PyG 2.x GATv2Conv, the attention baseline of the reference's nets (state-dict compatible): lin_l and lin_r as
+                       one dense product, the per-destination edge softmax and the weighted gather fused in one launch with
+                       an online softmax; the backward recomputes the scores; no [E, .] array forward or backward
   FusedEGCBlock        conv -> BatchNorm1d -> ReLU (-> dropout) -> + identity: eval mode in the kernel's store, training
                        mode in two passes each way
   global_mean_pool / global_add_pool / global_max_pool, readout(name)
@@ -34,6 +37,7 @@ from .layers import EfficientGraphConv  # noqa: F401
 from .optimized_layers import EGConv  # noqa: F401
 from .relational import REGC, REGConv, RGCNConv  # noqa: F401
 from ._mpnn import Mpnn  # noqa: F401
+from ._gat import GATv2Conv  # noqa: F401
 from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean_pool, readout  # noqa: F401
 from .encoders import ASTNodeEncoder, AtomEncoder, Embedding, NodeEncoder  # noqa: F401
 from ._softmax import RowSelection, cross_entropy, log_softmax, nll_log_softmax  # noqa: F401

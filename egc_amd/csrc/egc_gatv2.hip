@@ -1,0 +1,836 @@
+// GATv2 attention aggregate (PyG 2.x GATv2Conv's propagate) without any [E, .] array.  xl and xr are the two [N, H C] halves of
+// one dense product; for an entry j -> i and head h
+//
+//   z = xl_j^h + xr_i^h      s_ij^h = sum_c att^h_c leaky_relu(z_c)      alpha_ij^h = softmax over i's entries of s_ij^h
+//   out_i^h = sum_j alpha_ij^h xl_j^h      lse_i^h = log sum_j exp(s_ij^h)   (0 and -inf for a row without entries)
+//
+// With the self-loop flag the row's entries whose col equals the row are skipped and ONE self entry (j = i) is taken LAST, as
+// PyG's remove_self_loops + add_self_loops leaves it.  gfx950 only.  Forward: one gather pass over xl with an online softmax
+// (running maximum m, running sum l and accumulator rescaled by exp(m_old - m_new); the maximum is subtracted before every exp).
+// Backward, nothing per-edge kept: with g = d out, D_i^h = g_i^h . out_i^h, alpha = exp(s - lse), d alpha = g_i^h . xl_j^h,
+// d s = alpha (d alpha - D_i), d z = d s att leaky_relu'(z):
+//   destination pass (forward CSR)       d xr_i = sum_j d z_ij,   d att = sum_ij d s_ij leaky_relu(z_ij),   D into the workspace
+//   source pass (transposed CSR)         d xl_j = sum_i (alpha_ij g_i + d z_ij)
+// Every output element is written exactly once: no zero fill, no atomics.
+//
+// Mapping (egc_mpnn.hip's, with the group padded): a lane owns four adjacent columns (16-byte accesses; 4-byte ones of the same
+// columns when a width, stride or pointer is not a multiple of 16 bytes).  A row's group is G = the power of two >=
+// ceil(H C / 4) lanes, at most 64, so it lies inside one wavefront; for H C > 256 the group is a whole wavefront and a lane owns
+// two such quads (S = 2 slots, 256 columns apart).  "Virtual lane" v = lane + G * slot owns columns 4 v .. 4 v + 3.  Groups are
+// laid back to back over the grid.  AHEAD entries' indices, then their rows, are requested before the first consumer; a partial
+// batch issues all its loads too (index clamped, surplus not taken).  Column indices are clamped to the gathered array's rows,
+// offsets to the entry count: malformed input gives garbage, never an access outside.
+//
+// Order rule of a per-head sum over the head's C columns (the score, d alpha, D).  It depends on H and C only, never on where in
+// the grid the row lands.
+//   C >= 4: per virtual lane, a = its columns of the head of its FIRST column added in ascending column order, b = its later
+//   columns (they belong to the next head) likewise.  The first virtual lane of a head's segment (the lanes whose first column
+//   lies in the head) takes a = b(v - 1) + a when the head starts inside lane v - 1.  Then a Hillis-Steele inclusive scan over
+//   the segment: for d = 1, 2, 4, ... < ceil(C / 4) + 1, a(v) = a(v) + a(v - d) where v - d is still in the segment (all lanes
+//   read before any writes).  The head's sum is a of the segment's last lane.
+//   C < 4: a head lies within virtual lanes v - 1 .. v + 1; every column adds the head's columns in ascending column order.
+// Order rule of a row: its entries are cut into consecutive chunks of EGC_TYPED_MEAN_CHUNK counted from the row's first entry
+// (skipped entries keep their place).  Inside a chunk, batches of AHEAD entries (8 forward, 4 backward) from the chunk's start.
+// Forward, per batch: bm = max(m, the live scores in entry order); l = l * r + sum in entry order of exp(s_k - bm), acc likewise
+// with exp(s_k - bm) * xl_k, r = exp(m - bm) (1 when m == bm); m = bm.  The row is chunk 0's state with the states of chunks
+// 1, 2, ... merged in ascending order (M = max(m1, m2); l = l1 exp(m1 - M) + l2 exp(m2 - M)), then the self entry as a batch of
+// one, then out = acc / l and lse = m + log l.  Backward sums: ((0 + v0) + v1) + ... in entry order per chunk, chunk 0's sum
+// with those of chunks 1, 2, ... added in ascending order, the self entry last.  d att: a lane's sum over its row (entry order,
+// chunk by chunk), the workgroup's groups added in ascending order, the workgroups' partials (row workgroups, then chunk
+// workgroups) added in ascending order in blocks of 64, and those block sums again, until one is left.  -ffp-contract=off.
+#include "egc_common.h"
+
+namespace egc {
+
+constexpr int GAT_CHUNK = EGC_TYPED_MEAN_CHUNK;
+constexpr int GAT_AHEAD = 8;
+constexpr int GAT_AHEAD_BWD = 4;
+constexpr int GAT_SUM_BLOCK = 64;
+
+// The score's per-column term: s = per-head sum of att * act(z), z = xl_j + xr_i.  (GAT v1's additive score is another functor
+// with act = identity on a pre-reduced pair and the nonlinearity after the sum; the walks below do not change.)
+struct GatV2Score {
+  float slope;
+  __device__ inline f4 act(f4 z) const {
+    f4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = z[i] > 0.f ? z[i] : slope * z[i];
+    return r;
+  }
+  __device__ inline f4 dact(f4 z) const {
+    f4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = z[i] > 0.f ? 1.f : slope;
+    return r;
+  }
+};
+
+struct GatWalk {
+  const int32_t* rowptr;   // the CSR walked: n_rows + 1 offsets
+  const int32_t* col;      // n_edges entries: rows of the gathered arrays
+  const float* xl;         // forward / destination pass: gathered (n_in_rows rows); source pass: the row's own
+  const float* xr;         // forward / destination pass: the row's own; source pass: gathered
+  const float* att;        // [H C]
+  const float* g;          // backward: d out.  destination pass: the row's own; source pass: gathered
+  const float* out;        // destination pass: the forward's output
+  const float* lse;        // backward: [n_nodes, H]
+  const float* D;          // source pass: [n_nodes, H] (the destination pass writes it)
+  int64_t n_rows, n_edges, n_in_rows;
+  int32_t ld_xl, ld_xr, ld_g, ld_out;
+  int32_t H, C, width, G, V, seg, self_loops;
+  float slope;
+};
+
+template <int S>
+struct GatLane {
+  int base;            // wavefront lane of the group's lane 0
+  int v[S], c[S];      // virtual lane and its first column
+  int na[S];           // how many of the four columns belong to the head of the first one (C >= 4)
+  int first_a[S];      // first virtual lane of that head's segment
+  int last_a[S], last_b[S];
+  bool prev_b[S];      // the segment's first lane, and the head starts inside the lane before
+  int hd[S][4];        // head of every column (clamped to H - 1)
+  bool head_first[S][4];   // the column is its head's first (and exists)
+};
+
+template <int S>
+__device__ inline GatLane<S> gat_lane(const GatWalk& W, int lane_in_group) {
+  GatLane<S> L;
+  L.base = ((int)threadIdx.x & 63) & ~(W.G - 1);
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int v = lane_in_group + W.G * s, c = 4 * v;
+    L.v[s] = v, L.c[s] = c;
+    const bool live = c < W.width;
+    const int ha = live ? c / W.C : 0;
+    const int end_a = (ha + 1) * W.C;
+    L.na[s] = live ? min(4, end_a - c) : 4;
+    L.first_a[s] = live ? (ha * W.C + 3) / 4 : v;
+    L.last_a[s] = live ? (end_a - 1) / 4 : v;
+    const int hb = min(ha + 1, W.H - 1);
+    L.last_b[s] = live ? min(((hb + 1) * W.C - 1) / 4, W.V - 1) : v;
+    L.prev_b[s] = live && v > 0 && v == L.first_a[s] && (ha * W.C) % 4 != 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int h = min((c + j) / W.C, W.H - 1);
+      L.hd[s][j] = h;
+      L.head_first[s][j] = c + j < W.width && c + j == h * W.C;
+    }
+  }
+  return L;
+}
+
+// x of virtual lane src (0 <= src < V) of this group
+template <int S>
+__device__ inline float gat_vget(const GatWalk& W, const GatLane<S>& L, const float (&x)[S], int src) {
+  const int lane = L.base + (src & (W.G - 1));
+  float t = __shfl(x[0], lane);
+  if (S == 2) {
+    const float t1 = __shfl(x[S - 1], lane);
+    t = src >= W.G ? t1 : t;
+  }
+  return t;
+}
+
+// out[s][j] = the sum of p over the columns of column (c[s] + j)'s head, in the order of the file header
+template <int S, bool SMALL>
+__device__ inline void gat_head_sums(const GatWalk& W, const GatLane<S>& L, const f4 (&p)[S], f4 (&out)[S]) {
+  if (SMALL) {
+    float q[S][12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float x[S];
+#pragma unroll
+      for (int s = 0; s < S; ++s) x[s] = p[s][j];
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        q[s][j] = gat_vget<S>(W, L, x, max(L.v[s] - 1, 0));
+        q[s][4 + j] = x[s];
+        q[s][8 + j] = gat_vget<S>(W, L, x, min(L.v[s] + 1, W.V - 1));
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int lo = L.hd[s][j] * W.C, hi = lo + W.C;
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < 12; ++t) {
+          const int cc = L.c[s] - 4 + t;
+          sum = (cc >= lo && cc < hi) ? sum + q[s][t] : sum;
+        }
+        out[s][j] = sum;
+      }
+    return;
+  }
+  float a[S], b[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    a[s] = p[s][0], b[s] = 0.f;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+      a[s] = j < L.na[s] ? a[s] + p[s][j] : a[s];
+      b[s] = j < L.na[s] ? b[s] : b[s] + p[s][j];
+    }
+  }
+  float t[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) t[s] = gat_vget<S>(W, L, b, max(L.v[s] - 1, 0));
+#pragma unroll
+  for (int s = 0; s < S; ++s) a[s] = L.prev_b[s] ? t[s] + a[s] : a[s];
+#pragma unroll 1
+  for (int d = 1; d < W.seg; d <<= 1) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) t[s] = gat_vget<S>(W, L, a, max(L.v[s] - d, 0));
+#pragma unroll
+    for (int s = 0; s < S; ++s) a[s] = L.v[s] - d >= L.first_a[s] ? a[s] + t[s] : a[s];
+  }
+  float sa[S], sb[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) sa[s] = gat_vget<S>(W, L, a, L.last_a[s]), sb[s] = gat_vget<S>(W, L, a, L.last_b[s]);
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[s][j] = j < L.na[s] ? sa[s] : sb[s];
+}
+
+template <bool VEC>
+__device__ inline f4 gat_load(const float* __restrict__ p, int c, int width) {
+  if (VEC) return c < width ? *reinterpret_cast<const f4*>(p) : f4{0.f, 0.f, 0.f, 0.f};
+  return tm_load<false>(p, c, width);
+}
+
+template <bool VEC>
+__device__ inline void gat_store(float* __restrict__ p, int c, int width, f4 v) {
+  if (VEC) {
+    if (c < width) *reinterpret_cast<f4*>(p) = v;
+    return;
+  }
+  tm_store<false>(p, c, width, v);
+}
+
+template <int S, bool VEC>
+__device__ inline void gat_load_row(f4 (&v)[S], const float* __restrict__ base, int64_t row, int ld, const GatLane<S>& L, int width) {
+#pragma unroll
+  for (int s = 0; s < S; ++s) v[s] = gat_load<VEC>(base + row * ld + L.c[s], L.c[s], width);
+}
+
+// a per-(row, head) value for every column of the lane
+template <int S>
+__device__ inline void gat_load_heads(f4 (&v)[S], const float* __restrict__ a, int64_t row, const GatWalk& W, const GatLane<S>& L) {
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[s][j] = a[row * W.H + L.hd[s][j]];
+}
+
+__device__ inline f4 gat_exp(f4 x) { return f4{expf(x[0]), expf(x[1]), expf(x[2]), expf(x[3])}; }
+
+__device__ inline void gat_row_range(const GatWalk& W, int64_t row, int64_t& p0, int64_t& p1) {
+  p0 = min(max((int64_t)W.rowptr[row], (int64_t)0), W.n_edges);
+  p1 = min(max((int64_t)W.rowptr[row + 1], p0), W.n_edges);
+}
+
+// the chunk k >= 1 of some row that starts in [slot * CHUNK, (slot + 1) * CHUNK): its row and range (false: there is none)
+__device__ inline bool gat_slot_chunk(const GatWalk& W, int64_t slot, int64_t& row, int64_t& s0, int64_t& s1) {
+  const int64_t at = slot * GAT_CHUNK;
+  int64_t lo = 0, hi = W.n_rows;   // the last row that starts at or before `at`
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)W.rowptr[mid] <= at) lo = mid;
+    else hi = mid;
+  }
+  int64_t p0, p1;
+  gat_row_range(W, lo, p0, p1);
+  if (p1 - p0 <= GAT_CHUNK || at <= p0) return false;   // a short row; or chunk 0, which the row kernel takes
+  s0 = p0 + (at - p0 + GAT_CHUNK - 1) / GAT_CHUNK * GAT_CHUNK;
+  if (s0 >= p1) return false;
+  s1 = min(s0 + GAT_CHUNK, p1);
+  row = lo;
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- forward
+
+template <int S>
+struct GatState {
+  f4 m[S], l[S], acc[S];
+};
+
+template <int S>
+__device__ inline void gat_state_init(GatState<S>& st) {
+  const float ninf = -__builtin_inff();
+#pragma unroll
+  for (int s = 0; s < S; ++s) st.m[s] = f4{ninf, ninf, ninf, ninf}, st.l[s] = f4{0.f, 0.f, 0.f, 0.f}, st.acc[s] = st.l[s];
+}
+
+// one batch of N entries with scores e and rows v folded into the state (file header)
+template <int S, int N>
+__device__ inline void gat_state_take(GatState<S>& st, const f4 (&e)[N][S], const f4 (&v)[N][S], const bool (&live)[N]) {
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    f4 bm = st.m[s];
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) bm[i] = (live[k] && e[k][s][i] > bm[i]) ? e[k][s][i] : bm[i];
+    f4 r = gat_exp(st.m[s] - bm);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = st.m[s][i] == bm[i] ? 1.f : r[i];
+    f4 l = st.l[s] * r, acc = st.acc[s] * r;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      f4 w = gat_exp(e[k][s] - bm);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) w[i] = live[k] ? w[i] : 0.f;
+      l = l + w;
+      acc = acc + w * v[k][s];
+    }
+    st.m[s] = bm, st.l[s] = l, st.acc[s] = acc;
+  }
+}
+
+template <int S>
+__device__ inline void gat_state_merge(GatState<S>& st, const f4 (&m2)[S], const f4 (&l2)[S], const f4 (&acc2)[S]) {
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    f4 bm, r1, r2;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bm[i] = m2[s][i] > st.m[s][i] ? m2[s][i] : st.m[s][i];
+    r1 = gat_exp(st.m[s] - bm), r2 = gat_exp(m2[s] - bm);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r1[i] = st.m[s][i] == bm[i] ? 1.f : r1[i], r2[i] = m2[s][i] == bm[i] ? 1.f : r2[i];
+    st.l[s] = st.l[s] * r1 + l2[s] * r2;
+    st.acc[s] = st.acc[s] * r1 + acc2[s] * r2;
+    st.m[s] = bm;
+  }
+}
+
+template <int S, bool VEC, bool SMALL, class Score, bool FULL>
+__device__ inline void gat_fwd_batch(GatState<S>& st, const GatWalk& W, const GatLane<S>& L, const Score& sc, const f4 (&xr)[S],
+                                     const f4 (&att)[S], int64_t p, int64_t p1, int64_t row) {
+  constexpr int N = FULL ? GAT_AHEAD : GAT_AHEAD - 1;
+  const int last_in = (int)W.n_in_rows - 1;
+  int j[N];
+  bool live[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
+    const int raw = W.col[q];
+    j[k] = min(max(raw, 0), last_in);
+    live[k] = (FULL || p + k < p1) && !(W.self_loops && raw == (int)row);
+  }
+  f4 v[N][S], e[N][S];
+#pragma unroll
+  for (int k = 0; k < N; ++k) gat_load_row<S, VEC>(v[k], W.xl, j[k], W.ld_xl, L, W.width);
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    f4 t[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) t[s] = att[s] * sc.act(v[k][s] + xr[s]);
+    gat_head_sums<S, SMALL>(W, L, t, e[k]);
+  }
+  gat_state_take<S, N>(st, e, v, live);
+}
+
+template <int S, bool VEC, bool SMALL, class Score>
+__device__ inline void gat_fwd_entries(GatState<S>& st, const GatWalk& W, const GatLane<S>& L, const Score& sc, const f4 (&xr)[S],
+                                       const f4 (&att)[S], int64_t p0, int64_t p1, int64_t row) {
+  gat_state_init<S>(st);
+  int64_t p = p0;
+#pragma unroll 1
+  for (; p + GAT_AHEAD <= p1; p += GAT_AHEAD) gat_fwd_batch<S, VEC, SMALL, Score, true>(st, W, L, sc, xr, att, p, p1, row);
+  if (p < p1) gat_fwd_batch<S, VEC, SMALL, Score, false>(st, W, L, sc, xr, att, p, p1, row);
+}
+
+// workspace: per slot and virtual lane three f4: m, l, acc
+template <int S, bool VEC, bool SMALL, class Score>
+__global__ void __launch_bounds__(256) gat_fwd_chunks_kernel(const GatWalk W, const Score sc, int64_t slots, float* __restrict__ ws) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t g = t / W.G;
+  if (g >= slots) return;
+  const GatLane<S> L = gat_lane<S>(W, (int)(t - g * W.G));
+  int64_t row, s0, s1;
+  if (!gat_slot_chunk(W, g, row, s0, s1)) return;
+  f4 xr[S], att[S];
+  gat_load_row<S, VEC>(xr, W.xr, row, W.ld_xr, L, W.width);
+  gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
+  GatState<S> st;
+  gat_fwd_entries<S, VEC, SMALL, Score>(st, W, L, sc, xr, att, s0, s1, row);
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    f4* o = reinterpret_cast<f4*>(ws) + (g * W.V + L.v[s]) * 3;
+    o[0] = st.m[s], o[1] = st.l[s], o[2] = st.acc[s];
+  }
+}
+
+template <int S, bool VEC, bool SMALL, class Score>
+__global__ void __launch_bounds__(256) gat_fwd_rows_kernel(const GatWalk W, const Score sc, float* __restrict__ out, int ld_out,
+                                                           float* __restrict__ lse, int64_t slots, const float* __restrict__ ws) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = t / W.G;
+  if (row >= W.n_rows) return;
+  const GatLane<S> L = gat_lane<S>(W, (int)(t - row * W.G));
+  int64_t p0, p1;
+  gat_row_range(W, row, p0, p1);
+  f4 xr[S], att[S];
+  gat_load_row<S, VEC>(xr, W.xr, row, W.ld_xr, L, W.width);
+  gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
+  GatState<S> st;
+  gat_fwd_entries<S, VEC, SMALL, Score>(st, W, L, sc, xr, att, p0, min(p0 + GAT_CHUNK, p1), row);
+  if (p1 - p0 > GAT_CHUNK) {
+    const int64_t first = (p0 + GAT_CHUNK) / GAT_CHUNK, n_part = (p1 - p0 - 1) / GAT_CHUNK;
+#pragma unroll 1
+    for (int64_t k = 0; k < n_part; ++k) {
+      f4 m2[S], l2[S], a2[S];
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const f4* o = reinterpret_cast<const f4*>(ws) + ((first + k) * W.V + L.v[s]) * 3;
+        m2[s] = o[0], l2[s] = o[1], a2[s] = o[2];
+      }
+      gat_state_merge<S>(st, m2, l2, a2);
+    }
+  }
+  if (W.self_loops) {
+    f4 v[1][S], e[1][S], tt[S];
+    const bool live[1] = {true};
+    gat_load_row<S, VEC>(v[0], W.xl, min(row, W.n_in_rows - 1), W.ld_xl, L, W.width);
+#pragma unroll
+    for (int s = 0; s < S; ++s) tt[s] = att[s] * sc.act(v[0][s] + xr[s]);
+    gat_head_sums<S, SMALL>(W, L, tt, e[0]);
+    gat_state_take<S, 1>(st, e, v, live);
+  }
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    f4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool any = st.l[s][i] > 0.f;
+      o[i] = any ? st.acc[s][i] / st.l[s][i] : 0.f;
+      if (L.head_first[s][i]) lse[row * W.H + L.hd[s][i]] = any ? st.m[s][i] + logf(st.l[s][i]) : -__builtin_inff();
+    }
+    gat_store<VEC>(out + row * ld_out + L.c[s], L.c[s], W.width, o);
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------- backward
+
+// destination pass: N entries of row `row` -> d xr and d att partial sums
+template <int S, bool VEC, bool SMALL, class Score, int N, bool FULL>
+__device__ inline void gat_dst_batch(f4 (&dxr)[S], f4 (&datt)[S], const GatWalk& W, const GatLane<S>& L, const Score& sc,
+                                     const f4 (&xr)[S], const f4 (&att)[S], const f4 (&g)[S], const f4 (&lse)[S], const f4 (&D)[S],
+                                     int64_t p, int64_t p1, int64_t row, bool self) {
+  const int last_in = (int)W.n_in_rows - 1;
+  int j[N];
+  bool live[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
+    const int raw = self ? (int)row : W.col[q];
+    j[k] = min(max(raw, 0), last_in);
+    live[k] = self || ((FULL || p + k < p1) && !(W.self_loops && raw == (int)row));
+  }
+  f4 v[N][S];
+#pragma unroll
+  for (int k = 0; k < N; ++k) gat_load_row<S, VEC>(v[k], W.xl, j[k], W.ld_xl, L, W.width);
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    f4 z[S], lz[S], t[S], u[S], e[S], da[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) z[s] = v[k][s] + xr[s], lz[s] = sc.act(z[s]), t[s] = att[s] * lz[s], u[s] = g[s] * v[k][s];
+    gat_head_sums<S, SMALL>(W, L, t, e);
+    gat_head_sums<S, SMALL>(W, L, u, da);
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      f4 alpha = gat_exp(e[s] - lse[s]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) alpha[i] = live[k] ? alpha[i] : 0.f;
+      const f4 ds = alpha * (da[s] - D[s]);
+      dxr[s] = dxr[s] + ds * att[s] * sc.dact(z[s]);
+      datt[s] = datt[s] + ds * lz[s];
+    }
+  }
+}
+
+// the workgroup's d att partial: its groups' lane sums added in ascending group order into part[blockIdx.x]
+template <int S>
+__device__ inline void gat_block_datt(const f4 (&datt)[S], const GatWalk& W, const GatLane<S>& L, float* __restrict__ part) {
+  __shared__ float red[1024 * S];
+  const int gi = (int)threadIdx.x / W.G;
+#pragma unroll
+  for (int s = 0; s < S; ++s) *reinterpret_cast<f4*>(red + (gi * W.V + L.v[s]) * 4) = datt[s];
+  __syncthreads();
+  const int groups = 256 / W.G;
+  for (int c = (int)threadIdx.x; c < W.width; c += 256) {
+    float sum = 0.f;
+    for (int k = 0; k < groups; ++k) sum += red[k * W.V * 4 + c];
+    part[(int64_t)blockIdx.x * W.width + c] = sum;
+  }
+}
+
+// CHUNKS: group = slot, the chunk's d xr sum into ws_xr; else group = row: chunk 0, the partials, the self entry; d xr and D
+// stored.  Both: the workgroup's d att partial (part == NULL: not wanted).  No thread leaves before the barrier.
+template <int S, bool VEC, bool SMALL, class Score, bool CHUNKS>
+__global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatWalk W, const Score sc, float* __restrict__ dxr_out, int ld_dxr,
+                                                          float* __restrict__ D_out, int64_t slots, float* __restrict__ ws_xr,
+                                                          float* __restrict__ part) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t g = t / W.G;
+  const GatLane<S> L = gat_lane<S>(W, (int)(t - g * W.G));
+  int64_t row = g, p0 = 0, p1 = 0;
+  bool active;
+  if (CHUNKS) {
+    active = g < slots && gat_slot_chunk(W, g, row, p0, p1);
+  } else {
+    active = g < W.n_rows;
+    if (active) {
+      gat_row_range(W, row, p0, p1);
+    }
+  }
+  f4 dxr[S], datt[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) dxr[s] = f4{0.f, 0.f, 0.f, 0.f}, datt[s] = dxr[s];
+  if (active) {
+    f4 xr[S], att[S], gr[S], o[S], lse[S], D[S], u[S];
+    gat_load_row<S, VEC>(xr, W.xr, row, W.ld_xr, L, W.width);
+    gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
+    gat_load_row<S, VEC>(gr, W.g, row, W.ld_g, L, W.width);
+    gat_load_row<S, VEC>(o, W.out, row, W.ld_out, L, W.width);
+    gat_load_heads<S>(lse, W.lse, row, W, L);
+#pragma unroll
+    for (int s = 0; s < S; ++s) u[s] = gr[s] * o[s];
+    gat_head_sums<S, SMALL>(W, L, u, D);
+    const int64_t e1 = CHUNKS ? p1 : min(p0 + GAT_CHUNK, p1);
+    int64_t p = p0;
+#pragma unroll 1
+    for (; p + GAT_AHEAD_BWD <= e1; p += GAT_AHEAD_BWD)
+      gat_dst_batch<S, VEC, SMALL, Score, GAT_AHEAD_BWD, true>(dxr, datt, W, L, sc, xr, att, gr, lse, D, p, e1, row, false);
+    if (p < e1) gat_dst_batch<S, VEC, SMALL, Score, GAT_AHEAD_BWD - 1, false>(dxr, datt, W, L, sc, xr, att, gr, lse, D, p, e1, row, false);
+    if (CHUNKS) {
+#pragma unroll
+      for (int s = 0; s < S; ++s) *reinterpret_cast<f4*>(ws_xr + (g * W.V + L.v[s]) * 4) = dxr[s];
+    } else {
+      if (p1 - p0 > GAT_CHUNK) {
+        const int64_t first = (p0 + GAT_CHUNK) / GAT_CHUNK, n_part = (p1 - p0 - 1) / GAT_CHUNK;
+#pragma unroll 1
+        for (int64_t k = 0; k < n_part; ++k)
+#pragma unroll
+          for (int s = 0; s < S; ++s) dxr[s] = dxr[s] + *reinterpret_cast<const f4*>(ws_xr + ((first + k) * W.V + L.v[s]) * 4);
+      }
+      if (W.self_loops) gat_dst_batch<S, VEC, SMALL, Score, 1, true>(dxr, datt, W, L, sc, xr, att, gr, lse, D, 0, 0, row, true);
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        if (dxr_out != nullptr) gat_store<VEC>(dxr_out + row * ld_dxr + L.c[s], L.c[s], W.width, dxr[s]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (L.head_first[s][i]) D_out[row * W.H + L.hd[s][i]] = D[s][i];
+      }
+    }
+  }
+  if (part != nullptr) gat_block_datt<S>(datt, W, L, part);
+}
+
+// source pass: N entries (destinations i) of transposed row `row` (= source j) -> d xl partial sum
+template <int S, bool VEC, bool SMALL, class Score, int N, bool FULL>
+__device__ inline void gat_src_batch(f4 (&acc)[S], const GatWalk& W, const GatLane<S>& L, const Score& sc, const f4 (&xl)[S],
+                                     const f4 (&att)[S], int64_t p, int64_t p1, int64_t row, bool self) {
+  const int last_in = (int)W.n_in_rows - 1;
+  int i_[N];
+  bool live[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
+    const int raw = self ? (int)row : W.col[q];
+    i_[k] = min(max(raw, 0), last_in);
+    live[k] = self || ((FULL || p + k < p1) && !(W.self_loops && raw == (int)row));
+  }
+  f4 xr[N][S], gr[N][S], lse[N][S], D[N][S];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    gat_load_row<S, VEC>(xr[k], W.xr, i_[k], W.ld_xr, L, W.width);
+    gat_load_row<S, VEC>(gr[k], W.g, i_[k], W.ld_g, L, W.width);
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    gat_load_heads<S>(lse[k], W.lse, i_[k], W, L);
+    gat_load_heads<S>(D[k], W.D, i_[k], W, L);
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    f4 z[S], t[S], u[S], e[S], da[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) z[s] = xl[s] + xr[k][s], t[s] = att[s] * sc.act(z[s]), u[s] = gr[k][s] * xl[s];
+    gat_head_sums<S, SMALL>(W, L, t, e);
+    gat_head_sums<S, SMALL>(W, L, u, da);
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      f4 alpha = gat_exp(e[s] - lse[k][s]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) alpha[i] = live[k] ? alpha[i] : 0.f;
+      const f4 ds = alpha * (da[s] - D[k][s]);
+      acc[s] = acc[s] + (alpha * gr[k][s] + ds * att[s] * sc.dact(z[s]));
+    }
+  }
+}
+
+template <int S, bool VEC, bool SMALL, class Score, bool CHUNKS>
+__global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatWalk W, const Score sc, float* __restrict__ dxl, int ld_dxl,
+                                                          int64_t slots, float* __restrict__ ws) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t g = t / W.G;
+  const GatLane<S> L = gat_lane<S>(W, (int)(t - g * W.G));
+  int64_t row = g, p0 = 0, p1 = 0;
+  if (CHUNKS) {
+    if (g >= slots || !gat_slot_chunk(W, g, row, p0, p1)) return;
+  } else {
+    if (g >= W.n_rows) return;
+    gat_row_range(W, row, p0, p1);
+  }
+  f4 xl[S], att[S], acc[S];
+  gat_load_row<S, VEC>(xl, W.xl, row, W.ld_xl, L, W.width);
+  gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
+#pragma unroll
+  for (int s = 0; s < S; ++s) acc[s] = f4{0.f, 0.f, 0.f, 0.f};
+  const int64_t e1 = CHUNKS ? p1 : min(p0 + GAT_CHUNK, p1);
+  int64_t p = p0;
+#pragma unroll 1
+  for (; p + GAT_AHEAD_BWD <= e1; p += GAT_AHEAD_BWD)
+    gat_src_batch<S, VEC, SMALL, Score, GAT_AHEAD_BWD, true>(acc, W, L, sc, xl, att, p, e1, row, false);
+  if (p < e1) gat_src_batch<S, VEC, SMALL, Score, GAT_AHEAD_BWD - 1, false>(acc, W, L, sc, xl, att, p, e1, row, false);
+  if (CHUNKS) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) *reinterpret_cast<f4*>(ws + (g * W.V + L.v[s]) * 4) = acc[s];
+    return;
+  }
+  if (p1 - p0 > GAT_CHUNK) {
+    const int64_t first = (p0 + GAT_CHUNK) / GAT_CHUNK, n_part = (p1 - p0 - 1) / GAT_CHUNK;
+#pragma unroll 1
+    for (int64_t k = 0; k < n_part; ++k)
+#pragma unroll
+      for (int s = 0; s < S; ++s) acc[s] = acc[s] + *reinterpret_cast<const f4*>(ws + ((first + k) * W.V + L.v[s]) * 4);
+  }
+  if (W.self_loops) gat_src_batch<S, VEC, SMALL, Score, 1, true>(acc, W, L, sc, xl, att, 0, 0, row, true);
+#pragma unroll
+  for (int s = 0; s < S; ++s) gat_store<VEC>(dxl + row * ld_dxl + L.c[s], L.c[s], W.width, acc[s]);
+}
+
+// out[b, c] = in[b * 64, c] + in[b * 64 + 1, c] + ... (ascending, from 0)
+__global__ void __launch_bounds__(256) gat_sum_rows_kernel(const float* __restrict__ in, int64_t n_in, int width, float* __restrict__ out) {
+  const int c = (int)threadIdx.x + 256 * (int)blockIdx.y;
+  if (c >= width) return;
+  const int64_t r0 = (int64_t)blockIdx.x * GAT_SUM_BLOCK, r1 = min(r0 + GAT_SUM_BLOCK, n_in);
+  float sum = 0.f;
+#pragma unroll 8
+  for (int64_t r = r0; r < r1; ++r) sum += in[r * width + c];
+  out[(int64_t)blockIdx.x * width + c] = sum;
+}
+
+// ------------------------------------------------------------------------------------------------------------------- host
+
+struct GatGeom {
+  int32_t S, G, V;
+};
+
+static inline GatGeom gat_geom(int32_t width) {
+  const int lanes = (width + 3) / 4;
+  GatGeom q;
+  q.S = lanes > 64 ? 2 : 1;
+  int G = 1;
+  while (G < lanes && G < 64) G <<= 1;
+  q.G = G, q.V = q.S * G;
+  return q;
+}
+
+static inline int64_t gat_slots(int64_t n_edges) { return n_edges > GAT_CHUNK ? ceil_div(n_edges, GAT_CHUNK) : 0; }
+static inline int64_t gat_blocks(int64_t groups, int32_t G) { return ceil_div(groups, 256 / G); }
+static inline size_t gat_align(size_t floats) { return (floats + 3) & ~(size_t)3; }
+
+static inline bool gat_shape_ok(int32_t H, int32_t C) { return H >= 1 && C >= 1 && (int64_t)H * C <= 512; }
+
+// backward workspace, in floats
+struct GatBwdWs {
+  size_t D, part_xr, part_xl, part_att, tmp0, tmp1, total;
+  int64_t slots, row_blocks, chunk_blocks;
+};
+
+static inline GatBwdWs gat_bwd_ws(int64_t n_rows, int64_t n_edges, int32_t H, int32_t C) {
+  const int32_t width = H * C;
+  const GatGeom q = gat_geom(width);
+  GatBwdWs w;
+  w.slots = gat_slots(n_edges);
+  w.row_blocks = gat_blocks(n_rows, q.G), w.chunk_blocks = gat_blocks(w.slots, q.G);
+  const int64_t parts = w.row_blocks + w.chunk_blocks;
+  size_t at = 0;
+  w.D = at, at += gat_align((size_t)n_rows * H);
+  w.part_xr = at, at += (size_t)w.slots * q.V * 4;
+  w.part_xl = at, at += (size_t)w.slots * q.V * 4;
+  w.part_att = at, at += gat_align((size_t)parts * width);
+  w.tmp0 = at, at += gat_align((size_t)ceil_div(parts, GAT_SUM_BLOCK) * width);
+  w.tmp1 = at, at += gat_align((size_t)ceil_div(ceil_div(parts, GAT_SUM_BLOCK), GAT_SUM_BLOCK) * width);
+  w.total = at;
+  return w;
+}
+
+static void gat_fill_walk(GatWalk& W, int32_t H, int32_t C, float slope, int32_t self_loops) {
+  const GatGeom q = gat_geom(H * C);
+  W.H = H, W.C = C, W.width = H * C, W.G = q.G, W.V = q.V, W.seg = (C + 3) / 4 + 1, W.self_loops = self_loops, W.slope = slope;
+}
+
+#define GAT_DISPATCH(LAUNCH)                                   \
+  do {                                                         \
+    if (S == 2) {                                              \
+      if (vec) { if (small) LAUNCH(2, true, true); else LAUNCH(2, true, false); }      \
+      else { if (small) LAUNCH(2, false, true); else LAUNCH(2, false, false); }        \
+    } else {                                                   \
+      if (vec) { if (small) LAUNCH(1, true, true); else LAUNCH(1, true, false); }      \
+      else { if (small) LAUNCH(1, false, true); else LAUNCH(1, false, false); }        \
+    }                                                          \
+  } while (0)
+
+}  // namespace egc
+
+using namespace egc;
+
+size_t egc_gatv2_forward_workspace_bytes(int64_t n_edges, int32_t heads, int32_t channels) {
+  if (n_edges <= 0 || !gat_shape_ok(heads, channels)) return 0;
+  return (size_t)gat_slots(n_edges) * (size_t)gat_geom(heads * channels).V * 3 * 16;
+}
+
+size_t egc_gatv2_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32_t heads, int32_t channels) {
+  if (n_rows <= 0 || n_edges < 0 || !gat_shape_ok(heads, channels)) return 0;
+  return gat_bwd_ws(n_rows, n_edges, heads, channels).total * sizeof(float);
+}
+
+int egc_gatv2_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                          const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att, int32_t heads,
+                          int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out, float* lse,
+                          void* workspace, size_t workspace_bytes, egc_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0 || n_src_rows < 0) return EGC_ERR_INVALID;
+  const int32_t width = heads * channels;
+  if (ld_xl < width || ld_xr < width || ld_out < width) return EGC_ERR_INVALID;
+  if (self_loops && n_src_rows != n_rows) return EGC_ERR_INVALID;
+  if (n_rows == 0) return EGC_OK;
+  if (rowptr == nullptr || xr == nullptr || att == nullptr || out == nullptr || lse == nullptr) return EGC_ERR_INVALID;
+  if ((n_edges > 0 || self_loops) && xl == nullptr) return EGC_ERR_INVALID;
+  if (n_edges > 0 && (col == nullptr || n_src_rows == 0)) return EGC_ERR_INVALID;
+  if (n_rows >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31) || n_src_rows >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  GatWalk W = {};
+  W.rowptr = rowptr, W.col = col, W.xl = xl, W.xr = xr, W.att = att;
+  W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_src_rows, W.ld_xl = ld_xl, W.ld_xr = ld_xr;
+  gat_fill_walk(W, heads, channels, negative_slope, self_loops ? 1 : 0);
+  const GatV2Score sc = {negative_slope};
+  const int S = gat_geom(width).S;
+  const bool small = channels < 4;
+  const bool vec = (width & 3) == 0 && (ld_xl & 3) == 0 && (ld_xr & 3) == 0 && (ld_out & 3) == 0 && tm_aligned16(xl) &&
+                   tm_aligned16(xr) && tm_aligned16(out);
+  const int64_t slots = gat_slots(n_edges);
+  float* ws = static_cast<float*>(workspace);
+  if (slots > 0) {
+    if (ws == nullptr || !tm_aligned16(ws) || workspace_bytes < egc_gatv2_forward_workspace_bytes(n_edges, heads, channels))
+      return EGC_ERR_WORKSPACE;
+    const int64_t blocks = gat_blocks(slots, W.G);
+    if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+#define GAT_FWD_CHUNKS(S_, V_, M_) gat_fwd_chunks_kernel<S_, V_, M_, GatV2Score><<<(unsigned)blocks, 256, 0, stream>>>(W, sc, slots, ws)
+    GAT_DISPATCH(GAT_FWD_CHUNKS);
+#undef GAT_FWD_CHUNKS
+    EGC_LAUNCH_CHECK("gat_fwd_chunks_kernel");
+  }
+  const int64_t blocks = gat_blocks(n_rows, W.G);
+  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+#define GAT_FWD_ROWS(S_, V_, M_) \
+  gat_fwd_rows_kernel<S_, V_, M_, GatV2Score><<<(unsigned)blocks, 256, 0, stream>>>(W, sc, out, ld_out, lse, slots, ws)
+  GAT_DISPATCH(GAT_FWD_ROWS);
+#undef GAT_FWD_ROWS
+  EGC_LAUNCH_CHECK("gat_fwd_rows_kernel");
+  return EGC_OK;
+}
+
+int egc_gatv2_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_rows,
+                           int64_t n_edges, const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att,
+                           int32_t heads, int32_t channels, float negative_slope, int32_t self_loops, const float* out,
+                           int32_t ld_out, const float* lse, const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* dxr,
+                           int32_t ld_dxr, float* datt, void* workspace, size_t workspace_bytes, egc_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0) return EGC_ERR_INVALID;
+  const int32_t width = heads * channels;
+  if (ld_xl < width || ld_xr < width || ld_out < width || ld_g < width) return EGC_ERR_INVALID;
+  if ((dxl != nullptr && ld_dxl < width) || (dxr != nullptr && ld_dxr < width)) return EGC_ERR_INVALID;
+  if (dxl == nullptr && dxr == nullptr && datt == nullptr) return EGC_OK;
+  if (n_rows == 0) return datt == nullptr ? EGC_OK : EGC_ERR_INVALID;   // (d att of nothing is the caller's zero)
+  if (rowptr == nullptr || xl == nullptr || xr == nullptr || att == nullptr || out == nullptr || lse == nullptr || g == nullptr)
+    return EGC_ERR_INVALID;
+  if (n_edges > 0 && col == nullptr) return EGC_ERR_INVALID;
+  if (dxl != nullptr && (t_rowptr == nullptr || (n_edges > 0 && t_col == nullptr))) return EGC_ERR_INVALID;
+  if (n_rows >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  const GatBwdWs L = gat_bwd_ws(n_rows, n_edges, heads, channels);
+  float* ws = static_cast<float*>(workspace);
+  if (ws == nullptr || !tm_aligned16(ws) || workspace_bytes < L.total * sizeof(float)) return EGC_ERR_WORKSPACE;
+  GatWalk W = {};
+  W.rowptr = rowptr, W.col = col, W.xl = xl, W.xr = xr, W.att = att, W.g = g, W.out = out, W.lse = lse, W.D = ws + L.D;
+  W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_rows;
+  W.ld_xl = ld_xl, W.ld_xr = ld_xr, W.ld_g = ld_g, W.ld_out = ld_out;
+  gat_fill_walk(W, heads, channels, negative_slope, self_loops ? 1 : 0);
+  const GatV2Score sc = {negative_slope};
+  const int S = gat_geom(width).S;
+  const bool small = channels < 4;
+  const bool vec = (width & 3) == 0 && (ld_xl & 3) == 0 && (ld_xr & 3) == 0 && (ld_out & 3) == 0 && (ld_g & 3) == 0 &&
+                   (ld_dxl & 3) == 0 && (ld_dxr & 3) == 0 && tm_aligned16(xl) && tm_aligned16(xr) && tm_aligned16(out) &&
+                   tm_aligned16(g) && tm_aligned16(dxl) && tm_aligned16(dxr);
+  if (L.row_blocks >= ((int64_t)1 << 31) || L.chunk_blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  float* part = datt != nullptr ? ws + L.part_att : nullptr;
+  // destination pass: chunks (only when something they produce is wanted), then rows (always: the source pass reads D)
+  if (L.slots > 0 && (dxr != nullptr || datt != nullptr)) {
+    float* cpart = part != nullptr ? part + (size_t)L.row_blocks * width : nullptr;
+#define GAT_DST_CHUNKS(S_, V_, M_)                                                                               \
+  gat_bwd_dst_kernel<S_, V_, M_, GatV2Score, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(W, sc, nullptr, 0, nullptr, L.slots, \
+                                                                                                 ws + L.part_xr, cpart)
+    GAT_DISPATCH(GAT_DST_CHUNKS);
+#undef GAT_DST_CHUNKS
+    EGC_LAUNCH_CHECK("gat_bwd_dst_kernel(chunks)");
+  }
+  {
+    GatWalk Wr = W;
+    if (dxr == nullptr && datt == nullptr) Wr.n_edges = 0;   // only D is wanted: no entries, and the self entry's sums are unused
+    if (dxr == nullptr && datt == nullptr) Wr.self_loops = 0;
+#define GAT_DST_ROWS(S_, V_, M_)                                                                                                   \
+  gat_bwd_dst_kernel<S_, V_, M_, GatV2Score, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(Wr, sc, dxr, ld_dxr, ws + L.D, L.slots, \
+                                                                                                ws + L.part_xr, part)
+    GAT_DISPATCH(GAT_DST_ROWS);
+#undef GAT_DST_ROWS
+    EGC_LAUNCH_CHECK("gat_bwd_dst_kernel(rows)");
+  }
+  if (datt != nullptr) {
+    const bool chunks_ran = L.slots > 0;
+    int64_t n = L.row_blocks + (chunks_ran ? L.chunk_blocks : 0);
+    const float* in = part;
+    float* tmp[2] = {ws + L.tmp0, ws + L.tmp1};
+    int flip = 0;
+    for (;;) {
+      const int64_t n_out = ceil_div(n, GAT_SUM_BLOCK);
+      float* o = n_out == 1 ? datt : tmp[flip];
+      gat_sum_rows_kernel<<<dim3((unsigned)n_out, (unsigned)ceil_div(width, 256)), 256, 0, stream>>>(in, n, width, o);
+      EGC_LAUNCH_CHECK("gat_sum_rows_kernel");
+      if (n_out == 1) break;
+      in = o, n = n_out, flip ^= 1;
+    }
+  }
+  if (dxl != nullptr) {
+    GatWalk T = W;
+    T.rowptr = t_rowptr, T.col = t_col;
+    if (L.slots > 0) {
+#define GAT_SRC_CHUNKS(S_, V_, M_) \
+  gat_bwd_src_kernel<S_, V_, M_, GatV2Score, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(T, sc, nullptr, 0, L.slots, ws + L.part_xl)
+      GAT_DISPATCH(GAT_SRC_CHUNKS);
+#undef GAT_SRC_CHUNKS
+      EGC_LAUNCH_CHECK("gat_bwd_src_kernel(chunks)");
+    }
+#define GAT_SRC_ROWS(S_, V_, M_) \
+  gat_bwd_src_kernel<S_, V_, M_, GatV2Score, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(T, sc, dxl, ld_dxl, L.slots, ws + L.part_xl)
+    GAT_DISPATCH(GAT_SRC_ROWS);
+#undef GAT_SRC_ROWS
+    EGC_LAUNCH_CHECK("gat_bwd_src_kernel(rows)");
+  }
+  return EGC_OK;
+}

@@ -699,6 +699,39 @@ int egc_mpnn_message_backward_f32(const int32_t* rowptr, const int32_t* edge_id,
                                   int32_t ld_dp, float* dQ, int32_t ld_dq, void* workspace, size_t workspace_bytes,
                                   egc_stream_t stream);
 
+/* GATv2 attention aggregate (egc_gatv2.hip): PyG 2.x GATv2Conv's propagate without an [E, .] array.  H = heads, C = channels
+ * per head, width = H * C <= 512 (any H >= 1, C >= 1).  xl (n_src_rows rows) and xr (n_rows rows) are the lin_l / lin_r
+ * projections (column blocks of one wider array are fine); att is [H * C].  For an entry j -> i of the CSR by destination and head h
+ *   s_ij = sum_c att[h, c] * leaky_relu(xl[j, h, c] + xr[i, h, c])      alpha_ij = softmax of s over row i's entries
+ *   out[i, h, :] = sum_j alpha_ij * xl[j, h, :]                          lse[i, h] = log sum_j exp(s_ij)
+ * and out = 0, lse = -inf for a row without entries.  self_loops != 0: the entries whose col equals their row are skipped and
+ * one self entry (j = i) is taken last (needs n_src_rows == n_rows).  One gather pass with an online softmax (the maximum is
+ * subtracted before every exp); rows longer than EGC_TYPED_MEAN_CHUNK entries are cut into chunks whose partial states a first
+ * launch leaves in `workspace` (egc_gatv2_forward_workspace_bytes; 16-byte aligned, any content; 0 when n_edges <= one chunk).
+ * out: n_rows rows of stride ld_out; lse: dense [n_rows, H].  Every element is written exactly once, no atomics; the order of
+ * every sum is fixed by H, C and the row's entries alone (egc_gatv2.hip's header), so results are bit-reproducible.
+ * Column indices are clamped to [0, n_src_rows), offsets to [0, n_edges].
+ *
+ * egc_gatv2_backward_f32 (a square graph: xl and xr both have n_rows rows): from g = d out, the forward's out and lse, with the
+ * scores recomputed.  t_rowptr / t_col: the transposed CSR (rows = sources, entries = destinations), read for d xl only.
+ *   d xr[i] = sum_j d z_ij     d xl[j] = sum_i (alpha_ij g_i + d z_ij)     d att = sum_ij d s_ij leaky_relu(z_ij)
+ *   d s_ij = alpha_ij (g_i . xl_j - g_i . out_i)  per head,   d z_ij = d s_ij att leaky_relu'(z_ij)
+ * Any of d xl, d xr (rows of stride ld_dxl / ld_dxr: the halves of one [N, 2 H C] array are fine), d att ([H * C]) may be NULL.
+ * Workspace: egc_gatv2_backward_workspace_bytes (always > 0 for n_rows > 0), 16-byte aligned, any content.
+ * EGC_ERR_INVALID: H < 1, C < 1, H * C > 512, a missing pointer, a negative count, a stride smaller than H * C, self_loops with
+ * n_src_rows != n_rows; EGC_ERR_UNSUPPORTED: a count >= 2^31; EGC_ERR_WORKSPACE: workspace missing, misaligned or too small. */
+size_t egc_gatv2_forward_workspace_bytes(int64_t n_edges, int32_t heads, int32_t channels);
+int egc_gatv2_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                          const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att, int32_t heads,
+                          int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out, float* lse,
+                          void* workspace, size_t workspace_bytes, egc_stream_t stream);
+size_t egc_gatv2_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32_t heads, int32_t channels);
+int egc_gatv2_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_rows,
+                           int64_t n_edges, const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att,
+                           int32_t heads, int32_t channels, float negative_slope, int32_t self_loops, const float* out,
+                           int32_t ld_out, const float* lse, const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* dxr,
+                           int32_t ld_dxr, float* datt, void* workspace, size_t workspace_bytes, egc_stream_t stream);
+
 /* Training form of egc_aggregate_combine_f32: same `out`, plus what the backward needs instead of a second
  * gather.  stats (n_nodes * egc_train_stats_floats(layer) floats, opaque to the caller, handed to the backward
  * as it is) receives every row's raw running aggregates after the self-loop term (those of sum / variance -- as the
