@@ -9,7 +9,11 @@ live scores), l = l exp(m - bm) + sum exp(s_k - bm), the accumulator likewise, m
 order; the self entry LAST; out = acc / l, lse = m + log l (0 and -inf for a row without entries).  Nothing per-edge is kept:
 the backward recomputes z and s from xl, xr and att and uses alpha = exp(s - lse), D_i = g_i . out_i per head,
 d s = alpha (g_i . xl_j - D_i), d z = d s att leaky_relu'(z): a destination pass (d xr, d att) over the CSR and a source pass
-(d xl) over the transposed CSR, the self entry last in both."""
+(d xl) over the transposed CSR, the self entry last in both.
+
+``SWEEP_SHAPES`` / ``geometry`` / ``sweep_graph`` / ``sweep_inputs``: the (H, C) table of the geometry sweep
+(tests/test_gat_shapes_cpu.py guards the table, tests/test_gat_shapes_gpu.py runs the kernels over it), which needs no fixture:
+the restatement above is its float64 truth and, in float32, its yardstick."""
 import json
 import os
 
@@ -24,6 +28,97 @@ AHEAD = 8
 CASES = ("messy", "hub", "w104h1", "w112h8", "h8c13", "mean", "shared", "noloops", "bigscore", "slope")
 SHAPES = dict(messy=(4, 5), hub=(2, 4), w104h1=(1, 104), w112h8=(8, 14), h8c13=(8, 13), mean=(3, 6), shared=(2, 8), noloops=(4, 5),
               bigscore=(2, 8), slope=(2, 8))
+
+
+# (H, C) of the geometry sweep (tests/test_gat_shapes_*.py): every template instance (S, VEC, SMALL) and every group size G of
+# egc_gatv2.hip, and the places where the per-head scan's lane bookkeeping changes.  Columns 4 v .. 4 v + 3 belong to virtual
+# lane v; slot 1 (S = 2) starts at column 256.
+SWEEP_SHAPES = (
+    # ---- S = 1 (H C <= 256)
+    (1, 1),      # G 1, SMALL: one live column of the lane's four
+    (4, 1),      # G 1, SMALL, 16-byte rows: four heads in one lane
+    (1, 3),      # G 1, SMALL, scalar: a head of three columns inside one lane
+    (1, 4),      # G 1: the smallest scanned head, a segment of one lane (seg = 2)
+    (1, 5),      # G 2, scalar: the head runs into a second lane with one live column
+    (2, 3),      # G 2, SMALL, scalar: head 1 = columns 3..5 straddles lanes 0 and 1
+    (4, 2),      # G 2, SMALL, 16-byte rows: two heads per lane, none straddles
+    (3, 3),      # G 4 with one idle lane, SMALL, scalar: 9 columns on 3 lanes
+    (16, 2),     # G 8, SMALL, 16-byte rows
+    (7, 3),      # G 8 with two idle lanes, SMALL, scalar: heads straddle at every phase
+    (12, 5),     # G 16 with one idle lane, 16-byte rows: C mod 4 = 1, every head start phase
+    (9, 7),      # G 16, scalar: 63 columns, the last lane has three live columns, C mod 4 = 3
+    (1, 64),     # G 16: one head over the whole group (scan distances 1 .. 16)
+    (3, 43),     # G 64, scalar: 129 columns on 33 lanes, 31 idle lanes
+    (5, 50),     # G 64, scalar: 250 columns, C mod 4 = 2, one idle lane
+    (85, 3),     # G 64, SMALL, scalar: 255 columns, the last lane has three live columns
+    (64, 4),     # G 64: every lane is a head of its own
+    (4, 64),     # G 64: four aligned heads of 16 lanes
+    (1, 256),    # G 64: one head scanning the whole wavefront, the widest S = 1
+    # ---- S = 2 (257 <= H C <= 512)
+    (1, 257),    # scalar: one live column in slot 1, the head crosses 256 into it
+    (1, 260),    # 16-byte rows: one live lane in slot 1, the head crosses 256
+    (3, 100),    # head 2 = columns 200..299 crosses 256 (virtual lane 63 -> 64)
+    (8, 33),     # head 7 = columns 231..263 crosses 256, C mod 4 = 1
+    (37, 13),    # scalar: head 19 = columns 247..259 crosses 256
+    (2, 256),    # a head boundary exactly at column 256: head 1 is all of slot 1
+    (1, 512),    # seg = 129: scan distances up to 128, across both slots
+    (128, 4),    # every virtual lane is a head of its own, both slots full
+    (128, 3),    # SMALL, 16-byte rows: head 85 = columns 255..257 crosses 256
+    (170, 3),    # SMALL, scalar: 510 columns, the last virtual lane has two live columns
+    (256, 2),    # SMALL, 16-byte rows, both slots full
+    (512, 1),    # SMALL, 16-byte rows: 512 heads of one column
+)
+
+
+def geometry(h, c):
+    """The kernel's launch geometry for (H, C), restated from gat_geom / gat_fill_walk and the host dispatch of egc_gatv2.hip:
+    S slots per lane, G lanes per row (group), V = S G virtual lanes, seg = the scan's distance limit, small = the C < 4
+    window sum, vec_by_width = the width allows 16-byte accesses (pointers and strides permitting); spans_256 = some head has
+    columns on both sides of column 256 (slot 0 / slot 1), boundary_256 = a head starts exactly at column 256."""
+    width = h * c
+    lanes = (width + 3) // 4
+    g = 1
+    while g < lanes and g < 64:
+        g *= 2
+    s = 2 if lanes > 64 else 1
+    return dict(S=s, G=g, V=s * g, seg=(c + 3) // 4 + 1, small=c < 4, vec_by_width=width % 4 == 0,
+                spans_256=width > 256 and 256 % c != 0, boundary_256=width > 256 and 256 % c == 0)
+
+
+def datt_partials(h, c, n, e):
+    """How many workgroup partials of d att the backward sums for n rows and e entries: 256 / G rows (or chunk slots) per
+    workgroup, the row workgroups and, when some row can be longer than a chunk, the chunk workgroups."""
+    per = 256 // geometry(h, c)["G"]
+    slots = -(-e // CHUNK) if e > CHUNK else 0
+    return -(-n // per) + -(-slots // per)
+
+
+def sweep_graph(seed, n=40):
+    """(edge_index int64 [2, E], n), shuffled: 160 random edges among nodes 0 .. n - 4 (the last three nodes are isolated),
+    12 self loops, 20 duplicates of random edges, one destination (node 1) with exactly 2 CHUNK + 9 in-edges and one source
+    (node 2) with exactly 2 CHUNK + 9 out-edges -- three chunks each: two full ones and a tail of 9 (one full forward batch
+    and one entry; two backward batches and one entry).  The hubs' own entries may name the hub itself (skipped entries
+    inside a chunked row when self loops are added).  E = 1,234."""
+    assert n >= 20
+    rng = np.random.default_rng(seed)
+    live, hub_dst, hub_src, long_row = n - 3, 1, 2, 2 * CHUNK + 9
+    not_hub_src = np.array([i for i in range(live) if i != hub_src])
+    not_hub_dst = np.array([i for i in range(live) if i != hub_dst])
+    plain = np.array([i for i in range(live) if i not in (hub_dst, hub_src)])
+    rand = np.stack([rng.choice(not_hub_src, 160), rng.choice(not_hub_dst, 160)])
+    loops = np.tile(rng.choice(plain, 12, replace=False), (2, 1))
+    dups = rand[:, rng.choice(160, 20, replace=False)]
+    into = np.stack([rng.choice(not_hub_src, long_row), np.full(long_row, hub_dst)])
+    out_of = np.stack([np.full(long_row, hub_src), rng.choice(not_hub_dst, long_row)])
+    ei = np.concatenate([rand, loops, dups, into, out_of], axis=1).astype(np.int64)
+    return np.ascontiguousarray(ei[:, rng.permutation(ei.shape[1])]), n
+
+
+def sweep_inputs(h, c, n, seed):
+    """xl, xr, gout ~ N(0, 1) float32 [n, H C] and att ~ N(0, 1) / sqrt(C) float32 [H, C]."""
+    rng = np.random.default_rng(seed)
+    xl, xr, gout = (rng.standard_normal((n, h * c)).astype(np.float32) for _ in range(3))
+    return xl, xr, gout, (rng.standard_normal((h, c)) / np.sqrt(c)).astype(np.float32)
 
 
 def load_gat_golden(name):
