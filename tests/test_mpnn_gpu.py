@@ -3,7 +3,8 @@ reference's own Mpnn and against the sequential CPU restatement in the documente
 
 Bound of everything compared with a reference-derived fixture (the rule of test_rgcn_gpu.py): the relative max error against the
 float64 fixture is at most max(1e-5, 5 x the reference's own float32-vs-float64 distance on that fixture) -- for the output the
-distance between the two outputs stored, for a gradient the distance the generator recorded for that gradient."""
+distance between the two outputs stored, for a gradient the distance the generator recorded for that gradient.
+tests/test_mpnn_shapes_gpu.py runs the two kernels at every row length and width they dispatch on."""
 import functools
 
 import numpy as np

@@ -3,7 +3,8 @@ own RGCNConv / REGC.forward and against the sequential CPU restatement in the do
 
 Bound of everything compared with a reference-derived fixture: the relative max error against the float64 fixture is at most
 max(1e-5, 5 x the reference's own float32-vs-float64 distance on that fixture) -- for outputs the distance between the two
-outputs stored in the fixture, for a gradient the distance the generator recorded for that gradient."""
+outputs stored in the fixture, for a gradient the distance the generator recorded for that gradient.
+tests/test_typed_mean_shapes_gpu.py runs the kernel, in both of its forms, at every row length and width it dispatches on."""
 import functools
 
 import numpy as np
