@@ -30,6 +30,9 @@ SOFTMAX_MAX_CLASSES = 1024   # EGC_SOFTMAX_MAX_CLASSES
 TYPED_MAX_RELATIONS = 8      # EGC_TYPED_MAX_RELATIONS
 # EGC_MPNN_*
 MPNN_ADD, MPNN_MEAN, MPNN_MAX = range(3)
+# EGC_PNA_* aggregators and scalers
+PNA_SUM, PNA_MEAN, PNA_MIN, PNA_MAX, PNA_VAR, PNA_STD = range(6)
+PNA_IDENTITY, PNA_AMPLIFICATION, PNA_ATTENUATION, PNA_LINEAR, PNA_INVERSE_LINEAR = range(5)
 
 _STATUS = {1: "EGC_ERR_INVALID", 2: "EGC_ERR_WORKSPACE", 3: "EGC_ERR_HIP", 4: "EGC_ERR_UNSUPPORTED"}
 
@@ -201,6 +204,19 @@ SYMBOLS = {
     "egc_mpnn_message_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                                 C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                                 C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egc_pna_aggregate_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_void_p, C.c_int32]),
+    "egc_pna_aggregate_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egc_pna_aggregate_backward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "egc_pna_aggregate_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                 C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egc_pna_scale_combine_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "egc_pna_scale_combine_backward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "egc_gatv2_forward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "egc_gatv2_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_int32,

@@ -12,6 +12,13 @@ Public surface (mirrors the reference's layer API):
   GATv2Conv            PyG 2.x GATv2Conv, the attention baseline of the reference's nets (state-dict compatible): lin_l and lin_r as
                        one dense product, the per-destination edge softmax and the weighted gather fused in one launch with
                        an online softmax; the backward recomputes the scores; no [E, .] array forward or backward
+  PNAConv              PyG 2.x PNAConv (edge_dim=None, one pre and one post layer), the strongest baseline of the reference's nets
+                       (state-dict compatible): the per-edge pre-transform split into two [N, W] projections, every listed
+                       aggregator (sum / mean / min / max / var / std) out of one gather launch, the degree scalers moved behind
+                       the folded post o lin product and applied by one combine launch; no [E, .] and no [N, S A W] array
+  degree_histogram     the in-degree histogram PNAConv's ``deg`` wants, from an edge_index, a SparseTensor or a CSRGraph
+  pna_aggregate / pna_aggregate_backward / pna_scale_combine
+                       the kernel-level calls under PNAConv
   FusedEGCBlock        conv -> BatchNorm1d -> ReLU (-> dropout) -> + identity: eval mode in the kernel's store, training
                        mode in two passes each way
   global_mean_pool / global_add_pool / global_max_pool, readout(name)
@@ -38,6 +45,7 @@ from .optimized_layers import EGConv  # noqa: F401
 from .relational import REGC, REGConv, RGCNConv  # noqa: F401
 from ._mpnn import Mpnn  # noqa: F401
 from ._gat import GATv2Conv  # noqa: F401
+from ._pna import PNAConv, degree_histogram, pna_aggregate, pna_aggregate_backward, pna_scale_combine  # noqa: F401
 from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean_pool, readout  # noqa: F401
 from .encoders import ASTNodeEncoder, AtomEncoder, Embedding, NodeEncoder  # noqa: F401
 from ._softmax import RowSelection, cross_entropy, log_softmax, nll_log_softmax  # noqa: F401

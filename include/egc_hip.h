@@ -699,6 +699,82 @@ int egc_mpnn_message_backward_f32(const int32_t* rowptr, const int32_t* edge_id,
                                   int32_t ld_dp, float* dQ, int32_t ld_dq, void* workspace, size_t workspace_bytes,
                                   egc_stream_t stream);
 
+/* Multi-aggregator aggregation of PNAConv (egc_pna.hip): PyG 2.x PNAConv (edge_dim = None, pre_layers = post_layers = 1) without
+ * its [E, 2 F] endpoint features, [E, T F] messages, four scatter passes and [N, T, A S F] scaled concatenation.  The pre-transform
+ * splits as Mpnn's message Linear does: P = x Ms^T (n_src_rows rows), Q = x Md^T + b_pre (n_rows rows), both `width` = T F_in wide,
+ * the message of entry j -> i is P_j + Q_i.  `ops` lists n_ops (1 .. 6) distinct aggregators; block k of the output (columns
+ * k * width .. (k + 1) * width of `out`, n_rows rows of stride ld_out >= n_ops * width) receives, for a row of n entries, per column
+ *   EGC_PNA_SUM   S0 + float(n) * Q_i         S0 = sum of P[col[p]]
+ *   EGC_PNA_MEAN  S0 / float(n) + Q_i
+ *   EGC_PNA_MIN   (min of P[col[p]]) + Q_i    EGC_PNA_MAX   (max of P[col[p]]) + Q_i
+ *   EGC_PNA_VAR   v = max(S2 / n - (S1 / n)^2, 0),  S1 = sum of (P[col[p]] - s), S2 = sum of (P[col[p]] - s)^2,
+ *                 s = P[col[first entry of the row]] (the variance of P alone: Q_i is a row constant)
+ *   EGC_PNA_STD   sqrt(v + 1e-5)
+ * and 0 (EGC_PNA_STD: sqrt(1e-5)) for a row without entries.  Columns of `out` outside the n_ops blocks are not touched.
+ *   rowptr / col / edge_id, P, ld_p, Q, ld_q   as for egc_mpnn_message_f32
+ *   arg_min, arg_max   NULL (the inference form), or int32 [n_rows, width], dense: the edge_id of the FIRST entry of the row, in
+ *                  entry order, attaining the column's extremum (strict compare; a NaN is never selected); -1 for an empty row.
+ *                  Read only when MIN / MAX is listed.
+ *   mu, var        NULL, or float [n_rows, width] each, dense (VAR / STD listed): s + S1 / n, the row mean of P, and the clamped
+ *                  variance v -- what the backward needs (0 for an empty row)
+ * One gather pass over P whatever the list; only what the list needs is carried (no shift and no S2 without VAR / STD, no
+ * positions without MIN / MAX).  Order: egc_mpnn_message_f32's chunks of EGC_TYPED_MEAN_CHUNK entries from the row's first entry,
+ * every accumulator taking a chunk's entries in order from 0 (+-inf), the chunks merged in ascending order by plain addition (the
+ * shift is the row's in every chunk) or a strict compare (the first chunk keeps a tie); then each finishing step one IEEE
+ * operation as listed in egc_pna.hip's header.  SUM and MEAN use the unshifted S0, so a block's bits do not depend on the rest of
+ * the list.  workspace: egc_pna_aggregate_workspace_bytes(n_edges, width, ops, n_ops), 16-byte aligned, any content, 0 when
+ * n_edges <= one chunk.  Indices are clamped as in egc_mpnn_message_f32; any width >= 1 (16-byte accesses when width, strides and
+ * pointers allow, 4-byte ones otherwise).
+ *
+ * egc_pna_aggregate_backward_f32: from dagg (n_rows rows of stride ld_dagg, the blocks in list order), with nf = float(n):
+ *   d Q_i = ((nf * g_sum + g_mean) + g_min) + g_max, 0 for an empty row
+ *   per-row records  lin = g_sum + g_mean / nf;  c = g_var + g_std / (2 * sqrt(v_i + 1e-5f)), and c = 0 where v_i == 0 (the
+ *           derivative 2 (P_j - mu) / n of v is 0 there, as PyG's relu'(0));  b_i = (2 * c) / nf;  a_i = lin - b_i * mu_i
+ *   d P_j = ((A + P_j * B) + Mn) + Mx over j's entries of the TRANSPOSED CSR (t_rowptr / t_col / t_edge_id as for
+ *           egc_mpnn_message_backward_f32, ascending forward position, chunked as above): A = sum a_i, B = sum b_i,
+ *           Mn / Mx = sum of g_min[i] / g_max[i] where arg_min / arg_max [i] names this edge and 0 elsewhere
+ * (terms of aggregators not listed are skipped).  mu, var (the forward's), P, ld_p: read when VAR / STD is listed.  d P (n_src_rows rows) or d Q (n_rows rows) may be NULL and is then not computed.
+ * The records a and b live in `workspace`, in front of the chunk partials: egc_pna_aggregate_backward_workspace_bytes(n_rows,
+ * n_edges, width) bytes, 16-byte aligned, any content.  Atomic-free, every element written once, bit-reproducible.
+ *
+ * egc_pna_scale_combine_f32: out_i = base_i + sum_k f_k(d_i) * Y_i[k * dim .. (k + 1) * dim], d_i = max(n_i, 1) from rowptr,
+ *   IDENTITY 1   AMPLIFICATION log(d + 1) / avg_log   ATTENUATION avg_log / log(d + 1)   LINEAR d / avg_lin   INVERSE_LINEAR avg_lin / d
+ * each factor formed in double and rounded once to float; acc = base, then acc = acc + f_k * Y_k in list order.  One read of Y
+ * (n_rows rows of stride ld_y >= n_scalers * dim) and base, one write of out (may alias base).  _backward: dY_i[k] = f_k * g_i.
+ *
+ * EGC_ERR_INVALID: width / dim <= 0, an unknown or duplicate op or scaler, an empty list, a missing pointer, a negative count, a
+ * stride smaller than the block; EGC_ERR_WORKSPACE: workspace missing, misaligned or too small; EGC_ERR_UNSUPPORTED: a count >= 2^31. */
+#define EGC_PNA_SUM 0
+#define EGC_PNA_MEAN 1
+#define EGC_PNA_MIN 2
+#define EGC_PNA_MAX 3
+#define EGC_PNA_VAR 4
+#define EGC_PNA_STD 5
+#define EGC_PNA_IDENTITY 0
+#define EGC_PNA_AMPLIFICATION 1
+#define EGC_PNA_ATTENUATION 2
+#define EGC_PNA_LINEAR 3
+#define EGC_PNA_INVERSE_LINEAR 4
+#define EGC_PNA_MAX_SCALERS 5
+size_t egc_pna_aggregate_workspace_bytes(int64_t n_edges, int32_t width, const int32_t* ops, int32_t n_ops);
+int egc_pna_aggregate_f32(const int32_t* rowptr, const int32_t* col, const int32_t* edge_id, int64_t n_rows, int64_t n_edges,
+                          int64_t n_src_rows, const float* P, int32_t ld_p, const float* Q, int32_t ld_q, int32_t width,
+                          const int32_t* ops, int32_t n_ops, float* out, int32_t ld_out, int32_t* arg_min, int32_t* arg_max,
+                          float* mu, float* var, void* workspace, size_t workspace_bytes, egc_stream_t stream);
+size_t egc_pna_aggregate_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32_t width);
+int egc_pna_aggregate_backward_f32(const int32_t* rowptr, const int32_t* edge_id, int64_t n_rows, const int32_t* t_rowptr,
+                                   const int32_t* t_col, const int32_t* t_edge_id, int64_t n_src_rows, int64_t n_edges,
+                                   const float* dagg, int32_t ld_dagg, const int32_t* ops, int32_t n_ops, int32_t width,
+                                   const float* P, int32_t ld_p, const int32_t* arg_min, const int32_t* arg_max, const float* mu,
+                                   const float* var, float* dP, int32_t ld_dp, float* dQ, int32_t ld_dq,
+                                   void* workspace, size_t workspace_bytes, egc_stream_t stream);
+int egc_pna_scale_combine_f32(const int32_t* rowptr, int64_t n_rows, const int32_t* scalers, int32_t n_scalers, double avg_lin,
+                              double avg_log, int32_t dim, const float* Y, int32_t ld_y, const float* base, int32_t ld_base,
+                              float* out, int32_t ld_out, egc_stream_t stream);
+int egc_pna_scale_combine_backward_f32(const int32_t* rowptr, int64_t n_rows, const int32_t* scalers, int32_t n_scalers,
+                                       double avg_lin, double avg_log, int32_t dim, const float* g, int32_t ld_g, float* dY,
+                                       int32_t ld_dy, egc_stream_t stream);
+
 /* GATv2 attention aggregate (egc_gatv2.hip): PyG 2.x GATv2Conv's propagate without an [E, .] array.  H = heads, C = channels
  * per head, width = H * C <= 512 (any H >= 1, C >= 1).  xl (n_src_rows rows) and xr (n_rows rows) are the lin_l / lin_r
  * projections (column blocks of one wider array are fine); att is [H * C].  For an entry j -> i of the CSR by destination and head h
