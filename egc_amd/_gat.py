@@ -19,8 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _C
-from ._args import _check_f32, _ptr
-from ._mpnn import _as_csr, _rows2d
+from ._args import _as_csr, _check_f32, _ptr, _rows2d, _unit_columns, _workspace
 from .graph import CSRGraph, _device_guard, _stream_ptr
 
 
@@ -43,8 +42,7 @@ def _launch_forward(xl, xr, att, g: CSRGraph, heads, channels, slope, loops, out
     if loops and g.n_src_rows != g.n_nodes:
         raise RuntimeError(f"egc_amd: add_self_loops needs a square graph, got [{g.n_nodes}, {g.n_src_rows}]")
     with _device_guard(dev):
-        nbytes = int(lib.egc_gatv2_forward_workspace_bytes(g.n_edges, heads, channels))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws, nbytes = _workspace(lib.egc_gatv2_forward_workspace_bytes(g.n_edges, heads, channels), dev)
         _C.check(lib.egc_gatv2_forward_f32(g.rowptr.data_ptr(), g.col.data_ptr(), g.n_nodes, g.n_edges, g.n_src_rows, xl.data_ptr(),
                                            ld_xl, xr.data_ptr(), ld_xr, att.data_ptr(), heads, channels, float(slope), int(loops),
                                            out.data_ptr(), ld_out, lse.data_ptr(), _ptr(ws), nbytes, _stream_ptr(dev)),
@@ -63,8 +61,7 @@ def _launch_backward(xl, xr, att, g: CSRGraph, heads, channels, slope, loops, ou
     ld_dxr = _rows2d(dxr, "d xr", n, width, dev) if dxr is not None else 0
     t = g.transposed() if dxl is not None else None
     with _device_guard(dev):
-        nbytes = int(lib.egc_gatv2_backward_workspace_bytes(n, g.n_edges, heads, channels))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws, nbytes = _workspace(lib.egc_gatv2_backward_workspace_bytes(n, g.n_edges, heads, channels), dev)
         _C.check(lib.egc_gatv2_backward_f32(
             g.rowptr.data_ptr(), g.col.data_ptr(), _ptr(t.rowptr if t else None), _ptr(t.col if t else None), n, g.n_edges,
             xl.data_ptr(), ld_xl, xr.data_ptr(), ld_xr, att.data_ptr(), heads, channels, float(slope), int(loops), out.data_ptr(),
@@ -86,8 +83,7 @@ def _backward(saved, needs, gout):
     """(d xl, d xr, d att) for one saved forward; d xl and d xr are the halves of one [N, 2 H C] array when both are wanted."""
     xl, xr, att2, g, heads, channels, slope, loops, out, lse, att_shape = saved
     width, n, dev = heads * channels, g.n_nodes, gout.device
-    if gout.stride(1) != 1 and gout.numel() > 0:
-        gout = gout.contiguous()
+    gout = _unit_columns(gout)
     both = torch.empty((n, 2 * width), dtype=torch.float32, device=dev) if needs[0] and needs[1] else None
     dxl = both[:, :width] if both is not None else (torch.empty((n, width), dtype=torch.float32, device=dev) if needs[0] else None)
     dxr = both[:, width:] if both is not None else (torch.empty((n, width), dtype=torch.float32, device=dev) if needs[1] else None)

@@ -18,8 +18,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _C
-from ._args import _check_f32, _ptr
-from .graph import CSRGraph, GraphBatch, _device_guard, _stream_ptr, graph_from_input
+from ._args import _as_csr, _check_f32, _ptr, _rows2d, _unit_columns, _workspace
+from .graph import CSRGraph, _device_guard, _stream_ptr
 
 _OP = {"add": _C.MPNN_ADD, "mean": _C.MPNN_MEAN, "max": _C.MPNN_MAX}
 
@@ -28,15 +28,6 @@ def _op_code(aggr) -> int:
     if aggr not in _OP:
         raise ValueError(f"egc_amd.Mpnn: aggr must be one of {sorted(_OP)}, got {aggr!r}")
     return _OP[aggr]
-
-
-def _rows2d(t, name, n, width, dev):
-    """A float32 [n, width] device tensor with unit column stride (a column block of a wider array is fine)."""
-    _check_f32(t, name)
-    if t.dim() != 2 or tuple(t.shape) != (n, width) or t.device != dev or (t.numel() > 0 and t.stride(1) != 1):
-        raise RuntimeError(f"egc_amd: {name} must be [{n}, {width}] with unit column stride on {dev} "
-                           f"(got {tuple(t.shape)} on {t.device})")
-    return t.stride(0) if n > 1 else max(t.stride(0), width)
 
 
 def _launch_forward(P, Q, g: CSRGraph, op: int, out, arg):
@@ -48,8 +39,7 @@ def _launch_forward(P, Q, g: CSRGraph, op: int, out, arg):
     if g.device != dev:
         raise RuntimeError(f"egc_amd: the graph is on {g.device}, P and Q on {dev}")
     with _device_guard(dev):
-        nbytes = int(lib.egc_mpnn_message_workspace_bytes(g.n_edges, width, op))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws, nbytes = _workspace(lib.egc_mpnn_message_workspace_bytes(g.n_edges, width, op), dev)
         _C.check(lib.egc_mpnn_message_f32(g.rowptr.data_ptr(), g.col.data_ptr(), g.edge_id.data_ptr(), g.n_nodes, g.n_edges,
                                           g.n_src_rows, P.data_ptr(), ld_p, Q.data_ptr(), ld_q, width, op, out.data_ptr(), ld_out,
                                           _ptr(arg), _ptr(ws), nbytes, _stream_ptr(dev)), "egc_mpnn_message_f32")
@@ -64,8 +54,7 @@ def _launch_backward(dm, g: CSRGraph, op: int, arg, dP, dQ):
     ld_dq = _rows2d(dQ, "d Q", g.n_nodes, width, dev) if dQ is not None else 0
     t = g.transposed() if dP is not None else None
     with _device_guard(dev):
-        nbytes = int(lib.egc_mpnn_message_backward_workspace_bytes(g.n_edges, width)) if dP is not None else 0
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws, nbytes = _workspace(lib.egc_mpnn_message_backward_workspace_bytes(g.n_edges, width) if dP is not None else 0, dev)
         _C.check(lib.egc_mpnn_message_backward_f32(
             g.rowptr.data_ptr(), g.edge_id.data_ptr(), g.n_nodes, _ptr(t.rowptr if t else None), _ptr(t.col if t else None),
             _ptr(t.edge_id if t else None), g.n_src_rows, g.n_edges, dm.data_ptr(), ld_dm, _ptr(arg), width, op, _ptr(dP), ld_dp,
@@ -91,8 +80,7 @@ class _MpnnMessage(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dm):
         g, width = ctx.g, dm.size(1)
-        if dm.stride(1) != 1 and dm.numel() > 0:
-            dm = dm.contiguous()
+        dm = _unit_columns(dm)
         dP = torch.empty((g.n_src_rows, width), dtype=torch.float32, device=dm.device) if ctx.needs_input_grad[0] else None
         dQ = torch.empty((g.n_nodes, width), dtype=torch.float32, device=dm.device) if ctx.needs_input_grad[1] else None
         _launch_backward(dm, g, ctx.op, ctx.arg, dP, dQ)
@@ -117,18 +105,12 @@ class _MpnnOperand(torch.autograd.Function):
     @staticmethod
     def backward(ctx, da):
         g, d = ctx.g, ctx.d
-        if da.stride(1) != 1 and da.numel() > 0:
-            da = da.contiguous()
+        da = _unit_columns(da)
         dpq = None
         if ctx.needs_input_grad[0]:
             dpq = torch.empty((g.n_nodes, 2 * d), dtype=torch.float32, device=da.device)
             _launch_backward(da[:, :d], g, ctx.op, ctx.arg, dpq[:, :d], dpq[:, d:])
         return dpq, (da[:, d:] if ctx.needs_input_grad[1] else None), None, None
-
-
-def _as_csr(graph, n: int) -> CSRGraph:
-    g = graph_from_input(graph, n)
-    return g.csr() if isinstance(g, GraphBatch) else g
 
 
 def mpnn_message(P, Q, graph, aggr, out=None, out_col=0):

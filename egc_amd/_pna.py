@@ -23,8 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _C
-from ._args import _check_f32, _ptr
-from ._mpnn import _as_csr, _rows2d
+from ._args import _as_csr, _check_f32, _ptr, _rows2d, _unit_columns, _workspace
 from .graph import CSRGraph, GraphBatch, SparseTensor, _device_guard, _stream_ptr
 
 AGGREGATORS = {"sum": _C.PNA_SUM, "mean": _C.PNA_MEAN, "min": _C.PNA_MIN, "max": _C.PNA_MAX, "var": _C.PNA_VAR, "std": _C.PNA_STD}
@@ -87,8 +86,7 @@ def _launch_aggregate(P, Q, g: CSRGraph, codes, out, arg_min=None, arg_max=None,
         raise RuntimeError(f"egc_amd: the graph is on {g.device}, P and Q on {dev}")
     ops = _int_array(codes)
     with _device_guard(dev):
-        nbytes = int(lib.egc_pna_aggregate_workspace_bytes(g.n_edges, width, C.addressof(ops), a))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws, nbytes = _workspace(lib.egc_pna_aggregate_workspace_bytes(g.n_edges, width, C.addressof(ops), a), dev)
         _C.check(lib.egc_pna_aggregate_f32(g.rowptr.data_ptr(), g.col.data_ptr(), g.edge_id.data_ptr(), g.n_nodes, g.n_edges,
                                            g.n_src_rows, P.data_ptr(), ld_p, Q.data_ptr(), ld_q, width, C.addressof(ops), a,
                                            out.data_ptr(), ld_out, _ptr(arg_min), _ptr(arg_max), _ptr(mu), _ptr(var), _ptr(ws), nbytes,
@@ -107,8 +105,8 @@ def _launch_aggregate_backward(dagg, g: CSRGraph, codes, P, arg_min, arg_max, mu
     t = g.transposed() if dP is not None else None
     ops = _int_array(codes)
     with _device_guard(dev):
-        nbytes = int(lib.egc_pna_aggregate_backward_workspace_bytes(g.n_nodes, g.n_edges, width)) if dP is not None else 0
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws, nbytes = _workspace(lib.egc_pna_aggregate_backward_workspace_bytes(g.n_nodes, g.n_edges, width) if dP is not None else 0,
+                                dev)
         _C.check(lib.egc_pna_aggregate_backward_f32(
             g.rowptr.data_ptr(), g.edge_id.data_ptr(), g.n_nodes, _ptr(t.rowptr if t else None), _ptr(t.col if t else None),
             _ptr(t.edge_id if t else None), g.n_src_rows, g.n_edges, dagg.data_ptr(), ld_g, C.addressof(ops), a, width, _ptr(P), ld_p,
@@ -168,8 +166,7 @@ class _PnaAggregate(torch.autograd.Function):
     def backward(ctx, dagg):
         g, width, codes = ctx.g, ctx.width, ctx.codes
         P, = ctx.saved_tensors
-        if dagg.stride(1) != 1 and dagg.numel() > 0:
-            dagg = dagg.contiguous()
+        dagg = _unit_columns(dagg)
         dP = torch.empty((g.n_src_rows, width), dtype=torch.float32, device=dagg.device) if ctx.needs_input_grad[0] else None
         dQ = torch.empty((g.n_nodes, width), dtype=torch.float32, device=dagg.device) if ctx.needs_input_grad[1] else None
         _launch_aggregate_backward(dagg, g, codes, P, *ctx.saved, dP, dQ)
@@ -194,8 +191,7 @@ class _PnaAggregatePQ(torch.autograd.Function):
     def backward(ctx, dagg):
         g, width, codes = ctx.g, ctx.width, ctx.codes
         pq, = ctx.saved_tensors
-        if dagg.stride(1) != 1 and dagg.numel() > 0:
-            dagg = dagg.contiguous()
+        dagg = _unit_columns(dagg)
         dpq = torch.empty((g.n_nodes, 2 * width), dtype=torch.float32, device=dagg.device)
         _launch_aggregate_backward(dagg, g, codes, pq[:, :width], *ctx.saved, dpq[:, :width], dpq[:, width:])
         return dpq, None, None
@@ -215,8 +211,7 @@ class _PnaCombine(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         g, scodes = ctx.g, ctx.scodes
-        if gout.stride(1) != 1 and gout.numel() > 0:
-            gout = gout.contiguous()
+        gout = _unit_columns(gout)
         dY = None
         if ctx.needs_input_grad[0]:
             dY = torch.empty((g.n_nodes, len(scodes) * gout.size(1)), dtype=torch.float32, device=gout.device)

@@ -9,7 +9,7 @@ from typing import NamedTuple
 import torch
 
 from . import _C
-from ._args import _check_f32
+from ._args import _check_f32, _ptr, _workspace
 from .graph import CSRGraph, _device_guard, _stream_ptr
 
 
@@ -73,11 +73,10 @@ def typed_mean(rels, n_rows: int, width: int, out: torch.Tensor, accumulate: boo
         d.out_col, d.post_mean = int(r.out_col), int(bool(r.post_mean))
     ld_out = out.stride(0) if n_rows > 1 else max(out.size(1), 1)
     with _device_guard(dev):
-        nbytes = int(lib.egc_typed_mean_workspace_bytes(table, len(rels), width))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        ws, nbytes = _workspace(lib.egc_typed_mean_workspace_bytes(table, len(rels), width), dev)
         _C.check(lib.egc_typed_mean_f32(table, len(rels), n_rows, width, int(bool(accumulate)),
                                         out.data_ptr() if out.numel() else None, ld_out,
-                                        ws.data_ptr() if ws is not None else None, nbytes, _stream_ptr(dev)),
+                                        _ptr(ws), nbytes, _stream_ptr(dev)),
                  "egc_typed_mean_f32")
     return out
 

@@ -118,6 +118,30 @@ __device__ inline void tm_store(float* __restrict__ p, int c, int width, f4 v) {
     if (c + j < width) p[j] = v[j];
 }
 
+// the same four columns of an int32 row (edge ids, CSR positions); a column that does not exist reads as -1
+typedef int i4 __attribute__((ext_vector_type(4)));
+
+template <bool VEC>
+__device__ inline i4 tm_load_i(const int32_t* __restrict__ p, int c, int width) {
+  if (VEC) return *reinterpret_cast<const i4*>(p);
+  i4 v = i4{-1, -1, -1, -1};
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (c + j < width) v[j] = p[j];
+  return v;
+}
+
+template <bool VEC>
+__device__ inline void tm_store_i(int32_t* __restrict__ p, int c, int width, i4 v) {
+  if (VEC) {
+    *reinterpret_cast<i4*>(p) = v;
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (c + j < width) p[j] = v[j];
+}
+
 static inline bool tm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // egc_backward.hip: CSR positions of the first entries attaining each row's max / min (training forward)

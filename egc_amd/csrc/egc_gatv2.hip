@@ -13,13 +13,9 @@
 //   source pass (transposed CSR)         d xl_j = sum_i (alpha_ij g_i + d z_ij)
 // Every output element is written exactly once: no zero fill, no atomics.
 //
-// Mapping (egc_mpnn.hip's, with the group padded): a lane owns four adjacent columns (16-byte accesses; 4-byte ones of the same
-// columns when a width, stride or pointer is not a multiple of 16 bytes).  A row's group is G = the power of two >=
-// ceil(H C / 4) lanes, at most 64, so it lies inside one wavefront; for H C > 256 the group is a whole wavefront and a lane owns
-// two such quads (S = 2 slots, 256 columns apart).  "Virtual lane" v = lane + G * slot owns columns 4 v .. 4 v + 3.  Groups are
-// laid back to back over the grid.  AHEAD entries' indices, then their rows, are requested before the first consumer; a partial
-// batch issues all its loads too (index clamped, surplus not taken).  Column indices are clamped to the gathered array's rows,
-// offsets to the entry count: malformed input gives garbage, never an access outside.
+// Mapping: egc_row_chunks.h's, with the group padded.  A row's group is G = the power of two >= ceil(H C / 4) lanes, at most 64,
+// so it lies inside one wavefront; for H C > 256 the group is a whole wavefront and a lane owns two quads of columns (S = 2
+// slots, 256 columns apart).  "Virtual lane" v = lane + G * slot owns columns 4 v .. 4 v + 3.
 //
 // Order rule of a per-head sum over the head's C columns (the score, d alpha, D).  It depends on H and C only, never on where in
 // the grid the row lands.
@@ -29,8 +25,8 @@
 //   the segment: for d = 1, 2, 4, ... < ceil(C / 4) + 1, a(v) = a(v) + a(v - d) where v - d is still in the segment (all lanes
 //   read before any writes).  The head's sum is a of the segment's last lane.
 //   C < 4: a head lies within virtual lanes v - 1 .. v + 1; every column adds the head's columns in ascending column order.
-// Order rule of a row: its entries are cut into consecutive chunks of EGC_TYPED_MEAN_CHUNK counted from the row's first entry
-// (skipped entries keep their place).  Inside a chunk, batches of AHEAD entries (8 forward, 4 backward) from the chunk's start.
+// Order rule of a row: egc_row_chunks.h's chunks (skipped entries keep their place).  Inside a chunk, batches of AHEAD entries
+// (8 forward, 4 backward) from the chunk's start.
 // Forward, per batch: bm = max(m, the live scores in entry order); l = l * r + sum in entry order of exp(s_k - bm), acc likewise
 // with exp(s_k - bm) * xl_k, r = exp(m - bm) (1 when m == bm); m = bm.  The row is chunk 0's state with the states of chunks
 // 1, 2, ... merged in ascending order (M = max(m1, m2); l = l1 exp(m1 - M) + l2 exp(m2 - M)), then the self entry as a batch of
@@ -38,11 +34,10 @@
 // with those of chunks 1, 2, ... added in ascending order, the self entry last.  d att: a lane's sum over its row (entry order,
 // chunk by chunk), the workgroup's groups added in ascending order, the workgroups' partials (row workgroups, then chunk
 // workgroups) added in ascending order in blocks of 64, and those block sums again, until one is left.  -ffp-contract=off.
-#include "egc_common.h"
+#include "egc_row_chunks.h"
 
 namespace egc {
 
-constexpr int GAT_CHUNK = EGC_TYPED_MEAN_CHUNK;
 constexpr int GAT_AHEAD = 8;
 constexpr int GAT_AHEAD_BWD = 4;
 constexpr int GAT_SUM_BLOCK = 64;
@@ -227,30 +222,6 @@ __device__ inline void gat_load_heads(f4 (&v)[S], const float* __restrict__ a, i
 
 __device__ inline f4 gat_exp(f4 x) { return f4{expf(x[0]), expf(x[1]), expf(x[2]), expf(x[3])}; }
 
-__device__ inline void gat_row_range(const GatWalk& W, int64_t row, int64_t& p0, int64_t& p1) {
-  p0 = min(max((int64_t)W.rowptr[row], (int64_t)0), W.n_edges);
-  p1 = min(max((int64_t)W.rowptr[row + 1], p0), W.n_edges);
-}
-
-// the chunk k >= 1 of some row that starts in [slot * CHUNK, (slot + 1) * CHUNK): its row and range (false: there is none)
-__device__ inline bool gat_slot_chunk(const GatWalk& W, int64_t slot, int64_t& row, int64_t& s0, int64_t& s1) {
-  const int64_t at = slot * GAT_CHUNK;
-  int64_t lo = 0, hi = W.n_rows;   // the last row that starts at or before `at`
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)W.rowptr[mid] <= at) lo = mid;
-    else hi = mid;
-  }
-  int64_t p0, p1;
-  gat_row_range(W, lo, p0, p1);
-  if (p1 - p0 <= GAT_CHUNK || at <= p0) return false;   // a short row; or chunk 0, which the row kernel takes
-  s0 = p0 + (at - p0 + GAT_CHUNK - 1) / GAT_CHUNK * GAT_CHUNK;
-  if (s0 >= p1) return false;
-  s1 = min(s0 + GAT_CHUNK, p1);
-  row = lo;
-  return true;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- forward
 
 template <int S>
@@ -316,9 +287,8 @@ __device__ inline void gat_fwd_batch(GatState<S>& st, const GatWalk& W, const Ga
   bool live[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
-    const int raw = W.col[q];
-    j[k] = min(max(raw, 0), last_in);
+    const int raw = W.col[batch_entry<FULL>(p, k, p1)];
+    j[k] = clamp_index(raw, last_in);
     live[k] = (FULL || p + k < p1) && !(W.self_loops && raw == (int)row);
   }
   f4 v[N][S], e[N][S];
@@ -347,12 +317,12 @@ __device__ inline void gat_fwd_entries(GatState<S>& st, const GatWalk& W, const 
 // workspace: per slot and virtual lane three f4: m, l, acc
 template <int S, bool VEC, bool SMALL, class Score>
 __global__ void __launch_bounds__(256) gat_fwd_chunks_kernel(const GatWalk W, const Score sc, int64_t slots, float* __restrict__ ws) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t g = t / W.G;
+  int64_t g, row, s0, s1;
+  int c;
+  group_lane(W.G, g, c);
   if (g >= slots) return;
-  const GatLane<S> L = gat_lane<S>(W, (int)(t - g * W.G));
-  int64_t row, s0, s1;
-  if (!gat_slot_chunk(W, g, row, s0, s1)) return;
+  const GatLane<S> L = gat_lane<S>(W, c / 4);
+  if (!slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, s0, s1)) return;
   f4 xr[S], att[S];
   gat_load_row<S, VEC>(xr, W.xr, row, W.ld_xr, L, W.width);
   gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
@@ -368,29 +338,28 @@ __global__ void __launch_bounds__(256) gat_fwd_chunks_kernel(const GatWalk W, co
 template <int S, bool VEC, bool SMALL, class Score>
 __global__ void __launch_bounds__(256) gat_fwd_rows_kernel(const GatWalk W, const Score sc, float* __restrict__ out, int ld_out,
                                                            float* __restrict__ lse, int64_t slots, const float* __restrict__ ws) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = t / W.G;
+  int64_t row, p0, p1;
+  int c;
+  group_lane(W.G, row, c);
   if (row >= W.n_rows) return;
-  const GatLane<S> L = gat_lane<S>(W, (int)(t - row * W.G));
-  int64_t p0, p1;
-  gat_row_range(W, row, p0, p1);
+  const GatLane<S> L = gat_lane<S>(W, c / 4);
+  row_range(W.rowptr, W.n_edges, row, p0, p1);
   f4 xr[S], att[S];
   gat_load_row<S, VEC>(xr, W.xr, row, W.ld_xr, L, W.width);
   gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
   GatState<S> st;
-  gat_fwd_entries<S, VEC, SMALL, Score>(st, W, L, sc, xr, att, p0, min(p0 + GAT_CHUNK, p1), row);
-  if (p1 - p0 > GAT_CHUNK) {
-    const int64_t first = (p0 + GAT_CHUNK) / GAT_CHUNK, n_part = (p1 - p0 - 1) / GAT_CHUNK;
+  gat_fwd_entries<S, VEC, SMALL, Score>(st, W, L, sc, xr, att, p0, min(p0 + ROW_CHUNK, p1), row);
+  int64_t first, n_part;
+  row_partials(p0, p1, first, n_part);
 #pragma unroll 1
-    for (int64_t k = 0; k < n_part; ++k) {
-      f4 m2[S], l2[S], a2[S];
+  for (int64_t k = 0; k < n_part; ++k) {
+    f4 m2[S], l2[S], a2[S];
 #pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const f4* o = reinterpret_cast<const f4*>(ws) + ((first + k) * W.V + L.v[s]) * 3;
-        m2[s] = o[0], l2[s] = o[1], a2[s] = o[2];
-      }
-      gat_state_merge<S>(st, m2, l2, a2);
+    for (int s = 0; s < S; ++s) {
+      const f4* o = reinterpret_cast<const f4*>(ws) + ((first + k) * W.V + L.v[s]) * 3;
+      m2[s] = o[0], l2[s] = o[1], a2[s] = o[2];
     }
+    gat_state_merge<S>(st, m2, l2, a2);
   }
   if (W.self_loops) {
     f4 v[1][S], e[1][S], tt[S];
@@ -426,9 +395,8 @@ __device__ inline void gat_dst_batch(f4 (&dxr)[S], f4 (&datt)[S], const GatWalk&
   bool live[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
-    const int raw = self ? (int)row : W.col[q];
-    j[k] = min(max(raw, 0), last_in);
+    const int raw = self ? (int)row : W.col[batch_entry<FULL>(p, k, p1)];
+    j[k] = clamp_index(raw, last_in);
     live[k] = self || ((FULL || p + k < p1) && !(W.self_loops && raw == (int)row));
   }
   f4 v[N][S];
@@ -475,17 +443,18 @@ template <int S, bool VEC, bool SMALL, class Score, bool CHUNKS>
 __global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatWalk W, const Score sc, float* __restrict__ dxr_out, int ld_dxr,
                                                           float* __restrict__ D_out, int64_t slots, float* __restrict__ ws_xr,
                                                           float* __restrict__ part) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t g = t / W.G;
-  const GatLane<S> L = gat_lane<S>(W, (int)(t - g * W.G));
+  int64_t g;
+  int c;
+  group_lane(W.G, g, c);
+  const GatLane<S> L = gat_lane<S>(W, c / 4);
   int64_t row = g, p0 = 0, p1 = 0;
   bool active;
   if (CHUNKS) {
-    active = g < slots && gat_slot_chunk(W, g, row, p0, p1);
+    active = g < slots && slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, p0, p1);
   } else {
     active = g < W.n_rows;
     if (active) {
-      gat_row_range(W, row, p0, p1);
+      row_range(W.rowptr, W.n_edges, row, p0, p1);
     }
   }
   f4 dxr[S], datt[S];
@@ -501,7 +470,7 @@ __global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatWalk W, const
 #pragma unroll
     for (int s = 0; s < S; ++s) u[s] = gr[s] * o[s];
     gat_head_sums<S, SMALL>(W, L, u, D);
-    const int64_t e1 = CHUNKS ? p1 : min(p0 + GAT_CHUNK, p1);
+    const int64_t e1 = CHUNKS ? p1 : min(p0 + ROW_CHUNK, p1);
     int64_t p = p0;
 #pragma unroll 1
     for (; p + GAT_AHEAD_BWD <= e1; p += GAT_AHEAD_BWD)
@@ -511,13 +480,12 @@ __global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatWalk W, const
 #pragma unroll
       for (int s = 0; s < S; ++s) *reinterpret_cast<f4*>(ws_xr + (g * W.V + L.v[s]) * 4) = dxr[s];
     } else {
-      if (p1 - p0 > GAT_CHUNK) {
-        const int64_t first = (p0 + GAT_CHUNK) / GAT_CHUNK, n_part = (p1 - p0 - 1) / GAT_CHUNK;
+      int64_t first, n_part;
+      row_partials(p0, p1, first, n_part);
 #pragma unroll 1
-        for (int64_t k = 0; k < n_part; ++k)
+      for (int64_t k = 0; k < n_part; ++k)
 #pragma unroll
-          for (int s = 0; s < S; ++s) dxr[s] = dxr[s] + *reinterpret_cast<const f4*>(ws_xr + ((first + k) * W.V + L.v[s]) * 4);
-      }
+        for (int s = 0; s < S; ++s) dxr[s] = dxr[s] + *reinterpret_cast<const f4*>(ws_xr + ((first + k) * W.V + L.v[s]) * 4);
       if (W.self_loops) gat_dst_batch<S, VEC, SMALL, Score, 1, true>(dxr, datt, W, L, sc, xr, att, gr, lse, D, 0, 0, row, true);
 #pragma unroll
       for (int s = 0; s < S; ++s) {
@@ -540,9 +508,8 @@ __device__ inline void gat_src_batch(f4 (&acc)[S], const GatWalk& W, const GatLa
   bool live[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
-    const int raw = self ? (int)row : W.col[q];
-    i_[k] = min(max(raw, 0), last_in);
+    const int raw = self ? (int)row : W.col[batch_entry<FULL>(p, k, p1)];
+    i_[k] = clamp_index(raw, last_in);
     live[k] = self || ((FULL || p + k < p1) && !(W.self_loops && raw == (int)row));
   }
   f4 xr[N][S], gr[N][S], lse[N][S], D[N][S];
@@ -577,22 +544,23 @@ __device__ inline void gat_src_batch(f4 (&acc)[S], const GatWalk& W, const GatLa
 template <int S, bool VEC, bool SMALL, class Score, bool CHUNKS>
 __global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatWalk W, const Score sc, float* __restrict__ dxl, int ld_dxl,
                                                           int64_t slots, float* __restrict__ ws) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t g = t / W.G;
-  const GatLane<S> L = gat_lane<S>(W, (int)(t - g * W.G));
+  int64_t g;
+  int c;
+  group_lane(W.G, g, c);
+  const GatLane<S> L = gat_lane<S>(W, c / 4);
   int64_t row = g, p0 = 0, p1 = 0;
   if (CHUNKS) {
-    if (g >= slots || !gat_slot_chunk(W, g, row, p0, p1)) return;
+    if (g >= slots || !slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, p0, p1)) return;
   } else {
     if (g >= W.n_rows) return;
-    gat_row_range(W, row, p0, p1);
+    row_range(W.rowptr, W.n_edges, row, p0, p1);
   }
   f4 xl[S], att[S], acc[S];
   gat_load_row<S, VEC>(xl, W.xl, row, W.ld_xl, L, W.width);
   gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
 #pragma unroll
   for (int s = 0; s < S; ++s) acc[s] = f4{0.f, 0.f, 0.f, 0.f};
-  const int64_t e1 = CHUNKS ? p1 : min(p0 + GAT_CHUNK, p1);
+  const int64_t e1 = CHUNKS ? p1 : min(p0 + ROW_CHUNK, p1);
   int64_t p = p0;
 #pragma unroll 1
   for (; p + GAT_AHEAD_BWD <= e1; p += GAT_AHEAD_BWD)
@@ -603,13 +571,12 @@ __global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatWalk W, const
     for (int s = 0; s < S; ++s) *reinterpret_cast<f4*>(ws + (g * W.V + L.v[s]) * 4) = acc[s];
     return;
   }
-  if (p1 - p0 > GAT_CHUNK) {
-    const int64_t first = (p0 + GAT_CHUNK) / GAT_CHUNK, n_part = (p1 - p0 - 1) / GAT_CHUNK;
+  int64_t first, n_part;
+  row_partials(p0, p1, first, n_part);
 #pragma unroll 1
-    for (int64_t k = 0; k < n_part; ++k)
+  for (int64_t k = 0; k < n_part; ++k)
 #pragma unroll
-      for (int s = 0; s < S; ++s) acc[s] = acc[s] + *reinterpret_cast<const f4*>(ws + ((first + k) * W.V + L.v[s]) * 4);
-  }
+    for (int s = 0; s < S; ++s) acc[s] = acc[s] + *reinterpret_cast<const f4*>(ws + ((first + k) * W.V + L.v[s]) * 4);
   if (W.self_loops) gat_src_batch<S, VEC, SMALL, Score, 1, true>(acc, W, L, sc, xl, att, 0, 0, row, true);
 #pragma unroll
   for (int s = 0; s < S; ++s) gat_store<VEC>(dxl + row * ld_dxl + L.c[s], L.c[s], W.width, acc[s]);
@@ -642,7 +609,6 @@ static inline GatGeom gat_geom(int32_t width) {
   return q;
 }
 
-static inline int64_t gat_slots(int64_t n_edges) { return n_edges > GAT_CHUNK ? ceil_div(n_edges, GAT_CHUNK) : 0; }
 static inline int64_t gat_blocks(int64_t groups, int32_t G) { return ceil_div(groups, 256 / G); }
 static inline size_t gat_align(size_t floats) { return (floats + 3) & ~(size_t)3; }
 
@@ -658,7 +624,7 @@ static inline GatBwdWs gat_bwd_ws(int64_t n_rows, int64_t n_edges, int32_t H, in
   const int32_t width = H * C;
   const GatGeom q = gat_geom(width);
   GatBwdWs w;
-  w.slots = gat_slots(n_edges);
+  w.slots = chunk_slots(n_edges);
   w.row_blocks = gat_blocks(n_rows, q.G), w.chunk_blocks = gat_blocks(w.slots, q.G);
   const int64_t parts = w.row_blocks + w.chunk_blocks;
   size_t at = 0;
@@ -694,7 +660,7 @@ using namespace egc;
 
 size_t egc_gatv2_forward_workspace_bytes(int64_t n_edges, int32_t heads, int32_t channels) {
   if (n_edges <= 0 || !gat_shape_ok(heads, channels)) return 0;
-  return (size_t)gat_slots(n_edges) * (size_t)gat_geom(heads * channels).V * 3 * 16;
+  return (size_t)chunk_slots(n_edges) * (size_t)gat_geom(heads * channels).V * 3 * 16;
 }
 
 size_t egc_gatv2_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32_t heads, int32_t channels) {
@@ -715,7 +681,7 @@ int egc_gatv2_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_r
   if (rowptr == nullptr || xr == nullptr || att == nullptr || out == nullptr || lse == nullptr) return EGC_ERR_INVALID;
   if ((n_edges > 0 || self_loops) && xl == nullptr) return EGC_ERR_INVALID;
   if (n_edges > 0 && (col == nullptr || n_src_rows == 0)) return EGC_ERR_INVALID;
-  if (n_rows >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31) || n_src_rows >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  if (!counts_fit_int32(n_rows, n_edges, n_src_rows)) return EGC_ERR_UNSUPPORTED;
   GatWalk W = {};
   W.rowptr = rowptr, W.col = col, W.xl = xl, W.xr = xr, W.att = att;
   W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_src_rows, W.ld_xl = ld_xl, W.ld_xr = ld_xr;
@@ -723,24 +689,22 @@ int egc_gatv2_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_r
   const GatV2Score sc = {negative_slope};
   const int S = gat_geom(width).S;
   const bool small = channels < 4;
-  const bool vec = (width & 3) == 0 && (ld_xl & 3) == 0 && (ld_xr & 3) == 0 && (ld_out & 3) == 0 && tm_aligned16(xl) &&
-                   tm_aligned16(xr) && tm_aligned16(out);
-  const int64_t slots = gat_slots(n_edges);
+  const bool vec = all_mult4(width, ld_xl, ld_xr, ld_out) && all_aligned16(xl, xr, out);
+  const int64_t slots = chunk_slots(n_edges);
   float* ws = static_cast<float*>(workspace);
   if (slots > 0) {
-    if (ws == nullptr || !tm_aligned16(ws) || workspace_bytes < egc_gatv2_forward_workspace_bytes(n_edges, heads, channels))
-      return EGC_ERR_WORKSPACE;
-    const int64_t blocks = gat_blocks(slots, W.G);
-    if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
-#define GAT_FWD_CHUNKS(S_, V_, M_) gat_fwd_chunks_kernel<S_, V_, M_, GatV2Score><<<(unsigned)blocks, 256, 0, stream>>>(W, sc, slots, ws)
+    if (!workspace_ok(ws, workspace_bytes, egc_gatv2_forward_workspace_bytes(n_edges, heads, channels))) return EGC_ERR_WORKSPACE;
+    unsigned blocks;
+    if (grid_blocks(slots, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
+#define GAT_FWD_CHUNKS(S_, V_, M_) gat_fwd_chunks_kernel<S_, V_, M_, GatV2Score><<<blocks, 256, 0, stream>>>(W, sc, slots, ws)
     GAT_DISPATCH(GAT_FWD_CHUNKS);
 #undef GAT_FWD_CHUNKS
     EGC_LAUNCH_CHECK("gat_fwd_chunks_kernel");
   }
-  const int64_t blocks = gat_blocks(n_rows, W.G);
-  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  unsigned blocks;
+  if (grid_blocks(n_rows, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
 #define GAT_FWD_ROWS(S_, V_, M_) \
-  gat_fwd_rows_kernel<S_, V_, M_, GatV2Score><<<(unsigned)blocks, 256, 0, stream>>>(W, sc, out, ld_out, lse, slots, ws)
+  gat_fwd_rows_kernel<S_, V_, M_, GatV2Score><<<blocks, 256, 0, stream>>>(W, sc, out, ld_out, lse, slots, ws)
   GAT_DISPATCH(GAT_FWD_ROWS);
 #undef GAT_FWD_ROWS
   EGC_LAUNCH_CHECK("gat_fwd_rows_kernel");
@@ -763,10 +727,10 @@ int egc_gatv2_backward_f32(const int32_t* rowptr, const int32_t* col, const int3
     return EGC_ERR_INVALID;
   if (n_edges > 0 && col == nullptr) return EGC_ERR_INVALID;
   if (dxl != nullptr && (t_rowptr == nullptr || (n_edges > 0 && t_col == nullptr))) return EGC_ERR_INVALID;
-  if (n_rows >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  if (!counts_fit_int32(n_rows, n_edges)) return EGC_ERR_UNSUPPORTED;
   const GatBwdWs L = gat_bwd_ws(n_rows, n_edges, heads, channels);
   float* ws = static_cast<float*>(workspace);
-  if (ws == nullptr || !tm_aligned16(ws) || workspace_bytes < L.total * sizeof(float)) return EGC_ERR_WORKSPACE;
+  if (!workspace_ok(ws, workspace_bytes, L.total * sizeof(float))) return EGC_ERR_WORKSPACE;
   GatWalk W = {};
   W.rowptr = rowptr, W.col = col, W.xl = xl, W.xr = xr, W.att = att, W.g = g, W.out = out, W.lse = lse, W.D = ws + L.D;
   W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_rows;
@@ -775,10 +739,8 @@ int egc_gatv2_backward_f32(const int32_t* rowptr, const int32_t* col, const int3
   const GatV2Score sc = {negative_slope};
   const int S = gat_geom(width).S;
   const bool small = channels < 4;
-  const bool vec = (width & 3) == 0 && (ld_xl & 3) == 0 && (ld_xr & 3) == 0 && (ld_out & 3) == 0 && (ld_g & 3) == 0 &&
-                   (ld_dxl & 3) == 0 && (ld_dxr & 3) == 0 && tm_aligned16(xl) && tm_aligned16(xr) && tm_aligned16(out) &&
-                   tm_aligned16(g) && tm_aligned16(dxl) && tm_aligned16(dxr);
-  if (L.row_blocks >= ((int64_t)1 << 31) || L.chunk_blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  const bool vec = all_mult4(width, ld_xl, ld_xr, ld_out, ld_g, ld_dxl, ld_dxr) && all_aligned16(xl, xr, out, g, dxl, dxr);
+  if (!counts_fit_int32(L.row_blocks, L.chunk_blocks)) return EGC_ERR_UNSUPPORTED;
   float* part = datt != nullptr ? ws + L.part_att : nullptr;
   // destination pass: chunks (only when something they produce is wanted), then rows (always: the source pass reads D)
   if (L.slots > 0 && (dxr != nullptr || datt != nullptr)) {

@@ -12,28 +12,16 @@
 // names that edge and 0 elsewhere (max: the transposed entry q is forward CSR position t_edge_id[q], edge edge_id[that]).
 // Every output element is written exactly once: no zero fill, no atomics, nothing read back.
 //
-// Order rule = egc_typed_mean.hip's: a row's entries are cut into consecutive chunks of EGC_TYPED_MEAN_CHUNK counted from the
-// row's first entry; a chunk's sum is ((0 + v0) + v1) + ... in entry order, the row's sum is chunk 0's with the sums of chunks
-// 1, 2, ... added in ascending order; then the division (mean), then the self term -- each one IEEE operation
-// (-ffp-contract=off).  The max is exact in any order; its argument follows the same walk with a strict `>`, so the first
-// entry wins a tie inside a chunk and the first chunk wins between chunks (a NaN is never selected).  Two launches: the CHUNK
-// kernel reduces chunks 1.. of the rows longer than one chunk into the workspace (one group of lanes per chunk; the group of
-// slot b looks at CSR position b * CHUNK, finds its row by bisection and owns the one chunk k >= 1 of that row that starts in
-// [b * CHUNK, (b + 1) * CHUNK)), the ROW kernel reduces every row's chunk 0, folds the row's partials in, finishes and stores.
-//
-// Mapping (egc_typed_mean.hip's): a lane owns four adjacent columns (16-byte accesses; 4-byte ones of the same columns when a
-// width, stride or pointer is not a multiple of 16 bytes), ceil(width / 4) lanes form a group, one group per row, groups laid back
-// to back over the grid.  MP_AHEAD entries' indices, then their rows, are requested before the first operation that consumes
-// them; a partial batch issues all its loads too (index clamped, surplus not taken).  Column indices are clamped to the
-// input's rows, offsets and edge positions to the entry count: malformed input gives garbage, never an access outside.
-#include "egc_common.h"
+// Order rule and mapping: egc_row_chunks.h.  A chunk's sum is ((0 + v0) + v1) + ... in entry order, the row's sum is chunk 0's
+// with the sums of chunks 1, 2, ... added in ascending order; then the division (mean), then the self term -- each one IEEE
+// operation (-ffp-contract=off).  The max is exact in any order; its argument follows the same walk with a strict `>`, so the
+// first entry wins a tie inside a chunk and the first chunk wins between chunks (a NaN is never selected).  A batch is MP_AHEAD
+// entries; edge positions are clamped to the entry count like row offsets.
+#include "egc_row_chunks.h"
 
 namespace egc {
 
-constexpr int MP_CHUNK = EGC_TYPED_MEAN_CHUNK;
 constexpr int MP_AHEAD = 8;
-
-typedef int i4 __attribute__((ext_vector_type(4)));
 
 // what an entry contributes: the row it names; that row over the named row's forward degree; that row where arg names the edge
 enum { MP_PLAIN = 0, MP_DIV_DEG = 1, MP_MATCH = 2 };
@@ -50,27 +38,6 @@ struct MpWalk {
   int32_t ld_in, width, lanes;
 };
 
-template <bool VEC>
-__device__ inline i4 mp_load_i(const int32_t* __restrict__ p, int c, int width) {
-  if (VEC) return *reinterpret_cast<const i4*>(p);
-  i4 v = i4{-1, -1, -1, -1};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (c + j < width) v[j] = p[j];
-  return v;
-}
-
-template <bool VEC>
-__device__ inline void mp_store_i(int32_t* __restrict__ p, int c, int width, i4 v) {
-  if (VEC) {
-    *reinterpret_cast<i4*>(p) = v;
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (c + j < width) p[j] = v[j];
-}
-
 // MP_AHEAD consecutive entries from p on (FULL: all of them exist; else those before p1, the others load entry p1 - 1 again
 // and are not taken) folded into acc (and pos: the entry of the running max) in entry order
 template <bool VEC, bool MAX, int KIND, bool FULL>
@@ -78,11 +45,13 @@ __device__ inline void mp_take_batch(f4& acc, i4& pos, const MpWalk& W, int64_t 
   constexpr int N = FULL ? MP_AHEAD : MP_AHEAD - 1;
   const int last_in = (int)W.n_in_rows - 1, last_e = (int)W.n_edges - 1;   // (both < 2^31: the entries are int32)
   int j[N], e[N];
+  batch_rows<N, FULL>(j, W.col, p, p1, last_in);
+  if (KIND == MP_MATCH) {
 #pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
-    j[k] = min(max(W.col[q], 0), last_in);
-    if (KIND == MP_MATCH) e[k] = W.eid != nullptr ? min(max(W.eid[q], 0), last_e) : (int)q;
+    for (int k = 0; k < N; ++k) {
+      const int64_t q = batch_entry<FULL>(p, k, p1);
+      e[k] = W.eid != nullptr ? clamp_index(W.eid[q], last_e) : (int)q;
+    }
   }
   if (KIND == MP_MATCH && W.f_eid != nullptr) {
 #pragma unroll
@@ -99,7 +68,7 @@ __device__ inline void mp_take_batch(f4& acc, i4& pos, const MpWalk& W, int64_t 
   if (KIND == MP_MATCH) {
     i4 a[N];
 #pragma unroll
-    for (int k = 0; k < N; ++k) a[k] = mp_load_i<VEC>(W.arg + (int64_t)j[k] * W.width + c, c, W.width);
+    for (int k = 0; k < N; ++k) a[k] = tm_load_i<VEC>(W.arg + (int64_t)j[k] * W.width + c, c, W.width);
 #pragma unroll
     for (int k = 0; k < N; ++k)
 #pragma unroll
@@ -137,33 +106,16 @@ __device__ inline void mp_reduce_entries(f4& acc, i4& pos, const MpWalk& W, int6
   if (p < p1) mp_take_batch<VEC, MAX, KIND, false>(acc, pos, W, p, p1, c);
 }
 
-__device__ inline void mp_row_range(const MpWalk& W, int64_t row, int64_t& p0, int64_t& p1) {
-  p0 = min(max((int64_t)W.rowptr[row], (int64_t)0), W.n_edges);
-  p1 = min(max((int64_t)W.rowptr[row + 1], p0), W.n_edges);
-}
-
 // workspace: [slots][lanes] f4 partial values, then (MAX) [slots][lanes] i4 CSR positions of the partial maxima
 template <bool VEC, bool MAX, int KIND>
 __global__ void __launch_bounds__(256) mpnn_chunks_kernel(const MpWalk W, int64_t slots, float* __restrict__ ws) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t g = t / W.lanes;
-  if (g >= slots) return;
-  const int c = (int)(t - g * W.lanes) * 4;
-  const int64_t at = g * MP_CHUNK;
-  int64_t lo = 0, hi = W.n_rows;   // the last row that starts at or before `at`
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)W.rowptr[mid] <= at) lo = mid;
-    else hi = mid;
-  }
-  int64_t p0, p1;
-  mp_row_range(W, lo, p0, p1);
-  if (p1 - p0 <= MP_CHUNK || at <= p0) return;   // a short row; or chunk 0, which the row kernel reduces
-  const int64_t s = p0 + (at - p0 + MP_CHUNK - 1) / MP_CHUNK * MP_CHUNK;   // the row's chunk that starts in this window
-  if (s >= p1) return;
+  int64_t g, row, s0, s1;
+  int c;
+  group_lane(W.lanes, g, c);
+  if (g >= slots || !slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, s0, s1)) return;
   f4 acc;
   i4 pos;
-  mp_reduce_entries<VEC, MAX, KIND>(acc, pos, W, s, min(s + MP_CHUNK, p1), c);
+  mp_reduce_entries<VEC, MAX, KIND>(acc, pos, W, s0, s1, c);
   *reinterpret_cast<f4*>(ws + (g * W.lanes) * 4 + c) = acc;
   if (MAX) *reinterpret_cast<i4*>(ws + ((slots + g) * W.lanes) * 4 + c) = pos;
 }
@@ -172,9 +124,9 @@ __global__ void __launch_bounds__(256) mpnn_chunks_kernel(const MpWalk W, int64_
 template <bool VEC, bool MAX, int KIND>
 __device__ inline void mp_reduce_row(f4& acc, i4& pos, const MpWalk& W, int64_t p0, int64_t p1, int c, int64_t slots,
                                   const float* __restrict__ ws) {
-  mp_reduce_entries<VEC, MAX, KIND>(acc, pos, W, p0, min(p0 + MP_CHUNK, p1), c);
-  if (p1 - p0 <= MP_CHUNK) return;
-  const int64_t first = (p0 + MP_CHUNK) / MP_CHUNK, n_part = (p1 - p0 - 1) / MP_CHUNK;
+  mp_reduce_entries<VEC, MAX, KIND>(acc, pos, W, p0, min(p0 + ROW_CHUNK, p1), c);
+  int64_t first, n_part;
+  row_partials(p0, p1, first, n_part);
 #pragma unroll 4
   for (int64_t k = 0; k < n_part; ++k) {
     const f4 v = *reinterpret_cast<const f4*>(ws + ((first + k) * W.lanes) * 4 + c);
@@ -198,12 +150,11 @@ __global__ void __launch_bounds__(256) mpnn_message_rows_kernel(const MpWalk W, 
                                                                 int ld_out, int32_t* __restrict__ arg, int64_t slots,
                                                                 const float* __restrict__ ws) {
   constexpr bool MAX = OP == EGC_MPNN_MAX;
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = t / W.lanes;
+  int64_t row, p0, p1;
+  int c;
+  group_lane(W.lanes, row, c);
   if (row >= W.n_rows) return;
-  const int c = (int)(t - row * W.lanes) * 4;
-  int64_t p0, p1;
-  mp_row_range(W, row, p0, p1);
+  row_range(W.rowptr, W.n_edges, row, p0, p1);
   f4 m = f4{0.f, 0.f, 0.f, 0.f};
   i4 e = i4{-1, -1, -1, -1};
   if (p1 > p0) {
@@ -221,7 +172,7 @@ __global__ void __launch_bounds__(256) mpnn_message_rows_kernel(const MpWalk W, 
     }
   }
   tm_store<VEC>(out + row * ld_out + c, c, W.width, m);
-  if (MAX && arg != nullptr) mp_store_i<VEC>(arg + row * W.width + c, c, W.width, e);
+  if (MAX && arg != nullptr) tm_store_i<VEC>(arg + row * W.width + c, c, W.width, e);
 }
 
 // group g: d P of transposed row g (g < W.n_rows) and d Q of forward row g (g < W.n_in_rows)
@@ -229,12 +180,12 @@ template <bool VEC, int KIND>
 __global__ void __launch_bounds__(256) mpnn_backward_rows_kernel(const MpWalk W, const int32_t* __restrict__ f_rowptr, int op,
                                                                  float* __restrict__ dP, int ld_dp, float* __restrict__ dQ,
                                                                  int ld_dq, int64_t slots, const float* __restrict__ ws) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t g = t / W.lanes;
-  const int c = (int)(t - g * W.lanes) * 4;
+  int64_t g;
+  int c;
+  group_lane(W.lanes, g, c);
   if (dP != nullptr && g < W.n_rows) {
     int64_t p0, p1;
-    mp_row_range(W, g, p0, p1);
+    row_range(W.rowptr, W.n_edges, g, p0, p1);
     f4 acc = f4{0.f, 0.f, 0.f, 0.f};
     i4 pos;
     if (p1 > p0) mp_reduce_row<VEC, false, KIND>(acc, pos, W, p0, p1, c, slots, ws);
@@ -251,19 +202,17 @@ __global__ void __launch_bounds__(256) mpnn_backward_rows_kernel(const MpWalk W,
   }
 }
 
-static inline int64_t mp_slots(int64_t n_edges) { return n_edges > MP_CHUNK ? ceil_div(n_edges, MP_CHUNK) : 0; }
-
 static inline size_t mp_workspace_bytes(int64_t n_edges, int32_t width, bool with_pos) {
   if (n_edges <= 0 || width <= 0) return 0;
-  return (size_t)mp_slots(n_edges) * (size_t)((width + 3) / 4) * 16 * (with_pos ? 2 : 1);
+  return (size_t)chunk_slots(n_edges) * (size_t)((width + 3) / 4) * 16 * (with_pos ? 2 : 1);
 }
 
 template <bool MAX, int KIND>
 static int launch_chunks(const MpWalk& W, bool vec, int64_t slots, float* ws, hipStream_t stream) {
-  const int64_t blocks = ceil_div(slots * W.lanes, 256);
-  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
-  if (vec) mpnn_chunks_kernel<true, MAX, KIND><<<(unsigned)blocks, 256, 0, stream>>>(W, slots, ws);
-  else mpnn_chunks_kernel<false, MAX, KIND><<<(unsigned)blocks, 256, 0, stream>>>(W, slots, ws);
+  unsigned blocks;
+  if (grid_blocks(slots * W.lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
+  if (vec) mpnn_chunks_kernel<true, MAX, KIND><<<blocks, 256, 0, stream>>>(W, slots, ws);
+  else mpnn_chunks_kernel<false, MAX, KIND><<<blocks, 256, 0, stream>>>(W, slots, ws);
   EGC_LAUNCH_CHECK("mpnn_chunks_kernel");
   return EGC_OK;
 }
@@ -291,26 +240,24 @@ int egc_mpnn_message_f32(const int32_t* rowptr, const int32_t* col, const int32_
   if (n_rows == 0) return EGC_OK;
   if (rowptr == nullptr || Q == nullptr || out == nullptr) return EGC_ERR_INVALID;
   if (n_edges > 0 && (col == nullptr || P == nullptr || n_src_rows == 0)) return EGC_ERR_INVALID;
-  if (n_rows >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31) || n_src_rows >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  if (!counts_fit_int32(n_rows, n_edges, n_src_rows)) return EGC_ERR_UNSUPPORTED;
   MpWalk W = {};
   W.rowptr = rowptr, W.col = col, W.in = P;
   W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_src_rows;
   W.ld_in = ld_p, W.width = width, W.lanes = (width + 3) / 4;
-  const bool vec = (width & 3) == 0 && (ld_p & 3) == 0 && (ld_q & 3) == 0 && (ld_out & 3) == 0 && tm_aligned16(P) &&
-                   tm_aligned16(Q) && tm_aligned16(out) && tm_aligned16(arg);
-  const int64_t slots = mp_slots(n_edges);
+  const bool vec = all_mult4(width, ld_p, ld_q, ld_out) && all_aligned16(P, Q, out, arg);
+  const int64_t slots = chunk_slots(n_edges);
   float* ws = static_cast<float*>(workspace);
   if (slots > 0) {
-    if (ws == nullptr || !tm_aligned16(ws) || workspace_bytes < mp_workspace_bytes(n_edges, width, op == EGC_MPNN_MAX))
-      return EGC_ERR_WORKSPACE;
+    if (!workspace_ok(ws, workspace_bytes, mp_workspace_bytes(n_edges, width, op == EGC_MPNN_MAX))) return EGC_ERR_WORKSPACE;
     const int st = op == EGC_MPNN_MAX ? launch_chunks<true, MP_PLAIN>(W, vec, slots, ws, stream)
                                       : launch_chunks<false, MP_PLAIN>(W, vec, slots, ws, stream);
     if (st != EGC_OK) return st;
   }
-  const int64_t blocks = ceil_div(n_rows * W.lanes, 256);
-  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  unsigned blocks;
+  if (grid_blocks(n_rows * W.lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
 #define EGC_MPNN_ROWS(V, O) \
-  mpnn_message_rows_kernel<V, O><<<(unsigned)blocks, 256, 0, stream>>>(W, edge_id, Q, ld_q, out, ld_out, arg, slots, ws)
+  mpnn_message_rows_kernel<V, O><<<blocks, 256, 0, stream>>>(W, edge_id, Q, ld_q, out, ld_out, arg, slots, ws)
   if (op == EGC_MPNN_ADD) { if (vec) EGC_MPNN_ROWS(true, EGC_MPNN_ADD); else EGC_MPNN_ROWS(false, EGC_MPNN_ADD); }
   else if (op == EGC_MPNN_MEAN) { if (vec) EGC_MPNN_ROWS(true, EGC_MPNN_MEAN); else EGC_MPNN_ROWS(false, EGC_MPNN_MEAN); }
   else { if (vec) EGC_MPNN_ROWS(true, EGC_MPNN_MAX); else EGC_MPNN_ROWS(false, EGC_MPNN_MAX); }
@@ -334,26 +281,25 @@ int egc_mpnn_message_backward_f32(const int32_t* rowptr, const int32_t* edge_id,
   if (rowptr == nullptr || (n_rows > 0 && dm == nullptr)) return EGC_ERR_INVALID;
   if (dP != nullptr && (t_rowptr == nullptr || (n_edges > 0 && (t_col == nullptr || n_rows == 0)))) return EGC_ERR_INVALID;
   if (dP != nullptr && op == EGC_MPNN_MAX && n_edges > 0 && arg == nullptr) return EGC_ERR_INVALID;
-  if (n_rows >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31) || n_src_rows >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  if (!counts_fit_int32(n_rows, n_edges, n_src_rows)) return EGC_ERR_UNSUPPORTED;
   MpWalk W = {};
   W.rowptr = t_rowptr, W.col = t_col, W.eid = t_edge_id, W.f_rowptr = rowptr, W.f_eid = edge_id, W.arg = arg, W.in = dm;
   W.n_rows = n_src_rows, W.n_edges = n_edges, W.n_in_rows = n_rows;
   W.ld_in = ld_dm, W.width = width, W.lanes = (width + 3) / 4;
-  const bool vec = (width & 3) == 0 && (ld_dm & 3) == 0 && (ld_dp & 3) == 0 && (ld_dq & 3) == 0 && tm_aligned16(dm) &&
-                   tm_aligned16(dP) && tm_aligned16(dQ) && tm_aligned16(arg);
-  const int64_t slots = dP != nullptr ? mp_slots(n_edges) : 0;
+  const bool vec = all_mult4(width, ld_dm, ld_dp, ld_dq) && all_aligned16(dm, dP, dQ, arg);
+  const int64_t slots = dP != nullptr ? chunk_slots(n_edges) : 0;
   float* ws = static_cast<float*>(workspace);
   if (slots > 0) {
-    if (ws == nullptr || !tm_aligned16(ws) || workspace_bytes < mp_workspace_bytes(n_edges, width, false)) return EGC_ERR_WORKSPACE;
+    if (!workspace_ok(ws, workspace_bytes, mp_workspace_bytes(n_edges, width, false))) return EGC_ERR_WORKSPACE;
     const int st = op == EGC_MPNN_ADD    ? launch_chunks<false, MP_PLAIN>(W, vec, slots, ws, stream)
                    : op == EGC_MPNN_MEAN ? launch_chunks<false, MP_DIV_DEG>(W, vec, slots, ws, stream)
                                          : launch_chunks<false, MP_MATCH>(W, vec, slots, ws, stream);
     if (st != EGC_OK) return st;
   }
-  const int64_t blocks = ceil_div(groups * W.lanes, 256);
-  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  unsigned blocks;
+  if (grid_blocks(groups * W.lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
 #define EGC_MPNN_BWD(V, K) \
-  mpnn_backward_rows_kernel<V, K><<<(unsigned)blocks, 256, 0, stream>>>(W, rowptr, op, dP, ld_dp, dQ, ld_dq, slots, ws)
+  mpnn_backward_rows_kernel<V, K><<<blocks, 256, 0, stream>>>(W, rowptr, op, dP, ld_dp, dQ, ld_dq, slots, ws)
   if (op == EGC_MPNN_ADD) { if (vec) EGC_MPNN_BWD(true, MP_PLAIN); else EGC_MPNN_BWD(false, MP_PLAIN); }
   else if (op == EGC_MPNN_MEAN) { if (vec) EGC_MPNN_BWD(true, MP_DIV_DEG); else EGC_MPNN_BWD(false, MP_DIV_DEG); }
   else { if (vec) EGC_MPNN_BWD(true, MP_MATCH); else EGC_MPNN_BWD(false, MP_MATCH); }

@@ -17,14 +17,12 @@
 // a list without VAR / STD loads no shift and one without MIN / MAX carries no positions.  SUM and MEAN come from the unshifted
 // S0 so that their bits do not depend on what else is listed.
 //
-// Order rule = egc_mpnn.hip's: a row's entries are cut into consecutive chunks of EGC_TYPED_MEAN_CHUNK counted from the row's
-// first entry; inside a chunk every accumulator starts at 0 (+inf / -inf, position = the chunk's first entry) and takes the
-// entries in order -- S0 = S0 + v;  d = v - s, S1 = S1 + d, S2 = S2 + d * d;  v < min, v > max strict -- and the row's value is
-// chunk 0's with chunks 1, 2, ... merged in ascending order: plain addition for S0, S1, S2 (the shift s is the row's in every
-// chunk), a strict compare for min / max, so the first chunk keeps a tie (a NaN is never selected).  Then, each one IEEE operation
-// (-ffp-contract=off):  nf = float(n);  SUM = S0 + nf * q;  MEAN = S0 / nf + q;  MIN = mn + q;  MAX = mx + q;  m1 = S1 / nf;
-// t = S2 / nf - m1 * m1;  v = t > 0 ? t : 0;  STD = sqrt(v + 1e-5f);  mu = s + m1.  Two launches: the CHUNK kernel reduces chunks
-// 1.. of the rows longer than one chunk into the workspace (slot arithmetic of egc_mpnn.hip), the ROW kernel does the rest.
+// Order rule: egc_row_chunks.h.  Inside a chunk every accumulator starts at 0 (+inf / -inf, position = the chunk's first entry)
+// and takes the entries in order -- S0 = S0 + v;  d = v - s, S1 = S1 + d, S2 = S2 + d * d;  v < min, v > max strict -- and the
+// row's value is chunk 0's with chunks 1, 2, ... merged in ascending order: plain addition for S0, S1, S2 (the shift s is the
+// row's in every chunk), a strict compare for min / max, so the first chunk keeps a tie (a NaN is never selected).  Then, each
+// one IEEE operation (-ffp-contract=off):  nf = float(n);  SUM = S0 + nf * q;  MEAN = S0 / nf + q;  MIN = mn + q;  MAX = mx + q;
+// m1 = S1 / nf;  t = S2 / nf - m1 * m1;  v = t > 0 ? t : 0;  STD = sqrt(v + 1e-5f);  mu = s + m1.
 //
 // Backward, two launches after the chunk launch, no atomics, every element written once:
 //   destination pass (one read of the row's gradients and saved statistics), nf = float(n), rows without entries give zeros:
@@ -39,23 +37,16 @@
 //   since d v / d P_j = 2 (P_j - mu) / n, the var / std / mean / sum part of d P_j is sum_i a_i + P_j * sum_i b_i.
 // The records a and b live in the caller's workspace, in front of the chunk partials.
 //
-// Mapping (egc_mpnn.hip's): a lane owns four adjacent columns (16-byte accesses; 4-byte ones of the same columns when a width,
-// stride or pointer is not a multiple of 16 bytes), ceil(width / 4) lanes form a group, one group per row.  PN_AHEAD entries'
-// indices, then their rows, are requested before the first operation that consumes them; a partial batch issues all its loads too
-// (index clamped, surplus not taken).  Column indices are clamped to the input's rows, offsets and edge positions to the entry
-// count: malformed input gives garbage, never an access outside.
+// Mapping: egc_row_chunks.h, a batch is PN_AHEAD entries; edge positions are clamped to the entry count like row offsets.
 //
 // The scaler combine at the end of the file: out_i = base_i + sum_k f_k(d_i) Y_i[k D : (k + 1) D], d_i = max(n_i, 1), the factors
 // formed per row in double and rounded once to float.
-#include "egc_common.h"
+#include "egc_row_chunks.h"
 
 namespace egc {
 
-constexpr int PN_CHUNK = EGC_TYPED_MEAN_CHUNK;
 constexpr int PN_AHEAD = 8;
 constexpr int PN_OPS = 6;
-
-typedef int i4 __attribute__((ext_vector_type(4)));
 
 struct PnWalk {
   const int32_t* rowptr;   // the CSR walked: n_rows + 1 offsets
@@ -69,50 +60,6 @@ struct PnAcc {
   f4 s0, s1, s2, mn, mx;
   i4 pmn, pmx;
 };
-
-template <bool VEC>
-__device__ inline i4 pn_load_i(const int32_t* __restrict__ p, int c, int width) {
-  if (VEC) return *reinterpret_cast<const i4*>(p);
-  i4 v = i4{-1, -1, -1, -1};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (c + j < width) v[j] = p[j];
-  return v;
-}
-
-template <bool VEC>
-__device__ inline void pn_store_i(int32_t* __restrict__ p, int c, int width, i4 v) {
-  if (VEC) {
-    *reinterpret_cast<i4*>(p) = v;
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (c + j < width) p[j] = v[j];
-}
-
-__device__ inline void pn_row_range(const int32_t* __restrict__ rowptr, int64_t n_edges, int64_t row, int64_t& p0, int64_t& p1) {
-  p0 = min(max((int64_t)rowptr[row], (int64_t)0), n_edges);
-  p1 = min(max((int64_t)rowptr[row + 1], p0), n_edges);
-}
-
-// the last row that starts at or before CSR position `at`
-__device__ inline int64_t pn_row_of(const int32_t* __restrict__ rowptr, int64_t n_rows, int64_t at) {
-  int64_t lo = 0, hi = n_rows;
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)rowptr[mid] <= at) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// the chunk k >= 1 of row [p0, p1) that starts in [at, at + CHUNK), or -1 (a short row, chunk 0, none)
-__device__ inline int64_t pn_chunk_start(int64_t p0, int64_t p1, int64_t at) {
-  if (p1 - p0 <= PN_CHUNK || at <= p0) return -1;
-  const int64_t s = p0 + (at - p0 + PN_CHUNK - 1) / PN_CHUNK * PN_CHUNK;
-  return s < p1 ? s : -1;
-}
 
 // field f of slot g: [fields][slots][lanes] 16-byte pieces
 __device__ inline float* pn_ws(float* ws, int f, int64_t slots, int64_t g, int lanes, int c) {
@@ -128,11 +75,7 @@ __device__ inline void pn_take_batch(PnAcc& A, const PnWalk& W, f4 shift, int64_
   constexpr int N = FULL ? PN_AHEAD : PN_AHEAD - 1;
   const int last_in = (int)W.n_in_rows - 1;
   int j[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
-    j[k] = min(max(W.col[q], 0), last_in);
-  }
+  batch_rows<N, FULL>(j, W.col, p, p1, last_in);
   f4 v[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) v[k] = tm_load<VEC>(W.in + (int64_t)j[k] * W.ld_in + c, c, W.width);
@@ -176,7 +119,7 @@ __device__ inline void pn_reduce_entries(PnAcc& A, const PnWalk& W, f4 shift, in
 // the row's shift: its first entry's row of P
 template <bool VEC>
 __device__ inline f4 pn_shift(const PnWalk& W, int64_t p0, int c) {
-  const int j = min(max(W.col[p0], 0), (int)W.n_in_rows - 1);
+  const int j = clamp_index(W.col[p0], (int)W.n_in_rows - 1);
   return tm_load<VEC>(W.in + (int64_t)j * W.ld_in + c, c, W.width);
 }
 
@@ -190,20 +133,18 @@ struct PnFields {
 template <bool VEC, bool SUM, bool MOM2, bool EXT>
 __global__ void __launch_bounds__(256) pna_chunks_kernel(const PnWalk W, int64_t slots, float* __restrict__ ws) {
   typedef PnFields<SUM, MOM2, EXT> F;
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t g = t / W.lanes;
-  if (g >= slots) return;
-  const int c = (int)(t - g * W.lanes) * 4;
-  const int64_t at = g * PN_CHUNK;
-  const int64_t row = pn_row_of(W.rowptr, W.n_rows, at);
-  int64_t p0, p1;
-  pn_row_range(W.rowptr, W.n_edges, row, p0, p1);
-  const int64_t s = pn_chunk_start(p0, p1, at);
-  if (s < 0) return;
+  int64_t g, row, s0, s1;
+  int c;
+  group_lane(W.lanes, g, c);
+  if (g >= slots || !slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, s0, s1)) return;
   f4 shift = f4{0.f, 0.f, 0.f, 0.f};
-  if (MOM2) shift = pn_shift<VEC>(W, p0, c);
+  if (MOM2) {
+    int64_t p0, p1;
+    row_range(W.rowptr, W.n_edges, row, p0, p1);
+    shift = pn_shift<VEC>(W, p0, c);
+  }
   PnAcc A;
-  pn_reduce_entries<VEC, SUM, MOM2, EXT>(A, W, shift, s, min(s + PN_CHUNK, p1), c);
+  pn_reduce_entries<VEC, SUM, MOM2, EXT>(A, W, shift, s0, s1, c);
   if (SUM) *reinterpret_cast<f4*>(pn_ws(ws, F::s0, slots, g, W.lanes, c)) = A.s0;
   if (MOM2) {
     *reinterpret_cast<f4*>(pn_ws(ws, F::s1, slots, g, W.lanes, c)) = A.s1;
@@ -233,12 +174,11 @@ template <bool VEC, bool SUM, bool MOM2, bool EXT>
 __global__ void __launch_bounds__(256) pna_aggregate_rows_kernel(const PnWalk W, const PnOut O, int64_t slots,
                                                                  float* __restrict__ ws) {
   typedef PnFields<SUM, MOM2, EXT> F;
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = t / W.lanes;
+  int64_t row, p0, p1;
+  int c;
+  group_lane(W.lanes, row, c);
   if (row >= W.n_rows) return;
-  const int c = (int)(t - row * W.lanes) * 4;
-  int64_t p0, p1;
-  pn_row_range(W.rowptr, W.n_edges, row, p0, p1);
+  row_range(W.rowptr, W.n_edges, row, p0, p1);
   const f4 zero = f4{0.f, 0.f, 0.f, 0.f};
   f4 r[PN_OPS] = {zero, zero, zero, zero, zero, zero};
   f4 mu = zero;
@@ -248,9 +188,10 @@ __global__ void __launch_bounds__(256) pna_aggregate_rows_kernel(const PnWalk W,
     f4 shift = zero;
     if (MOM2) shift = pn_shift<VEC>(W, p0, c);
     PnAcc A;
-    pn_reduce_entries<VEC, SUM, MOM2, EXT>(A, W, shift, p0, min(p0 + PN_CHUNK, p1), c);
-    if (p1 - p0 > PN_CHUNK) {
-      const int64_t first = (p0 + PN_CHUNK) / PN_CHUNK, n_part = (p1 - p0 - 1) / PN_CHUNK;
+    pn_reduce_entries<VEC, SUM, MOM2, EXT>(A, W, shift, p0, min(p0 + ROW_CHUNK, p1), c);
+    if (p1 - p0 > ROW_CHUNK) {   // (n_part is 0 otherwise: the test only spares the short rows the division)
+      int64_t first, n_part;
+      row_partials(p0, p1, first, n_part);
 #pragma unroll 2
       for (int64_t k = 0; k < n_part; ++k) {
         const int64_t g = first + k;
@@ -311,8 +252,8 @@ __global__ void __launch_bounds__(256) pna_aggregate_rows_kernel(const PnWalk W,
     if (O.blk[op] >= 0) tm_store<VEC>(O.out + row * O.ld_out + (int64_t)O.blk[op] * W.width + c, c, W.width, r[op]);
   if (MOM2 && O.mu != nullptr) tm_store<VEC>(O.mu + row * W.width + c, c, W.width, mu);
   if (MOM2 && O.var != nullptr) tm_store<VEC>(O.var + row * W.width + c, c, W.width, r[EGC_PNA_VAR]);
-  if (EXT && O.arg_min != nullptr) pn_store_i<VEC>(O.arg_min + row * W.width + c, c, W.width, emn);
-  if (EXT && O.arg_max != nullptr) pn_store_i<VEC>(O.arg_max + row * W.width + c, c, W.width, emx);
+  if (EXT && O.arg_min != nullptr) tm_store_i<VEC>(O.arg_min + row * W.width + c, c, W.width, emn);
+  if (EXT && O.arg_max != nullptr) tm_store_i<VEC>(O.arg_max + row * W.width + c, c, W.width, emx);
 }
 
 // --------------------------------------------------------------------------------------------------------------- backward
@@ -332,12 +273,11 @@ struct PnGrad {
 
 template <bool VEC>
 __global__ void __launch_bounds__(256) pna_backward_dst_kernel(const PnGrad G) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = t / G.lanes;
+  int64_t row, p0, p1;
+  int c;
+  group_lane(G.lanes, row, c);
   if (row >= G.n_rows) return;
-  const int c = (int)(t - row * G.lanes) * 4;
-  int64_t p0, p1;
-  pn_row_range(G.rowptr, G.n_edges, row, p0, p1);
+  row_range(G.rowptr, G.n_edges, row, p0, p1);
   const f4 zero = f4{0.f, 0.f, 0.f, 0.f};
   f4 dq = zero, a = zero, b = zero;
   if (p1 > p0) {
@@ -407,9 +347,9 @@ __device__ inline void pn_back_batch(PnBAcc& A, const PnBack& W, int64_t p, int6
   int j[N], e[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
-    j[k] = min(max(W.col[q], 0), last_in);
-    e[k] = ext && W.eid != nullptr ? min(max(W.eid[q], 0), last_e) : (int)q;
+    const int64_t q = batch_entry<FULL>(p, k, p1);
+    j[k] = clamp_index(W.col[q], last_in);
+    e[k] = ext && W.eid != nullptr ? clamp_index(W.eid[q], last_e) : (int)q;
   }
   if (ext && W.f_eid != nullptr) {
 #pragma unroll
@@ -442,7 +382,7 @@ __device__ inline void pn_back_batch(PnBAcc& A, const PnBack& W, int64_t p, int6
 #pragma unroll
     for (int k = 0; k < N; ++k) {
       v[k] = tm_load<VEC>(g + (int64_t)j[k] * W.ld_g + c, c, W.width);
-      r[k] = pn_load_i<VEC>(arg + (int64_t)j[k] * W.width + c, c, W.width);
+      r[k] = tm_load_i<VEC>(arg + (int64_t)j[k] * W.width + c, c, W.width);
     }
     f4& acc = side == 0 ? A.mn : A.mx;
 #pragma unroll
@@ -469,18 +409,12 @@ __device__ inline void pn_back_entries(PnBAcc& A, const PnBack& W, int64_t p0, i
 // workspace of the source pass: fields A | B | Mn | Mx, [4][slots][lanes] 16-byte pieces
 template <bool VEC, bool MOM2>
 __global__ void __launch_bounds__(256) pna_backward_chunks_kernel(const PnBack W, int64_t slots, float* __restrict__ ws) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t g = t / W.lanes;
-  if (g >= slots) return;
-  const int c = (int)(t - g * W.lanes) * 4;
-  const int64_t at = g * PN_CHUNK;
-  const int64_t row = pn_row_of(W.rowptr, W.n_rows, at);
-  int64_t p0, p1;
-  pn_row_range(W.rowptr, W.n_edges, row, p0, p1);
-  const int64_t s = pn_chunk_start(p0, p1, at);
-  if (s < 0) return;
+  int64_t g, row, s0, s1;
+  int c;
+  group_lane(W.lanes, g, c);
+  if (g >= slots || !slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, s0, s1)) return;
   PnBAcc A;
-  pn_back_entries<VEC, MOM2>(A, W, s, min(s + PN_CHUNK, p1), c);
+  pn_back_entries<VEC, MOM2>(A, W, s0, s1, c);
   *reinterpret_cast<f4*>(pn_ws(ws, 0, slots, g, W.lanes, c)) = A.a;
   if (MOM2) *reinterpret_cast<f4*>(pn_ws(ws, 1, slots, g, W.lanes, c)) = A.b;
   if (W.g_min != nullptr) *reinterpret_cast<f4*>(pn_ws(ws, 2, slots, g, W.lanes, c)) = A.mn;
@@ -489,18 +423,18 @@ __global__ void __launch_bounds__(256) pna_backward_chunks_kernel(const PnBack W
 
 template <bool VEC, bool MOM2>
 __global__ void __launch_bounds__(256) pna_backward_src_kernel(const PnBack W, int64_t slots, float* __restrict__ ws) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = t / W.lanes;
+  int64_t row, p0, p1;
+  int c;
+  group_lane(W.lanes, row, c);
   if (row >= W.n_rows) return;
-  const int c = (int)(t - row * W.lanes) * 4;
-  int64_t p0, p1;
-  pn_row_range(W.rowptr, W.n_edges, row, p0, p1);
+  row_range(W.rowptr, W.n_edges, row, p0, p1);
   f4 d = f4{0.f, 0.f, 0.f, 0.f};
   if (p1 > p0) {
     PnBAcc A;
-    pn_back_entries<VEC, MOM2>(A, W, p0, min(p0 + PN_CHUNK, p1), c);
-    if (p1 - p0 > PN_CHUNK) {
-      const int64_t first = (p0 + PN_CHUNK) / PN_CHUNK, n_part = (p1 - p0 - 1) / PN_CHUNK;
+    pn_back_entries<VEC, MOM2>(A, W, p0, min(p0 + ROW_CHUNK, p1), c);
+    if (p1 - p0 > ROW_CHUNK) {   // (n_part is 0 otherwise: the test only spares the short rows the division)
+      int64_t first, n_part;
+      row_partials(p0, p1, first, n_part);
 #pragma unroll 2
       for (int64_t k = 0; k < n_part; ++k) {
         const int64_t g = first + k;
@@ -546,10 +480,10 @@ template <bool VEC, bool BACKWARD>
 __global__ void __launch_bounds__(256) pna_scale_kernel(const PnScale S, const float* __restrict__ x, int ld_x,
                                                         const float* __restrict__ base, int ld_base, float* __restrict__ out,
                                                         int ld_out) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = t / S.lanes;
+  int64_t row;
+  int c;
+  group_lane(S.lanes, row, c);
   if (row >= S.n_rows) return;
-  const int c = (int)(t - row * S.lanes) * 4;
   const int n = S.rowptr[row + 1] - S.rowptr[row];
   if (BACKWARD) {
     const f4 g = tm_load<VEC>(x + row * ld_x + c, c, S.dim);
@@ -564,8 +498,6 @@ __global__ void __launch_bounds__(256) pna_scale_kernel(const PnScale S, const f
 }
 
 // ------------------------------------------------------------------------------------------------------------------- host
-
-static inline int64_t pn_slots(int64_t n_edges) { return n_edges > PN_CHUNK ? ceil_div(n_edges, PN_CHUNK) : 0; }
 
 // blk[op] = the block of op in the list, -1 when absent; false: an unknown or duplicate op, an empty or overlong list
 static bool pn_blocks(const int32_t* ops, int32_t n_ops, int32_t* blk) {
@@ -594,14 +526,14 @@ static PnNeeds pn_needs(const int32_t* blk) {
 template <bool VEC, bool SUM, bool MOM2, bool EXT>
 static int pn_forward_launch(const PnWalk& W, const PnOut& O, int64_t slots, float* ws, hipStream_t stream) {
   if (slots > 0) {
-    const int64_t blocks = ceil_div(slots * W.lanes, 256);
-    if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
-    pna_chunks_kernel<VEC, SUM, MOM2, EXT><<<(unsigned)blocks, 256, 0, stream>>>(W, slots, ws);
+    unsigned blocks;
+    if (grid_blocks(slots * W.lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
+    pna_chunks_kernel<VEC, SUM, MOM2, EXT><<<blocks, 256, 0, stream>>>(W, slots, ws);
     EGC_LAUNCH_CHECK("pna_chunks_kernel");
   }
-  const int64_t blocks = ceil_div(W.n_rows * W.lanes, 256);
-  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
-  pna_aggregate_rows_kernel<VEC, SUM, MOM2, EXT><<<(unsigned)blocks, 256, 0, stream>>>(W, O, slots, ws);
+  unsigned blocks;
+  if (grid_blocks(W.n_rows * W.lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
+  pna_aggregate_rows_kernel<VEC, SUM, MOM2, EXT><<<blocks, 256, 0, stream>>>(W, O, slots, ws);
   EGC_LAUNCH_CHECK("pna_aggregate_rows_kernel");
   return EGC_OK;
 }
@@ -622,14 +554,14 @@ static int pn_forward_dispatch(const PnNeeds& n, const PnWalk& W, const PnOut& O
 template <bool VEC, bool MOM2>
 static int pn_backward_src_launch(const PnBack& B, int64_t slots, float* ws, hipStream_t stream) {
   if (slots > 0) {
-    const int64_t blocks = ceil_div(slots * B.lanes, 256);
-    if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
-    pna_backward_chunks_kernel<VEC, MOM2><<<(unsigned)blocks, 256, 0, stream>>>(B, slots, ws);
+    unsigned blocks;
+    if (grid_blocks(slots * B.lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
+    pna_backward_chunks_kernel<VEC, MOM2><<<blocks, 256, 0, stream>>>(B, slots, ws);
     EGC_LAUNCH_CHECK("pna_backward_chunks_kernel");
   }
-  const int64_t blocks = ceil_div(B.n_rows * B.lanes, 256);
-  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
-  pna_backward_src_kernel<VEC, MOM2><<<(unsigned)blocks, 256, 0, stream>>>(B, slots, ws);
+  unsigned blocks;
+  if (grid_blocks(B.n_rows * B.lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
+  pna_backward_src_kernel<VEC, MOM2><<<blocks, 256, 0, stream>>>(B, slots, ws);
   EGC_LAUNCH_CHECK("pna_backward_src_kernel");
   return EGC_OK;
 }
@@ -643,12 +575,12 @@ using namespace egc;
 size_t egc_pna_aggregate_workspace_bytes(int64_t n_edges, int32_t width, const int32_t* ops, int32_t n_ops) {
   int32_t blk[PN_OPS];
   if (n_edges <= 0 || width <= 0 || !pn_blocks(ops, n_ops, blk)) return 0;
-  return (size_t)pn_slots(n_edges) * (size_t)((width + 3) / 4) * 16 * (size_t)pn_needs(blk).fields;
+  return (size_t)chunk_slots(n_edges) * (size_t)((width + 3) / 4) * 16 * (size_t)pn_needs(blk).fields;
 }
 
 size_t egc_pna_aggregate_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32_t width) {
   if (n_rows <= 0 || width <= 0) return 0;
-  const int64_t slots = n_edges > 0 ? pn_slots(n_edges) : 0;
+  const int64_t slots = n_edges > 0 ? chunk_slots(n_edges) : 0;
   return 2 * pn_record_bytes(n_rows, width) + (size_t)slots * (size_t)((width + 3) / 4) * 16 * 4;
 }
 
@@ -663,7 +595,7 @@ int egc_pna_aggregate_f32(const int32_t* rowptr, const int32_t* col, const int32
   if (n_rows == 0) return EGC_OK;
   if (rowptr == nullptr || Q == nullptr || out == nullptr) return EGC_ERR_INVALID;
   if (n_edges > 0 && (col == nullptr || P == nullptr || n_src_rows == 0)) return EGC_ERR_INVALID;
-  if (n_rows >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31) || n_src_rows >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  if (!counts_fit_int32(n_rows, n_edges, n_src_rows)) return EGC_ERR_UNSUPPORTED;
   const PnNeeds needs = pn_needs(O.blk);
   PnWalk W = {};
   W.rowptr = rowptr, W.col = col, W.in = P;
@@ -674,13 +606,10 @@ int egc_pna_aggregate_f32(const int32_t* rowptr, const int32_t* col, const int32
   O.var = needs.mom2 ? var : nullptr;
   O.arg_min = O.blk[EGC_PNA_MIN] >= 0 ? arg_min : nullptr;
   O.arg_max = O.blk[EGC_PNA_MAX] >= 0 ? arg_max : nullptr;
-  const bool vec = (width & 3) == 0 && (ld_p & 3) == 0 && (ld_q & 3) == 0 && (ld_out & 3) == 0 && tm_aligned16(P) &&
-                   tm_aligned16(Q) && tm_aligned16(out) && tm_aligned16(O.arg_min) && tm_aligned16(O.arg_max) && tm_aligned16(O.mu) &&
-                   tm_aligned16(O.var);
-  const int64_t slots = pn_slots(n_edges);
+  const bool vec = all_mult4(width, ld_p, ld_q, ld_out) && all_aligned16(P, Q, out, O.arg_min, O.arg_max, O.mu, O.var);
+  const int64_t slots = chunk_slots(n_edges);
   float* ws = static_cast<float*>(workspace);
-  if (slots > 0 && (ws == nullptr || !tm_aligned16(ws) ||
-                    workspace_bytes < (size_t)slots * (size_t)W.lanes * 16 * (size_t)needs.fields))
+  if (slots > 0 && !workspace_ok(ws, workspace_bytes, (size_t)slots * (size_t)W.lanes * 16 * (size_t)needs.fields))
     return EGC_ERR_WORKSPACE;
   return vec ? pn_forward_dispatch<true>(needs, W, O, slots, ws, stream) : pn_forward_dispatch<false>(needs, W, O, slots, ws, stream);
 }
@@ -699,7 +628,7 @@ int egc_pna_aggregate_backward_f32(const int32_t* rowptr, const int32_t* edge_id
   const int64_t p_rows = dP != nullptr ? n_src_rows : 0, q_rows = dQ != nullptr ? n_rows : 0;
   if (p_rows == 0 && q_rows == 0) return EGC_OK;
   if (rowptr == nullptr || (n_rows > 0 && dagg == nullptr)) return EGC_ERR_INVALID;
-  if (n_rows >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31) || n_src_rows >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  if (!counts_fit_int32(n_rows, n_edges, n_src_rows)) return EGC_ERR_UNSUPPORTED;
   const PnNeeds needs = pn_needs(G.blk);
   const bool has_min = G.blk[EGC_PNA_MIN] >= 0, has_max = G.blk[EGC_PNA_MAX] >= 0;
   const bool lin = needs.sum || needs.mom2;          // the a record exists
@@ -711,25 +640,22 @@ int egc_pna_aggregate_backward_f32(const int32_t* rowptr, const int32_t* edge_id
   }
   const int32_t lanes = (width + 3) / 4;
   const bool records = want_p && lin && n_rows > 0;
-  const int64_t slots = want_p ? pn_slots(n_edges) : 0;
+  const int64_t slots = want_p ? chunk_slots(n_edges) : 0;
   float* ws = static_cast<float*>(workspace);
   const size_t rec = pn_record_bytes(n_rows, width);
-  if ((records || slots > 0) &&
-      (ws == nullptr || !tm_aligned16(ws) || workspace_bytes < egc_pna_aggregate_backward_workspace_bytes(n_rows, n_edges, width)))
+  if ((records || slots > 0) && !workspace_ok(ws, workspace_bytes, egc_pna_aggregate_backward_workspace_bytes(n_rows, n_edges, width)))
     return EGC_ERR_WORKSPACE;
-  const bool vec = (width & 3) == 0 && (ld_dagg & 3) == 0 && (ld_dp & 3) == 0 && (ld_dq & 3) == 0 && (ld_p & 3) == 0 &&
-                   tm_aligned16(dagg) && tm_aligned16(dP) && tm_aligned16(dQ) && tm_aligned16(P) &&
-                   tm_aligned16(arg_min) && tm_aligned16(arg_max) && tm_aligned16(mu) && tm_aligned16(var);
+  const bool vec = all_mult4(width, ld_dagg, ld_dp, ld_dq, ld_p) && all_aligned16(dagg, dP, dQ, P, arg_min, arg_max, mu, var);
   if (n_rows > 0 && (q_rows > 0 || records)) {
     G.rowptr = rowptr, G.g = dagg, G.mu = mu, G.var = var, G.dQ = dQ;
     G.a = records ? ws : nullptr;
     G.b = records && needs.mom2 ? ws + rec / 4 : nullptr;
     G.n_rows = n_rows, G.n_edges = n_edges;
     G.ld_g = ld_dagg, G.ld_dq = ld_dq, G.width = width, G.lanes = lanes;
-    const int64_t blocks = ceil_div(n_rows * lanes, 256);
-    if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
-    if (vec) pna_backward_dst_kernel<true><<<(unsigned)blocks, 256, 0, stream>>>(G);
-    else pna_backward_dst_kernel<false><<<(unsigned)blocks, 256, 0, stream>>>(G);
+    unsigned blocks;
+    if (grid_blocks(n_rows * lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
+    if (vec) pna_backward_dst_kernel<true><<<blocks, 256, 0, stream>>>(G);
+    else pna_backward_dst_kernel<false><<<blocks, 256, 0, stream>>>(G);
     EGC_LAUNCH_CHECK("pna_backward_dst_kernel");
   }
   if (!want_p) return EGC_OK;
@@ -763,19 +689,18 @@ static int pn_scale(bool backward, const int32_t* rowptr, int64_t n_rows, const 
   if (backward ? (ld_x < dim || ld_out < wide) : (ld_x < wide || ld_base < dim || ld_out < dim)) return EGC_ERR_INVALID;
   if (n_rows == 0) return EGC_OK;
   if (rowptr == nullptr || x == nullptr || out == nullptr || (!backward && base == nullptr)) return EGC_ERR_INVALID;
-  if (n_rows >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  if (!counts_fit_int32(n_rows)) return EGC_ERR_UNSUPPORTED;
   S.rowptr = rowptr, S.n_rows = n_rows, S.avg_lin = avg_lin, S.avg_log = avg_log;
   S.n_scalers = n_scalers, S.dim = dim, S.lanes = (dim + 3) / 4;
-  const bool vec = (dim & 3) == 0 && (ld_x & 3) == 0 && (ld_base & 3) == 0 && (ld_out & 3) == 0 && tm_aligned16(x) &&
-                   tm_aligned16(base) && tm_aligned16(out);
-  const int64_t blocks = ceil_div(n_rows * S.lanes, 256);
-  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  const bool vec = all_mult4(dim, ld_x, ld_base, ld_out) && all_aligned16(x, base, out);
+  unsigned blocks;
+  if (grid_blocks(n_rows * S.lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
   if (backward) {
-    if (vec) pna_scale_kernel<true, true><<<(unsigned)blocks, 256, 0, stream>>>(S, x, ld_x, base, ld_base, out, ld_out);
-    else pna_scale_kernel<false, true><<<(unsigned)blocks, 256, 0, stream>>>(S, x, ld_x, base, ld_base, out, ld_out);
+    if (vec) pna_scale_kernel<true, true><<<blocks, 256, 0, stream>>>(S, x, ld_x, base, ld_base, out, ld_out);
+    else pna_scale_kernel<false, true><<<blocks, 256, 0, stream>>>(S, x, ld_x, base, ld_base, out, ld_out);
   } else {
-    if (vec) pna_scale_kernel<true, false><<<(unsigned)blocks, 256, 0, stream>>>(S, x, ld_x, base, ld_base, out, ld_out);
-    else pna_scale_kernel<false, false><<<(unsigned)blocks, 256, 0, stream>>>(S, x, ld_x, base, ld_base, out, ld_out);
+    if (vec) pna_scale_kernel<true, false><<<blocks, 256, 0, stream>>>(S, x, ld_x, base, ld_base, out, ld_out);
+    else pna_scale_kernel<false, false><<<blocks, 256, 0, stream>>>(S, x, ld_x, base, ld_base, out, ld_out);
   }
   EGC_LAUNCH_CHECK("pna_scale_kernel");
   return EGC_OK;

@@ -12,28 +12,14 @@
 // forward copies x_t into block 0 of A_t with it, the backward starts d x_s from d A_s' block 0.  Every element of `out` is
 // written exactly once: no zero fill, no atomics.
 //
-// Order rule.  A row's entries are cut into consecutive chunks of EGC_TYPED_MEAN_CHUNK entries, counted from the row's first
-// entry.  A chunk's sum is ((0 + v0) + v1) + ... in entry order, one IEEE add each (-ffp-contract=off), v = pre * in (one
-// multiply) where there is a pre.  The row's sum is the sum of chunk 0 with the sums of chunks 1, 2, ... added in ascending
-// order.  So the bits are a function of the CSR and the inputs alone, never of the launch geometry.  Two launches: the CHUNK
-// kernel sums chunks 1.. of the rows longer than one chunk into the workspace (one group of lanes per chunk: a hub row of 10^5
-// entries is spread over 400 groups), then the ROW kernel sums every row's chunk 0, adds the row's partials in order, applies
-// post and stores.  The chunk list is derived on the device: the group of workspace slot b looks at CSR position b * CHUNK,
-// finds its row by bisection of rowptr, and owns the one chunk k >= 1 of that row that starts inside [b * CHUNK, (b + 1) * CHUNK)
-// if there is one (chunks of a row are CHUNK apart, so there is at most one, and every chunk k >= 1 starts in exactly one such
-// window of its own row).  Nothing is read back, the slot of a chunk is floor(start / CHUNK), ceil(n_edges / CHUNK) slots per
-// relation whose n_edges exceed one chunk.
-//
-// Mapping (egc_readout.hip's): a lane owns four adjacent columns (16-byte accesses; scalar ones of the same columns when a
-// width, stride or pointer is not a multiple of 16 bytes), ceil(width / 4) lanes form a group, groups are laid back to back over
-// the grid.  TM_AHEAD entries' column indices, then their rows, are requested before the first add that consumes them; the
-// last, partial batch issues all its loads too (index clamped, surplus not taken: DESIGN.md section 3.9).  Column indices are
-// clamped to the input's rows and row offsets to the entry count: malformed input gives garbage, never an access outside.
-#include "egc_common.h"
+// Order rule and mapping: egc_row_chunks.h.  A chunk's sum is ((0 + v0) + v1) + ... in entry order, one IEEE add each
+// (-ffp-contract=off), v = pre * in (one multiply) where there is a pre; the row's sum is the sum of chunk 0 with the sums of
+// chunks 1, 2, ... added in ascending order; then post.  Every relation whose n_edges exceed one chunk has its own run of
+// workspace slots (TypedTable::slot0).  A batch is TM_AHEAD entries.
+#include "egc_row_chunks.h"
 
 namespace egc {
 
-constexpr int TM_CHUNK = EGC_TYPED_MEAN_CHUNK;
 constexpr int TM_AHEAD = 8;
 
 struct TypedTable {
@@ -51,9 +37,8 @@ __device__ inline void take_batch(f4& acc, const egc_typed_rel& R, int64_t p, in
   int j[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    const int64_t q = FULL ? p + k : min(p + k, p1 - 1);
-    const int jj = R.col != nullptr ? R.col[q] : (int)q;
-    j[k] = min(max(jj, 0), last_in);
+    const int64_t q = batch_entry<FULL>(p, k, p1);
+    j[k] = clamp_index(R.col != nullptr ? R.col[q] : (int)q, last_in);
   }
   float s[N];
   if (R.pre_rowptr != nullptr) {
@@ -93,33 +78,22 @@ __device__ inline void row_range(const egc_typed_rel& R, int64_t row, int64_t& p
     p1 = row < R.n_in_rows ? row + 1 : row;
     return;
   }
-  p0 = min(max((int64_t)R.rowptr[row], (int64_t)0), R.n_edges);
-  p1 = min(max((int64_t)R.rowptr[row + 1], p0), R.n_edges);
+  row_range(R.rowptr, R.n_edges, row, p0, p1);
 }
 
 template <bool VEC>
 __global__ void __launch_bounds__(256) typed_mean_chunks_kernel(const TypedTable T, int64_t n_rows, int width, int lanes,
                                                                 float* __restrict__ ws) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t g = t / lanes;
+  int64_t g;
+  int c;
+  group_lane(lanes, g, c);
   if (g >= T.slot0[T.n_rels]) return;
-  const int c = (int)(t - g * lanes) * 4;
   int r = 0;
   while (r + 1 < T.n_rels && g >= T.slot0[r + 1]) ++r;
   const egc_typed_rel& R = T.rel[r];
-  const int64_t pos = (g - T.slot0[r]) * TM_CHUNK;
-  int64_t lo = 0, hi = n_rows;   // the last row that starts at or before pos
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)R.rowptr[mid] <= pos) lo = mid;
-    else hi = mid;
-  }
-  int64_t p0, p1;
-  row_range(R, lo, p0, p1);
-  if (p1 - p0 <= TM_CHUNK || pos <= p0) return;   // a short row; or chunk 0, which the row kernel sums
-  const int64_t s = p0 + (pos - p0 + TM_CHUNK - 1) / TM_CHUNK * TM_CHUNK;   // the row's chunk that starts in this window
-  if (s >= p1) return;
-  const f4 acc = sum_entries<VEC>(R, s, min(s + TM_CHUNK, p1), c, width);
+  int64_t row, s0, s1;
+  if (!slot_chunk(R.rowptr, n_rows, R.n_edges, g - T.slot0[r], row, s0, s1)) return;
+  const f4 acc = sum_entries<VEC>(R, s0, s1, c, width);
   *reinterpret_cast<f4*>(ws + (g * lanes) * 4 + c) = acc;
 }
 
@@ -127,10 +101,10 @@ template <bool VEC, bool ACCUM>
 __global__ void __launch_bounds__(256) typed_mean_rows_kernel(const TypedTable T, int64_t n_rows, int width, int lanes,
                                                               float* __restrict__ out, int ld_out,
                                                               const float* __restrict__ ws) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t g = t / lanes;
+  int64_t g;
+  int c;
+  group_lane(lanes, g, c);
   if (g >= (ACCUM ? n_rows : n_rows * T.n_rels)) return;
-  const int c = (int)(t - g * lanes) * 4;
   const int64_t row = ACCUM ? g : g / T.n_rels;
   const int r_begin = ACCUM ? 0 : (int)(g - row * T.n_rels), r_end = ACCUM ? T.n_rels : r_begin + 1;
   f4 total = f4{0.f, 0.f, 0.f, 0.f};
@@ -140,13 +114,12 @@ __global__ void __launch_bounds__(256) typed_mean_rows_kernel(const TypedTable T
     const egc_typed_rel& R = T.rel[r];
     int64_t p0, p1;
     row_range(R, row, p0, p1);
-    f4 acc = sum_entries<VEC>(R, p0, min(p0 + TM_CHUNK, p1), c, width);
-    if (p1 - p0 > TM_CHUNK) {   // chunks 1, 2, ...: their sums wait in the workspace, added in ascending order
-      const float* part = ws + ((T.slot0[r] + (p0 + TM_CHUNK) / TM_CHUNK) * lanes) * 4 + c;
-      const int64_t n_part = (p1 - p0 - 1) / TM_CHUNK;
+    f4 acc = sum_entries<VEC>(R, p0, min(p0 + ROW_CHUNK, p1), c, width);
+    int64_t first, n_part;   // chunks 1, 2, ...: their sums wait in the workspace, added in ascending order
+    row_partials(p0, p1, first, n_part);
+    const float* part = ws + ((T.slot0[r] + first) * lanes) * 4 + c;
 #pragma unroll 4
-      for (int64_t k = 0; k < n_part; ++k) acc += *reinterpret_cast<const f4*>(part + k * lanes * 4);
-    }
+    for (int64_t k = 0; k < n_part; ++k) acc += *reinterpret_cast<const f4*>(part + k * lanes * 4);
     if (R.post_mean) {
       const float deg = (float)(p1 - p0);
       acc = p1 > p0 ? acc / deg : f4{0.f, 0.f, 0.f, 0.f};
@@ -158,14 +131,14 @@ __global__ void __launch_bounds__(256) typed_mean_rows_kernel(const TypedTable T
 }
 
 static inline int64_t tm_slots(const egc_typed_rel& R) {
-  return (R.rowptr != nullptr && R.n_edges > TM_CHUNK) ? ceil_div(R.n_edges, TM_CHUNK) : 0;
+  return R.rowptr != nullptr ? chunk_slots(R.n_edges) : 0;
 }
 
 }  // namespace egc
 
 using namespace egc;
 
-int32_t egc_typed_mean_chunk(void) { return TM_CHUNK; }
+int32_t egc_typed_mean_chunk(void) { return ROW_CHUNK; }
 
 size_t egc_typed_mean_workspace_bytes(const egc_typed_rel* rels, int32_t n_rels, int32_t width) {
   if (rels == nullptr || n_rels <= 0 || n_rels > EGC_TYPED_MAX_RELATIONS || width <= 0) return 0;
@@ -186,13 +159,13 @@ int egc_typed_mean_f32(const egc_typed_rel* rels, int32_t n_rels, int64_t n_rows
   T.n_rels = n_rels;
   T.slot0[0] = 0;
   int64_t cols_end = accumulate ? width : 0;
-  bool vec = (width & 3) == 0 && (ld_out & 3) == 0 && tm_aligned16(out);
+  bool vec = all_mult4(width, ld_out) && all_aligned16(out);
   for (int r = 0; r < n_rels; ++r) {
     const egc_typed_rel& R = rels[r];
     if (R.n_edges < 0 || R.n_in_rows < 0 || R.ld_in < width || R.out_col < 0) return EGC_ERR_INVALID;
     if (R.rowptr != nullptr && R.n_edges > 0 && (R.col == nullptr || R.n_in_rows == 0)) return EGC_ERR_INVALID;
     if (R.in == nullptr && R.n_in_rows > 0) return EGC_ERR_INVALID;
-    if (R.n_edges >= ((int64_t)1 << 31) || R.n_in_rows >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;   // int32 rowptr / col
+    if (!counts_fit_int32(R.n_edges, R.n_in_rows)) return EGC_ERR_UNSUPPORTED;   // int32 rowptr / col
     T.rel[r] = R;
     if (R.rowptr == nullptr) T.rel[r].col = nullptr, T.rel[r].n_edges = 0;
     T.slot0[r + 1] = T.slot0[r] + tm_slots(R);
@@ -202,19 +175,19 @@ int egc_typed_mean_f32(const egc_typed_rel* rels, int32_t n_rels, int64_t n_rows
   if (ld_out < cols_end) return EGC_ERR_INVALID;
   const int64_t slots = T.slot0[n_rels];
   if (slots > 0) {
-    if (workspace == nullptr || !tm_aligned16(workspace) || workspace_bytes < (size_t)slots * lanes * 16) return EGC_ERR_WORKSPACE;
-    const int64_t blocks = ceil_div(slots * lanes, 256);
-    if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+    if (!workspace_ok(workspace, workspace_bytes, (size_t)slots * lanes * 16)) return EGC_ERR_WORKSPACE;
+    unsigned blocks;
+    if (grid_blocks(slots * lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
     float* ws = static_cast<float*>(workspace);
-    if (vec) typed_mean_chunks_kernel<true><<<(unsigned)blocks, 256, 0, stream>>>(T, n_rows, width, lanes, ws);
-    else typed_mean_chunks_kernel<false><<<(unsigned)blocks, 256, 0, stream>>>(T, n_rows, width, lanes, ws);
+    if (vec) typed_mean_chunks_kernel<true><<<blocks, 256, 0, stream>>>(T, n_rows, width, lanes, ws);
+    else typed_mean_chunks_kernel<false><<<blocks, 256, 0, stream>>>(T, n_rows, width, lanes, ws);
     EGC_LAUNCH_CHECK("typed_mean_chunks_kernel");
   }
-  const int64_t blocks = ceil_div((accumulate ? n_rows : n_rows * n_rels) * lanes, 256);
-  if (blocks >= ((int64_t)1 << 31)) return EGC_ERR_UNSUPPORTED;
+  unsigned blocks;
+  if (grid_blocks((accumulate ? n_rows : n_rows * n_rels) * lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
   const float* ws = static_cast<const float*>(workspace);
 #define EGC_TYPED_ROWS(V, A) \
-  typed_mean_rows_kernel<V, A><<<(unsigned)blocks, 256, 0, stream>>>(T, n_rows, width, lanes, out, ld_out, ws)
+  typed_mean_rows_kernel<V, A><<<blocks, 256, 0, stream>>>(T, n_rows, width, lanes, out, ld_out, ws)
   if (vec && accumulate) EGC_TYPED_ROWS(true, true);
   else if (vec) EGC_TYPED_ROWS(true, false);
   else if (accumulate) EGC_TYPED_ROWS(false, true);
