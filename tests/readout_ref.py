@@ -51,3 +51,36 @@ def backward(d_out: torch.Tensor, seg: torch.Tensor, op: str, n_rows: int, arg=N
     src = d_out / cnt.clamp(min=1).to(torch.float32)[:, None] if op == "mean" else d_out
     d_x[rows] = src[owner]
     return d_x
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The sweep of tests/test_readout_shapes_gpu.py (its properties are asserted without a GPU in tests/test_readout_shapes_cpu.py).
+# ---------------------------------------------------------------------------------------------------------------------
+RD_AHEAD = 8                   # rows requested together by the forward kernel
+# segment lengths around one, two and three batches of rows, the empty one and a long one
+LADDER = (0, 1, 7, 8, 9, 15, 16, 17, 23, 24, 25, 64)
+# one lane; two; a scalar width; 63 / 64 / 65 lanes; 256 / 257 / 258 lanes, a group wider than a workgroup; both forms
+WIDTHS = (1, 2, 3, 4, 5, 8, 77, 252, 256, 260, 1024, 1028, 1030)
+
+
+def ladder_sizes(order):
+    """Segment sizes: the ladder ("up": as listed, "down": reversed) with an empty segment first, in the middle and last."""
+    body = list(LADDER if order == "up" else LADDER[::-1])
+    body = [n for n in body if n != 0]
+    half = len(body) // 2
+    return [0] + body[:half] + [0] + body[half:] + [0]
+
+
+def ladder_batch(order):
+    """(batch vector int64 [N], number of graphs) of ladder_sizes(order)."""
+    sizes = torch.tensor(ladder_sizes(order))
+    return torch.repeat_interleave(torch.arange(sizes.numel()), sizes), int(sizes.numel())
+
+
+def same_bits_or_both_nan(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """Equality of two float tensors where a NaN equals a NaN (an add that makes a NaN need not make the same payload on
+    two machines); everything else must be equal."""
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    na, nb = torch.isnan(a), torch.isnan(b)
+    return torch.equal(na, nb) and torch.equal(torch.where(na, torch.zeros_like(a), a), torch.where(nb, torch.zeros_like(b), b))

@@ -131,3 +131,74 @@ def log_softmax_grad_bound(g, out, n_classes):
     s = g.sum(dim=1, keepdim=True)
     dx = g - e * s
     return 1.01 * (e * (n_classes - 1) * U * s_abs + 4.0 * U * (e * s).abs() + U * dx.abs()) + TINY * (1.0 + s.abs())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Inputs, and the geometry table of tests/test_softmax_shapes_gpu.py (guarded without a GPU by test_softmax_shapes_cpu.py).
+# ---------------------------------------------------------------------------------------------------------------------
+KINDS = ["randn1", "randn10", "randn50", "dominant", "equal"]
+
+
+def logits(n, c, ld, kind, seed):
+    """CPU float32 logits [n, ld]: the class columns by `kind` ("mixed": the five kinds row after row), NaN in the padding."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(n, ld, generator=g)
+    kinds = [kind] * n if kind != "mixed" else [KINDS[r % len(KINDS)] for r in range(n)]
+    for k in set(kinds):
+        rows = torch.tensor([r for r in range(n) if kinds[r] == k], dtype=torch.int64)
+        if k.startswith("randn"):
+            x[rows] *= float(k[5:])
+        elif k == "dominant":
+            x[rows, torch.randint(0, c, (rows.numel(),), generator=g)] += 100.0
+        else:
+            x[rows] = x[rows, :1].expand(-1, ld).clone()
+    x[:, c:] = float("nan")
+    return x
+
+
+def ties_logits(n, c, ld, seed):
+    """Integer-valued rows drawn from {0, 1, 2}: the maximum occurs several times in most rows.  NaN in the padding."""
+    x = torch.randint(0, 3, (n, ld), generator=torch.Generator().manual_seed(seed)).float()
+    x[:, c:] = float("nan")
+    return x
+
+
+def tied_share(x, n_classes):
+    """The share of rows whose maximum occurs twice or more."""
+    v = x[:, :n_classes]
+    return float(((v == v.max(dim=1, keepdim=True).values).sum(dim=1) >= 2).float().mean())
+
+
+def sample_index(n, share, seed):
+    """A permutation sample of round(share n) of the n rows, unsorted."""
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:int(round(n * share))]
+
+
+SM_CHUNK = 128          # rows of a workgroup (include/egc_hip.h)
+SM_BLOCK = 256          # threads of a workgroup = chunk sums a finalize trip takes in
+# The ten (lanes G = 2^gl, pieces K per lane) cells of the launcher as (first, last) class count: gl 0..5 with K = 1, then
+# gl = 6 with K = 1..4.
+CELLS = [(1, 4), (5, 8), (9, 16), (17, 32), (33, 64), (65, 128), (129, 256), (257, 512), (513, 768), (769, 1024)]
+
+
+def roundup4(c):
+    return (c + 3) // 4 * 4
+
+
+def cell_geometries(c_lo, c_hi):
+    """(n_classes, ld) x 3 of a cell: the vector form in all four kernels; a scalar log-softmax with vector NLL kernels whose
+    last piece straddles n_classes; an odd stride, scalar everywhere."""
+    return [(c_hi, c_hi), (c_lo, roundup4(c_lo)), (c_lo, c_lo)]
+
+
+# ld far beyond 4 K G: the zero-fill loop behind the registers' columns runs several trips (both forms)
+WIDE_PADDING = [(10, 64), (10, 63), (40, 128), (349, 1024)]
+GEOMETRIES = [g for cell in CELLS for g in cell_geometries(*cell)] + WIDE_PADDING
+SWEEP_ROWS = 300        # two full chunks and a part
+# rows on, one before and one after a chunk edge, at G = 1 (256 groups for 128 rows: half of them idle), G = 16 and G = 64
+LADDER_ROWS = [1, 127, 128, 129, 255, 256, 257]
+LADDER_GEOMETRIES = [(4, 4), (61, 64), (349, 352)]
+# one, two and three trips of the finalize kernel's loop over the chunk sums
+FINALIZE_ROWS = [SM_CHUNK * SM_BLOCK, SM_CHUNK * SM_BLOCK + 1, SM_CHUNK * 2 * SM_BLOCK + 1]
+FINALIZE_GEOMETRY = (4, 4)
+UNALIGNED_GEOMETRIES = [(40, 40), (349, 352), (768, 768)]

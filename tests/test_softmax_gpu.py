@@ -27,34 +27,17 @@ import torch.nn.functional as F
 
 import egc_amd
 import softmax_ref as ref
+from softmax_ref import KINDS, logits as _logits
 from egc_amd.graph import _IndexFlag
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(40, 40), (10, 10), (349, 352), (349, 349), (1024, 1024), (1, 1), (7, 9)]
-KINDS = ["randn1", "randn10", "randn50", "dominant", "equal"]
 INDEX_MODES = ["none", "all", "p54", "p85"]
 
 
 def _dev():
     return torch.device("cuda:0")
-
-
-def _logits(n, c, ld, kind, seed):
-    """CPU float32 logits [n, ld]: the class columns by `kind` ("mixed": the five kinds row after row), NaN in the padding."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, ld, generator=g)
-    kinds = [kind] * n if kind != "mixed" else [KINDS[r % len(KINDS)] for r in range(n)]
-    for k in set(kinds):
-        rows = torch.tensor([r for r in range(n) if kinds[r] == k], dtype=torch.int64)
-        if k.startswith("randn"):
-            x[rows] *= float(k[5:])
-        elif k == "dominant":
-            x[rows, torch.randint(0, c, (rows.numel(),), generator=g)] += 100.0
-        else:
-            x[rows] = x[rows, :1].expand(-1, ld).clone()
-    x[:, c:] = float("nan")
-    return x
 
 
 def _index(mode, n, seed):
@@ -134,11 +117,12 @@ def test_log_softmax_backward_within_bound_and_zero_padding(c, ld):
 
 
 # 3. fused NLL: loss, gradient, structure, determinism
-def _check_nll(x, y, idx, c, reduction, g=1.0, sel=None):
-    """Runs nll_log_softmax on the device twice and holds loss and gradient to the float64 reference's bounds."""
+def _check_nll(x, y, idx, c, reduction, g=1.0, sel=None, place=None):
+    """Runs nll_log_softmax on the device twice and holds loss and gradient to the float64 reference's bounds.  `place`:
+    how the CPU logits reach the device (default: a plain copy)."""
     dev = _dev()
     n, ld = x.shape
-    xd = x.to(dev).requires_grad_(True)
+    xd = (x.to(dev) if place is None else place(x)).requires_grad_(True)
     yd = y.to(dev)
     index = sel if sel is not None else (idx.to(dev) if idx is not None else None)
     mean = reduction == "mean"
