@@ -26,16 +26,15 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "egc_common.h"
+#include "egc_gemm_host.h"
 #include "egc_gemm_split.h"
 
 namespace egc {
 
-constexpr int XBM = 128;      // rows per block
-constexpr int XBN = 192;      // virtual columns per block (6 MFMA tiles)
-constexpr int XKT = 32;       // k per staging step
-constexpr int XLD = 40;       // LDS row stride in bf16 (80 B: conflict-free ds_read_b128 of 16-byte k-runs)
+constexpr int XKT = GEMM_KT;  // k per staging step (XBM, XBN, XLD: egc_gemm_host.h)
 
 __device__ inline u16 bf16_rn(float f) {
   const unsigned u = __float_as_uint(f);
@@ -82,7 +81,6 @@ __global__ void __launch_bounds__(256) pack_bf16x3_kernel(const float* __restric
   packed[base + (int64_t)NV * XKT] = m;
   packed[base + 2 * (int64_t)NV * XKT] = l;
 }
-
 
 // LDS operand read with an immediate offset (one address register for the whole tile loop)
 constexpr unsigned A_PLANE = XBM * XLD * 2, B_TILE = 32 * XLD * 2, SUB = 16 * 2;
@@ -370,7 +368,6 @@ __global__ void __launch_bounds__(256) basis_gemm_bf16x3_kernel(const float* __r
 // lane holds, for ONE x row, columns {8j + 4*(lane>>5) + 0..3}: four 16-byte stores per tile, no LDS
 // transpose; comb.bias is preloaded into the accumulators.
 // ---------------------------------------------------------------------------------------------
-constexpr int WS_ROWS = 32;
 
 template <int KSUB>  // number of 16-k MFMA sub-steps kept in registers: F_in <= 16 * KSUB
 __global__ void __launch_bounds__(512) basis_gemm_ws_kernel(const float* __restrict__ x, const u16* __restrict__ packed,
@@ -508,77 +505,38 @@ __global__ void __launch_bounds__(512) basis_gemm_ws_kernel(const float* __restr
   }
 }
 
-template <int KSUB>
-static int launch_ws(const float* x, const u16* packed, const float* bcat, int64_t M, int K, int W, float* bases, int ldb,
-                     float* weightings, int NV, hipStream_t stream) {
-  const int nt = NV / 32;               // wavefronts per block (<= 16)
-  const int threads = 64 * nt;
-  const int pieces = WS_ROWS * (16 * KSUB) / 4;
-  if (threads * 4 < pieces) return EGC_ERR_UNSUPPORTED;
-  const int64_t n_tiles64 = ceil_div(M, WS_ROWS);
-  if (n_tiles64 >= ((int64_t)1 << 31)) return EGC_ERR_INVALID;
-  const int n_tiles = (int)n_tiles64;
-  const size_t lds = (size_t)2 * 3 * WS_ROWS * (16 * KSUB + 8) * sizeof(u16);
-  // persistent grid: enough blocks to fill the chip a few times over, each walks tiles with stride gridDim
-  int blocks_per_cu = nt <= 4 ? 4 : (nt <= 8 ? 2 : 1);
-  int grid = 256 * blocks_per_cu;
-  if (grid > n_tiles) grid = n_tiles;
-  const int x_vec4 = (K % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  basis_gemm_ws_kernel<KSUB><<<grid, threads, lds, stream>>>(x, packed, bcat, M, K, W, bases, ldb, weightings, NV, n_tiles,
-                                                             x_vec4);
-  EGC_LAUNCH_CHECK("basis_gemm_ws_kernel");
-  return EGC_OK;
-}
-
-static inline int round_up32(int v) { return (v + 31) & ~31; }
-
 // (egc_layer_forward_packed, egc_aggregate.hip)
 int basis_transform_packed_folded(const float* x, const void* packed, const float* bcat, int64_t n_nodes, int32_t f_in,
                                   int32_t f_g, int32_t w_cols, int32_t flags, float* bases, int32_t ldb, float* weightings,
                                   const float* dis, int fold_s, int fold_m, hipStream_t stream) {
-  if (n_nodes < 0 || f_in <= 0 || f_g <= 0 || w_cols <= 0 || ldb != ((f_g + 3) & ~3)) return EGC_ERR_INVALID;
-  if (x == nullptr || packed == nullptr || bases == nullptr || weightings == nullptr || dis == nullptr) return EGC_ERR_INVALID;
-  const int NV = round_up32(ldb + w_cols);
-  if ((flags & EGC_GEMM_24BIT) != 0 || !f16x2_shape(f_in, ldb, NV, w_cols) || w_cols % 32 != 0) return EGC_ERR_UNSUPPORTED;  // (= use_f16x2)
+  if (w_cols <= 0 || dis == nullptr || !gemm_sizes_ok(n_nodes, f_in, f_g, w_cols, ldb)) return EGC_ERR_INVALID;
+  if (!gemm_pointers_ok(x, packed, bases, weightings, w_cols)) return EGC_ERR_INVALID;
+  const GemmPlan p = gemm_plan(f_in, f_g, w_cols, flags);
+  if (p.layout != GEMM_F16X2 || w_cols % 32 != 0) return EGC_ERR_UNSUPPORTED;
   if (n_nodes == 0) return EGC_OK;
-  return f16x2_launch(x, packed, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, stream, dis, fold_s, fold_m);
+  return f16x2_launch(x, packed, bcat, n_nodes, p, bases, weightings, stream, dis, fold_s, fold_m);
 }
 
 }  // namespace egc
 
 using namespace egc;
+template <int V>
+using int_c = std::integral_constant<int, V>;
 
 extern "C" {
 
 size_t egc_basis_pack_bytes(int32_t f_in, int32_t f_g, int32_t w_cols) {
-  if (f_in <= 0 || f_g <= 0 || w_cols < 0) return 0;
-  const int ldb = (f_g + 3) & ~3;
-  const int NV = round_up32(ldb + w_cols);
-  const int KS = (f_in + XKT - 1) / XKT;
-  return std::max(std::max((size_t)KS * 3 * NV * XKT * sizeof(u16), f16x2_pack_bytes(KS, NV)),
-                  f16x2k_pack_bytes(f_in, f_g, ldb, w_cols));
-}
-
-// flags & EGC_GEMM_24BIT: operands split into THREE bf16 planes (24 significand bits: nothing of an fp32 operand is
-// dropped) whatever the shape -- the fp16x2 forms keep 22 bits, which layers with std / var amplify (egc_hip.h)
-static bool use_f16x2(int f_in, int ldb, int NV, int flags, int w_cols) {
-  return (flags & EGC_GEMM_24BIT) == 0 && f16x2_shape(f_in, ldb, NV, w_cols);
-}
-static bool use_f16x2k(int f_in, int f_g, int ldb, int w_cols, int flags) {
-  return (flags & EGC_GEMM_24BIT) == 0 && f16x2k_shape(f_in, f_g, ldb, w_cols);
+  return gemm_plan(f_in, f_g, w_cols, 0).pack_bytes_max;
 }
 
 static int basis_pack_strided(const float* wcat, int64_t rs, int64_t cs, int32_t f_in, int32_t f_g, int32_t w_cols,
                               void* packed, size_t packed_bytes, hipStream_t stream, int flags = 0) {
-  if (wcat == nullptr || packed == nullptr || f_in <= 0 || f_g <= 0 || w_cols < 0) return EGC_ERR_INVALID;
-  if (packed_bytes < egc_basis_pack_bytes(f_in, f_g, w_cols)) return EGC_ERR_WORKSPACE;
-  const int ldb = (f_g + 3) & ~3;
-  const int NV = round_up32(ldb + w_cols);
-  const int KS = (f_in + XKT - 1) / XKT;
-  if (use_f16x2(f_in, ldb, NV, flags, w_cols)) return f16x2_pack(wcat, rs, cs, f_in, f_g, w_cols, ldb, NV, KS, packed, stream);
-  if (use_f16x2k(f_in, f_g, ldb, w_cols, flags)) return f16x2k_pack(wcat, rs, cs, f_in, f_g, ldb, w_cols, packed, stream);
-  const int total = KS * NV * XKT;
-  pack_bf16x3_kernel<<<(total + 255) / 256, 256, 0, stream>>>(wcat, rs, cs, f_in, f_g, w_cols, ldb, NV, KS, (u16*)packed);
+  const GemmPlan p = gemm_plan(f_in, f_g, w_cols, flags);
+  if (wcat == nullptr || packed == nullptr || !p.valid) return EGC_ERR_INVALID;
+  if (packed_bytes < p.pack_bytes_max) return EGC_ERR_WORKSPACE;
+  if (p.layout == GEMM_F16X2) return f16x2_pack(wcat, rs, cs, p, packed, stream);
+  if (p.layout == GEMM_F16X2K) return f16x2k_pack(wcat, rs, cs, p, packed, stream);
+  pack_bf16x3_kernel<<<(p.KS * p.NV * XKT + 255) / 256, 256, 0, stream>>>(wcat, rs, cs, f_in, f_g, w_cols, p.ldb, p.NV, p.KS, (u16*)packed);
   EGC_LAUNCH_CHECK("pack_bf16x3_kernel");
   return EGC_OK;
 }
@@ -602,73 +560,52 @@ int egc_basis_pack_transposed(const float* wt, int64_t ld, int32_t f_in, int32_t
 int egc_basis_transform_packed(const float* x, const void* packed, const float* bcat, int64_t n_nodes, int32_t f_in,
                                int32_t f_g, int32_t w_cols, float* bases, int32_t ldb, float* weightings,
                                egc_stream_t stream_) {
-  return egc_basis_transform_packed_ex(x, packed, bcat, n_nodes, f_in, f_g, w_cols, 0, bases, ldb, weightings, stream_);
-}
-
-int egc_basis_transform_packed_add(const float* x, const void* packed, const float* bcat, int64_t n_nodes, int32_t f_in,
-                                   int32_t f_g, int32_t w_cols, int32_t flags, const float* bases_addend, float* bases, int32_t ldb,
-                                   float* weightings, egc_stream_t stream_) {
-  if (bases_addend == nullptr) return egc_basis_transform_packed_ex(x, packed, bcat, n_nodes, f_in, f_g, w_cols, flags, bases, ldb, weightings, stream_);
-  if (n_nodes < 0 || f_in <= 0 || f_g <= 0 || w_cols < 0 || ldb != ((f_g + 3) & ~3)) return EGC_ERR_INVALID;
-  if (n_nodes == 0) return EGC_OK;
-  if (x == nullptr || packed == nullptr || bases == nullptr || (w_cols > 0 && weightings == nullptr)) return EGC_ERR_INVALID;
-  if (!use_f16x2k(f_in, f_g, ldb, w_cols, flags)) return EGC_ERR_UNSUPPORTED;   // only the long-k kernels carry the addend
-  return f16x2k_launch(x, packed, bcat, n_nodes, f_in, f_g, ldb, w_cols, bases, weightings, (hipStream_t)stream_, bases_addend);
+  return egc_basis_transform_packed_add(x, packed, bcat, n_nodes, f_in, f_g, w_cols, 0, nullptr, bases, ldb, weightings, stream_);
 }
 
 int egc_basis_transform_packed_ex(const float* x, const void* packed, const float* bcat, int64_t n_nodes, int32_t f_in,
                                   int32_t f_g, int32_t w_cols, int32_t flags, float* bases, int32_t ldb, float* weightings,
                                   egc_stream_t stream_) {
+  return egc_basis_transform_packed_add(x, packed, bcat, n_nodes, f_in, f_g, w_cols, flags, nullptr, bases, ldb, weightings, stream_);
+}
+
+// The planes were packed in the plan's layout, each family's in its own fragment order: the plan's family and no other reads them.
+int egc_basis_transform_packed_add(const float* x, const void* packed, const float* bcat, int64_t n_nodes, int32_t f_in,
+                                   int32_t f_g, int32_t w_cols, int32_t flags, const float* bases_addend, float* bases, int32_t ldb,
+                                   float* weightings, egc_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (n_nodes < 0 || f_in <= 0 || f_g <= 0 || w_cols < 0 || ldb != ((f_g + 3) & ~3)) return EGC_ERR_INVALID;
+  if (!gemm_sizes_ok(n_nodes, f_in, f_g, w_cols, ldb)) return EGC_ERR_INVALID;
   if (n_nodes == 0) return EGC_OK;
-  if (x == nullptr || packed == nullptr || bases == nullptr || (w_cols > 0 && weightings == nullptr)) return EGC_ERR_INVALID;
-  const int NV = round_up32(ldb + w_cols);
-  const int KS = (f_in + XKT - 1) / XKT;
-  if (use_f16x2(f_in, ldb, NV, flags, w_cols))  // the planes were packed for this kernel: no other form can read them
-    return f16x2_launch(x, packed, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, stream);
-  if (use_f16x2k(f_in, f_g, ldb, w_cols, flags))  // likewise: its planes are in its own fragment order
-    return f16x2k_launch(x, packed, bcat, n_nodes, f_in, f_g, ldb, w_cols, bases, weightings, stream);
-  if (f_in <= 128 && NV <= 256) {  // weight-stationary form (<= 8 wavefronts)
-    const u16* pk = (const u16*)packed;
-    int st;
-    if (f_in <= 32) st = launch_ws<2>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, stream);
-    else if (f_in <= 64) st = launch_ws<4>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, stream);
-    else if (f_in <= 96) st = launch_ws<6>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, stream);
-    else st = launch_ws<8>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, stream);
-    if (st != EGC_ERR_UNSUPPORTED) return st;  // too few wavefronts to stage a tile: use the LDS-staged kernel
-  }
-  const int64_t mblocks = ceil_div(n_nodes, XBM);
-  if (mblocks >= ((int64_t)1 << 31)) return EGC_ERR_INVALID;
-  const bool vec4 = (f_in % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  const int full = NV / XBN;  // column blocks of the full 192 columns; a narrower remainder block follows
+  if (!gemm_pointers_ok(x, packed, bases, weightings, w_cols)) return EGC_ERR_INVALID;
+  const GemmPlan p = gemm_plan(f_in, f_g, w_cols, flags);
+  if (p.layout == GEMM_F16X2K) return f16x2k_launch(x, packed, bcat, n_nodes, p, bases, weightings, stream, bases_addend);
+  if (bases_addend != nullptr) return EGC_ERR_UNSUPPORTED;   // only the long-k kernels carry the addend
+  if (p.layout == GEMM_F16X2) return f16x2_launch(x, packed, bcat, n_nodes, p, bases, weightings, stream);
+  const auto ls = gemm_bf16x3_launches(n_nodes, f_in, p.NV, f_in % 4 == 0 && gemm_aligned16(x));
   const u16* pk = (const u16*)packed;
-  if (NV == 224 && vec4) {  // 193..224 columns: one 7-tile block, one pass over x
-    dim3 grid((unsigned)mblocks, 1);
-    basis_gemm_bf16x3_kernel<true, 7><<<grid, 256, 0, stream>>>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, KS, 0);
-    EGC_LAUNCH_CHECK("basis_gemm_bf16x3_kernel");
-    return EGC_OK;
+  for (int l = 0; l < ls.n; ++l) {   // as described there: the instances compiled are exactly these
+    const GemmBf16x3Launch& g = ls.l[l];
+    auto ws = [&](auto ksub) {
+      basis_gemm_ws_kernel<ksub()><<<g.grid_x, g.threads, g.lds, stream>>>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, p.NV,
+                                                                          g.n_tiles, (int)g.vec4);
+    };
+    auto staged = [&](auto vec4, auto nt) {
+      basis_gemm_bf16x3_kernel<vec4(), nt()><<<dim3(g.grid_x, g.grid_y), g.threads, 0, stream>>>(x, pk, bcat, n_nodes, f_in, w_cols, bases,
+                                                                                                ldb, weightings, p.NV, p.KS, g.vblock0);
+    };
+    if (g.ksub == 2) ws(int_c<2>{});
+    else if (g.ksub == 4) ws(int_c<4>{});
+    else if (g.ksub == 6) ws(int_c<6>{});
+    else if (g.ksub == 8) ws(int_c<8>{});
+    else if (g.nt == 7) staged(std::true_type{}, int_c<7>{});   // (the 7- and 4-tile blocks come with vec4 only)
+    else if (g.nt == 4) staged(std::true_type{}, int_c<4>{});
+    else if (g.nt == 6 && g.vec4) staged(std::true_type{}, int_c<6>{});
+    else if (g.nt == 6) staged(std::false_type{}, int_c<6>{});
+    else if (g.vec4) staged(std::true_type{}, int_c<0>{});
+    else staged(std::false_type{}, int_c<0>{});
+    EGC_LAUNCH_CHECK(g.ksub > 0 ? "basis_gemm_ws_kernel" : "basis_gemm_bf16x3_kernel");
   }
-  if (full > 0) {
-    dim3 grid((unsigned)mblocks, (unsigned)full);
-    if (vec4)
-      basis_gemm_bf16x3_kernel<true, 6><<<grid, 256, 0, stream>>>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, KS, 0);
-    else
-      basis_gemm_bf16x3_kernel<false, 6><<<grid, 256, 0, stream>>>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, KS, 0);
-    EGC_LAUNCH_CHECK("basis_gemm_bf16x3_kernel");
-  }
-  if (NV % XBN != 0) {
-    dim3 grid((unsigned)mblocks, 1);
-    const bool four = (NV - full * XBN) == 128;  // a 128-column remainder (or a 128-column GEMM): pipelined too
-    if (vec4 && four)
-      basis_gemm_bf16x3_kernel<true, 4><<<grid, 256, 0, stream>>>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, KS, full);
-    else if (vec4)
-      basis_gemm_bf16x3_kernel<true, 0><<<grid, 256, 0, stream>>>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, KS, full);
-    else
-      basis_gemm_bf16x3_kernel<false, 0><<<grid, 256, 0, stream>>>(x, pk, bcat, n_nodes, f_in, w_cols, bases, ldb, weightings, NV, KS, full);
-    EGC_LAUNCH_CHECK("basis_gemm_bf16x3_kernel");
-  }
-  return EGC_OK;
+  return ls.status;
 }
 
 }  // extern "C"

@@ -24,8 +24,10 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "egc_common.h"
+#include "egc_gemm_host.h"
 #include "egc_gemm_split.h"
 
 namespace egc {
@@ -58,7 +60,6 @@ __global__ void __launch_bounds__(64) pack_f16x2_kernel(const float* __restrict_
   }
   if (lane == 0) reinterpret_cast<float*>(packed + (int64_t)KS * 2 * NV * GEMM_KT)[v] = col.inv;
 }
-
 
 // What bounds this kernel is each SIMD's vector issue port and its matrix pipe TOGETHER: a VALU instruction
 // holds the port for 4 cycles, a v_mfma_f32_32x32x16_f16 for 8 and the pipe for 32 (MI355X_MICROARCH.md,
@@ -375,72 +376,42 @@ __global__ void __launch_bounds__(F16X2_THREADS) basis_gemm_f16x2_kernel(const f
   EGC_VMCNT(0);  // no DMA may still be writing this block's LDS when it is handed to the next block
 }
 
-size_t f16x2_pack_bytes(int KS, int NV) { return (size_t)KS * 2 * NV * GEMM_KT * sizeof(u16) + (size_t)NV * sizeof(float); }
-
-int f16x2_pack(const float* wcat, int64_t rs, int64_t cs, int f_in, int f_g, int w_cols, int ldb, int NV, int KS, void* packed,
-               hipStream_t stream) {
-  pack_f16x2_kernel<<<NV, 64, 0, stream>>>(wcat, rs, cs, f_in, f_g, w_cols, ldb, NV, KS, (u16*)packed);
+int f16x2_pack(const float* wcat, int64_t rs, int64_t cs, const GemmPlan& p, void* packed, hipStream_t stream) {
+  pack_f16x2_kernel<<<p.NV, 64, 0, stream>>>(wcat, rs, cs, p.f_in, p.f_g, p.w_cols, p.ldb, p.NV, p.KS, (u16*)packed);
   EGC_LAUNCH_CHECK("pack_f16x2_kernel");
   return EGC_OK;
 }
 
-// one instantiation per place of the mean in the quad (FM) and the plain form (FM = -1)
-template <int FM>
-static int f16x2_launch_fm(int grid, size_t lds, const float* x, const void* packed, const float* bcat, int64_t M, int K, int W,
-                           float* bases, int ldb, float* weightings, int NV, int rows_per_block, const float* dis, int fold_s,
-                           hipStream_t stream) {
-  EGC_ALLOW_DYNAMIC_LDS(&basis_gemm_f16x2_kernel<FM>, 160 * 1024, "f16x2");
-  basis_gemm_f16x2_kernel<FM><<<grid, F16X2_THREADS, lds, stream>>>(x, (const u16*)packed, bcat, M, K, W, bases, ldb, weightings,
-                                                                    NV, rows_per_block, dis, fold_s);
-  EGC_LAUNCH_CHECK("basis_gemm_f16x2_kernel");
-  return EGC_OK;
-}
-
-static int f16x2_launch_rows(const float* x, const void* packed, const float* bcat, int64_t M, int K, int W, float* bases,
-                             int ldb, float* weightings, int NV, const float* dis, int fold_s, int fold_m, hipStream_t stream) {
-  constexpr int ROWS = F16X2_ROWS;
-  const int threads = F16X2_THREADS;
-  (void)threads;
-  const int64_t n_tiles64 = (M + ROWS - 1) / ROWS;
-  if (n_tiles64 >= ((int64_t)1 << 31)) return EGC_ERR_INVALID;
-  const int n_tiles = (int)n_tiles64;
-  const size_t lds = (size_t)F16X2_LDS_BYTES;
-  static_assert(F16X2_LDS_BYTES <= 160 * 1024, "LDS of one CU");
-  int grid = 256;  // one 12-wavefront block per CU (registers: 3 wavefronts per SIMD)
-  if (grid > n_tiles) grid = n_tiles;
-  const int rows_per_block = (int)((M + grid - 1) / grid);   // contiguous, equal row ranges
-  int st;
-  switch (fold_m) {
-    case 0: st = f16x2_launch_fm<0>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, dis, fold_s, stream); break;
-    case 1: st = f16x2_launch_fm<1>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, dis, fold_s, stream); break;
-    case 2: st = f16x2_launch_fm<2>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, dis, fold_s, stream); break;
-    case 3: st = f16x2_launch_fm<3>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, dis, fold_s, stream); break;
-    default: st = f16x2_launch_fm<-1>(grid, lds, x, packed, bcat, M, K, W, bases, ldb, weightings, NV, rows_per_block, nullptr, -1, stream);
-  }
-  if (st != EGC_OK) return st;
-  return EGC_OK;
-}
-
-// The kernel addresses x, bases and weightings through 32-bit buffer offsets (and drops masked stores at
-// offset 2^31 + scalar row offset): row ranges of less than 2 GiB per array are launched one after another.
-int f16x2_launch(const float* x, const void* packed, const float* bcat, int64_t M, int K, int W, float* bases, int ldb,
-                 float* weightings, int NV, hipStream_t stream, const float* dis, int fold_s, int fold_m) {
-  if (NV != 192 || K > F16X2_KP || K % 4 != 0 || (ldb % 32 != 0 && W != 0) || (reinterpret_cast<uintptr_t>(x) & 15) != 0)
-    return EGC_ERR_UNSUPPORTED;
+int f16x2_launch(const float* x, const void* packed, const float* bcat, int64_t M, const GemmPlan& p, float* bases,
+                 float* weightings, hipStream_t stream, const float* dis, int fold_s, int fold_m) {
+  const int K = p.f_in, W = p.w_cols, ldb = p.ldb, NV = p.NV;
+  if (p.layout != GEMM_F16X2 || !gemm_aligned16(x)) return EGC_ERR_UNSUPPORTED;   // (the kernel's shapes: gemm_f16x2_shape)
   const bool fold = fold_m >= 0;
   if (fold && (dis == nullptr || W % 32 != 0 || fold_m > 3 || fold_s < 0 || fold_s > 3 || fold_s == fold_m)) return EGC_ERR_INVALID;
   const int W_out = fold ? W / 4 * 3 : W;
-  const int64_t widest = std::max(std::max(K, ldb), W);
-  int64_t max_rows = ((int64_t)0x7FFFFFF0 / (4 * widest)) & ~(int64_t)(F16X2_ROWS - 1);
-  if (const char* e = getenv("EGC_GEMM_MAX_ROWS")) max_rows = std::max<int64_t>(F16X2_ROWS, atoll(e) & ~(int64_t)(F16X2_ROWS - 1));  // tests
-  for (int64_t r0 = 0; r0 < M; r0 += max_rows) {
-    const int64_t rows = std::min(max_rows, M - r0);
-    const int st = f16x2_launch_rows(x + r0 * K, packed, bcat, rows, K, W, bases + r0 * ldb, ldb,
-                                     weightings != nullptr ? weightings + r0 * W_out : nullptr, NV, fold ? dis + r0 : nullptr,
-                                     fold_s, fold ? fold_m : -1, stream);
-    if (st != EGC_OK) return st;
-  }
-  return EGC_OK;
+  static_assert(F16X2_LDS_BYTES <= 160 * 1024, "LDS of one CU");
+  return gemm_for_row_ranges(M, std::max(std::max(K, ldb), W), F16X2_ROWS, [&](int64_t r0, int64_t rows) -> int {
+    int n_tiles;
+    if (const int st = gemm_row_tiles(rows, F16X2_ROWS, n_tiles); st != EGC_OK) return st;
+    const int grid = gemm_grid(1, n_tiles);  // one 12-wavefront block per CU (registers: 3 wavefronts per SIMD)
+    const int rows_per_block = (int)((rows + grid - 1) / grid);   // contiguous, equal row ranges
+    // one instantiation per place of the mean in the quad (FM) and the plain form (FM = -1)
+    auto launch = [&](auto fm) -> int {
+      EGC_ALLOW_DYNAMIC_LDS(&basis_gemm_f16x2_kernel<fm()>, 160 * 1024, "f16x2");
+      basis_gemm_f16x2_kernel<fm()><<<grid, F16X2_THREADS, (size_t)F16X2_LDS_BYTES, stream>>>(
+          x + r0 * K, (const u16*)packed, bcat, rows, K, W, bases + r0 * ldb, ldb, weightings != nullptr ? weightings + r0 * W_out : nullptr,
+          NV, rows_per_block, fold ? dis + r0 : nullptr, fold ? fold_s : -1);
+      EGC_LAUNCH_CHECK("basis_gemm_f16x2_kernel");
+      return EGC_OK;
+    };
+    switch (fold_m) {
+      case 0: return launch(std::integral_constant<int, 0>{});
+      case 1: return launch(std::integral_constant<int, 1>{});
+      case 2: return launch(std::integral_constant<int, 2>{});
+      case 3: return launch(std::integral_constant<int, 3>{});
+      default: return launch(std::integral_constant<int, -1>{});
+    }
+  });
 }
 
 }  // namespace egc

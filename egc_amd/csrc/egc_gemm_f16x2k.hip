@@ -26,13 +26,13 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "egc_common.h"
+#include "egc_gemm_host.h"
 #include "egc_gemm_split.h"
 
 namespace egc {
-
-constexpr int KROWS = 16;  // rows of an x tile = one MFMA row block
 
 // Virtual column space: column tiles of 16; tiles [0, TB) hold the bases columns (ldb of them, the rest of the last
 // tile is padding that is never stored), tiles [TB, NT) the weightings columns.
@@ -90,7 +90,6 @@ __device__ inline void vmwait_rt(int n) {
     default: vmwait_k<0>(); break;
   }
 }
-
 
 template <int KS, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_kernel(const float* __restrict__ x, const u16* __restrict__ packed,
@@ -550,203 +549,74 @@ __global__ void __launch_bounds__(WAVES * 64) basis_gemm_f16x2k_spec_kernel(cons
   }
 }
 
-bool f16x2k_shape(int f_in, int f_g, int ldb, int w_cols) {
-  if (f_in <= 128 || f_in > 384 || (f_in & 3) != 0) return false;
-  const int NT = (ldb + 15) / 16 + (w_cols + 15) / 16;
-  const int per_launch = NT <= 16 ? NT : (NT + 1) / 2;   // two launches beyond 16 column tiles
-  if ((f_in + 31) / 32 == 12 && per_launch > 12) return false;  // 96 weight registers do not fit four wavefronts per SIMD
-  if (NT < 1 || NT > 32) return false;
-  // launch_k's staging limits, on the narrower launch: a thread stages at most 16 pieces of 16 bytes of the x tile,
-  // and the tile, its planes and the bias rows fit the LDS (a narrow GEMM over a long k -- the dx GEMM of a layer with
-  // few input features -- has too few wavefronts to stage its tile: bf16x3 kernels then)
-  const int narrow = NT <= 16 ? NT : NT / 2;
-  const int KS = (f_in + 31) / 32, threads = narrow * 64;
-  const int R = (KROWS * (f_in / 4) + threads - 1) / threads;
-  const size_t lds = (size_t)2 * R * threads * 16 + (size_t)4 * KROWS * (32 * KS + 16) * sizeof(u16) + (2 * KROWS + 2 * 16 * NT) * sizeof(float);
-  return R <= 16 && lds <= 160 * 1024;
-}
+static KCols kcols(const GemmPlan& p) { return KCols{p.f_g, p.ldb, p.w_cols, p.TB, p.NT}; }
 
-static KCols kcols(int f_g, int ldb, int w_cols) {
-  KCols c;
-  c.F_g = f_g; c.ldb = ldb; c.W = w_cols;
-  c.TB = (ldb + 15) / 16;
-  c.NT = c.TB + (w_cols + 15) / 16;
-  return c;
-}
-
-size_t f16x2k_pack_bytes(int f_in, int f_g, int ldb, int w_cols) {
-  const KCols c = kcols(f_g, ldb, w_cols);
-  const int KS = (f_in + 31) / 32;
-  return (size_t)c.NT * KS * 2 * 64 * 8 * sizeof(u16) + (size_t)c.NT * 16 * sizeof(float);
-}
-
-int f16x2k_pack(const float* wcat, int64_t rs, int64_t cs, int f_in, int f_g, int ldb, int w_cols, void* packed,
-                hipStream_t stream) {
-  const KCols c = kcols(f_g, ldb, w_cols);
-  const int KS = (f_in + 31) / 32;
-  pack_f16x2k_kernel<<<c.NT * 16, 64, 0, stream>>>(wcat, rs, cs, f_in, c, KS, (u16*)packed);
+int f16x2k_pack(const float* wcat, int64_t rs, int64_t cs, const GemmPlan& p, void* packed, hipStream_t stream) {
+  pack_f16x2k_kernel<<<p.NT * 16, 64, 0, stream>>>(wcat, rs, cs, p.f_in, kcols(p), p.KS, (u16*)packed);
   EGC_LAUNCH_CHECK("pack_f16x2k_kernel");
   return EGC_OK;
 }
 
-template <int KS, int WAVES>
-static int launch_k(const float* x, const u16* packed, const float* bcat, int64_t M, int K, const KCols& c, float* bases,
-                    float* weightings, hipStream_t stream, int tile0, int ntl, const float* addend) {
-  const int64_t n_tiles64 = ceil_div(M, KROWS);
-  if (n_tiles64 >= ((int64_t)1 << 31)) return EGC_ERR_INVALID;
-  const int n_tiles = (int)n_tiles64;
-  // row stride of the planes in fp16: the B fragments are ds_read_b128 of lanes (row j = lane & 15, k piece lane >> 4);
-  // with 32 KS + 16 every one of the instruction's four 16-lane groups touches 16 distinct 4-bank slots
-  // (32 KS + 8 leaves five 2-way conflicts per group)
-  const int LDX = 32 * KS + 16;
-  const size_t fixed = (size_t)4 * KROWS * LDX * sizeof(u16) + (2 * KROWS + 2 * 16 * c.NT) * sizeof(float);
-  // ---- separated roles: `nh` helper wavefronts next to the ntl multipliers (this launch: column tiles tile0 .. tile0 + ntl - 1)
-  const int nh = std::min(WAVES - ntl, 4);
-  // (where two workgroups of the everything-in-every-wavefront kernel share a CU -- short k, few column tiles -- that form
-  // stays: 52.7 against 62.3 us at 184 -> 96 + 32, N = 169,343)
-  bool two_per_cu = false;
-  {
-    const int threads = ntl * 64;
-    const int R0 = (int)ceil_div((int64_t)KROWS * (K / 4), threads);
-    const size_t lds0 = (size_t)2 * R0 * threads * 16 + fixed;
-    two_per_cu = KS <= 9 && std::min<size_t>((size_t)160 * 1024 / lds0, (size_t)(20 / ntl)) >= 2;
-  }
-  if (nh >= 2 && !two_per_cu) {
-    const int hthreads = nh * 64;
-    const int R = (int)ceil_div((int64_t)KROWS * (K / 4), hthreads);
-    const int slot_bytes = R * hthreads * 16;
-    int ring = (int)std::min<size_t>(4, ((size_t)160 * 1024 - fixed) / (size_t)slot_bytes);
-    while (ring > 2 && (ring - 2) * R > 32) --ring;
-    if (ring >= 2 && R <= 16) {
-      const size_t lds = (size_t)ring * slot_bytes + fixed;
-      auto kern = &basis_gemm_f16x2k_spec_kernel<KS, WAVES>;
-      EGC_ALLOW_DYNAMIC_LDS(kern, 160 * 1024, "f16x2 spec");
-      int grid = 256;
-      if (grid > n_tiles) grid = n_tiles;
-      kern<<<grid, (ntl + nh) * 64, lds, stream>>>(x, packed, bcat, M, K, c, bases, weightings, n_tiles, LDX, R, slot_bytes, tile0, ring,
-                                                   ntl, addend, ntl);
-      EGC_LAUNCH_CHECK("basis_gemm_f16x2k_spec_kernel");
-      return EGC_OK;
-    }
-  }
-  const int threads = ntl * 64;
-  const int R = (int)ceil_div((int64_t)KROWS * (K / 4), threads);
-  const int slot_bytes = R * threads * 16;
-  size_t lds = (size_t)2 * slot_bytes + fixed;
-  if (lds > 160 * 1024 || R > 16) return EGC_ERR_UNSUPPORTED;
-  auto kern = &basis_gemm_f16x2k_kernel<KS, WAVES>;
-  EGC_ALLOW_DYNAMIC_LDS(kern, 160 * 1024, "f16x2");
-  // workgroups per CU: as many as the LDS holds, within about five wavefronts per SIMD (the KS <= 9 kernels use up to
-  // 102 registers).  Short k leaves room for two (F_in = 192, 8 column tiles: 59 KB of LDS each), and the second one's
-  // matrix work covers the first one's barrier and split: 66.9 -> 50.1 us for the 192 -> 128 gradient GEMM at
-  // N = 169,343 (a third workgroup that does not fit measured 57 us: uneven CUs).
-  int per_cu = (int)std::min<size_t>((size_t)160 * 1024 / lds, (size_t)(20 / ntl));
-  if (KS > 9 || per_cu < 1) per_cu = 1;
-  int grid = 256 * per_cu;
-  if (grid > n_tiles) grid = n_tiles;
-  // depth of the raw-tile ring: what the LDS share of a workgroup holds next to the planes, at most 4 (and within the
-  // counted wait's range); a workgroup that shares its CU keeps 2
-  int ring = 2;
-  if (per_cu == 1) {
-    ring = (int)std::min<size_t>(4, ((size_t)160 * 1024 - fixed) / (size_t)slot_bytes);
-    while (ring > 2 && ((ring - 2) * (R + 1) + 4 > 32 || (size_t)ring * slot_bytes + fixed > (size_t)160 * 1024)) --ring;
-    if (ring < 2) ring = 2;
-    lds = (size_t)ring * slot_bytes + fixed;
-  }
-  kern<<<grid, threads, lds, stream>>>(x, packed, bcat, M, K, c, bases, weightings, n_tiles, LDX, R, slot_bytes, tile0, ring, addend);
-  EGC_LAUNCH_CHECK("basis_gemm_f16x2k_kernel");
-  return EGC_OK;
-}
-
-// One launch over ALL column tiles with two tiles per multiplier wavefront (K <= 224: 16 KS weight registers fit twelve wavefronts):
-// ceil(NT / 2) multipliers + the helpers that move and split x.  EGC_ERR_UNSUPPORTED where the tile ring does not fit.
+// One launch as gemm_longk_launches describes it (egc_gemm_host.h).  The instances compiled: the all-in-one kernel and the kernel
+// of multipliers and helpers with 12 and 16 wavefronts, and for KS <= 7 (16 KS weight registers fit twelve wavefronts) the
+// latter with two column tiles per multiplier.
 template <int KS>
-static int launch_k2(const float* x, const u16* packed, const float* bcat, int64_t M, int K, const KCols& c, float* bases,
-                     float* weightings, hipStream_t stream, const float* addend) {
-  constexpr int WAVES = 12;
-  const int64_t n_tiles64 = ceil_div(M, KROWS);
-  if (n_tiles64 >= ((int64_t)1 << 31)) return EGC_ERR_INVALID;
-  const int n_tiles = (int)n_tiles64;
-  const int LDX = 32 * KS + 16;
-  const size_t fixed = (size_t)4 * KROWS * LDX * sizeof(u16) + (2 * KROWS + 2 * 16 * c.NT) * sizeof(float);
-  const int nmf = (c.NT + 1) / 2, nh = WAVES - nmf;
-  if (nh < 2) return EGC_ERR_UNSUPPORTED;
-  const int hthreads = nh * 64;
-  const int R = (int)ceil_div((int64_t)KROWS * (K / 4), hthreads);
-  const int slot_bytes = R * hthreads * 16;
-  int ring = (int)std::min<size_t>(4, ((size_t)160 * 1024 - fixed) / (size_t)slot_bytes);
-  while (ring > 2 && (ring - 2) * R > 32) --ring;
-  if (ring < 2 || R > 16) return EGC_ERR_UNSUPPORTED;
-  const size_t lds = (size_t)ring * slot_bytes + fixed;
-  auto kern = &basis_gemm_f16x2k_spec_kernel<KS, WAVES, 2>;
-  EGC_ALLOW_DYNAMIC_LDS(kern, 160 * 1024, "f16x2 spec, two tiles");
-  int grid = 256;
-  if (grid > n_tiles) grid = n_tiles;
-  kern<<<grid, WAVES * 64, lds, stream>>>(x, packed, bcat, M, K, c, bases, weightings, n_tiles, LDX, R, slot_bytes, 0, ring, nmf, addend, c.NT);
-  EGC_LAUNCH_CHECK("basis_gemm_f16x2k_spec_kernel (two tiles per wavefront)");
-  return EGC_OK;
-}
-
-template <int KS>
-static int launch_ks(const float* x, const u16* packed, const float* bcat, int64_t M, int K, const KCols& c, float* bases,
-                     float* weightings, hipStream_t stream, const float* addend) {
-  if constexpr (KS <= 7) {
-    // 17 - 20 column tiles (224 / H4 / B4 with three aggregators forward: 14 + 3; the d x GEMM of 296 / H8 / B4: 19): ONE launch.
-    // From nine tiles on the two-tile form is also the faster single launch (half the operand reads per product, five to eight
-    // multipliers and as many wavefronts left to move and split x: 3 - 20 % at 9 - 16 tiles and 169 k rows, same bits; at eight tiles
-    // and fewer two workgroups of the all-in-one kernel per CU win: 60.6 against 67.0 us at 192 -> 128).
-    if (c.NT >= 9 && c.NT <= 20) {
-      const int st = launch_k2<KS>(x, packed, bcat, M, K, c, bases, weightings, stream, addend);
-      if (st != EGC_ERR_UNSUPPORTED) return st;
-    }
-  }
-  // more than 16 column tiles (e.g. 224/H4/B4 with three aggregators: 14 + 3; 300/H4/B4: 19 + 3; 304/H8/B8: 20 + 4): two
-  // launches over half of the tiles each -- x is read twice, which still beats the LDS-staged bf16x3 kernel 2 x
-  const int launches = c.NT <= 16 ? 1 : 2;
-  for (int l = 0, t0 = 0; l < launches; ++l) {
-    const int ntl = (c.NT - t0 + (launches - l) - 1) / (launches - l);
-    // up to 9 column tiles: 12 wavefronts (168 registers), 3-4 of them helpers; more: 16 wavefronts (128 registers) with
-    // 16 - ntl helpers (none at 16 tiles: the kernel in which every wavefront does everything)
-    const int st = ntl <= 9 ? launch_k<KS, 12>(x, packed, bcat, M, K, c, bases, weightings, stream, t0, ntl, addend)
-                            : launch_k<KS, 16>(x, packed, bcat, M, K, c, bases, weightings, stream, t0, ntl, addend);
-    if (st != EGC_OK) return st;
-    t0 += ntl;
-  }
-  return EGC_OK;
-}
-
-int f16x2k_launch(const float* x, const void* packed, const float* bcat, int64_t M, int K, int f_g, int ldb, int W,
-                  float* bases, float* weightings, hipStream_t stream, const float* addend) {
-  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(bases) & 15) != 0 ||
-      (W > 0 && (W & 3) == 0 && (reinterpret_cast<uintptr_t>(weightings) & 15) != 0))
+static int launch_ks(const GemmLongKLaunch& g, const float* x, const u16* packed, const float* bcat, int64_t M, int K, const KCols& c,
+                     float* bases, float* weightings, const float* addend, hipStream_t stream) {
+  int n_tiles;
+  if (const int st = gemm_row_tiles(M, KROWS, n_tiles); st != EGC_OK) return st;
+  const int grid = gemm_grid(g.per_cu, n_tiles);
+  auto all = [&](auto waves) -> int {
+    auto kern = &basis_gemm_f16x2k_kernel<KS, waves()>;
+    EGC_ALLOW_DYNAMIC_LDS(kern, 160 * 1024, "f16x2");
+    kern<<<grid, g.threads, g.lds, stream>>>(x, packed, bcat, M, K, c, bases, weightings, n_tiles, g.LDX, g.R, g.slot_bytes, g.tile0, g.ring,
+                                            addend);
+    EGC_LAUNCH_CHECK("basis_gemm_f16x2k_kernel");
+    return EGC_OK;
+  };
+  auto spec = [&](auto waves, auto tpw) -> int {
+    auto kern = &basis_gemm_f16x2k_spec_kernel<KS, waves(), tpw()>;
+    EGC_ALLOW_DYNAMIC_LDS(kern, 160 * 1024, "f16x2 spec");
+    kern<<<grid, g.threads, g.lds, stream>>>(x, packed, bcat, M, K, c, bases, weightings, n_tiles, g.LDX, g.R, g.slot_bytes, g.tile0, g.ring,
+                                            g.mult, addend, g.tiles);
+    EGC_LAUNCH_CHECK("basis_gemm_f16x2k_spec_kernel");
+    return EGC_OK;
+  };
+  constexpr std::integral_constant<int, 12> w12;
+  constexpr std::integral_constant<int, 16> w16;
+  if (g.form == LONGK_TWO_TILES) {
+    if constexpr (KS <= 7) return spec(w12, std::integral_constant<int, 2>{});
     return EGC_ERR_UNSUPPORTED;
-  if (addend != nullptr && ((reinterpret_cast<uintptr_t>(addend) & 15) != 0 || (ldb & 3) != 0)) return EGC_ERR_UNSUPPORTED;
-  const KCols c = kcols(f_g, ldb, W);
-  const u16* pk = (const u16*)packed;
-  const int64_t widest = std::max(std::max(K, ldb), W);
-  int64_t max_rows = ((int64_t)0x7FFFFFF0 / (4 * widest)) & ~(int64_t)(KROWS - 1);
-  if (const char* e = getenv("EGC_GEMM_MAX_ROWS")) max_rows = std::max<int64_t>(KROWS, atoll(e) & ~(int64_t)(KROWS - 1));  // tests
-  for (int64_t r0 = 0; r0 < M; r0 += max_rows) {
-    const int64_t rows = std::min(max_rows, M - r0);
-    const float* xr = x + r0 * K;
-    float* br = bases + r0 * ldb;
-    float* wr = weightings != nullptr ? weightings + r0 * W : nullptr;
-    const float* ar = addend != nullptr ? addend + r0 * ldb : nullptr;
-    int st;
-    switch ((K + 31) / 32) {
-      case 5: st = launch_ks<5>(xr, pk, bcat, rows, K, c, br, wr, stream, ar); break;
-      case 6: st = launch_ks<6>(xr, pk, bcat, rows, K, c, br, wr, stream, ar); break;
-      case 7: st = launch_ks<7>(xr, pk, bcat, rows, K, c, br, wr, stream, ar); break;
-      case 8: st = launch_ks<8>(xr, pk, bcat, rows, K, c, br, wr, stream, ar); break;
-      case 9: st = launch_ks<9>(xr, pk, bcat, rows, K, c, br, wr, stream, ar); break;
-      case 10: st = launch_ks<10>(xr, pk, bcat, rows, K, c, br, wr, stream, ar); break;
-      case 11: st = launch_ks<11>(xr, pk, bcat, rows, K, c, br, wr, stream, ar); break;
-      case 12: st = launch_ks<12>(xr, pk, bcat, rows, K, c, br, wr, stream, ar); break;
-      default: return EGC_ERR_UNSUPPORTED;
-    }
-    if (st != EGC_OK) return st;
   }
-  return EGC_OK;
+  if (g.form == LONGK_ROLES) return g.waves == 12 ? spec(w12, std::integral_constant<int, 1>{}) : spec(w16, std::integral_constant<int, 1>{});
+  return g.waves == 12 ? all(w12) : all(w16);
+}
+
+int f16x2k_launch(const float* x, const void* packed, const float* bcat, int64_t M, const GemmPlan& p, float* bases,
+                  float* weightings, hipStream_t stream, const float* addend) {
+  const int K = p.f_in, ldb = p.ldb, W = p.w_cols;
+  if (!gemm_aligned16(x) || !gemm_aligned16(bases) || (W > 0 && (W & 3) == 0 && !gemm_aligned16(weightings))) return EGC_ERR_UNSUPPORTED;
+  if (addend != nullptr && (!gemm_aligned16(addend) || (ldb & 3) != 0)) return EGC_ERR_UNSUPPORTED;
+  const auto ls = gemm_longk_launches(K, p.NT);
+  if (ls.status != EGC_OK) return ls.status;
+  const KCols c = kcols(p);
+  return gemm_for_row_ranges(M, std::max(std::max(K, ldb), W), KROWS, [&](int64_t r0, int64_t rows) -> int {
+    for (int l = 0; l < ls.n; ++l) {
+      auto run = [&](auto ks) {
+        return launch_ks<ks()>(ls.l[l], x + r0 * K, (const u16*)packed, bcat, rows, K, c, bases + r0 * ldb,
+                               weightings != nullptr ? weightings + r0 * W : nullptr, addend != nullptr ? addend + r0 * ldb : nullptr, stream);
+      };
+      int st;
+      switch (p.KS) {   // (gemm_longk_launches admits 5 .. 12)
+        case 5: st = run(std::integral_constant<int, 5>{}); break;     case 6: st = run(std::integral_constant<int, 6>{}); break;
+        case 7: st = run(std::integral_constant<int, 7>{}); break;     case 8: st = run(std::integral_constant<int, 8>{}); break;
+        case 9: st = run(std::integral_constant<int, 9>{}); break;     case 10: st = run(std::integral_constant<int, 10>{}); break;
+        case 11: st = run(std::integral_constant<int, 11>{}); break;   default: st = run(std::integral_constant<int, 12>{});
+      }
+      if (st != EGC_OK) return st;
+    }
+    return EGC_OK;
+  });
 }
 
 }  // namespace egc

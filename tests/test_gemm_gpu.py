@@ -83,7 +83,7 @@ def _check(x, wcat, bcat, f_g, w_cols, bases, wt, tol=4e-6):
     (116, 184, 0),    # the same, F_in < 128: arxiv EGC-S's d x GEMM shape class
     (384, 64, 128),   # long-k fp16x2: the longest k it takes
     (132, 20, 7),     # long-k fp16x2: ragged weightings width (dword stores), partial column tiles
-    (300, 300, 48),   # bf16x3, LDS-staged general kernel (too many column tiles for the long-k kernel)
+    (300, 300, 48),   # long-k fp16x2: 22 column tiles, two launches of 11 (tests/gemm_plan prints it); held to the bf16x3 bound
     (7, 5, 3),        # tiny ragged
 ])
 def test_packed_gemm_matches_float64(n, f_in, f_g, w_cols):
@@ -91,7 +91,7 @@ def test_packed_gemm_matches_float64(n, f_in, f_g, w_cols):
     x = torch.randn(n, f_in, generator=g).to(DEV)
     wcat = (torch.randn(f_in, f_g + w_cols, generator=g) * 0.2).to(DEV)
     bcat = torch.randn(w_cols, generator=g).to(DEV)
-    # the shapes the fp16x2 kernels serve (egc_gemm_split.h: f16x2_shape / f16x2k_shape) are held to 5e-7
+    # the shapes the fp16x2 kernels serve (egc_gemm_host.h: gemm_f16x2_shape / gemm_longk_shape) are held to 5e-7
     f16x2 = (f_in, f_g, w_cols) in {(128, 64, 128), (100, 64, 126), (128, 32, 160), (168, 84, 32), (352, 176, 32), (384, 64, 128),
                                     (132, 20, 7), (224, 224, 48), (200, 150, 30), (160, 296, 0), (224, 200, 100), (192, 320, 16), (128, 168, 0), (116, 184, 0)}
     _check(x, wcat, bcat, f_g, w_cols, *_transform(x, wcat, bcat, f_g, w_cols), tol=F16X2_TOL if f16x2 else 4e-6)
