@@ -33,6 +33,8 @@ MPNN_ADD, MPNN_MEAN, MPNN_MAX = range(3)
 # EGC_PNA_* aggregators and scalers
 PNA_SUM, PNA_MEAN, PNA_MIN, PNA_MAX, PNA_VAR, PNA_STD = range(6)
 PNA_IDENTITY, PNA_AMPLIFICATION, PNA_ATTENUATION, PNA_LINEAR, PNA_INVERSE_LINEAR = range(5)
+# EGC_NBR_*
+NBR_SUM, NBR_MEAN, NBR_MEAN_T, NBR_SYM = range(4)
 
 _STATUS = {1: "EGC_ERR_INVALID", 2: "EGC_ERR_WORKSPACE", 3: "EGC_ERR_HIP", 4: "EGC_ERR_UNSUPPORTED"}
 
@@ -217,6 +219,10 @@ SYMBOLS = {
                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "egc_pna_scale_combine_backward_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "egc_nbr_sum_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "egc_nbr_sum_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "egc_gatv2_forward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "egc_gatv2_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_int32,

@@ -19,6 +19,12 @@ Public surface (mirrors the reference's layer API):
   degree_histogram     the in-degree histogram PNAConv's ``deg`` wants, from an edge_index, a SparseTensor or a CSRGraph
   pna_aggregate / pna_aggregate_backward / pna_scale_combine
                        the kernel-level calls under PNAConv
+  GCNConv / SAGEConv / GINConv
+                       PyG 2.x GCNConv, SAGEConv (mean / sum) and GINConv, the three cheapest baselines of the reference's nets
+                       (state-dict compatible), on one neighbour-sum launch: the symmetric normalisation, the mean's division,
+                       the self loop / root / (1 + eps) term fused in, forward and backward; no [E, .] array
+  neighbor_sum         the kernel-level call under the three: a row-scaled sum of source-scaled neighbour rows plus a
+                       multiple of the row's own features (sum / mean / mean_t / sym), differentiable
   FusedEGCBlock        conv -> BatchNorm1d -> ReLU (-> dropout) -> + identity: eval mode in the kernel's store, training
                        mode in two passes each way
   global_mean_pool / global_add_pool / global_max_pool, readout(name)
@@ -46,6 +52,7 @@ from .relational import REGC, REGConv, RGCNConv  # noqa: F401
 from ._mpnn import Mpnn  # noqa: F401
 from ._gat import GATv2Conv  # noqa: F401
 from ._pna import PNAConv, degree_histogram, pna_aggregate, pna_aggregate_backward, pna_scale_combine  # noqa: F401
+from ._nbr import GCNConv, GINConv, SAGEConv, neighbor_sum  # noqa: F401
 from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean_pool, readout  # noqa: F401
 from .encoders import ASTNodeEncoder, AtomEncoder, Embedding, NodeEncoder  # noqa: F401
 from ._softmax import RowSelection, cross_entropy, log_softmax, nll_log_softmax  # noqa: F401

@@ -775,6 +775,50 @@ int egc_pna_scale_combine_backward_f32(const int32_t* rowptr, int64_t n_rows, co
                                        double avg_lin, double avg_log, int32_t dim, const float* g, int32_t ld_g, float* dY,
                                        int32_t ld_dy, egc_stream_t stream);
 
+/* Neighbour sum of GCNConv, SAGEConv and GINConv (egc_nbr_sum.hip; PyG 2.x layers, the baselines of experiments/code/models.py):
+ * the sparse step all three share, a row-scaled sum of source-scaled neighbour rows plus a multiple of the row's own features.
+ * With agg_i the sum over row i's entries p of the term t_p (0 for a row without entries, which is never divided):
+ *   EGC_NBR_SUM      t_p = x[col[p]]                                    out_i = agg_i + s * x_self_i
+ *   EGC_NBR_MEAN     t_p = x[col[p]]                                    out_i = agg_i / float(deg_i) + s * x_self_i
+ *   EGC_NBR_MEAN_T   t_p = x[col[p]] / float(max(deg_of(col[p]), 1))    out_i = agg_i + s * x_self_i
+ *   EGC_NBR_SYM      t_p = e_p * x[col[p]]                              out_i = row_scale[i] * (agg_i + row_scale[i] * x_self_i)
+ * and without x_self: agg_i, agg_i / float(deg_i), agg_i, row_scale[i] * agg_i.
+ *   rowptr / col   int32 CSR (n_rows + 1 offsets, n_edges entries naming rows of x); deg_i is the walked row's entry count
+ *   x, ld_x        n_src_rows rows of stride ld_x; x_self, ld_self: n_rows rows of stride ld_self, may be the array x is, NULL: no
+ *                  self term; out, ld_out: n_rows rows of stride ld_out.  Column blocks of wider arrays are fine (the pointers
+ *                  name the blocks' first columns); only the `width` columns named are written
+ *   self_scale, eps   s = self_scale, or 1.f + *eps when the DEVICE pointer eps is not NULL (never read on the host)
+ *   deg_rowptr     EGC_NBR_MEAN_T: a second rowptr, n_src_rows + 1 offsets, deg_of(j) = deg_rowptr[j + 1] - deg_rowptr[j] (the
+ *                  CSR whose transpose is walked: MEAN_T over the transposed CSR is the transpose of MEAN)
+ *   row_scale, src_scale, edge_scale   EGC_NBR_SYM: row_scale [n_rows]; e_p = edge_scale[p] when edge_scale [n_edges] is given,
+ *                  else src_scale[col[p]] (src_scale [n_src_rows])
+ *   skip_self_entries   != 0: an entry with col[p] == i is not taken; it keeps its place in the chunk layout and contributes
+ *                  nothing (the LOOPED edge set above, with the self term standing for the one self loop)
+ * The transpose of a form is a form on the transposed CSR -- SUM: SUM; MEAN: MEAN_T with the forward rowptr; SYM: SYM with the
+ * same tables, e_p gathered -- and the self term transposes to itself, so this entry point is its own backward.
+ * Order of a row's float32 sum: egc_mpnn_message_f32's -- chunks of EGC_TYPED_MEAN_CHUNK entries counted from the row's first
+ * entry, a chunk ((0 + t0) + t1) + ... in entry order, the chunk sums added in ascending order; a term's product or division and
+ * every step of the finish are one IEEE operation each.  Every element named is written exactly once: no zero fill, no atomics,
+ * nothing read back.  Chunks 1.. of the rows longer than one chunk go through a first launch into `workspace`
+ * (egc_nbr_sum_workspace_bytes: a function of n_edges and width only; 16-byte aligned, any content; 0 when n_edges <= one chunk).
+ * Column indices (and with them the deg_rowptr and src_scale lookups) are clamped to [0, n_src_rows), offsets to [0, n_edges].
+ * Any width >= 1: 16-byte accesses when width and the strides are multiples of 4 and the pointers 16-byte aligned, 4-byte ones
+ * otherwise.  Compiled: SUM plain, with x_self, and with x_self and skip; MEAN plain; MEAN_T plain and with x_self; SYM plain and
+ * with x_self and skip (either source of e_p).  EGC_ERR_UNSUPPORTED: any other combination, a count >= 2^31.
+ * EGC_ERR_INVALID: width <= 0, an unknown form, a missing pointer, a negative count, a stride smaller than width, MEAN_T without
+ * deg_rowptr, SYM without row_scale or without both edge_scale and src_scale; EGC_ERR_WORKSPACE: workspace missing, misaligned or
+ * too small. */
+#define EGC_NBR_SUM 0
+#define EGC_NBR_MEAN 1
+#define EGC_NBR_MEAN_T 2
+#define EGC_NBR_SYM 3
+size_t egc_nbr_sum_workspace_bytes(int64_t n_edges, int32_t width);
+int egc_nbr_sum_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows, const float* x,
+                    int32_t ld_x, const float* x_self, int32_t ld_self, int32_t width, int32_t form, int32_t skip_self_entries,
+                    float self_scale, const float* eps, const int32_t* deg_rowptr, const float* row_scale, const float* src_scale,
+                    const float* edge_scale, float* out, int32_t ld_out, void* workspace, size_t workspace_bytes,
+                    egc_stream_t stream);
+
 /* GATv2 attention aggregate (egc_gatv2.hip): PyG 2.x GATv2Conv's propagate without an [E, .] array.  H = heads, C = channels
  * per head, width = H * C <= 512 (any H >= 1, C >= 1).  xl (n_src_rows rows) and xr (n_rows rows) are the lin_l / lin_r
  * projections (column blocks of one wider array are fine); att is [H * C].  For an entry j -> i of the CSR by destination and head h
