@@ -474,7 +474,7 @@ static WsLayout ws_layout(const egc_layer* L, int64_t n_nodes, int64_t n_edges, 
   // (65..128 slots: the two-slots-per-lane kernel publishes 5 aggregates x 2 sets x 64 lanes = 640 slots-of-16-bytes per chunk)
   const int rec_lanes = slots <= 16 ? 16 : slots <= 32 ? 32 : slots <= 64 ? 64 : slots <= 128 ? 128 : slots;
   // chunk slots that can be written: the plan's capacity, or the host-known chunk count of this graph
-  const int64_t rec_chunks = (n_chunks >= 0 && n_chunks <= c.cap_chunks) ? n_chunks : c.cap_chunks;
+  const int64_t rec_chunks = plan_chunks(c, n_chunks);
   w.partial_bytes = align256((size_t)rec_chunks * 7 * rec_lanes * 16);
   w.nself_bytes = align256((size_t)rec_chunks * sizeof(int));
   w.queue_bytes = align256((size_t)FUSEDW_QUEUE_INTS * sizeof(int));  // (reserved: keeps the workspace layout of rounds 2-4)
@@ -513,8 +513,7 @@ extern "C" {
 
 int32_t egc_bases_ld(const egc_layer* layer) {
   if (layer == nullptr || layer->num_heads <= 0) return -1;
-  const int fg = layer->num_bases * layer_basis_stride(layer);
-  return (fg + 3) & ~3;
+  return layer_bases_ld(layer);
 }
 
 size_t egc_aggregate_workspace_bytes_for(const egc_layer* layer, const egc_graph* graph) {

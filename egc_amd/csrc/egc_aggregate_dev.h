@@ -11,8 +11,6 @@
 
 namespace egc {
 
-constexpr unsigned OOB = 0xFFFFFFF0u;  // any offset >= num_records makes a buffer load return 0
-
 // first index i in [0, n) with arr[i] >= key (n if none), by HALF a wavefront (lanes [32 h, 32 h + 32) share `key`): 32-ary
 // narrowing, then one probe per lane -- the two halves of a wavefront run two searches side by side.  On an array that
 // is not sorted the result is still a deterministic function of (arr, key): the tiles' edge ranges therefore always
@@ -133,32 +131,7 @@ struct AggArgs {
   int* queue;                // [FUSEDW_QUEUES + 1] work counters + exit counter (zero on entry, zero on exit)
 };
 
-// an aggregator list as one word: 3 bits per code, first aggregator in the low bits (what the compiled-in configurations of
-// the forward -- StCfg's AGG, agg_pack -- and of the backward -- bwd_agg_pack -- are matched against)
-static inline unsigned pack_aggr_codes(const int* aggr, int A) {
-  unsigned pk = 0;
-  for (int t = 0; t < A; ++t) pk |= (unsigned)aggr[t] << (3 * t);
-  return pk;
-}
-
-enum { STAT_SUM = 0, STAT_SQ = 1, STAT_MX = 2, STAT_MN = 3, STAT_WS = 4 };
-
-// Which raw statistics a layer's aggregator list needs (shared by the forward store and the backward load).
-static inline int stat_layout(const int* aggr, int A, int (&slot)[5]) {
-  bool need[5] = {false, false, false, false, false};
-  for (int t = 0; t < A; ++t) {
-    switch (aggr[t]) {
-      case EGC_AGGR_SUM: case EGC_AGGR_MEAN: need[STAT_SUM] = true; break;
-      case EGC_AGGR_VAR: case EGC_AGGR_STD: need[STAT_SUM] = need[STAT_SQ] = true; break;
-      case EGC_AGGR_MAX: need[STAT_MX] = true; break;
-      case EGC_AGGR_MIN: need[STAT_MN] = true; break;
-      default: need[STAT_WS] = true; break;
-    }
-  }
-  int k = 0;
-  for (int s = 0; s < 5; ++s) slot[s] = need[s] ? k++ : -1;
-  return k;
-}
+// (pack_aggr_codes, STAT_* and stat_layout: egc_plain.h)
 
 template <int CHUNKS>
 struct Acc {

@@ -28,6 +28,7 @@
 #include <stdlib.h>
 
 #include "egc_aggregate_dev.h"
+#include "egc_backward_host.h"
 
 namespace egc {
 
@@ -186,22 +187,17 @@ int arg_extrema(const egc_graph* graph, const egc_layer* layer, const float* bas
   a.ldb = ldb; a.slots = ldb / 4; a.stat_k = k; a.slot_mx = slot[STAT_MX]; a.slot_mn = slot[STAT_MN];
   a.x_looped = layer->agg_set == EGC_SET_LOOPED;
   a.bases_bytes = (unsigned)((uint64_t)n_src * ldb * 4ull);
-  int lg = 4;
-  while ((1 << lg) < a.slots && lg < 6) ++lg;
-  a.lpr_log2 = lg;
+  const ArgPlan p = arg_plan(a.slots, n, e, graph->n_chunks);
+  a.lpr_log2 = p.lpr_log2;
   a.plan = graph->plan;
   if (e > 0) {
     if (graph->plan == nullptr) return EGC_ERR_INVALID;
-    const PlanCaps caps = plan_caps(n, e);
-    const int64_t n_chunks = (graph->n_chunks >= 0 && graph->n_chunks <= caps.cap_chunks) ? graph->n_chunks : caps.cap_chunks;
-    a.chunk_blocks = (int)ceil_div(n_chunks, 4);
-    const unsigned grid = (unsigned)(a.chunk_blocks + ceil_div(n, (int64_t)4 * (64 >> lg)));
-    switch ((a.slots + (1 << lg) - 1) >> lg) {
-      case 1: arg_extrema_kernel<1><<<grid, 256, 0, stream>>>(a); break;
-      case 2: arg_extrema_kernel<2><<<grid, 256, 0, stream>>>(a); break;
-      case 3: arg_extrema_kernel<3><<<grid, 256, 0, stream>>>(a); break;
-      case 4: arg_extrema_kernel<4><<<grid, 256, 0, stream>>>(a); break;
-      default: return EGC_ERR_UNSUPPORTED;
+    if (p.status != EGC_OK) return p.status;
+    a.chunk_blocks = p.chunk_blocks;
+    switch (p.ns) {
+#define EGC_ROW(NS) case NS: arg_extrema_kernel<NS><<<p.grid, 256, 0, stream>>>(a); break;
+      EGC_BWD_NS(EGC_ROW)
+#undef EGC_ROW
     }
     EGC_LAUNCH_CHECK("arg_extrema_kernel");
   }
@@ -407,7 +403,6 @@ __global__ void __launch_bounds__(256) bwd_dst_kernel(BwdArgs a) {
 #endif
 constexpr int REC_ITEMS = 12;             // (value, column) pairs per record
 constexpr unsigned REC_OVERFLOW = 0xffu;  // dword 15: count, or this
-constexpr int REC_FIT_COLUMNS = 10;        // records are built where an entry receives at most this many columns on average (ldb N / E)
 constexpr int REC_BALLOT_MAX = 8;         // entries of a one-row wavefront up to which the columns are ranked by ballots
 // record = 16 dwords: [0..11] values, [12..14] their columns (one byte each: ldb <= 256), [15] count
 
@@ -595,15 +590,10 @@ __global__ void __launch_bounds__(256) bwd_records_kernel(RecArgs a) {
 // weights sit in per-group LDS strips; a lane forms  d agg_t = sum_h w'[h][b][t] g[h][l..l+3]  and its share of
 // d w'[h][b][t] = sum_l g[h][l] agg_t[b][l]  in one pass over h, the shares meet in an xor butterfly over the P
 // lanes of the basis, and lane l4 stores the heads l4 H/P .. (l4+1) H/P - 1.
-constexpr int BWD_HMAX = 16;   // heads supported by the register form
 // HT / AT: compile-time head and aggregator counts (the d = 128, H = 8 layers; everything else: bwd_dst_kernel)
 // AGG: the aggregator codes packed 3 bits each (first in the low bits) with bit 31 set, or 0 = read them from
 // the arguments.  With the list compiled in, the per-aggregator switches, the statistics layout and the weight
 // nonlinearity (none) fold away -- the run-time form is mostly scalar branches.
-constexpr unsigned BWD_STATIC = 0x80000000u;
-constexpr unsigned bwd_agg_pack(int a0, int a1 = 0, int a2 = 0, int a3 = 0) {
-  return BWD_STATIC | (unsigned)a0 | ((unsigned)a1 << 3) | ((unsigned)a2 << 6) | ((unsigned)a3 << 9);
-}
 template <unsigned AGG, int AT>
 struct BwdAggs {
   static constexpr bool fixed = (AGG & BWD_STATIC) != 0;
@@ -899,8 +889,6 @@ __global__ void __launch_bounds__(256, EGC_BWD_DST_MINW) bwd_dst_fast_kernel(Bwd
 // FL: which tables exist and which edge sets are LOOPED, compiled in (bit 0 set) or read from the arguments (0).
 // The run-time form makes the compiler clone the gather loop per flag combination (9,000 lines of ISA, SGPR
 // spills); the shipped layer kinds get a lean kernel each.
-constexpr unsigned SRC_STATIC = 1u, SRC_S = 2u, SRC_V = 4u, SRC_X = 8u, SRC_N = 16u, SRC_XL = 32u, SRC_YL = 64u, SRC_T = 128u,
-                   SRC_REC = 256u;   // max / min gradients arrive as per-entry records (REC_*) instead of arg bytes + X sectors
 template <unsigned FL>
 struct SrcCfg {
   static constexpr bool fixed = (FL & SRC_STATIC) != 0;
@@ -1195,6 +1183,70 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS == 
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// the launches: the plan (egc_backward_host.h) names the instance, the lists there expand to the instances that exist
+// ---------------------------------------------------------------------------------------------
+template <int LPR_LOG2, int HT, int AT, unsigned AGG>
+static void launch_dst_fast(const BwdPlan& p, const BwdArgs& a, hipStream_t stream) {
+  bwd_dst_fast_kernel<LPR_LOG2, HT, AT, AGG><<<p.dst_grid, p.dst_threads, p.dst_lds, stream>>>(a);
+}
+
+static int launch_dst(const BwdPlan& p, const BwdArgs& a, hipStream_t stream) {
+  if (!p.fast) {
+    bwd_dst_kernel<<<p.dst_grid, p.dst_threads, p.dst_lds, stream>>>(a);
+    EGC_LAUNCH_CHECK("bwd_dst_kernel");
+    return EGC_OK;
+  }
+#define EGC_ROW(LG, HT, AT, ...) \
+  if (p.dst_lpr_log2 == LG && p.H == HT && p.A == AT && p.agg == bwd_agg_pack(__VA_ARGS__)) launch_dst_fast<LG, HT, AT, bwd_agg_pack(__VA_ARGS__)>(p, a, stream);
+  EGC_BWD_DST_LISTS(EGC_ROW)
+#undef EGC_ROW
+#define EGC_ROW(LG, HT, AT) if (p.dst_lpr_log2 == LG && p.H == HT && p.A == AT && p.agg == 0u) launch_dst_fast<LG, HT, AT, 0u>(p, a, stream);
+  EGC_BWD_DST_TRIPLES(EGC_ROW)
+#undef EGC_ROW
+  EGC_LAUNCH_CHECK("bwd_dst_fast_kernel");
+  return EGC_OK;
+}
+
+// (arg, X) rows -> per-entry records, once per extremum (with the records built inside bwd_dst_fast_kernel -- rows AND hub
+// chunks -- there is nothing left to launch: grid 0)
+static int launch_records(const BwdPlan& p, const BwdArgs& a, hipStream_t stream) {
+  if (p.rec_grid == 0) return EGC_OK;
+  RecArgs r;
+  r.rowptr = a.rowptr; r.plan = a.d_plan;
+  r.n_nodes = a.n_nodes; r.ldb = a.ldb; r.slots = a.slots;
+  r.group_u32 = p.rec_group_u32; r.chunk_blocks = p.rec_blocks; r.short_rows = p.rec_short_rows;
+  for (int e = 0; e < 2; ++e) {
+    r.arg = e == 0 ? a.arg_max : a.arg_min;
+    r.x = e == 0 ? a.tab_x : a.tab_n;
+    r.rec = const_cast<unsigned*>(e == 0 ? a.rec_x : a.rec_n);
+    if (r.rec == nullptr) continue;
+    switch (p.rec_ns) {
+#define EGC_ROW(NS) case NS: bwd_records_kernel<NS><<<p.rec_grid, 256, p.rec_lds, stream>>>(r); break;
+      EGC_BWD_NS(EGC_ROW)
+#undef EGC_ROW
+    }
+    EGC_LAUNCH_CHECK("bwd_records_kernel");
+  }
+  return EGC_OK;
+}
+
+template <int NS, unsigned FL>
+static void launch_src_instance(const BwdPlan& p, const BwdArgs& a, hipStream_t stream) {
+  bwd_src_kernel<NS, FL><<<p.src_grid, 256, 0, stream>>>(a);
+}
+
+static int launch_src(const BwdPlan& p, const BwdArgs& a, hipStream_t stream) {
+#define EGC_ROW(FL) if (p.src_flags == (SRC_STATIC | (FL))) launch_src_instance<1, SRC_STATIC | (FL)>(p, a, stream);
+  EGC_BWD_SRC_FLAGS(EGC_ROW)
+#undef EGC_ROW
+#define EGC_ROW(NS) if (p.src_flags == 0u && p.src_ns == NS) launch_src_instance<NS, 0u>(p, a, stream);
+  EGC_BWD_NS(EGC_ROW)
+#undef EGC_ROW
+  EGC_LAUNCH_CHECK("bwd_src_kernel");
+  return EGC_OK;
+}
+
 }  // namespace egc
 
 using namespace egc;
@@ -1203,38 +1255,12 @@ extern "C" {
 
 size_t egc_backward_workspace_bytes(const egc_layer* layer, int64_t n_nodes) {
   if (layer == nullptr || n_nodes < 0 || layer->num_heads <= 0) return 0;
-  const int ldb = egc_bases_ld(layer);
-  return (((size_t)5 * (size_t)n_nodes * ldb * sizeof(float) + 255) & ~(size_t)255) + 256;  // tables T, S, V, X, N
-}
-
-static int layer_extrema(const egc_layer* layer) {
-  int mx = 0, mn = 0;
-  for (int t = 0; t < layer->num_aggrs && t < EGC_MAX_AGGRS; ++t) {
-    if (layer->aggrs[t] == EGC_AGGR_MAX) mx = 1;
-    if (layer->aggrs[t] == EGC_AGGR_MIN) mn = 1;
-  }
-  return mx + mn;
-}
-
-// records of the extremum gradients (bwd_records_kernel): one 64-byte line per entry and extremum, behind the tables
-// A record holds REC_ITEMS (value, column) pairs; an entry that receives more is marked REC_OVERFLOW and the source side reads
-// the destination's whole X row and int32 arg row for it on top of the record.  An entry receives ldb / degree columns on
-// average: 4.6 on the ogbn-arxiv graph at 64 basis columns, but 108 on a molhiv batch at 224 (two entries per row) -- there
-// EVERY record overflowed, the source kernel fetched 282 MB per launch for 110 MB of payload (FETCH_SIZE, round 6) and the
-// destination kernel spent a fifth of its time building records nobody could use.  Records only where they mostly fit.
-static bool records_apply(const egc_layer* layer, int64_t n_nodes, int64_t n_edges) {
-  const int ldb = egc_bases_ld(layer);
-  if (!(layer_extrema(layer) > 0 && n_edges > 0 && ldb <= 256 && (uint64_t)n_edges * 64ull < (uint64_t)OOB &&
-        getenv("EGC_BWD_NO_REC") == nullptr))
-    return false;
-  return (double)ldb * (double)std::max<int64_t>(n_nodes, 1) <= (double)REC_FIT_COLUMNS * (double)n_edges;
+  return bwd_workspace(layer, n_nodes, 0, BwdSwitches{}).tables;
 }
 
 size_t egc_backward_workspace_bytes_for(const egc_layer* layer, const egc_graph* graph) {
-  if (layer == nullptr || graph == nullptr || graph->n_nodes < 0 || graph->n_edges < 0) return 0;
-  const size_t base = egc_backward_workspace_bytes(layer, graph->n_nodes);
-  if (base == 0 || !records_apply(layer, graph->n_nodes, graph->n_edges)) return base;
-  return base + (size_t)layer_extrema(layer) * (size_t)graph->n_edges * 64;
+  if (layer == nullptr || graph == nullptr || graph->n_nodes < 0 || graph->n_edges < 0 || layer->num_heads <= 0) return 0;
+  return bwd_workspace(layer, graph->n_nodes, graph->n_edges, bwd_switches()).total;
 }
 
 int egc_aggregate_combine_backward_f32(const egc_graph* graph, const egc_graph* t_graph, const egc_layer* layer,
@@ -1259,247 +1285,63 @@ int egc_aggregate_combine_backward_f32(const egc_graph* graph, const egc_graph* 
     return EGC_ERR_INVALID;
   if (ldb != egc_bases_ld(layer)) return EGC_ERR_INVALID;
   if (layer->weight_layout != EGC_LAYOUT_HBA) return EGC_ERR_UNSUPPORTED;  // the host packs [h][b][a]
-  if (workspace == nullptr || workspace_bytes < egc_backward_workspace_bytes(layer, n)) return EGC_ERR_WORKSPACE;
-  if ((uint64_t)n * (uint64_t)ldb * 4ull > (uint64_t)OOB) return EGC_ERR_UNSUPPORTED;  // 32-bit buffer offsets
+  if (workspace == nullptr) return EGC_ERR_WORKSPACE;
+  // the plan is a function of the layer and the counts alone.  Its refusals by size answer here, where they always have: before
+  // the pointer checks below; a launch that does not fit answers behind them.
+  const BwdPlan p = bwd_plan(layer, BwdCounts{n, n_src, graph->n_edges, graph->n_chunks, t_graph->n_edges, t_graph->n_chunks,
+                                              workspace_bytes, graph->plan != nullptr}, bwd_switches());
+  if (p.size_status != EGC_OK) return p.size_status;
 
   BwdArgs a;
-  a.col = graph->col;
-  a.max_index = graph->max_index;
-  a.t_rowptr = t_graph->rowptr;
-  a.t_col = t_graph->col;
-  a.t_plan = t_graph->plan;
-  a.bases = bases;
-  a.weightings = weightings;
-  a.grad_out = grad_out;
-  a.stats = stats;
-  a.cnt = cnt;
-  a.arg_max = arg_max;
-  a.arg_min = arg_min;
-  a.d_bases = d_bases;
-  a.d_weightings = d_weightings;
+  a.col = graph->col; a.rowptr = graph->rowptr; a.max_index = graph->max_index; a.d_plan = graph->plan;
+  a.t_rowptr = t_graph->rowptr; a.t_col = t_graph->col; a.t_plan = t_graph->plan; a.t_edge_id = t_graph->edge_id;
+  a.bases = bases; a.weightings = weightings; a.grad_out = grad_out; a.stats = stats; a.cnt = cnt;
+  a.arg_max = arg_max; a.arg_min = arg_min;
+  a.d_bases = d_bases; a.d_weightings = d_weightings;
   a.ld_db = ld_d_bases > 0 ? ld_d_bases : ldb;
-  a.ld_dw = ld_d_weightings > 0 ? ld_d_weightings : layer->num_heads * layer->num_bases * layer->num_aggrs;
+  a.ld_dw = ld_d_weightings > 0 ? ld_d_weightings : p.W;
   // 16-byte row accesses of d_bases; both arrays at least as wide as what is written
-  if (a.ld_db < ldb || (a.ld_db & 3) != 0 || (reinterpret_cast<uintptr_t>(d_bases) & 15) != 0 ||
-      a.ld_dw < layer->num_heads * layer->num_bases * layer->num_aggrs)
-    return EGC_ERR_INVALID;
-  a.n_nodes = (int)n;
-  a.n_src_rows = (int)n_src;
+  if (a.ld_db < ldb || (a.ld_db & 3) != 0 || (reinterpret_cast<uintptr_t>(d_bases) & 15) != 0 || a.ld_dw < p.W) return EGC_ERR_INVALID;
+  a.n_nodes = (int)n; a.n_src_rows = (int)n_src; a.n_edges = (int)graph->n_edges;
   a.overwrite_db = n_src == n;
-  a.n_edges = (int)graph->n_edges;
-  a.ldb = ldb;
-  a.slots = ldb / 4;
-  a.H = layer->num_heads;
-  a.B = layer->num_bases;
-  a.A = layer->num_aggrs;
-  a.L = layer->out_channels / layer->num_heads;
-  a.Ls = layer_basis_stride(layer);
-  a.F_g = a.B * a.Ls;
-  a.F_out = layer->out_channels;
-  a.W = a.H * a.B * a.A;
-  bool sym = false, var = false;
-  for (int t = 0; t < EGC_MAX_AGGRS; ++t) {
-    a.aggr[t] = t < a.A ? layer->aggrs[t] : 0;
-    if (t < a.A && layer->aggrs[t] == EGC_AGGR_SYMNORM) sym = true;
-    if (t < a.A && (layer->aggrs[t] == EGC_AGGR_VAR || layer->aggrs[t] == EGC_AGGR_STD)) var = true;
-    if (t < a.A && layer->aggrs[t] == EGC_AGGR_MAX && arg_max == nullptr) return EGC_ERR_INVALID;
-    if (t < a.A && layer->aggrs[t] == EGC_AGGR_MIN && arg_min == nullptr) return EGC_ERR_INVALID;
-  }
-  a.stat_k = stat_layout(a.aggr, a.A, a.stat_slot);
+  a.ldb = p.ldb; a.slots = p.slots; a.H = p.H; a.B = p.B; a.A = p.A; a.L = p.L; a.Ls = p.Ls; a.F_g = p.F_g; a.F_out = p.F_out; a.W = p.W;
+  std::copy(p.aggr, p.aggr + EGC_MAX_AGGRS, a.aggr);
+  std::copy(p.stat_slot, p.stat_slot + 5, a.stat_slot);
+  a.stat_k = p.stat_k;
+  if ((p.has_x && arg_max == nullptr) || (p.has_n && arg_min == nullptr)) return EGC_ERR_INVALID;
   a.x_looped = layer->agg_set == EGC_SET_LOOPED;
   a.y_looped = layer->sym_set == EGC_SET_LOOPED;
   a.loops_all = layer->loops_all_nodes != 0;
   if (!a.loops_all && graph->max_index == nullptr) return EGC_ERR_INVALID;
   a.act = layer->weight_act;
-  a.dis = nullptr;
-  if (sym) {
-    a.dis = a.y_looped ? graph->dis_looped : graph->dis_raw;
-    if (a.dis == nullptr) return EGC_ERR_INVALID;
-  }
+  a.dis = !p.has_s ? nullptr : a.y_looped ? graph->dis_looped : graph->dis_raw;
+  if (p.has_s && a.dis == nullptr) return EGC_ERR_INVALID;
   float* ws = (float*)workspace;
   a.tab_t = ws;
-  a.need_t = 0;
-  for (int t = 0; t < a.A; ++t)
-    if (a.aggr[t] == EGC_AGGR_SUM || a.aggr[t] == EGC_AGGR_MEAN || a.aggr[t] == EGC_AGGR_VAR || a.aggr[t] == EGC_AGGR_STD)
-      a.need_t = 1;
-  a.tab_s = sym ? ws + (size_t)n * ldb : nullptr;
-  a.tab_v = var ? ws + (size_t)2 * n * ldb : nullptr;
-  a.tab_x = a.stat_slot[STAT_MX] >= 0 ? ws + (size_t)3 * n * ldb : nullptr;
-  a.tab_n = a.stat_slot[STAT_MN] >= 0 ? ws + (size_t)4 * n * ldb : nullptr;
-  a.t_edge_id = t_graph->edge_id;
-  if ((a.tab_x != nullptr || a.tab_n != nullptr) && a.t_edge_id == nullptr) return EGC_ERR_INVALID;
-  a.rowptr = graph->rowptr;
-  {  // the 8-bit in-row arg positions the training forward left behind the raw aggregates (egc_aggregate_dev.h)
-    unsigned char* bytes = reinterpret_cast<unsigned char*>(const_cast<float*>(stats) + (size_t)n * a.stat_k * ldb);
-    a.arg8_max = a.tab_x != nullptr ? bytes : nullptr;
-    a.arg8_min = a.tab_n != nullptr ? bytes + (a.tab_x != nullptr ? (size_t)n * ldb : 0) : nullptr;
-    if ((a.arg8_max != nullptr || a.arg8_min != nullptr) && a.rowptr == nullptr) return EGC_ERR_INVALID;
-  }
-  a.tab_bytes = (unsigned)((uint64_t)n * ldb * 4ull);
-  // per-entry records when the caller's workspace holds them (egc_backward_workspace_bytes_for)
-  a.rec_x = a.rec_n = nullptr;
-  a.rec_bytes = 0;
-  const size_t tables_bytes = egc_backward_workspace_bytes(layer, n);   // (a multiple of 256: 64-byte aligned records)
-  if ((a.tab_x != nullptr || a.tab_n != nullptr) && records_apply(layer, graph->n_nodes, graph->n_edges) && graph->plan != nullptr &&
-      workspace_bytes >= tables_bytes + (size_t)layer_extrema(layer) * (size_t)graph->n_edges * 64) {
-    unsigned char* r = reinterpret_cast<unsigned char*>(workspace) + tables_bytes;
-    if (a.tab_x != nullptr) { a.rec_x = reinterpret_cast<const unsigned*>(r); r += (size_t)graph->n_edges * 64; }
-    if (a.tab_n != nullptr) a.rec_n = reinterpret_cast<const unsigned*>(r);
-    a.rec_bytes = (unsigned)((uint64_t)graph->n_edges * 64ull);
-  }
-  a.rec_fused = 0;
-  a.d_plan = graph->plan;
-  a.dst_row_blocks = 0;
-  a.lds_floats_per_wave = a.A * ldb + ((a.F_out + 3) & ~3) + 2 * ((a.W + 3) & ~3);
-  int wpb = 4;
-  if ((size_t)wpb * a.lds_floats_per_wave * sizeof(float) > 48 * 1024) wpb = 1;
-  const size_t lds = (size_t)wpb * a.lds_floats_per_wave * sizeof(float);
-  if (lds > 64 * 1024) return EGC_ERR_UNSUPPORTED;
-  {
-    // register-resident form when the layout allows (see bwd_dst_fast_kernel), else the LDS-based kernel
-    const int P = a.Ls / 4;
-    const bool p2 = (P & (P - 1)) == 0;
-    const bool fast = getenv("EGC_BWD_GENERIC") == nullptr && (a.Ls & 3) == 0 && a.ldb == a.B * a.Ls && P >= 1 && P <= 16 &&
-                      (a.B & (a.B - 1)) == 0 && a.slots <= 64 && a.A <= 4 && a.H <= BWD_HMAX &&
-                      (!p2 || a.H % P == 0 || a.H < P) && a.act != EGC_ACT_SOFTMAX &&
-                      // only the compiled head / aggregator counts: with run-time counts the LDS kernel is faster
-                      ((a.slots <= 16 && a.H == 8 && (a.A == 1 || a.A == 3 || a.A == 4)) ||
-                       // the other trained nets of the reference (hyperparameters.md): zinc EGC-M 124/H4/B4, CIFAR EGC-M
-                       // 128/H4/B4 (32 slots); zinc / CIFAR EGC-S 168/H8/B4, arxiv EGC-S 184/H8/B4 (24 slots); arxiv EGC-M
-                       // 136/H4/B4 (36), molhiv EGC-M 224/H4/B4 (56); molhiv EGC-S 296/H8/B4 (40)
-                       (a.slots > 16 && a.slots <= 32 && ((a.H == 4 && a.A == 3) || (a.H == 8 && a.A == 1))) ||
-                       (a.slots > 32 && ((a.H == 4 && a.A == 3) || (a.H == 8 && a.A == 1))));
-    if (fast) {
-      const int lpr = a.slots <= 16 ? 16 : a.slots <= 32 ? 32 : 64;
-      const int G = 64 / lpr;
-      a.rec_fused = a.rec_bytes != 0 && getenv("EGC_BWD_REC_SEPARATE") == nullptr;
-      // per lane group: the strips of g and w'; afterwards the record builder's count | offset | values | column bytes
-      // (64 entries per group in the row role; 256 per WAVEFRONT in the hub-chunk role of the trailing blocks)
-      // (+ the transposed d w' shares of a basis that is not a power-of-two number of lanes wide: [H A][lpr + 1])
-      a.dst_group_floats = std::max(((a.H * a.Ls + 3) & ~3) + ((a.W + 3) & ~3) + (p2 ? 0 : a.H * a.A * (lpr + 1)),
-                                    a.rec_fused ? std::max(128 + a.ldb + a.ldb / 4 + 4, (512 + a.ldb + a.ldb / 4 + 4 + G - 1) / G) : 0);
-      const size_t flds = (size_t)4 * G * a.dst_group_floats * sizeof(float);
-      a.dst_row_blocks = (int)ceil_div(n, (int64_t)4 * G);
-      a.d_plan = graph->plan;
-      int rec_chunk_blocks = 0;
-      if (a.rec_fused) {
-        const PlanCaps dc = plan_caps(n, graph->n_edges);
-        rec_chunk_blocks = (int)ceil_div((graph->n_chunks >= 0 && graph->n_chunks <= dc.cap_chunks) ? graph->n_chunks : dc.cap_chunks, 4);
-      }
-      const unsigned fgrid = (unsigned)(a.dst_row_blocks + rec_chunk_blocks);
-      if (flds > 64 * 1024) return EGC_ERR_UNSUPPORTED;
-      const unsigned packed = BWD_STATIC | pack_aggr_codes(a.aggr, a.A);
-      constexpr int S = EGC_AGGR_SUM, M = EGC_AGGR_MEAN, X = EGC_AGGR_MAX, Y = EGC_AGGR_SYMNORM;
-      // the reference's own batched nets with their aggregator lists compiled in (round 6: these layers train on this path --
-      // DESIGN.md section 3.7 -- and the run-time form's per-aggregator switches are most of its instructions): molhiv EGC-M
-      // 224 / H4 / B4 add, mean, max; molhiv EGC-S 296 / H8 / B4 and zinc / cifar EGC-S 168 / H8 / B4 symadd
-      const bool plain = a.act == EGC_ACT_NONE;
-      if (a.slots > 32 && a.H == 4 && plain && packed == bwd_agg_pack(S, M, X)) bwd_dst_fast_kernel<6, 4, 3, bwd_agg_pack(S, M, X)><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.slots > 32 && a.H == 8 && plain && packed == bwd_agg_pack(Y)) bwd_dst_fast_kernel<6, 8, 1, bwd_agg_pack(Y)><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.slots > 16 && a.slots <= 32 && a.H == 8 && plain && packed == bwd_agg_pack(Y)) bwd_dst_fast_kernel<5, 8, 1, bwd_agg_pack(Y)><<<fgrid, 256, flds, stream>>>(a);
-      // arxiv EGC-M 136 / H4 / B4 symadd, max, mean (36 slots); zinc EGC-M 124 / H4 / B4 add, std, max and cifar EGC-M 128 / H4 / B4 symadd, std, max (32)
-      else if (a.slots > 32 && a.H == 4 && plain && packed == bwd_agg_pack(Y, X, M)) bwd_dst_fast_kernel<6, 4, 3, bwd_agg_pack(Y, X, M)><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.slots > 16 && a.slots <= 32 && a.H == 4 && plain && packed == bwd_agg_pack(S, EGC_AGGR_STD, X)) bwd_dst_fast_kernel<5, 4, 3, bwd_agg_pack(S, EGC_AGGR_STD, X)><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.slots > 16 && a.slots <= 32 && a.H == 4 && plain && packed == bwd_agg_pack(Y, EGC_AGGR_STD, X)) bwd_dst_fast_kernel<5, 4, 3, bwd_agg_pack(Y, EGC_AGGR_STD, X)><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.slots > 32 && a.H == 4) bwd_dst_fast_kernel<6, 4, 3><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.slots > 32) bwd_dst_fast_kernel<6, 8, 1><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.slots > 16 && a.H == 4) bwd_dst_fast_kernel<5, 4, 3><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.slots > 16) bwd_dst_fast_kernel<5, 8, 1><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.A == 4 && a.act == EGC_ACT_NONE && packed == bwd_agg_pack(S, M, X, Y))      // EGConv north star, compiled in
-        bwd_dst_fast_kernel<4, 8, 4, bwd_agg_pack(S, M, X, Y)><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.A == 3 && a.act == EGC_ACT_NONE && packed == bwd_agg_pack(Y, X, M))    // EfficientGraphConv EGC-M
-        bwd_dst_fast_kernel<4, 8, 3, bwd_agg_pack(Y, X, M)><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.A == 1 && a.act == EGC_ACT_NONE && packed == bwd_agg_pack(Y))          // EGC-S
-        bwd_dst_fast_kernel<4, 8, 1, bwd_agg_pack(Y)><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.A == 4) bwd_dst_fast_kernel<4, 8, 4><<<fgrid, 256, flds, stream>>>(a);
-      else if (a.A == 3) bwd_dst_fast_kernel<4, 8, 3><<<fgrid, 256, flds, stream>>>(a);
-      else bwd_dst_fast_kernel<4, 8, 1><<<fgrid, 256, flds, stream>>>(a);
-      EGC_LAUNCH_CHECK("bwd_dst_fast_kernel");
-    } else {
-      bwd_dst_kernel<<<(unsigned)ceil_div(n, wpb), wpb * 64, lds, stream>>>(a);
-      EGC_LAUNCH_CHECK("bwd_dst_kernel");
-    }
-  }
+  a.need_t = p.need_t;
+  a.tab_s = p.has_s ? ws + p.table_floats : nullptr;
+  a.tab_v = p.has_v ? ws + 2 * p.table_floats : nullptr;
+  a.tab_x = p.has_x ? ws + 3 * p.table_floats : nullptr;
+  a.tab_n = p.has_n ? ws + 4 * p.table_floats : nullptr;
+  a.tab_bytes = (unsigned)(p.table_floats * 4);
+  if ((p.has_x || p.has_n) && (a.t_edge_id == nullptr || a.rowptr == nullptr)) return EGC_ERR_INVALID;
+  // the 8-bit in-row arg positions the training forward left behind the raw aggregates (egc_aggregate_dev.h)
+  unsigned char* bytes = reinterpret_cast<unsigned char*>(const_cast<float*>(stats) + p.table_floats * p.stat_k);
+  a.arg8_max = p.has_x ? bytes : nullptr;
+  a.arg8_min = p.has_n ? bytes + (p.has_x ? p.table_floats : 0) : nullptr;
+  // per-entry records behind the tables (a multiple of 256 bytes: 64-byte aligned records), max first
+  const unsigned* rec = p.rec_mode != BWD_REC_OFF ? reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(workspace) + p.rec_offset) : nullptr;
+  a.rec_x = p.has_x ? rec : nullptr;
+  a.rec_n = !p.has_n || rec == nullptr ? nullptr : p.has_x ? rec + p.rec_entry_bytes / 4 : rec;
+  a.rec_bytes = p.rec_entry_bytes;
+  a.rec_fused = p.rec_mode == BWD_REC_FUSED;
+  a.dst_row_blocks = p.dst_row_blocks; a.dst_group_floats = p.dst_group_floats; a.lds_floats_per_wave = p.lds_floats_per_wave;
+  a.lpr_log2 = p.src_lpr_log2; a.chunk_blocks = p.src_chunk_blocks;
+  if (p.status != EGC_OK) return p.status;
 
-  if (a.rec_bytes != 0) {   // (arg, X) rows -> per-entry records
-    RecArgs r;
-    r.rowptr = graph->rowptr; r.plan = graph->plan;
-    r.n_nodes = (int)n; r.ldb = ldb; r.slots = a.slots;
-    r.group_u32 = 128 + ldb + ldb / 4 + 4;   // count | offset | values | column bytes (+ the over-read of the last list)
-    const PlanCaps dcaps = plan_caps(n, graph->n_edges);
-    const int64_t dchunks = (graph->n_chunks >= 0 && graph->n_chunks <= dcaps.cap_chunks) ? graph->n_chunks : dcaps.cap_chunks;
-    r.chunk_blocks = (int)ceil_div(dchunks, 4);
-    r.short_rows = a.rec_fused ? 0 : 1;
-    // (with the records built inside bwd_dst_fast_kernel -- rows AND hub chunks -- there is nothing left to launch)
-    const unsigned rgrid = a.rec_fused ? 0u : (unsigned)(r.chunk_blocks + ceil_div(n, (int64_t)16));
-    const size_t rlds = (size_t)16 * r.group_u32 * sizeof(unsigned);
-    for (int e = 0; e < 2; ++e) {
-      r.arg = e == 0 ? a.arg_max : a.arg_min;
-      r.x = e == 0 ? a.tab_x : a.tab_n;
-      r.rec = const_cast<unsigned*>(e == 0 ? a.rec_x : a.rec_n);
-      if (r.rec == nullptr || rgrid == 0) continue;
-      switch ((a.slots + 15) / 16) {
-        case 1: bwd_records_kernel<1><<<rgrid, 256, rlds, stream>>>(r); break;
-        case 2: bwd_records_kernel<2><<<rgrid, 256, rlds, stream>>>(r); break;
-        case 3: bwd_records_kernel<3><<<rgrid, 256, rlds, stream>>>(r); break;
-        default: bwd_records_kernel<4><<<rgrid, 256, rlds, stream>>>(r); break;
-      }
-      EGC_LAUNCH_CHECK("bwd_records_kernel");
-    }
-  }
-
-  int lg = 0;
-  while ((1 << lg) < a.slots && lg < 6) ++lg;
-  if (lg < 4) lg = 4;
-  a.lpr_log2 = lg;
-  const int G = 64 >> lg;
-  const int ns = (a.slots + (1 << lg) - 1) >> lg;  // slots per lane
-  const PlanCaps caps = plan_caps(n_src, t_graph->n_edges);
-  const int64_t n_chunks = (t_graph->n_chunks >= 0 && t_graph->n_chunks <= caps.cap_chunks) ? t_graph->n_chunks : caps.cap_chunks;
-  a.chunk_blocks = (int)ceil_div(n_chunks, 4);
-  const unsigned grid = (unsigned)(a.chunk_blocks + ceil_div(n_src, (int64_t)4 * G));
-  unsigned fl = SRC_STATIC | (a.need_t ? SRC_T : 0u) | (a.tab_s != nullptr ? SRC_S : 0u) | (a.tab_v != nullptr ? SRC_V : 0u) |
-                (a.tab_x != nullptr ? SRC_X : 0u) | (a.tab_n != nullptr ? SRC_N : 0u) | (a.x_looped ? SRC_XL : 0u) |
-                (a.y_looped ? SRC_YL : 0u) | (a.rec_bytes != 0 ? SRC_REC : 0u);
-  if (getenv("EGC_BWD_GENERIC") != nullptr) fl = 0;
-  // the same layer kinds on low-degree batches, where no records are built (records_apply): the arg-byte form, compiled in
-  if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_X | SRC_YL)) {                                // add+mean+max (molhiv EGC-M)
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_X | SRC_YL><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_S | SRC_X | SRC_YL)) {                 // symadd+max+mean
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_S | SRC_X | SRC_YL><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_V | SRC_X | SRC_YL)) {                 // add+std+max (zinc EGC-M)
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_V | SRC_X | SRC_YL><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_S | SRC_V | SRC_X | SRC_YL)) {         // symadd+std+max (CIFAR EGC-M)
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_S | SRC_V | SRC_X | SRC_YL><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_S | SRC_X | SRC_XL | SRC_YL)) {        // EGConv sum+mean+max+symnorm
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_S | SRC_X | SRC_XL | SRC_YL><<<grid, 256, 0, stream>>>(a);
-  } else
-  if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_S | SRC_X | SRC_XL | SRC_YL | SRC_REC)) {  // EGConv sum+mean+max+symnorm (north star)
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_S | SRC_X | SRC_XL | SRC_YL | SRC_REC><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_S | SRC_X | SRC_YL | SRC_REC)) {     // EfficientGraphConv symadd+max+mean
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_S | SRC_X | SRC_YL | SRC_REC><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_S | SRC_YL)) {                     // EfficientGraphConv symadd (EGC-S)
-    bwd_src_kernel<1, SRC_STATIC | SRC_S | SRC_YL><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_S | SRC_XL | SRC_YL)) {            // EGConv symnorm
-    bwd_src_kernel<1, SRC_STATIC | SRC_S | SRC_XL | SRC_YL><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_X | SRC_REC)) {                      // relational EGC: mean+max, raw
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_X | SRC_REC><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_V | SRC_X | SRC_YL | SRC_REC)) {     // EfficientGraphConv add+std+max (zinc EGC-M)
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_V | SRC_X | SRC_YL | SRC_REC><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_S | SRC_V | SRC_X | SRC_YL | SRC_REC)) {  // symadd+std+max (CIFAR EGC-M)
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_S | SRC_V | SRC_X | SRC_YL | SRC_REC><<<grid, 256, 0, stream>>>(a);
-  } else if (ns == 1 && fl == (SRC_STATIC | SRC_T | SRC_X | SRC_YL | SRC_REC)) {             // add+mean+max (molhiv EGC-M)
-    bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_X | SRC_YL | SRC_REC><<<grid, 256, 0, stream>>>(a);
-  } else
-  switch (ns) {
-    case 1: bwd_src_kernel<1><<<grid, 256, 0, stream>>>(a); break;
-    case 2: bwd_src_kernel<2><<<grid, 256, 0, stream>>>(a); break;
-    case 3: bwd_src_kernel<3><<<grid, 256, 0, stream>>>(a); break;
-    case 4: bwd_src_kernel<4><<<grid, 256, 0, stream>>>(a); break;
-    default: return EGC_ERR_UNSUPPORTED;
-  }
-  EGC_LAUNCH_CHECK("bwd_src_kernel");
-  return EGC_OK;
+  if (const int st = launch_dst(p, a, stream); st != EGC_OK) return st;
+  if (const int st = launch_records(p, a, stream); st != EGC_OK) return st;
+  return launch_src(p, a, stream);
 }
 
 }  // extern "C"

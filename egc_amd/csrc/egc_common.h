@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "egc_hip.h"
+#include "egc_plain.h"   // ceil_div, the layer's strides, the long-row plan's capacities: shared with the HIP-free planners
 
 #define EGC_WAVE 64
 
@@ -62,38 +63,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // the next one at every barrier -- microseconds of HBM latency per tile.  The tiles exchanged between wavefronts live in LDS,
 // so lgkmcnt(0) + s_barrier is all that is needed.
 __device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// floats between consecutive bases of a `bases` row (egc_layer.basis_stride; 0 = contiguous)
-static inline int layer_basis_stride(const egc_layer* L) {
-  const int len = L->out_channels / L->num_heads;
-  return L->basis_stride > len ? L->basis_stride : len;
-}
-
-static inline bool layer_uses_symnorm(const egc_layer* L) {
-  for (int t = 0; t < L->num_aggrs; ++t)
-    if (L->aggrs[t] == EGC_AGGR_SYMNORM) return true;
-  return false;
-}
-
-// Long-row plan layout (int32 words), shared by egc_csr_prepare and the aggregate kernels:
-//   [0] n_long   [1] n_chunks   [2] cap_long   [3] cap_chunks
-//   [4 .. 4+cap_long)                 long_row[s]      row id of long-row slot s
-//   [.. +cap_long)                    long_chunk0[s]   first chunk slot of that row
-//   [.. +cap_chunks)                  chunk_slot[c]    long-row slot the chunk belongs to
-//   [.. +cap_chunks)                  chunk_begin[c]   first CSR entry of the chunk
-struct PlanCaps {
-  int64_t cap_long;
-  int64_t cap_chunks;
-};
-static inline PlanCaps plan_caps(int64_t n_nodes, int64_t n_edges) {
-  PlanCaps c;
-  c.cap_long = n_edges / (EGC_LONG_ROW_THRESHOLD + 1) + 1;
-  if (c.cap_long > n_nodes + 1) c.cap_long = n_nodes + 1;
-  c.cap_chunks = n_edges / EGC_LONG_ROW_CHUNK + c.cap_long;
-  return c;
-}
 
 // A lane's four adjacent columns c .. c + 3 of a row of `width` floats (egc_typed_mean.hip, egc_mpnn.hip): one 16-byte access
 // (VEC: width, strides and pointers are multiples of 16 bytes) or 4-byte ones of the columns that exist.

@@ -20,8 +20,9 @@ the tail of a second chunk: 264 / 265).  ``rect`` (more or fewer source rows tha
 on) are its variants.
 
 ``dispatch`` restates, as data, which kernels ``egc_aggregate_combine_backward_f32`` launches for a layer on a graph, and
-``arg_extrema_instance`` the instance of the separate arg pass of the training forward.  ``source_instances`` reads the launches
-out of the HIP source, so that an instance added there without a case here is noticed.
+``arg_extrema_instance`` the instance of the separate arg pass of the training forward.  ``source_instances`` reads the rows of the
+instance lists of egc_backward_host.h, which the launches expand from, so that an instance added there without a case here is
+noticed; tests/test_backward_plan_cpu.py holds the C++ plan itself against ``dispatch``.
 
 ``CASES`` is the table: every cell of the rule at the smallest shape that reaches it, the trained nets' shapes among them."""
 import functools
@@ -346,36 +347,42 @@ def arg_extrema_instance(case):
     return (slots + (1 << lg) - 1) >> lg
 
 
-_NAMES = {"S": "sum", "M": "mean", "X": "max", "Y": "symnorm", "EGC_AGGR_STD": "std", "EGC_AGGR_MIN": "min", "EGC_AGGR_VAR": "var"}
+_NAMES = {"EGC_AGGR_" + k.upper(): k for k in CODES}
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "egc_amd", "csrc")
+KERNELS = ("bwd_dst_fast_kernel", "bwd_src_kernel", "bwd_records_kernel", "arg_extrema_kernel")
 
 
-def source_text():
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "egc_amd", "csrc", "egc_backward.hip")
-    with open(path) as f:
+def source_text(name="egc_backward.hip"):
+    with open(os.path.join(_CSRC, name)) as f:
         return f.read()
 
 
-def source_instances(text=None):
-    """The template instances egc_backward.hip launches, in the notation of ``Cell`` -- read from the HIP source text."""
-    text = source_text() if text is None else text
+def list_rows(lists, macro):
+    """The argument text of every ROW(...) of the list ``macro`` of egc_backward_host.h (a #define continued by backslashes)."""
+    body = re.search(r"#define %s\(ROW\)((?:.*\\\n)*.*)" % macro, lists).group(1)
+    return [m.group(1) for m in re.finditer(r"ROW\(([^()]*)\)", body)]
+
+
+def source_instances(lists=None, source=None):
+    """The template instances egc_backward.hip launches, in the notation of ``Cell`` -- read from the rows of the lists of
+    egc_backward_host.h, which the launches (one per kernel template in egc_backward.hip: asserted here) expand from."""
+    lists = source_text("egc_backward_host.h") if lists is None else lists
+    source = source_text() if source is None else source
+    for k in KERNELS:
+        assert len(re.findall(k + r"<[^;{}]*?><<<", source)) == 1, k
     got = dict(dst=set(), src=set(), rec=set(), arg=set())
-    for m in re.finditer(r"bwd_dst_fast_kernel<(.*?)><<<", text):
-        parts = [p.strip() for p in m.group(1).split(",", 3)]
-        name = f"fast<{parts[0]},{parts[1]},{parts[2]}"
-        if len(parts) == 4:
-            lst = re.fullmatch(r"bwd_agg_pack\((.*)\)", parts[3]).group(1)
-            name += "," + "+".join(_NAMES[a.strip()] for a in lst.split(","))
-        got["dst"].add(name + ">")
-    for m in re.finditer(r"bwd_src_kernel<(.*?)><<<", text):
-        parts = [p.strip() for p in m.group(1).split(",", 1)]
-        if len(parts) == 1:
-            got["src"].add(f"src<{parts[0]}>")
-        else:
-            fl = [f.strip()[len("SRC_"):] for f in parts[1].split("|")]
-            assert fl[0] == "STATIC"
-            got["src"].add(f"src<{parts[0]}," + "|".join(f for f in ("T", "S", "V", "X", "N", "XL", "YL", "REC") if f in fl) + ">")
-    got["rec"] = {f"sep<{m.group(1)}>" for m in re.finditer(r"bwd_records_kernel<(\d)><<<", text)}
-    got["arg"] = {int(m.group(1)) for m in re.finditer(r"arg_extrema_kernel<(\d)><<<", text)}
+    for row in list_rows(lists, "EGC_BWD_DST_LISTS"):
+        parts = [p.strip() for p in row.split(",")]
+        got["dst"].add(f"fast<{parts[0]},{parts[1]},{parts[2]}," + "+".join(_NAMES[a] for a in parts[3:]) + ">")
+    for row in list_rows(lists, "EGC_BWD_DST_TRIPLES"):
+        got["dst"].add("fast<" + ",".join(p.strip() for p in row.split(",")) + ">")
+    for row in list_rows(lists, "EGC_BWD_SRC_FLAGS"):
+        fl = [f.strip()[len("SRC_"):] for f in row.split("|")]
+        got["src"].add("src<1," + "|".join(f for f in ("T", "S", "V", "X", "N", "XL", "YL", "REC") if f in fl) + ">")
+    for ns in list_rows(lists, "EGC_BWD_NS"):
+        got["src"].add(f"src<{ns}>")
+        got["rec"].add(f"sep<{ns}>")
+        got["arg"].add(int(ns))
     return got
 
 

@@ -1,6 +1,6 @@
 """The table of the layer-backward sweep without a GPU (tests/backward_ref.py).  This guards the TABLE and the restatement, not
 the kernels: that the cases reach every kernel instance egc_backward.hip launches and every branch of its dispatch rule (the
-instances are read out of the HIP source, so one added there without a case fails here), that the rule agrees with the library
+instances are the rows of the lists of egc_backward_host.h, which the launches expand from, so one added there without a case fails here), that the rule agrees with the library
 where the library can be asked without a device, that the sweep graphs have the rows they are built for on both sides and sit on
 the intended side of the rule that turns the extremum records on, and that the operand-level restatement is the mathematics of the
 module-level one."""
@@ -93,7 +93,7 @@ def test_the_table_reaches_every_branch_of_the_rule():
 
 
 def test_removing_a_case_or_adding_an_instance_is_noticed():
-    """The two checks above do fail: without the only case of a cell, and with a launch the table does not know."""
+    """The two checks above do fail: without the only case of a cell, and with a row or a launch the table does not know."""
     src = source_instances()
     lone = "fast<5,4,3,symnorm+std+max>"
     fewer = tuple(c for c in CASES if c.dst != lone)
@@ -103,8 +103,12 @@ def test_removing_a_case_or_adding_an_instance_is_noticed():
         ei, n, _ = case_graph(c)
         reached |= {dispatch(c, n, ei.shape[1], m).dst for m in MODES}
     assert src["dst"] - reached == {lone}
-    more = backward_ref.source_text() + "\n  bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_N><<<grid, 256, 0, stream>>>(a);\n"
-    assert source_instances(more)["src"] - src["src"] == {"src<1,T|N>"}
+    lists = backward_ref.source_text("egc_backward_host.h")
+    head = "#define EGC_BWD_SRC_FLAGS(ROW)"
+    more = lists.replace(head, head + " ROW(SRC_T | SRC_N)")                    # one more row of the list
+    assert more != lists and source_instances(more)["src"] - src["src"] == {"src<1,T|N>"}
+    with pytest.raises(AssertionError):                                         # a literal launch beside the list
+        source_instances(source=backward_ref.source_text() + "\n  bwd_src_kernel<1, SRC_STATIC | SRC_T | SRC_N><<<grid, 256, 0, stream>>>(a);\n")
 
 
 def test_the_rule_agrees_with_the_library_on_records():
