@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "egc_aggregate_host.h"
+#include "egc_fused_tile_host.h"
 #include "egc_gemm_split.h"
 #include "egc_pack_map.h"
 
@@ -919,33 +920,54 @@ int egc_aggregate_combine_batch_f32(const int32_t* tiles, const int32_t* n_tiles
                             max_tile_edges, src, dst, max_index, status, host_flag, (hipStream_t)stream);
 }
 
-// ---- batches of small graphs, the whole layer in one launch (egc_fused_tile.hip) ----
+// ---- batches of small graphs, the whole layer in one launch (egc_fused_tile.hip; every number: egc_fused_tile_host.h) ----
+// The plans of a layer, where asked: the forward's (rows of 65 .. 128 slots included) and the backward's.  Not EGC_OK: not a
+// layer, or one no register-resident kernel serves; a plan may still say FT_FORM_NONE.  `a`: the layer's fields.
+static int fused_plans(const egc_layer* layer, bool with_post, AggArgs& a, FtPlan* fwd, FtPlan* bwd) {
+  int st = EGC_OK;
+  if (fwd != nullptr) {
+    *fwd = FtPlan{};
+    if ((st = tile_layer_args(layer, a, true)) != EGC_OK) return st;
+    *fwd = fused_tile_plan(a, layer->in_channels, with_post, false);
+  }
+  if (bwd != nullptr) {
+    *bwd = FtPlan{};
+    if ((st = tile_layer_args(layer, a)) != EGC_OK) return st;
+    *bwd = fused_tile_plan(a, layer->in_channels, false, true);
+  }
+  return st;
+}
+
 int32_t egc_batch_fused_tile_nodes(const egc_layer* layer, int32_t max_tile_edges, int32_t with_post) {
   AggArgs a;
-  if (tile_layer_args(layer, a, true) != EGC_OK) return 0;
-  return fused_tile_capacity(a, layer->in_channels, max_tile_edges, with_post != 0);
+  FtPlan p;
+  fused_plans(layer, with_post != 0, a, &p, nullptr);
+  return ft_capacity(p, max_tile_edges);
 }
 
 int32_t egc_batch_fused_tile_quantum(const egc_layer* layer) {
   AggArgs a;
-  if (tile_layer_args(layer, a, true) != EGC_OK) return 0;
-  return fused_tile_quantum(a, layer->in_channels);
+  FtPlan p;
+  fused_plans(layer, false, a, &p, nullptr);
+  return p.quantum;
 }
 
 int64_t egc_batch_fused_pack_bytes(const egc_layer* layer) {
   AggArgs a;
-  if (tile_layer_args(layer, a, true) != EGC_OK || !fused_tile_shape(a, layer->in_channels)) return 0;
-  return (int64_t)fused_tile_pack_bytes(a, layer->in_channels);
+  FtPlan p;
+  fused_plans(layer, false, a, &p, nullptr);
+  return (int64_t)p.packed.bytes();
 }
 
 int egc_batch_fused_pack(const egc_layer* layer, const float* wcat, const float* bcat, void* packed, int64_t packed_bytes,
                          egc_stream_t stream) {
   AggArgs a;
-  int st = tile_layer_args(layer, a, true);
+  FtPlan p;
+  int st = fused_plans(layer, false, a, &p, nullptr);
   if (st != EGC_OK) return st;
-  if (!fused_tile_shape(a, layer->in_channels)) return EGC_ERR_UNSUPPORTED;
-  if (wcat == nullptr || packed == nullptr || packed_bytes < (int64_t)fused_tile_pack_bytes(a, layer->in_channels)) return EGC_ERR_INVALID;
-  return fused_tile_pack(a, wcat, bcat, layer->in_channels, a.B * a.Ls, a.W, a.ldb, packed, (hipStream_t)stream);
+  if (p.form == FT_FORM_NONE) return EGC_ERR_UNSUPPORTED;
+  if (wcat == nullptr || packed == nullptr || packed_bytes < (int64_t)p.packed.bytes()) return EGC_ERR_INVALID;
+  return fused_tile_pack(p, a, wcat, bcat, layer->in_channels, packed, (hipStream_t)stream);
 }
 
 int egc_layer_forward_batch_fused_f32(const int64_t* graph_ptr, const int64_t* edge_ptr, int64_t n_graphs, const int64_t* src,
@@ -970,50 +992,53 @@ int egc_layer_forward_batch_fused_f32(const int64_t* graph_ptr, const int64_t* e
 // ---- the same batches, the layer's BACKWARD in one launch (egc_fused_tile.hip, MODE 1) ----
 int32_t egc_batch_fused_bwd_tile_nodes(const egc_layer* layer, int32_t max_tile_edges) {
   AggArgs a;
-  if (tile_layer_args(layer, a) != EGC_OK) return 0;
-  return fused_tile_bwd_capacity(a, layer->in_channels, max_tile_edges);
+  FtPlan pb;
+  fused_plans(layer, false, a, nullptr, &pb);
+  return ft_capacity(pb, max_tile_edges);
 }
 
 int64_t egc_batch_fused_bwd_pack_bytes(const egc_layer* layer) {
   AggArgs a;
-  if (tile_layer_args(layer, a) != EGC_OK || !fused_tile_bwd_shape(a, layer->in_channels)) return 0;
-  return (int64_t)fused_tile_bwd_pack_bytes();
+  FtPlan pb;
+  fused_plans(layer, false, a, nullptr, &pb);
+  return (int64_t)pb.packed_t.bytes();
 }
 
 int egc_batch_fused_bwd_pack(const egc_layer* layer, const float* wcat, void* packed_t, int64_t packed_bytes, egc_stream_t stream) {
   AggArgs a;
-  int st = tile_layer_args(layer, a);
+  FtPlan pb;
+  int st = fused_plans(layer, false, a, nullptr, &pb);
   if (st != EGC_OK) return st;
-  if (!fused_tile_bwd_shape(a, layer->in_channels)) return EGC_ERR_UNSUPPORTED;
-  if (wcat == nullptr || packed_t == nullptr || packed_bytes < (int64_t)fused_tile_bwd_pack_bytes()) return EGC_ERR_INVALID;
-  return fused_tile_bwd_pack(a, wcat, layer->in_channels, packed_t, (hipStream_t)stream);
+  if (pb.form == FT_FORM_NONE) return EGC_ERR_UNSUPPORTED;
+  if (wcat == nullptr || packed_t == nullptr || packed_bytes < (int64_t)pb.packed_t.bytes()) return EGC_ERR_INVALID;
+  return fused_tile_bwd_pack(pb, a, wcat, layer->in_channels, packed_t, (hipStream_t)stream);
 }
 
 int egc_batch_fused_train_pack(const egc_layer* layer, const float* wcat, const float* bcat, void* packed, int64_t packed_bytes,
                                void* packed_t, int64_t packed_t_bytes, egc_stream_t stream) {
-  AggArgs a, ab;
-  int st = tile_layer_args(layer, a, true);
-  if (st == EGC_OK) st = tile_layer_args(layer, ab);
+  AggArgs a;
+  FtPlan p, pb;
+  int st = fused_plans(layer, false, a, &p, &pb);
   if (st != EGC_OK) return st;
-  if (!fused_tile_shape(a, layer->in_channels) || !fused_tile_bwd_shape(ab, layer->in_channels)) return EGC_ERR_UNSUPPORTED;
-  if (wcat == nullptr || packed == nullptr || packed_t == nullptr || packed_bytes < (int64_t)fused_tile_pack_bytes(a, layer->in_channels) ||
-      packed_t_bytes < (int64_t)fused_tile_bwd_pack_bytes())
+  if (p.form == FT_FORM_NONE || pb.form == FT_FORM_NONE) return EGC_ERR_UNSUPPORTED;
+  if (wcat == nullptr || packed == nullptr || packed_t == nullptr || packed_bytes < (int64_t)p.packed.bytes() ||
+      packed_t_bytes < (int64_t)pb.packed_t.bytes())
     return EGC_ERR_INVALID;
-  return fused_tile_train_pack(ab, wcat, bcat, layer->in_channels, a.B * a.Ls, a.W, a.ldb, packed, packed_t, (hipStream_t)stream);
+  return fused_tile_train_pack(pb, a, wcat, bcat, layer->in_channels, packed, packed_t, (hipStream_t)stream);
 }
 
 int egc_batch_fused_train_pack_params(const egc_layer* layer, const float* const* bases_parts, int32_t n_parts, const float* comb_weight,
                                       const float* comb_bias, const float* bcat, int32_t num_heads, int32_t num_aggrs, int32_t num_bases,
                                       int32_t basis_len, int32_t basis_stride, int32_t permute_hab, void* packed, int64_t packed_bytes,
                                       void* packed_t, int64_t packed_t_bytes, egc_stream_t stream) {
-  AggArgs a, ab;
-  int st = tile_layer_args(layer, a, true);
-  if (st == EGC_OK) st = tile_layer_args(layer, ab);
+  AggArgs a;
+  FtPlan p, pb;
+  int st = fused_plans(layer, false, a, &p, &pb);
   if (st != EGC_OK) return st;
-  if (!fused_tile_shape(a, layer->in_channels) || !fused_tile_bwd_shape(ab, layer->in_channels)) return EGC_ERR_UNSUPPORTED;
+  if (p.form == FT_FORM_NONE || pb.form == FT_FORM_NONE) return EGC_ERR_UNSUPPORTED;
   if (bases_parts == nullptr || comb_weight == nullptr || packed == nullptr || packed_t == nullptr ||
       (n_parts != 1 && n_parts != num_bases) || n_parts > PACK_MAX_PARTS || (comb_bias != nullptr && bcat != nullptr) ||
-      packed_bytes < (int64_t)fused_tile_pack_bytes(a, layer->in_channels) || packed_t_bytes < (int64_t)fused_tile_bwd_pack_bytes())
+      packed_bytes < (int64_t)p.packed.bytes() || packed_t_bytes < (int64_t)pb.packed_t.bytes())
     return EGC_ERR_INVALID;
   // the parameters must describe the layer the planes are packed for
   if (num_bases != a.B || basis_stride != a.Ls || basis_len <= 0 || basis_len > basis_stride || num_heads != a.H ||
@@ -1024,8 +1049,7 @@ int egc_batch_fused_train_pack_params(const egc_layer* layer, const float* const
   for (int i = 0; i < n_parts; ++i)
     if (ptrs.part[i] == nullptr) return EGC_ERR_INVALID;
   const PackDims d{layer->in_channels, num_heads, num_aggrs, num_bases, basis_len, basis_stride, n_parts, permute_hab != 0};
-  return fused_tile_train_pack_params(ab, ptrs, comb_weight, comb_bias, bcat, d, a.B * a.Ls, a.W, a.ldb, packed, packed_t,
-                                      (hipStream_t)stream);
+  return fused_tile_train_pack_params(pb, a, ptrs, comb_weight, comb_bias, bcat, d, packed, packed_t, (hipStream_t)stream);
 }
 
 int egc_layer_backward_batch_fused_f32(const int64_t* graph_ptr, const int64_t* edge_ptr, int64_t n_graphs, const int64_t* src,

@@ -215,27 +215,23 @@ int launch_tile_simple(AggArgs a, const int4* tiles, const int* n_tiles_dev, int
                        hipStream_t stream);
 
 // egc_fused_tile.hip: the whole layer on tiles of whole graphs in ONE launch (plan + GEMM + CSR + aggregate + combine)
-bool fused_tile_shape(const AggArgs& a, int f_in);
-int fused_tile_capacity(const AggArgs& a, int f_in, int max_tile_edges, bool with_post);
-int fused_tile_quantum(const AggArgs& a, int f_in);      // rows per GEMM chunk: tile_nodes is a multiple of it (16 / 32; 0 = outside)
-size_t fused_tile_pack_bytes(const AggArgs& a, int f_in);
-int fused_tile_pack(const AggArgs& a, const float* wcat, const float* bcat, int f_in, int f_g, int w_cols, int ldb, void* packed,
-                    hipStream_t stream);
+// (FtPlan, egc_fused_tile_host.h: the layer's plan for either direction -- form, envelope, capacity, packed operands; the launches build
+// it themselves)
+struct FtPlan;
+FtPlan fused_tile_plan(const AggArgs& a, int f_in, bool with_post, bool bwd);
+int fused_tile_pack(const FtPlan& p, const AggArgs& a, const float* wcat, const float* bcat, int f_in, void* packed, hipStream_t stream);
 int launch_fused_tile(AggArgs a, const int64_t* ptr, const int64_t* edge_ptr, int64_t n_graphs, const int64_t* src,
                       const int64_t* dst, int64_t n_edges, const int* max_index, const float* x, int f_in, const void* packed,
                       int tcap, int emax, int32_t* status, int32_t* host_flag, hipStream_t stream);
 
 // the tile-local BACKWARD of the same launch (egc_fused_tile.hip: fused_tile_kernel<..., MODE = 1>)
-bool fused_tile_bwd_shape(const AggArgs& a, int f_in);
-int fused_tile_bwd_capacity(const AggArgs& a, int f_in, int max_tile_edges);
-size_t fused_tile_bwd_pack_bytes();
-int fused_tile_bwd_pack(const AggArgs& a, const float* wcat, int f_in, void* packed, hipStream_t stream);
+int fused_tile_bwd_pack(const FtPlan& pb, const AggArgs& a, const float* wcat, int f_in, void* packed_t, hipStream_t stream);
 struct PackPtrs;
 struct PackDims;
-int fused_tile_train_pack_params(const AggArgs& a, const PackPtrs& bases, const float* comb_w, const float* comb_b, const float* bcat,
-                                 const PackDims& d, int f_g, int w_cols, int ldb, void* packed, void* packed_t, hipStream_t stream);
-int fused_tile_train_pack(const AggArgs& a, const float* wcat, const float* bcat, int f_in, int f_g, int w_cols, int ldb, void* packed,
-                          void* packed_t, hipStream_t stream);
+int fused_tile_train_pack_params(const FtPlan& pb, const AggArgs& a, const PackPtrs& bases, const float* comb_w, const float* comb_b,
+                                 const float* bcat, const PackDims& d, void* packed, void* packed_t, hipStream_t stream);
+int fused_tile_train_pack(const FtPlan& pb, const AggArgs& a, const float* wcat, const float* bcat, int f_in, void* packed, void* packed_t,
+                          hipStream_t stream);
 int launch_fused_tile_bwd(AggArgs a, const int64_t* ptr, const int64_t* edge_ptr, int64_t n_graphs, const int64_t* src,
                           const int64_t* dst, int64_t n_edges, const int* max_index, const float* x, int f_in, const void* packed,
                           const void* packed_t, const float* grad_out, float* d_x, const float* d_x_add, float* d_cat, int ld_dcat, int tcap, int emax,

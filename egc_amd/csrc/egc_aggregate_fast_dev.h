@@ -7,7 +7,6 @@
 
 namespace egc {
 
-constexpr int AMAX = 4;     // aggregators supported by the register-resident combine
 // `out` is written once and read by a LATER kernel: non-temporal stores (aux bit 1) keep the rows from piling up
 // as dirty lines in the XCDs' L2s, whose write-back at the end of the kernel otherwise costs ~3 us per launch.
 constexpr int OUT_NT = 2;

@@ -3,15 +3,14 @@
 // an egc_layer before it can launch -- the layer-static fields of AggArgs, the lane geometry of a row, the need mask, the
 // per-wavefront LDS strips, the template-instance ladder and the matching of a layer against a compiled-in configuration.  One
 // definition each: a capacity query and its launch cannot disagree about LDS, and a change to the row schedule lands once.
+// (What only the one-launch batch kernel needs -- its forms, tile range, LDS image, packed operands, grid and switches -- is
+// egc_fused_tile_host.h's; agg_magic and the bias strip's size, which that HIP-free header shares with this one, are egc_plain.h's.)
 #pragma once
 #include <type_traits>
 
 #include "egc_aggregate_fast_dev.h"
 
 namespace egc {
-
-// floor(2^32 / d) + 1: q / d == umulhi(q, magic) for the q < 2^16 the kernels divide
-inline unsigned agg_magic(int d) { return (unsigned)(((uint64_t)1 << 32) / (uint64_t)d) + 1u; }
 
 // The fields of AggArgs that are a function of the layer alone (ldw: a plain weightings array; callers with a strided one
 // overwrite it).  magic_L and lpr_log2 belong to the generic kernels of egc_aggregate.hip and stay with that path.
@@ -70,7 +69,7 @@ inline int agg_need(AggArgs& a) {
 
 // Per-wavefront LDS of the epilogue: the bias strip in the (padded) head layout [h][Ls] (>= F_out floats), a second strip with
 // the scale when a post-op is fused, and one weightings strip per lane group of the wavefront.
-inline int agg_bias_floats(const AggArgs& a) { return (a.H * a.Ls + 3) & ~3; }
+inline int agg_bias_floats(const AggArgs& a) { return bias_strip_floats(a.H, a.Ls); }
 inline int agg_w_strip_floats(const AggArgs& a) { return (a.W + 3) & ~3; }
 inline int agg_strip_floats(const AggArgs& a, int groups_per_wave, bool with_post) {
   return (with_post ? 2 : 1) * agg_bias_floats(a) + groups_per_wave * agg_w_strip_floats(a);

@@ -1,53 +1,16 @@
 // The kernel of egc_fused_tile.hip (batches of whole graphs, the WHOLE layer in one launch) -- shared by its two translation
-// units: egc_fused_tile.hip (the register-stationary form: F_in <= 128, ldb + H B A <= 192) and egc_fused_tile_wide.hip (the
-// reference's wider batched shapes: weight slabs streamed from L2).  See egc_fused_tile.hip for the description.
+// units: egc_fused_tile.hip (the register-stationary form: F_in <= 128, ldb + H B A <= 192) and egc_fused_tile_wide.inc (the
+// reference's wider batched shapes: weight slabs streamed from L2).  See egc_fused_tile.hip for the description.  Every field of
+// FusedTileArgs beyond the pointers, the constants and the packed operands' layouts come from egc_fused_tile_host.h (FtPlan, ft_image,
+// FtPacked): the kernel derives none of them.
 #pragma once
 #include <algorithm>
 
 #include "egc_aggregate_fast_dev.h"
+#include "egc_fused_tile_host.h"   // the FT_* / FTW_* / FTB_* constants and the packed operands' layouts: shared with the host side
 #include "egc_gemm_split.h"
 
 namespace egc {
-
-constexpr int FT_THREADS = 1024;
-constexpr int FT_WAVES = FT_THREADS / 64;
-constexpr int FT_MFMA_WAVES = 12;       // 16-column tiles of the virtual column space [bases (ldb) | weightings (W)]
-constexpr int FT_FIRST_HELPER = 12;     // wavefronts 12-15: x rows -> planes
-constexpr int FT_HELPER_THREADS = (FT_WAVES - FT_FIRST_HELPER) * 64;
-constexpr int FT_KP = 128;              // k extent of the register-resident weight tiles (F_in <= 128, zero beyond)
-constexpr int FT_CHUNK = 16;            // rows per GEMM step (one MFMA tile)
-constexpr int FT_WORKER_THREADS = FT_FIRST_HELPER * 64;
-constexpr int FT_EDGE_REGS = 4;         // edges per worker thread kept in registers (16:16 packed local ids)
-constexpr int FT_CSR_WAVES = 3;         // helper wavefronts 12-14 build the tiles' CSR (15 plans the tiles)
-constexpr int FT_PER = 3;               // rows per lane of the one-wavefront scan: 3 x 64 >= 16 FT_RING
-constexpr int FT_RING = 10;             // 16-row chunks of x a tile may have: the helpers hold them all in registers (80 VGPRs)
-static_assert(FT_PER * 64 >= FT_CHUNK * FT_RING, "the scan covers a whole tile");
-constexpr int FT_MAX_NODES = 2048;      // local ids are 16-bit, the scan is one wavefront
-constexpr int FT_NV = FT_MFMA_WAVES * 16;
-constexpr int FT_PLANE_BYTES = FT_CHUNK * FT_KP * 2;     // one plane of one chunk
-constexpr int FT_PBUF = 3;                                // chunk buffers: the helpers stage two chunks ahead of the workers' MFMAs
-constexpr int FT_PLANES_BYTES = FT_PBUF * 2 * FT_PLANE_BYTES;  // [3 buffers][2 planes]
-// The backward form's second GEMM: d rows of K2 = ldb + H B 4 <= 192 columns as two fp16 planes, rows padded by 16 bytes
-constexpr int FTB_ROW_BYTES = 192 * 2 + 16;                // (25 sixteen-byte pieces: conflict-free A-operand reads)
-constexpr int FTB_PLANE_BYTES = FT_CHUNK * FTB_ROW_BYTES;  // one plane of one 16-row chunk
-constexpr int FTB_PBUF_BYTES = 2 * FTB_PLANE_BYTES;        // [2 planes]
-constexpr int FTB_PLANES_BYTES = 2 * FTB_PBUF_BYTES;       // [2 buffers]: 25,600 bytes (the first GEMM's three buffers take 24,576)
-// The WIDE form (egc_fused_tile_wide.hip: 128 < F_in <= 320 or more than 192 virtual columns -- the reference's 168 / 224 / 296 /
-// 300 / 304-wide batched nets, run_pretrained.sh:7-48): 32-row GEMM chunks on v_mfma_f32_32x32x16_f16, one 32-column tile per
-// worker (at most 12: 384 virtual columns), the weight fragments streamed from L2 per k-step (a 320 x 384 operand does not fit the
-// register files), x staged in k-slabs of 128 through two plane buffers.
-constexpr int FTW_CH = 32;                                 // rows per GEMM chunk
-constexpr int FTW_PP = 10;                                 // 16-byte pieces of x per helper thread and chunk: 8 threads per row, F_in <= 320
-constexpr int FTW_MAX_FIN = 8 * FTW_PP * 4;
-constexpr int FTW_SLAB = 128;                              // k per staged slab
-constexpr int FTW_LDX = FTW_SLAB + 8;                      // halves per plane row in LDS (+ 16 bytes: conflict-free A-operand reads)
-constexpr int FTW_PLANE_BYTES = FTW_CH * FTW_LDX * 2;      // one plane of one slab
-constexpr int FTW_PBUF_BYTES = 2 * FTW_PLANE_BYTES;        // [2 planes]
-constexpr int FTW_PLANES_BYTES = 2 * FTW_PBUF_BYTES;       // [2 buffers]
-constexpr int FTW_MAXCH = FT_CHUNK * FT_RING / FTW_CH;     // chunks of a tile (160 rows)
-constexpr int FTW_MAX_CT = FT_MFMA_WAVES;                  // 32-column tiles
-constexpr int FT_DBS_POISON = 0x7fffffff;                  // backward: the tile's fixed-point scale when its g or w' holds an Inf / NaN
-
 
 struct FusedTileArgs {
   const int64_t* ptr;        // node offsets of the graphs [G + 1]
@@ -1003,10 +966,12 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
   bool dst_act = false;
   if constexpr (WIDE == 0) {
   if (is_mfma) {
-    const float* tail = reinterpret_cast<const float*>(t.packed + (int64_t)FT_MFMA_WAVES * 4 * 2 * 64 * 8);
+    constexpr FtPacked PK = ft_packed_narrow();
+    constexpr int64_t TAIL_AT = PK.tail_at();
+    const float* tail = reinterpret_cast<const float*>(t.packed + TAIL_AT);
     const int v = 16 * wave + (lane & 15);
     col_inv = tail[v];
-    col_bias = tail[FT_NV + v];
+    col_bias = tail[PK.bias_at + v];
     if (v < a.ldb) {
       dst_off = t.off_bases + v * 4;
       dst_stride = a.ldb * 4;
@@ -1020,10 +985,10 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
   }
   } else if (is_mfma) {
     // WIDE: this wavefront's 32 virtual columns [bases: 0 .. ldb) | padding to a multiple of 32 | weightings: ldbp .. ldbp + W)
-    const float* tail = reinterpret_cast<const float*>(t.packed + (int64_t)t.n_ct * t.k16 * 2 * 64 * 8);
+    const float* tail = reinterpret_cast<const float*>(t.packed + ft_packed_wide(t.n_ct, t.k16).tail_at());
     const int v = 32 * wave + (lane & 31);
     col_inv = tail[v];
-    col_bias = tail[FTW_MAX_CT * 32 + v];
+    col_bias = tail[ft_packed_wide(t.n_ct, t.k16).bias_at + v];
     if (v < a.ldb) {
       dst_off = t.off_bases + v * 4;
       dst_stride = a.ldb * 4;
@@ -1060,7 +1025,8 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
     if (is_mfma) {
       int lv = lane;
       asm volatile("" : "+v"(lv));
-      const f4* wsrc = reinterpret_cast<const f4*>(t.packed) + (int64_t)wave * 8 * 64;   // wave-uniform base + lane
+      constexpr int64_t TILE_F4 = ft_packed_narrow().tile_halves() / 8;     // (a tile's four k-steps of two planes)
+      const f4* wsrc = reinterpret_cast<const f4*>(t.packed) + (int64_t)wave * TILE_F4;   // wave-uniform base + lane
 #pragma unroll
       for (int s = 0; s < 8; ++s) u[s] = wsrc[s * 64 + lv];
     } else {
@@ -1597,10 +1563,12 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
       {
         int lv = lane;
         asm volatile("" : "+v"(lv));
-        const f4* wsrc = reinterpret_cast<const f4*>(t.packed_t) + (int64_t)(is_mfma2 ? wave : 0) * 12 * 64;
+        constexpr int64_t TILE_F4 = ft_packed_t().tile_halves() / 8, TAIL_AT = ft_packed_t().tail_at();   // (the transposed operand's layout)
+        static_assert(TILE_F4 == 12 * 64, "u2[12]: a tile's six k-steps of two planes");
+        const f4* wsrc = reinterpret_cast<const f4*>(t.packed_t) + (int64_t)(is_mfma2 ? wave : 0) * TILE_F4;
 #pragma unroll
         for (int k2 = 0; k2 < 12; ++k2) u2[k2] = wsrc[k2 * 64 + lv];
-        col_inv2 = reinterpret_cast<const float*>(t.packed_t + (int64_t)8 * 6 * 2 * 64 * 8)[16 * (is_mfma2 ? wave : 0) + (lv & 15)];
+        col_inv2 = reinterpret_cast<const float*>(t.packed_t + TAIL_AT)[16 * (is_mfma2 ? wave : 0) + (lv & 15)];
       }
       lds_barrier();   // (B1: every row's d bases / d w' are in the images)
       if (tid == 0) lds_rec[27] = 0;
@@ -1655,8 +1623,8 @@ __global__ void __launch_bounds__(FT_THREADS) fused_tile_kernel(AggArgs a, Fused
 }
 
 // egc_fused_tile_wide.hip: the WIDE instances (lpr = lanes per row group: 16 / 32 / 64; need = NEED_* mask of the layer)
-int launch_fused_tile_wide1(const AggArgs& a, const FusedTileArgs& t, int need, unsigned grid, size_t lds, hipStream_t stream);
-int launch_fused_tile_wide2(const AggArgs& a, const FusedTileArgs& t, int need, unsigned grid, size_t lds, hipStream_t stream);
-int launch_fused_tile_wide3(const AggArgs& a, const FusedTileArgs& t, int need, unsigned grid, size_t lds, hipStream_t stream);
+int launch_fused_tile_wide1(const AggArgs& a, const FusedTileArgs& t, int need, const FtSwitches& sw, unsigned grid, size_t lds, hipStream_t stream);
+int launch_fused_tile_wide2(const AggArgs& a, const FusedTileArgs& t, int need, const FtSwitches& sw, unsigned grid, size_t lds, hipStream_t stream);
+int launch_fused_tile_wide3(const AggArgs& a, const FusedTileArgs& t, int need, const FtSwitches& sw, unsigned grid, size_t lds, hipStream_t stream);
 
 }  // namespace egc

@@ -4,8 +4,6 @@
 // 32-row chunks on v_mfma_f32_32x32x16_f16, weight fragments streamed from L2, x staged in k-slabs of 128.  Included by
 // egc_fused_tile_wide{1,2,3}.hip with EGC_FTW_NS = the number of k-slabs per chunk (ceil(F_in / 128): a template parameter of
 // the kernel) -- translation units of their own so that the instances compile side by side.
-#include <stdlib.h>
-
 #include "egc_aggregate_host.h"
 #include "egc_fused_tile_dev.h"
 
@@ -34,8 +32,9 @@ static bool ftw_cfg_matches(const AggArgs& a) {
   return cfg_layer_matches<C>(a) && (!has_sym || cfg_matches<C>(a));
 }
 
-int EGC_FTW_CAT(launch_fused_tile_wide, EGC_FTW_NS)(const AggArgs& a, const FusedTileArgs& t, int need, unsigned grid, size_t lds, hipStream_t stream) {
-  if (getenv("EGC_NO_STATIC_CFG") == nullptr) {
+int EGC_FTW_CAT(launch_fused_tile_wide, EGC_FTW_NS)(const AggArgs& a, const FusedTileArgs& t, int need, const FtSwitches& sw, unsigned grid, size_t lds,
+                                                    hipStream_t stream) {
+  if (sw.static_cfg) {
     using namespace cfg;     // S, M, X, Y
 #if EGC_FTW_NS == 2
     using ZincS = StCfg<8, 4, 21, 1, agg_pack(Y), EGC_ACT_NONE, false, true, true, 24>;          // zinc / cifar EGC-S 168 / H8 / B4 symadd

@@ -1,5 +1,6 @@
 // The plain host arithmetic every planner and launcher shares: no HIP header, no device code.  egc_common.h and
-// egc_aggregate_dev.h include it; egc_backward_host.h (and tests/backward_plan, compiled without HIP) builds on it.
+// egc_aggregate_dev.h include it; egc_backward_host.h and egc_fused_tile_host.h (and tests/backward_plan, tests/fused_tile_plan,
+// compiled without HIP) build on it.
 #pragma once
 #include <stdint.h>
 
@@ -10,6 +11,14 @@ namespace egc {
 constexpr unsigned OOB = 0xFFFFFFF0u;  // any offset >= num_records makes a buffer load return 0
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+constexpr int AMAX = 4;     // aggregators supported by the register-resident combine
+
+// floor(2^32 / d) + 1: q / d == umulhi(q, magic) for the q < 2^16 the kernels divide
+inline unsigned agg_magic(int d) { return (unsigned)(((uint64_t)1 << 32) / (uint64_t)d) + 1u; }
+
+// floats of the epilogue's bias strip in LDS: the (padded) head layout [h][Ls] (>= F_out floats)
+constexpr int bias_strip_floats(int H, int Ls) { return (H * Ls + 3) & ~3; }
 
 // floats between consecutive bases of a `bases` row (egc_layer.basis_stride; 0 = contiguous)
 static inline int layer_basis_stride(const egc_layer* L) {

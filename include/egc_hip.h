@@ -934,7 +934,8 @@ int egc_aggregate_combine_batch_f32(const int32_t* tiles, const int32_t* n_tiles
  *                               round32(ldb) + H B A <= 384, weight fragments streamed from L2; both need F_in % 4 == 0 and
  *                               the register-resident aggregate kernels' envelope (ldb <= 256, B a power of two, A <= 4).
  *                               A batch whose largest graph has more nodes than this must take
- *                               egc_aggregate_combine_batch_f32 or the CSR path.
+ *                               egc_aggregate_combine_batch_f32 or the CSR path.  The answer is a tile the launch runs: 0 also
+ *                               for a max_tile_edges the launch refuses whatever tile_nodes is (negative, or above 65535).
  *   egc_batch_fused_tile_quantum  rows per matrix-core step of the form that serves the layer (16 / 32; 0 = outside):
  *                               tile_nodes must be a multiple of it.
  *   egc_batch_fused_pack_bytes / egc_batch_fused_pack
@@ -978,7 +979,9 @@ int egc_layer_forward_batch_fused_f32(const int64_t* graph_ptr, const int64_t* e
  * agree to the bit (round 6: the tile's CSR is built in input order; a tile whose grad_out or weightings hold an Inf / NaN leaves its
  * d bases rows -- and with them its rows of d_x -- as NaN instead of a fixed-point image of them).  Envelope (egc_batch_fused_bwd_tile_nodes > 0): B = 4 bases of 16 channels, H = 4 or 8
  * (the d = 64 / 128 layers), F_in <= 128, aggregators of sum / mean / max / symnorm, no weight nonlinearity.
- *   egc_batch_fused_bwd_tile_nodes   rows of a tile (its image also holds d bases, 512 B per row: 80 at the north star), 0 = outside
+ *   egc_batch_fused_bwd_tile_nodes   rows of a tile (its image also holds d bases, 512 B per row: 80 at the north star), 0 = outside,
+ *                                    and 0 for a max_tile_edges the launch refuses whatever tile_nodes is (negative, or above 16384:
+ *                                    the query used to answer the rows whose image fits, e.g. 48 at H = 4 and 20000 edges)
  *   egc_batch_fused_bwd_pack[_bytes] wcat -> the transposed operand's fp16 planes; once per parameter update
  *   egc_layer_backward_batch_fused_f32   `packed` = egc_batch_fused_pack's buffer (the forward operand, for the recompute);
  *                                    `d_x_add` [n_nodes, in_channels] or NULL: added to d_x in its store -- the gradient that
