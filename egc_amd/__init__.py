@@ -12,6 +12,12 @@ Public surface (mirrors the reference's layer API):
   GATv2Conv            PyG 2.x GATv2Conv, the attention baseline of the reference's nets (state-dict compatible): lin_l and lin_r as
                        one dense product, the per-destination edge softmax and the weighted gather fused in one launch with
                        an online softmax; the backward recomputes the scores; no [E, .] array forward or backward
+  GATConv              PyG GATConv (non-bipartite, no edge features), the GAT baseline of the reference's nets at gat_version=1
+                       (state-dict compatible, PyG 2.0 - 2.2 names and the later single lin.weight): xl and the two per-node
+                       halves of the additive score as one dense product, the edge softmax and the weighted gather in one
+                       launch with no cross-lane work per entry; the backward takes one head sum per row; no [E, .] array
+  gat_aggregate / gat_aggregate_lse / gat_aggregate_backward
+                       the kernel-level calls under GATConv
   PNAConv              PyG 2.x PNAConv (edge_dim=None, one pre and one post layer), the strongest baseline of the reference's nets
                        (state-dict compatible): the per-edge pre-transform split into two [N, W] projections, every listed
                        aggregator (sum / mean / min / max / var / std) out of one gather launch, the degree scalers moved behind
@@ -50,7 +56,7 @@ from .layers import EfficientGraphConv  # noqa: F401
 from .optimized_layers import EGConv  # noqa: F401
 from .relational import REGC, REGConv, RGCNConv  # noqa: F401
 from ._mpnn import Mpnn  # noqa: F401
-from ._gat import GATv2Conv  # noqa: F401
+from ._gat import GATConv, GATv2Conv, gat_aggregate, gat_aggregate_backward, gat_aggregate_lse  # noqa: F401
 from ._pna import PNAConv, degree_histogram, pna_aggregate, pna_aggregate_backward, pna_scale_combine  # noqa: F401
 from ._nbr import GCNConv, GINConv, SAGEConv, neighbor_sum  # noqa: F401
 from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean_pool, readout  # noqa: F401

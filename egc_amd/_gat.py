@@ -1,4 +1,5 @@
-"""GATv2Conv (PyG 2.x formulas) on the fused edge-softmax aggregate kernels of egc_gatv2.hip.
+"""GATv2Conv (PyG 2.x formulas) on the fused edge-softmax aggregate kernels of egc_gatv2.hip, and, in the second half of
+this file, GATConv (GAT v1) on the additive-score kernels of egc_gat.hip.
 
 H = heads, C = out_channels per head.  xl = lin_l(x) and xr = lin_r(x) are the halves of ONE [N, 2 H C] dense product (one
 [N, H C] product when the weights are shared).  Over the edge set (``add_self_loops``: the given edges without their j == i
@@ -215,6 +216,234 @@ class GATv2Conv(nn.Module):
         else:
             lr = F.linear(x, torch.cat([self.lin_l.weight, self.lin_r.weight]), torch.cat([self.lin_l.bias, self.lin_r.bias]))
             out = _GatV2Fused.apply(lr, self.att, g, slope, loops)
+        if not self.concat:
+            out = out.view(-1, self.heads, self.out_channels).mean(dim=1)
+        return out if self.bias is None else out + self.bias
+
+    def extra_repr(self):
+        return f"{self.in_channels}, {self.out_channels}, heads={self.heads}, concat={self.concat}"
+
+
+# ------------------------------------------------------------------------------------------------------------------ GAT v1
+#
+# GATConv (PyG's first GAT layer) on the kernels of egc_gat.hip.  The score leaky_relu(a_src[j, h] + a_dst[i, h]) separates
+# into two per-node scalars per head, a_src[j, h] = sum_c xl[j, h, c] att_src[h, c] and a_dst likewise, so xl, a_src and a_dst
+# are the column blocks of ONE dense product x W_ext^T with W_ext = [W ; A_src ; A_dst ; 0], A_src[h, :] =
+# sum_c att_src[h, c] W[h C + c, :].  The forward kernel reads the two scalars per entry and needs no per-entry head sum; the
+# backward needs one head sum per row (egc_gat.hip's header).
+
+def _ext_width(heads, channels):
+    """Columns of [xl | a_src | a_dst | pad]: H C + 2 H rounded up to a multiple of four, so that xl keeps 16-byte rows."""
+    return (heads * channels + 2 * heads + 3) // 4 * 4
+
+
+def _gat1_shape(xl, a_src, a_dst):
+    for t, name in ((xl, "xl"), (a_src, "a_src"), (a_dst, "a_dst")):
+        if t.dim() != 2:
+            raise RuntimeError(f"egc_amd: {name} must be two-dimensional (got {tuple(t.shape)})")
+    for t, name in ((xl, "xl"), (a_src, "a_src"), (a_dst, "a_dst")):
+        _check_f32(t, name)
+    heads = a_dst.size(1)
+    if heads < 1 or a_src.size(1) != heads or xl.size(1) < heads or xl.size(1) % heads != 0 or xl.size(1) > 512:
+        raise RuntimeError(f"egc_amd: xl must be [rows, H C] with 1 <= H C <= 512, a_src and a_dst [rows, H] "
+                           f"(got {tuple(xl.shape)}, {tuple(a_src.shape)}, {tuple(a_dst.shape)})")
+    return heads, xl.size(1) // heads
+
+
+def _gat1_launch_forward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope, loops, out, lse):
+    lib = _C.load()
+    width, dev = heads * channels, a_dst.device
+    ld_xl, ld_as = _rows2d(xl, "xl", g.n_src_rows, width, dev), _rows2d(a_src, "a_src", g.n_src_rows, heads, dev)
+    ld_ad, ld_out = _rows2d(a_dst, "a_dst", g.n_nodes, heads, dev), _rows2d(out, "out", g.n_nodes, width, dev)
+    if g.device != dev:
+        raise RuntimeError(f"egc_amd: the graph is on {g.device}, xl, a_src and a_dst on {dev}")
+    if loops and g.n_src_rows != g.n_nodes:
+        raise RuntimeError(f"egc_amd: add_self_loops needs a square graph, got [{g.n_nodes}, {g.n_src_rows}]")
+    with _device_guard(dev):
+        ws, nbytes = _workspace(lib.egc_gat_forward_workspace_bytes(g.n_edges, heads, channels), dev)
+        _C.check(lib.egc_gat_forward_f32(g.rowptr.data_ptr(), g.col.data_ptr(), g.n_nodes, g.n_edges, g.n_src_rows, xl.data_ptr(),
+                                         ld_xl, a_src.data_ptr(), ld_as, a_dst.data_ptr(), ld_ad, heads, channels, float(slope),
+                                         int(loops), out.data_ptr(), ld_out, lse.data_ptr(), _ptr(ws), nbytes, _stream_ptr(dev)),
+                 "egc_gat_forward_f32")
+
+
+def _gat1_launch_backward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope, loops, out, lse, gout, dxl, das, dad):
+    """egc_gat_backward_f32: d xl [N, H C], d a_src and d a_dst [N, H] (column blocks are fine); any may be None."""
+    lib = _C.load()
+    width, dev, n = heads * channels, a_dst.device, g.n_nodes
+    if g.n_src_rows != n:
+        raise RuntimeError(f"egc_amd: the GAT backward needs a square graph, got [{n}, {g.n_src_rows}]")
+    ld_xl, ld_as, ld_ad = _rows2d(xl, "xl", n, width, dev), _rows2d(a_src, "a_src", n, heads, dev), _rows2d(a_dst, "a_dst", n, heads, dev)
+    ld_out, ld_g = _rows2d(out, "out", n, width, dev), _rows2d(gout, "d out", n, width, dev)
+    _check_f32(lse, "lse", (n, heads))
+    if not lse.is_contiguous() or lse.device != dev:
+        raise RuntimeError(f"egc_amd: lse must be a dense [{n}, {heads}] tensor on {dev}")
+    ld_dxl = _rows2d(dxl, "d xl", n, width, dev) if dxl is not None else 0
+    ld_das = _rows2d(das, "d a_src", n, heads, dev) if das is not None else 0
+    ld_dad = _rows2d(dad, "d a_dst", n, heads, dev) if dad is not None else 0
+    t = g.transposed() if dxl is not None or das is not None else None
+    with _device_guard(dev):
+        ws, nbytes = _workspace(lib.egc_gat_backward_workspace_bytes(n, g.n_edges, heads, channels), dev)
+        _C.check(lib.egc_gat_backward_f32(
+            g.rowptr.data_ptr(), g.col.data_ptr(), _ptr(t.rowptr if t else None), _ptr(t.col if t else None), n, g.n_edges,
+            xl.data_ptr(), ld_xl, a_src.data_ptr(), ld_as, a_dst.data_ptr(), ld_ad, heads, channels, float(slope), int(loops),
+            out.data_ptr(), ld_out, lse.data_ptr(), gout.data_ptr(), ld_g, _ptr(dxl), ld_dxl, _ptr(das), ld_das, _ptr(dad),
+            ld_dad, _ptr(ws), nbytes, _stream_ptr(dev)), "egc_gat_backward_f32")
+
+
+def _gat1_forward(xl, a_src, a_dst, g, slope, loops):
+    heads, channels = _gat1_shape(xl, a_src, a_dst)
+    n, dev = g.n_nodes, a_dst.device
+    out = torch.empty((n, heads * channels), dtype=torch.float32, device=dev)
+    lse = torch.empty((n, heads), dtype=torch.float32, device=dev)
+    _gat1_launch_forward(xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse)
+    return out, lse, heads, channels
+
+
+def _gat1_backward(saved, needs, gout):
+    """(d xl, d a_src, d a_dst, ext) for one saved forward: the wanted gradients are the blocks of ONE array ``ext`` in the layout
+    [d xl | d a_src | d a_dst | pad]; the blocks nobody wants and the pad columns are zero."""
+    xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse = saved
+    width, n, dev = heads * channels, g.n_nodes, gout.device
+    gout = _unit_columns(gout)
+    ext = torch.empty((n, _ext_width(heads, channels)), dtype=torch.float32, device=dev)
+    blocks = [ext[:, :width], ext[:, width:width + heads], ext[:, width + heads:width + 2 * heads]]
+    for b, need in zip(blocks + [ext[:, width + 2 * heads:]], tuple(needs) + (False,)):
+        if not need and b.numel() > 0:
+            b.zero_()
+    wanted = [b if need else None for b, need in zip(blocks, needs)]
+    if n > 0 and any(needs):
+        _gat1_launch_backward(xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse, gout, *wanted)
+    return wanted[0], wanted[1], wanted[2], ext
+
+
+class _GatAggregate(torch.autograd.Function):
+    """out [N, H C] from xl, a_src and a_dst (separate arrays or column blocks)."""
+
+    @staticmethod
+    def forward(ctx, xl, a_src, a_dst, g, slope, loops):
+        xl, a_src, a_dst = xl.detach(), a_src.detach(), a_dst.detach()
+        out, lse, heads, channels = _gat1_forward(xl, a_src, a_dst, g, slope, loops)
+        ctx.saved = (xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        dxl, das, dad, _ = _gat1_backward(ctx.saved, ctx.needs_input_grad[:3], gout)
+        return dxl, das, dad, None, None, None
+
+
+class _GatFused(torch.autograd.Function):
+    """out [N, H C] from ext = [xl | a_src | a_dst | pad] (one dense product): the backward writes the three gradients into the
+    blocks of ONE d ext of the same layout, the pad columns zero."""
+
+    @staticmethod
+    def forward(ctx, ext, heads, channels, g, slope, loops):
+        ext = ext.detach()
+        w = heads * channels
+        if ext.dim() != 2 or ext.size(1) != _ext_width(heads, channels):
+            raise RuntimeError(f"egc_amd: [xl | a_src | a_dst | pad] must be [N, {_ext_width(heads, channels)}] (got {tuple(ext.shape)})")
+        xl, a_src, a_dst = ext[:, :w], ext[:, w:w + heads], ext[:, w + heads:w + 2 * heads]
+        out, lse, _, _ = _gat1_forward(xl, a_src, a_dst, g, slope, loops)
+        ctx.saved = (xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        return _gat1_backward(ctx.saved, (True, True, True), gout)[3], None, None, None, None, None
+
+
+def gat_aggregate(xl, a_src, a_dst, graph, negative_slope=0.2, add_self_loops=True):
+    """out [N, H C] of the GAT attention aggregate from xl [rows the edges' sources name, H C], a_src [the same rows, H] and
+    a_dst [N, H] (separate arrays or column blocks of one wider array) over ``graph`` (a CSRGraph, SparseTensor, GraphBatch or
+    [2, E] int64 edge_index): s_ij = leaky_relu(a_src[j] + a_dst[i]), alpha = softmax over i's in-edges, out_i = sum_j alpha_ij
+    xl_j per head.  Differentiable with respect to xl, a_src and a_dst (the backward needs a square graph)."""
+    _gat1_shape(xl, a_src, a_dst)
+    return _GatAggregate.apply(xl, a_src, a_dst, _as_csr(graph, a_dst.size(0)), float(negative_slope), bool(add_self_loops))
+
+
+def gat_aggregate_lse(xl, a_src, a_dst, graph, negative_slope=0.2, add_self_loops=True):
+    """(out [N, H C], lse [N, H]) of the forward kernel: lse is the log-sum-exp of every row's scores, -inf for an empty row.
+    Not differentiable."""
+    _gat1_shape(xl, a_src, a_dst)
+    out, lse, _, _ = _gat1_forward(xl.detach(), a_src.detach(), a_dst.detach(), _as_csr(graph, a_dst.size(0)), float(negative_slope),
+                                   bool(add_self_loops))
+    return out, lse
+
+
+def gat_aggregate_backward(xl, a_src, a_dst, graph, out, lse, gout, negative_slope=0.2, add_self_loops=True):
+    """(d xl, d a_src, d a_dst) from d out: the backward kernels on their own (the three are the column blocks of one array in
+    the layout [d xl | d a_src | d a_dst | pad])."""
+    heads, channels = _gat1_shape(xl, a_src, a_dst)
+    saved = (xl, a_src, a_dst, _as_csr(graph, a_dst.size(0)), heads, channels, float(negative_slope), bool(add_self_loops), out, lse)
+    return _gat1_backward(saved, (True, True, True), gout)[:3]
+
+
+class GATConv(nn.Module):
+    """PyG ``GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
+    bias=True)``, non-bipartite (``in_channels`` an int); ``forward(x, edge_index)`` with edge_index a [2, E] int64 tensor, an
+    ``egc_amd.SparseTensor``, a ``CSRGraph`` or a ``GraphBatch``.  State dict in the PyG 2.0 - 2.2 layout, so such state dicts
+    load with strict=True: ``lin_src.weight`` [H C, F_in] and ``lin_dst.weight`` (lin_dst IS lin_src), ``att_src`` and
+    ``att_dst`` [1, H, C], ``bias`` ([H C], or [C] for concat=False); the later layout with a single ``lin.weight`` loads too.
+    Glorot weights and att, zero bias.  [xl | a_src | a_dst] is one dense product with the att vectors folded into 2 H extra
+    weight rows; autograd takes d W, d att_src and d att_dst from the one dense gradient.  Attention dropout is not implemented:
+    dropout > 0 raises in training mode and is ignored in eval mode.  Not implemented either: ``edge_dim`` (edge features),
+    bipartite ``in_channels`` (a pair), ``fill_value`` and ``residual``."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
+                 bias=True):
+        super().__init__()
+        if not isinstance(in_channels, int):
+            raise ValueError(f"egc_amd.GATConv: in_channels must be an int (bipartite inputs are not implemented), got {in_channels!r}")
+        if heads < 1 or out_channels < 1 or heads * out_channels > 512:
+            raise ValueError(f"egc_amd.GATConv: heads * out_channels must be in 1..512, got {heads} * {out_channels}")
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
+        self.negative_slope, self.dropout, self.add_self_loops = negative_slope, dropout, add_self_loops
+        self.lin_src = nn.Linear(in_channels, heads * out_channels, bias=False)
+        self.lin_dst = self.lin_src
+        self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.att_dst = nn.Parameter(torch.empty(1, heads, out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(heads * out_channels if concat else out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        _glorot_(self.lin_src.weight)
+        _glorot_(self.att_src)
+        _glorot_(self.att_dst)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # the later PyG layout: one lin.weight for both ends
+        if prefix + "lin_src.weight" not in state_dict and prefix + "lin.weight" in state_dict:
+            state_dict[prefix + "lin_src.weight"] = state_dict[prefix + "lin_dst.weight"] = state_dict.pop(prefix + "lin.weight")
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def extended_weight(self):
+        """W_ext = [W ; A_src ; A_dst ; 0], [H C + 2 H rounded up to a multiple of 4, F_in]: x W_ext^T = [xl | a_src | a_dst | pad]."""
+        h, c, w = self.heads, self.out_channels, self.lin_src.weight
+        w3 = w.view(h, c, self.in_channels)
+        rows = [w, (self.att_src.view(h, c, 1) * w3).sum(dim=1), (self.att_dst.view(h, c, 1) * w3).sum(dim=1)]
+        pad = _ext_width(h, c) - h * c - 2 * h
+        if pad:
+            rows.append(w.new_zeros((pad, self.in_channels)))
+        return torch.cat(rows)
+
+    def forward(self, x, edge_index):
+        if x.dim() != 2 or x.size(1) != self.in_channels:
+            raise RuntimeError(f"egc_amd.GATConv: x has shape {tuple(x.shape)}, expected (rows, {self.in_channels})")
+        if self.dropout > 0.0 and self.training:
+            raise NotImplementedError(f"egc_amd.GATConv: attention dropout ({self.dropout}) is not implemented for training; "
+                                      "construct the layer with dropout=0.0 (the reference's gat_dropout) or call .eval()")
+        _check_f32(x, "x")
+        g = _as_csr(edge_index, x.size(0))
+        if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
+            raise RuntimeError(f"egc_amd.GATConv: the graph is [{g.n_nodes}, {g.n_src_rows}], x has {x.size(0)} rows")
+        ext = F.linear(x, self.extended_weight())
+        out = _GatFused.apply(ext, self.heads, self.out_channels, g, float(self.negative_slope), bool(self.add_self_loops))
         if not self.concat:
             out = out.view(-1, self.heads, self.out_channels).mean(dim=1)
         return out if self.bias is None else out + self.bias

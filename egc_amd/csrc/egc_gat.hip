@@ -1,0 +1,515 @@
+// GAT (v1) attention aggregate (PyG GATConv's propagate) without any [E, .] array.  xl [N, H C], a_src [N, H] and a_dst [N, H]
+// are column blocks of one dense product (a_src[j, h] = sum_c xl[j, h, c] att_src[h, c], a_dst likewise); for an entry j -> i
+// and head h
+//
+//   z = a_src[j, h] + a_dst[i, h]      s_ij^h = leaky_relu(z)      alpha_ij^h = softmax over i's entries of s_ij^h
+//   out_i^h = sum_j alpha_ij^h xl_j^h      lse_i^h = log sum_j exp(s_ij^h)   (0 and -inf for a row without entries)
+//
+// The score separates into two per-node scalars per head, so NO per-entry operation crosses lanes: a lane reads a_dst of its
+// columns' heads once per row and, per entry, a_src of those heads and its quad of xl_j.  With the self-loop flag the row's
+// entries whose col equals the row are skipped and ONE self entry (j = i) is taken LAST.  gfx950 only.  Forward: one gather pass
+// over xl with egc_gat_dev.h's online softmax (the maximum is subtracted before every exp).  Backward, nothing per-edge kept:
+// with g = d out, D_i^h = g_i^h . out_i^h, alpha = exp(s - lse_i), w_ij = alpha_ij leaky_relu'(z_ij), the per-entry
+// d s_ij = w_ij (g_i . xl_j - D_i):
+//   destination pass (forward CSR)     FACTORED, one head sum per row: v_i = sum_j w_ij xl_j (per column), t_i = sum_j w_ij
+//                                      (per head), d a_dst[i, h] = g_i^h . v_i^h - D_i^h t_i^h,   D into the workspace
+//   source pass (transposed CSR)       d xl_j = sum_i alpha_ij g_i (the direct term only; the rest flows through a_src, a_dst),
+//                                      d a_src[j, h] = sum_i w_ij (g_i^h . xl_j^h - D_i^h): d s PER ENTRY, one gat_head_sums of
+//                                      g_i xl_j per entry (skipped when d a_src is not wanted)
+// The source pass is not factored (xl_j . sum_i w_ij g_i - sum_i w_ij D_i): where a source feeds the same few destinations many
+// times, out_i is close to xl_j, every g_i . xl_j - D_i nearly cancels and the two factored sums cancel only at the row's end --
+// in float32 that was 10 to 25 times the per-entry form's error on the sweep graph's out-hub.  The destination
+// pass shows no such loss.  Every output element is written exactly once: no zero fill, no atomics.
+//
+// Mapping: egc_gat_dev.h's (a lane owns four adjacent columns, a row's group is the power of two >= ceil(H C / 4) lanes, at most
+// 64, two quads per lane above 256 columns; 16-byte accesses of xl, g, out and d xl when the width, strides and pointers allow,
+// 4-byte ones otherwise; the per-head arrays are always read and written 4 bytes at a time).
+//
+// Order rule.  A per-head sum over the head's C columns (D, g . v, g . xl) is egc_gat_dev.h's gat_head_sums: it depends on H
+// and C only.  A row is cut into egc_row_chunks.h's chunks (skipped entries keep their place).  Forward: inside a chunk,
+// batches of 8 entries from the chunk's start, folded as egc_gat_dev.h's gat_state_take; the row is chunk 0's state with the
+// states of chunks 1, 2, ... merged in ascending order, then the self entry as a batch of one, then out = acc / l and
+// lse = m + log l.  Backward sums (v, t, d xl, d a_src): ((0 + x0) + x1) + ... in entry order per chunk, chunk 0's sum with
+// those of chunks 1, 2, ... added in ascending order, the self entry last; then, in the destination pass, the row's head sum
+// and one subtraction.  So the order of every sum is fixed by H, C and the row's entries alone, never by where in the grid the
+// row lands.  -ffp-contract=off.
+#include "egc_gat_dev.h"
+
+namespace egc {
+
+constexpr int GAT1_AHEAD_DST = 8;
+constexpr int GAT1_AHEAD_SRC = 4;
+
+struct Gat1Walk : GatWalk {
+  const float* a_src;   // forward / destination pass: gathered; source pass: the row's own
+  const float* a_dst;   // forward / destination pass: the row's own; source pass: gathered
+  int32_t ld_as, ld_ad;
+};
+
+__device__ inline f4 gat1_lrelu(f4 z, float slope) {
+  f4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = z[i] > 0.f ? z[i] : slope * z[i];
+  return r;
+}
+
+__device__ inline f4 gat1_dlrelu(f4 z, float slope) {
+  f4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = z[i] > 0.f ? 1.f : slope;
+  return r;
+}
+
+// a[row, head] of every column of the lane, rows of stride ld.  C >= 4: a quad lies in at most two heads, two loads.
+template <int S, bool SMALL>
+__device__ inline void gat1_heads(f4 (&v)[S], const float* __restrict__ a, int64_t row, int ld, const GatLane<S>& L) {
+  const float* __restrict__ r = a + row * ld;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    if (SMALL) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[s][j] = r[L.hd[s][j]];
+    } else {
+      const float first = r[L.hd[s][0]], next = r[L.hd[s][3]];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[s][j] = j < L.na[s] ? first : next;
+    }
+  }
+}
+
+// x[row, head] = v of the head's first column
+template <int S>
+__device__ inline void gat1_store_heads(float* __restrict__ x, int64_t row, int ld, const GatLane<S>& L, const f4 (&v)[S]) {
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (L.head_first[s][i]) x[row * ld + L.hd[s][i]] = v[s][i];
+}
+
+// the rows a batch of N entries from p on names, and which of them count
+template <int N, bool FULL>
+__device__ inline void gat1_batch_rows(int (&j)[N], bool (&live)[N], const Gat1Walk& W, int64_t p, int64_t p1, int64_t row, bool self) {
+  const int last_in = (int)W.n_in_rows - 1;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const int raw = self ? (int)row : W.col[batch_entry<FULL>(p, k, p1)];
+    j[k] = clamp_index(raw, last_in);
+    live[k] = self || ((FULL || p + k < p1) && !(W.self_loops && raw == (int)row));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- forward
+
+template <int S, bool VEC, bool SMALL, int N, bool FULL>
+__device__ inline void gat1_fwd_batch(GatState<S>& st, const Gat1Walk& W, const GatLane<S>& L, const f4 (&ad)[S], int64_t p,
+                                      int64_t p1, int64_t row, bool self) {
+  int j[N];
+  bool live[N];
+  gat1_batch_rows<N, FULL>(j, live, W, p, p1, row, self);
+  f4 v[N][S], e[N][S];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    gat_load_row<S, VEC>(v[k], W.xl, j[k], W.ld_xl, L, W.width);
+    gat1_heads<S, SMALL>(e[k], W.a_src, j[k], W.ld_as, L);
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+#pragma unroll
+    for (int s = 0; s < S; ++s) e[k][s] = gat1_lrelu(e[k][s] + ad[s], W.slope);
+  gat_state_take<S, N>(st, e, v, live);
+}
+
+template <int S, bool VEC, bool SMALL>
+__device__ inline void gat1_fwd_entries(GatState<S>& st, const Gat1Walk& W, const GatLane<S>& L, const f4 (&ad)[S], int64_t p0,
+                                        int64_t p1, int64_t row) {
+  gat_state_init<S>(st);
+  int64_t p = p0;
+#pragma unroll 1
+  for (; p + GAT_AHEAD <= p1; p += GAT_AHEAD) gat1_fwd_batch<S, VEC, SMALL, GAT_AHEAD, true>(st, W, L, ad, p, p1, row, false);
+  if (p < p1) gat1_fwd_batch<S, VEC, SMALL, GAT_AHEAD - 1, false>(st, W, L, ad, p, p1, row, false);
+}
+
+// workspace: per slot and virtual lane three f4: m, l, acc
+template <int S, bool VEC, bool SMALL>
+__global__ void __launch_bounds__(256) gat1_fwd_chunks_kernel(const Gat1Walk W, int64_t slots, float* __restrict__ ws) {
+  int64_t g, row, s0, s1;
+  int c;
+  group_lane(W.G, g, c);
+  if (g >= slots) return;
+  const GatLane<S> L = gat_lane<S>(W, c / 4);
+  if (!slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, s0, s1)) return;
+  f4 ad[S];
+  gat1_heads<S, SMALL>(ad, W.a_dst, row, W.ld_ad, L);
+  GatState<S> st;
+  gat1_fwd_entries<S, VEC, SMALL>(st, W, L, ad, s0, s1, row);
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    f4* o = reinterpret_cast<f4*>(ws) + (g * W.V + L.v[s]) * 3;
+    o[0] = st.m[s], o[1] = st.l[s], o[2] = st.acc[s];
+  }
+}
+
+template <int S, bool VEC, bool SMALL>
+__global__ void __launch_bounds__(256) gat1_fwd_rows_kernel(const Gat1Walk W, float* __restrict__ out, int ld_out,
+                                                            float* __restrict__ lse, const float* __restrict__ ws) {
+  int64_t row, p0, p1;
+  int c;
+  group_lane(W.G, row, c);
+  if (row >= W.n_rows) return;
+  const GatLane<S> L = gat_lane<S>(W, c / 4);
+  row_range(W.rowptr, W.n_edges, row, p0, p1);
+  f4 ad[S];
+  gat1_heads<S, SMALL>(ad, W.a_dst, row, W.ld_ad, L);
+  GatState<S> st;
+  gat1_fwd_entries<S, VEC, SMALL>(st, W, L, ad, p0, min(p0 + ROW_CHUNK, p1), row);
+  int64_t first, n_part;
+  row_partials(p0, p1, first, n_part);
+#pragma unroll 1
+  for (int64_t k = 0; k < n_part; ++k) {
+    f4 m2[S], l2[S], a2[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const f4* o = reinterpret_cast<const f4*>(ws) + ((first + k) * W.V + L.v[s]) * 3;
+      m2[s] = o[0], l2[s] = o[1], a2[s] = o[2];
+    }
+    gat_state_merge<S>(st, m2, l2, a2);
+  }
+  if (W.self_loops) gat1_fwd_batch<S, VEC, SMALL, 1, true>(st, W, L, ad, 0, 0, row, true);
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    f4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool any = st.l[s][i] > 0.f;
+      o[i] = any ? st.acc[s][i] / st.l[s][i] : 0.f;
+      if (L.head_first[s][i]) lse[row * W.H + L.hd[s][i]] = any ? st.m[s][i] + logf(st.l[s][i]) : -__builtin_inff();
+    }
+    gat_store<VEC>(out + row * ld_out + L.c[s], L.c[s], W.width, o);
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------- backward
+
+// destination pass: N entries of row `row` -> v += w xl_j, t += w
+template <int S, bool VEC, bool SMALL, int N, bool FULL>
+__device__ inline void gat1_dst_batch(f4 (&va)[S], f4 (&ta)[S], const Gat1Walk& W, const GatLane<S>& L, const f4 (&ad)[S],
+                                      const f4 (&lse)[S], int64_t p, int64_t p1, int64_t row, bool self) {
+  int j[N];
+  bool live[N];
+  gat1_batch_rows<N, FULL>(j, live, W, p, p1, row, self);
+  f4 v[N][S], as[N][S];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    gat_load_row<S, VEC>(v[k], W.xl, j[k], W.ld_xl, L, W.width);
+    gat1_heads<S, SMALL>(as[k], W.a_src, j[k], W.ld_as, L);
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const f4 z = as[k][s] + ad[s];
+      f4 w = gat_exp(gat1_lrelu(z, W.slope) - lse[s]) * gat1_dlrelu(z, W.slope);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) w[i] = live[k] ? w[i] : 0.f;
+      va[s] = va[s] + w * v[k][s];
+      ta[s] = ta[s] + w;
+    }
+}
+
+// CHUNKS: group = slot, the chunk's (v, t) into ws; else group = row: chunk 0, the partials, the self entry; then D into D_out
+// and, when wanted, d a_dst.  Workspace: per slot and virtual lane two f4: v, t.
+template <int S, bool VEC, bool SMALL, bool CHUNKS>
+__global__ void __launch_bounds__(256) gat1_bwd_dst_kernel(const Gat1Walk W, float* __restrict__ d_ad, int ld_d_ad,
+                                                           float* __restrict__ D_out, int64_t slots, float* __restrict__ ws) {
+  int64_t g;
+  int c;
+  group_lane(W.G, g, c);
+  const GatLane<S> L = gat_lane<S>(W, c / 4);
+  int64_t row = g, p0 = 0, p1 = 0;
+  if (CHUNKS) {
+    if (g >= slots || !slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, p0, p1)) return;
+  } else {
+    if (g >= W.n_rows) return;
+    row_range(W.rowptr, W.n_edges, row, p0, p1);
+  }
+  f4 ad[S], lse[S], va[S], ta[S];
+  gat1_heads<S, SMALL>(ad, W.a_dst, row, W.ld_ad, L);
+  gat1_heads<S, SMALL>(lse, W.lse, row, W.H, L);
+#pragma unroll
+  for (int s = 0; s < S; ++s) va[s] = f4{0.f, 0.f, 0.f, 0.f}, ta[s] = va[s];
+  const int64_t e1 = CHUNKS ? p1 : min(p0 + ROW_CHUNK, p1);
+  int64_t p = p0;
+#pragma unroll 1
+  for (; p + GAT1_AHEAD_DST <= e1; p += GAT1_AHEAD_DST) gat1_dst_batch<S, VEC, SMALL, GAT1_AHEAD_DST, true>(va, ta, W, L, ad, lse, p, e1, row, false);
+  if (p < e1) gat1_dst_batch<S, VEC, SMALL, GAT1_AHEAD_DST - 1, false>(va, ta, W, L, ad, lse, p, e1, row, false);
+  if (CHUNKS) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      f4* o = reinterpret_cast<f4*>(ws) + (g * W.V + L.v[s]) * 2;
+      o[0] = va[s], o[1] = ta[s];
+    }
+    return;
+  }
+  int64_t first, n_part;
+  row_partials(p0, p1, first, n_part);
+#pragma unroll 1
+  for (int64_t k = 0; k < n_part; ++k)
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const f4* o = reinterpret_cast<const f4*>(ws) + ((first + k) * W.V + L.v[s]) * 2;
+      va[s] = va[s] + o[0], ta[s] = ta[s] + o[1];
+    }
+  if (W.self_loops) gat1_dst_batch<S, VEC, SMALL, 1, true>(va, ta, W, L, ad, lse, 0, 0, row, true);
+  f4 gr[S], o[S], u[S], D[S], P[S];
+  gat_load_row<S, VEC>(gr, W.g, row, W.ld_g, L, W.width);
+  gat_load_row<S, VEC>(o, W.out, row, W.ld_out, L, W.width);
+#pragma unroll
+  for (int s = 0; s < S; ++s) u[s] = gr[s] * o[s];
+  gat_head_sums<S, SMALL>(W, L, u, D);
+  gat1_store_heads<S>(D_out, row, W.H, L, D);
+  if (d_ad == nullptr) return;
+#pragma unroll
+  for (int s = 0; s < S; ++s) u[s] = gr[s] * va[s];
+  gat_head_sums<S, SMALL>(W, L, u, P);
+#pragma unroll
+  for (int s = 0; s < S; ++s) P[s] = P[s] - D[s] * ta[s];
+  gat1_store_heads<S>(d_ad, row, ld_d_ad, L, P);
+}
+
+// source pass: N entries (destinations i) of transposed row `row` (= source j) -> d xl += alpha g_i, d a_src += w (g_i . xl_j - D_i)
+template <int S, bool VEC, bool SMALL, int N, bool FULL>
+__device__ inline void gat1_src_batch(f4 (&dx)[S], f4 (&sa)[S], const Gat1Walk& W, const GatLane<S>& L, const f4 (&as)[S],
+                                      const f4 (&xl)[S], bool want_das, int64_t p, int64_t p1, int64_t row, bool self) {
+  int i_[N];
+  bool live[N];
+  gat1_batch_rows<N, FULL>(i_, live, W, p, p1, row, self);
+  f4 gr[N][S], ad[N][S], lse[N][S], D[N][S];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    gat_load_row<S, VEC>(gr[k], W.g, i_[k], W.ld_g, L, W.width);
+    gat1_heads<S, SMALL>(ad[k], W.a_dst, i_[k], W.ld_ad, L);
+    gat1_heads<S, SMALL>(lse[k], W.lse, i_[k], W.H, L);
+    gat1_heads<S, SMALL>(D[k], W.D, i_[k], W.H, L);
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    f4 u[S], da[S];
+    if (want_das) {   // uniform over the launch
+#pragma unroll
+      for (int s = 0; s < S; ++s) u[s] = gr[k][s] * xl[s];
+      gat_head_sums<S, SMALL>(W, L, u, da);
+    } else {
+#pragma unroll
+      for (int s = 0; s < S; ++s) da[s] = f4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const f4 z = as[s] + ad[k][s];
+      f4 alpha = gat_exp(gat1_lrelu(z, W.slope) - lse[k][s]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) alpha[i] = live[k] ? alpha[i] : 0.f;
+      const f4 w = alpha * gat1_dlrelu(z, W.slope);
+      dx[s] = dx[s] + alpha * gr[k][s];
+      sa[s] = sa[s] + w * (da[s] - D[k][s]);
+    }
+  }
+}
+
+// workspace: per slot and virtual lane two f4: d xl, d a_src (the head's value in every column of the head)
+template <int S, bool VEC, bool SMALL, bool CHUNKS>
+__global__ void __launch_bounds__(256) gat1_bwd_src_kernel(const Gat1Walk W, float* __restrict__ dxl, int ld_dxl,
+                                                           float* __restrict__ d_as, int ld_d_as, int want_das_, int64_t slots,
+                                                           float* __restrict__ ws) {
+  int64_t g;
+  int c;
+  group_lane(W.G, g, c);
+  const GatLane<S> L = gat_lane<S>(W, c / 4);
+  const bool want_das = want_das_ != 0;
+  int64_t row = g, p0 = 0, p1 = 0;
+  if (CHUNKS) {
+    if (g >= slots || !slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, p0, p1)) return;
+  } else {
+    if (g >= W.n_rows) return;
+    row_range(W.rowptr, W.n_edges, row, p0, p1);
+  }
+  f4 as[S], xl[S], dx[S], sa[S];
+  gat1_heads<S, SMALL>(as, W.a_src, row, W.ld_as, L);
+  gat_load_row<S, VEC>(xl, W.xl, row, W.ld_xl, L, W.width);
+#pragma unroll
+  for (int s = 0; s < S; ++s) dx[s] = f4{0.f, 0.f, 0.f, 0.f}, sa[s] = dx[s];
+  const int64_t e1 = CHUNKS ? p1 : min(p0 + ROW_CHUNK, p1);
+  int64_t p = p0;
+#pragma unroll 1
+  for (; p + GAT1_AHEAD_SRC <= e1; p += GAT1_AHEAD_SRC)
+    gat1_src_batch<S, VEC, SMALL, GAT1_AHEAD_SRC, true>(dx, sa, W, L, as, xl, want_das, p, e1, row, false);
+  if (p < e1) gat1_src_batch<S, VEC, SMALL, GAT1_AHEAD_SRC - 1, false>(dx, sa, W, L, as, xl, want_das, p, e1, row, false);
+  if (CHUNKS) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      f4* o = reinterpret_cast<f4*>(ws) + (g * W.V + L.v[s]) * 2;
+      o[0] = dx[s], o[1] = sa[s];
+    }
+    return;
+  }
+  int64_t first, n_part;
+  row_partials(p0, p1, first, n_part);
+#pragma unroll 1
+  for (int64_t k = 0; k < n_part; ++k)
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const f4* o = reinterpret_cast<const f4*>(ws) + ((first + k) * W.V + L.v[s]) * 2;
+      dx[s] = dx[s] + o[0], sa[s] = sa[s] + o[1];
+    }
+  if (W.self_loops) gat1_src_batch<S, VEC, SMALL, 1, true>(dx, sa, W, L, as, xl, want_das, 0, 0, row, true);
+  if (dxl != nullptr) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) gat_store<VEC>(dxl + row * ld_dxl + L.c[s], L.c[s], W.width, dx[s]);
+  }
+  if (d_as != nullptr) gat1_store_heads<S>(d_as, row, ld_d_as, L, sa);
+}
+
+// ------------------------------------------------------------------------------------------------------------------- host
+
+// backward workspace, in floats
+struct Gat1BwdWs {
+  size_t D, part_dst, part_src, total;
+  int64_t slots, row_blocks, chunk_blocks;
+};
+
+static inline Gat1BwdWs gat1_bwd_ws(int64_t n_rows, int64_t n_edges, int32_t H, int32_t C) {
+  const GatGeom q = gat_geom(H * C);
+  Gat1BwdWs w;
+  w.slots = chunk_slots(n_edges);
+  w.row_blocks = gat_blocks(n_rows, q.G), w.chunk_blocks = gat_blocks(w.slots, q.G);
+  size_t at = 0;
+  w.D = at, at += gat_align((size_t)n_rows * H);
+  w.part_dst = at, at += (size_t)w.slots * q.V * 2 * 4;
+  w.part_src = at, at += (size_t)w.slots * q.V * 2 * 4;
+  w.total = at;
+  return w;
+}
+
+}  // namespace egc
+
+using namespace egc;
+
+size_t egc_gat_forward_workspace_bytes(int64_t n_edges, int32_t heads, int32_t channels) {
+  if (n_edges <= 0 || !gat_shape_ok(heads, channels)) return 0;
+  return (size_t)chunk_slots(n_edges) * (size_t)gat_geom(heads * channels).V * 3 * 16;
+}
+
+size_t egc_gat_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32_t heads, int32_t channels) {
+  if (n_rows <= 0 || n_edges < 0 || !gat_shape_ok(heads, channels)) return 0;
+  return gat1_bwd_ws(n_rows, n_edges, heads, channels).total * sizeof(float);
+}
+
+int egc_gat_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                        const float* xl, int32_t ld_xl, const float* a_src, int32_t ld_a_src, const float* a_dst, int32_t ld_a_dst,
+                        int32_t heads, int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out,
+                        float* lse, void* workspace, size_t workspace_bytes, egc_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0 || n_src_rows < 0) return EGC_ERR_INVALID;
+  const int32_t width = heads * channels;
+  if (ld_xl < width || ld_out < width || ld_a_src < heads || ld_a_dst < heads) return EGC_ERR_INVALID;
+  if (self_loops && n_src_rows != n_rows) return EGC_ERR_INVALID;
+  if (n_rows == 0) return EGC_OK;
+  if (rowptr == nullptr || a_dst == nullptr || out == nullptr || lse == nullptr) return EGC_ERR_INVALID;
+  if ((n_edges > 0 || self_loops) && (xl == nullptr || a_src == nullptr)) return EGC_ERR_INVALID;
+  if (n_edges > 0 && (col == nullptr || n_src_rows == 0)) return EGC_ERR_INVALID;
+  if (!counts_fit_int32(n_rows, n_edges, n_src_rows)) return EGC_ERR_UNSUPPORTED;
+  Gat1Walk W = {};
+  W.rowptr = rowptr, W.col = col, W.xl = xl, W.a_src = a_src, W.a_dst = a_dst;
+  W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_src_rows, W.ld_xl = ld_xl, W.ld_as = ld_a_src, W.ld_ad = ld_a_dst;
+  gat_fill_walk(W, heads, channels, negative_slope, self_loops ? 1 : 0);
+  const int S = gat_geom(width).S;
+  const bool small = channels < 4;
+  const bool vec = all_mult4(width, ld_xl, ld_out) && all_aligned16(xl, out);
+  const int64_t slots = chunk_slots(n_edges);
+  float* ws = static_cast<float*>(workspace);
+  if (slots > 0) {
+    if (!workspace_ok(ws, workspace_bytes, egc_gat_forward_workspace_bytes(n_edges, heads, channels))) return EGC_ERR_WORKSPACE;
+    unsigned blocks;
+    if (grid_blocks(slots, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
+#define GAT1_FWD_CHUNKS(S_, V_, M_) gat1_fwd_chunks_kernel<S_, V_, M_><<<blocks, 256, 0, stream>>>(W, slots, ws)
+    GAT_DISPATCH(GAT1_FWD_CHUNKS);
+#undef GAT1_FWD_CHUNKS
+    EGC_LAUNCH_CHECK("gat1_fwd_chunks_kernel");
+  }
+  unsigned blocks;
+  if (grid_blocks(n_rows, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
+#define GAT1_FWD_ROWS(S_, V_, M_) gat1_fwd_rows_kernel<S_, V_, M_><<<blocks, 256, 0, stream>>>(W, out, ld_out, lse, ws)
+  GAT_DISPATCH(GAT1_FWD_ROWS);
+#undef GAT1_FWD_ROWS
+  EGC_LAUNCH_CHECK("gat1_fwd_rows_kernel");
+  return EGC_OK;
+}
+
+int egc_gat_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_rows,
+                         int64_t n_edges, const float* xl, int32_t ld_xl, const float* a_src, int32_t ld_a_src, const float* a_dst,
+                         int32_t ld_a_dst, int32_t heads, int32_t channels, float negative_slope, int32_t self_loops,
+                         const float* out, int32_t ld_out, const float* lse, const float* g, int32_t ld_g, float* dxl,
+                         int32_t ld_dxl, float* d_a_src, int32_t ld_d_a_src, float* d_a_dst, int32_t ld_d_a_dst, void* workspace,
+                         size_t workspace_bytes, egc_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0) return EGC_ERR_INVALID;
+  const int32_t width = heads * channels;
+  if (ld_xl < width || ld_out < width || ld_g < width || ld_a_src < heads || ld_a_dst < heads) return EGC_ERR_INVALID;
+  if ((dxl != nullptr && ld_dxl < width) || (d_a_src != nullptr && ld_d_a_src < heads) || (d_a_dst != nullptr && ld_d_a_dst < heads))
+    return EGC_ERR_INVALID;
+  if (dxl == nullptr && d_a_src == nullptr && d_a_dst == nullptr) return EGC_OK;
+  if (n_rows == 0) return EGC_OK;
+  if (rowptr == nullptr || xl == nullptr || a_src == nullptr || a_dst == nullptr || out == nullptr || lse == nullptr || g == nullptr)
+    return EGC_ERR_INVALID;
+  if (n_edges > 0 && col == nullptr) return EGC_ERR_INVALID;
+  const bool src_pass = dxl != nullptr || d_a_src != nullptr;
+  if (src_pass && (t_rowptr == nullptr || (n_edges > 0 && t_col == nullptr))) return EGC_ERR_INVALID;
+  if (!counts_fit_int32(n_rows, n_edges)) return EGC_ERR_UNSUPPORTED;
+  const Gat1BwdWs L = gat1_bwd_ws(n_rows, n_edges, heads, channels);
+  float* ws = static_cast<float*>(workspace);
+  if (!workspace_ok(ws, workspace_bytes, L.total * sizeof(float))) return EGC_ERR_WORKSPACE;
+  if (!counts_fit_int32(L.row_blocks, L.chunk_blocks)) return EGC_ERR_UNSUPPORTED;
+  Gat1Walk W = {};
+  W.rowptr = rowptr, W.col = col, W.xl = xl, W.a_src = a_src, W.a_dst = a_dst, W.g = g, W.out = out, W.lse = lse, W.D = ws + L.D;
+  W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_rows;
+  W.ld_xl = ld_xl, W.ld_as = ld_a_src, W.ld_ad = ld_a_dst, W.ld_g = ld_g, W.ld_out = ld_out;
+  gat_fill_walk(W, heads, channels, negative_slope, self_loops ? 1 : 0);
+  const int S = gat_geom(width).S;
+  const bool small = channels < 4;
+  const bool vec = all_mult4(width, ld_xl, ld_out, ld_g, ld_dxl) && all_aligned16(xl, out, g, dxl);
+  // destination pass: chunks (only when d a_dst is wanted), then rows (d a_dst, and D, which the source pass reads for d a_src)
+  if (d_a_dst != nullptr || d_a_src != nullptr) {
+    if (L.slots > 0 && d_a_dst != nullptr) {
+#define GAT1_DST_CHUNKS(S_, V_, M_) \
+  gat1_bwd_dst_kernel<S_, V_, M_, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(W, nullptr, 0, nullptr, L.slots, ws + L.part_dst)
+      GAT_DISPATCH(GAT1_DST_CHUNKS);
+#undef GAT1_DST_CHUNKS
+      EGC_LAUNCH_CHECK("gat1_bwd_dst_kernel(chunks)");
+    }
+    Gat1Walk Wr = W;
+    if (d_a_dst == nullptr) Wr.n_edges = 0, Wr.self_loops = 0;   // only D is wanted: no entries, no self entry
+#define GAT1_DST_ROWS(S_, V_, M_) \
+  gat1_bwd_dst_kernel<S_, V_, M_, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(Wr, d_a_dst, ld_d_a_dst, ws + L.D, L.slots, ws + L.part_dst)
+    GAT_DISPATCH(GAT1_DST_ROWS);
+#undef GAT1_DST_ROWS
+    EGC_LAUNCH_CHECK("gat1_bwd_dst_kernel(rows)");
+  }
+  if (src_pass) {
+    Gat1Walk T = W;
+    T.rowptr = t_rowptr, T.col = t_col;
+    const int want_das = d_a_src != nullptr ? 1 : 0;
+    if (L.slots > 0) {
+#define GAT1_SRC_CHUNKS(S_, V_, M_) \
+  gat1_bwd_src_kernel<S_, V_, M_, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(T, nullptr, 0, nullptr, 0, want_das, L.slots, ws + L.part_src)
+      GAT_DISPATCH(GAT1_SRC_CHUNKS);
+#undef GAT1_SRC_CHUNKS
+      EGC_LAUNCH_CHECK("gat1_bwd_src_kernel(chunks)");
+    }
+#define GAT1_SRC_ROWS(S_, V_, M_) \
+  gat1_bwd_src_kernel<S_, V_, M_, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(T, dxl, ld_dxl, d_a_src, ld_d_a_src, want_das, L.slots, ws + L.part_src)
+    GAT_DISPATCH(GAT1_SRC_ROWS);
+#undef GAT1_SRC_ROWS
+    EGC_LAUNCH_CHECK("gat1_bwd_src_kernel(rows)");
+  }
+  return EGC_OK;
+}

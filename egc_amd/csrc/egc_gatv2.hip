@@ -34,16 +34,12 @@
 // with those of chunks 1, 2, ... added in ascending order, the self entry last.  d att: a lane's sum over its row (entry order,
 // chunk by chunk), the workgroup's groups added in ascending order, the workgroups' partials (row workgroups, then chunk
 // workgroups) added in ascending order in blocks of 64, and those block sums again, until one is left.  -ffp-contract=off.
-#include "egc_row_chunks.h"
+#include "egc_gat_dev.h"
 
 namespace egc {
 
-constexpr int GAT_AHEAD = 8;
-constexpr int GAT_AHEAD_BWD = 4;
-constexpr int GAT_SUM_BLOCK = 64;
-
-// The score's per-column term: s = per-head sum of att * act(z), z = xl_j + xr_i.  (GAT v1's additive score is another functor
-// with act = identity on a pre-reduced pair and the nonlinearity after the sum; the walks below do not change.)
+// The score's per-column term: s = per-head sum of att * act(z), z = xl_j + xr_i.  (GAT v1's additive score separates into two
+// per-node scalars per head and needs no per-entry head sum: it has a kernel of its own, egc_gat.hip, on egc_gat_dev.h's mapping.)
 struct GatV2Score {
   float slope;
   __device__ inline f4 act(f4 z) const {
@@ -60,223 +56,7 @@ struct GatV2Score {
   }
 };
 
-struct GatWalk {
-  const int32_t* rowptr;   // the CSR walked: n_rows + 1 offsets
-  const int32_t* col;      // n_edges entries: rows of the gathered arrays
-  const float* xl;         // forward / destination pass: gathered (n_in_rows rows); source pass: the row's own
-  const float* xr;         // forward / destination pass: the row's own; source pass: gathered
-  const float* att;        // [H C]
-  const float* g;          // backward: d out.  destination pass: the row's own; source pass: gathered
-  const float* out;        // destination pass: the forward's output
-  const float* lse;        // backward: [n_nodes, H]
-  const float* D;          // source pass: [n_nodes, H] (the destination pass writes it)
-  int64_t n_rows, n_edges, n_in_rows;
-  int32_t ld_xl, ld_xr, ld_g, ld_out;
-  int32_t H, C, width, G, V, seg, self_loops;
-  float slope;
-};
-
-template <int S>
-struct GatLane {
-  int base;            // wavefront lane of the group's lane 0
-  int v[S], c[S];      // virtual lane and its first column
-  int na[S];           // how many of the four columns belong to the head of the first one (C >= 4)
-  int first_a[S];      // first virtual lane of that head's segment
-  int last_a[S], last_b[S];
-  bool prev_b[S];      // the segment's first lane, and the head starts inside the lane before
-  int hd[S][4];        // head of every column (clamped to H - 1)
-  bool head_first[S][4];   // the column is its head's first (and exists)
-};
-
-template <int S>
-__device__ inline GatLane<S> gat_lane(const GatWalk& W, int lane_in_group) {
-  GatLane<S> L;
-  L.base = ((int)threadIdx.x & 63) & ~(W.G - 1);
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int v = lane_in_group + W.G * s, c = 4 * v;
-    L.v[s] = v, L.c[s] = c;
-    const bool live = c < W.width;
-    const int ha = live ? c / W.C : 0;
-    const int end_a = (ha + 1) * W.C;
-    L.na[s] = live ? min(4, end_a - c) : 4;
-    L.first_a[s] = live ? (ha * W.C + 3) / 4 : v;
-    L.last_a[s] = live ? (end_a - 1) / 4 : v;
-    const int hb = min(ha + 1, W.H - 1);
-    L.last_b[s] = live ? min(((hb + 1) * W.C - 1) / 4, W.V - 1) : v;
-    L.prev_b[s] = live && v > 0 && v == L.first_a[s] && (ha * W.C) % 4 != 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int h = min((c + j) / W.C, W.H - 1);
-      L.hd[s][j] = h;
-      L.head_first[s][j] = c + j < W.width && c + j == h * W.C;
-    }
-  }
-  return L;
-}
-
-// x of virtual lane src (0 <= src < V) of this group
-template <int S>
-__device__ inline float gat_vget(const GatWalk& W, const GatLane<S>& L, const float (&x)[S], int src) {
-  const int lane = L.base + (src & (W.G - 1));
-  float t = __shfl(x[0], lane);
-  if (S == 2) {
-    const float t1 = __shfl(x[S - 1], lane);
-    t = src >= W.G ? t1 : t;
-  }
-  return t;
-}
-
-// out[s][j] = the sum of p over the columns of column (c[s] + j)'s head, in the order of the file header
-template <int S, bool SMALL>
-__device__ inline void gat_head_sums(const GatWalk& W, const GatLane<S>& L, const f4 (&p)[S], f4 (&out)[S]) {
-  if (SMALL) {
-    float q[S][12];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float x[S];
-#pragma unroll
-      for (int s = 0; s < S; ++s) x[s] = p[s][j];
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        q[s][j] = gat_vget<S>(W, L, x, max(L.v[s] - 1, 0));
-        q[s][4 + j] = x[s];
-        q[s][8 + j] = gat_vget<S>(W, L, x, min(L.v[s] + 1, W.V - 1));
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < S; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int lo = L.hd[s][j] * W.C, hi = lo + W.C;
-        float sum = 0.f;
-#pragma unroll
-        for (int t = 0; t < 12; ++t) {
-          const int cc = L.c[s] - 4 + t;
-          sum = (cc >= lo && cc < hi) ? sum + q[s][t] : sum;
-        }
-        out[s][j] = sum;
-      }
-    return;
-  }
-  float a[S], b[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    a[s] = p[s][0], b[s] = 0.f;
-#pragma unroll
-    for (int j = 1; j < 4; ++j) {
-      a[s] = j < L.na[s] ? a[s] + p[s][j] : a[s];
-      b[s] = j < L.na[s] ? b[s] : b[s] + p[s][j];
-    }
-  }
-  float t[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) t[s] = gat_vget<S>(W, L, b, max(L.v[s] - 1, 0));
-#pragma unroll
-  for (int s = 0; s < S; ++s) a[s] = L.prev_b[s] ? t[s] + a[s] : a[s];
-#pragma unroll 1
-  for (int d = 1; d < W.seg; d <<= 1) {
-#pragma unroll
-    for (int s = 0; s < S; ++s) t[s] = gat_vget<S>(W, L, a, max(L.v[s] - d, 0));
-#pragma unroll
-    for (int s = 0; s < S; ++s) a[s] = L.v[s] - d >= L.first_a[s] ? a[s] + t[s] : a[s];
-  }
-  float sa[S], sb[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) sa[s] = gat_vget<S>(W, L, a, L.last_a[s]), sb[s] = gat_vget<S>(W, L, a, L.last_b[s]);
-#pragma unroll
-  for (int s = 0; s < S; ++s)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) out[s][j] = j < L.na[s] ? sa[s] : sb[s];
-}
-
-template <bool VEC>
-__device__ inline f4 gat_load(const float* __restrict__ p, int c, int width) {
-  if (VEC) return c < width ? *reinterpret_cast<const f4*>(p) : f4{0.f, 0.f, 0.f, 0.f};
-  return tm_load<false>(p, c, width);
-}
-
-template <bool VEC>
-__device__ inline void gat_store(float* __restrict__ p, int c, int width, f4 v) {
-  if (VEC) {
-    if (c < width) *reinterpret_cast<f4*>(p) = v;
-    return;
-  }
-  tm_store<false>(p, c, width, v);
-}
-
-template <int S, bool VEC>
-__device__ inline void gat_load_row(f4 (&v)[S], const float* __restrict__ base, int64_t row, int ld, const GatLane<S>& L, int width) {
-#pragma unroll
-  for (int s = 0; s < S; ++s) v[s] = gat_load<VEC>(base + row * ld + L.c[s], L.c[s], width);
-}
-
-// a per-(row, head) value for every column of the lane
-template <int S>
-__device__ inline void gat_load_heads(f4 (&v)[S], const float* __restrict__ a, int64_t row, const GatWalk& W, const GatLane<S>& L) {
-#pragma unroll
-  for (int s = 0; s < S; ++s)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[s][j] = a[row * W.H + L.hd[s][j]];
-}
-
-__device__ inline f4 gat_exp(f4 x) { return f4{expf(x[0]), expf(x[1]), expf(x[2]), expf(x[3])}; }
-
 // ---------------------------------------------------------------------------------------------------------------- forward
-
-template <int S>
-struct GatState {
-  f4 m[S], l[S], acc[S];
-};
-
-template <int S>
-__device__ inline void gat_state_init(GatState<S>& st) {
-  const float ninf = -__builtin_inff();
-#pragma unroll
-  for (int s = 0; s < S; ++s) st.m[s] = f4{ninf, ninf, ninf, ninf}, st.l[s] = f4{0.f, 0.f, 0.f, 0.f}, st.acc[s] = st.l[s];
-}
-
-// one batch of N entries with scores e and rows v folded into the state (file header)
-template <int S, int N>
-__device__ inline void gat_state_take(GatState<S>& st, const f4 (&e)[N][S], const f4 (&v)[N][S], const bool (&live)[N]) {
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    f4 bm = st.m[s];
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) bm[i] = (live[k] && e[k][s][i] > bm[i]) ? e[k][s][i] : bm[i];
-    f4 r = gat_exp(st.m[s] - bm);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = st.m[s][i] == bm[i] ? 1.f : r[i];
-    f4 l = st.l[s] * r, acc = st.acc[s] * r;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      f4 w = gat_exp(e[k][s] - bm);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[i] = live[k] ? w[i] : 0.f;
-      l = l + w;
-      acc = acc + w * v[k][s];
-    }
-    st.m[s] = bm, st.l[s] = l, st.acc[s] = acc;
-  }
-}
-
-template <int S>
-__device__ inline void gat_state_merge(GatState<S>& st, const f4 (&m2)[S], const f4 (&l2)[S], const f4 (&acc2)[S]) {
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    f4 bm, r1, r2;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bm[i] = m2[s][i] > st.m[s][i] ? m2[s][i] : st.m[s][i];
-    r1 = gat_exp(st.m[s] - bm), r2 = gat_exp(m2[s] - bm);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r1[i] = st.m[s][i] == bm[i] ? 1.f : r1[i], r2[i] = m2[s][i] == bm[i] ? 1.f : r2[i];
-    st.l[s] = st.l[s] * r1 + l2[s] * r2;
-    st.acc[s] = st.acc[s] * r1 + acc2[s] * r2;
-    st.m[s] = bm;
-  }
-}
 
 template <int S, bool VEC, bool SMALL, class Score, bool FULL>
 __device__ inline void gat_fwd_batch(GatState<S>& st, const GatWalk& W, const GatLane<S>& L, const Score& sc, const f4 (&xr)[S],
@@ -595,25 +375,6 @@ __global__ void __launch_bounds__(256) gat_sum_rows_kernel(const float* __restri
 
 // ------------------------------------------------------------------------------------------------------------------- host
 
-struct GatGeom {
-  int32_t S, G, V;
-};
-
-static inline GatGeom gat_geom(int32_t width) {
-  const int lanes = (width + 3) / 4;
-  GatGeom q;
-  q.S = lanes > 64 ? 2 : 1;
-  int G = 1;
-  while (G < lanes && G < 64) G <<= 1;
-  q.G = G, q.V = q.S * G;
-  return q;
-}
-
-static inline int64_t gat_blocks(int64_t groups, int32_t G) { return ceil_div(groups, 256 / G); }
-static inline size_t gat_align(size_t floats) { return (floats + 3) & ~(size_t)3; }
-
-static inline bool gat_shape_ok(int32_t H, int32_t C) { return H >= 1 && C >= 1 && (int64_t)H * C <= 512; }
-
 // backward workspace, in floats
 struct GatBwdWs {
   size_t D, part_xr, part_xl, part_att, tmp0, tmp1, total;
@@ -637,22 +398,6 @@ static inline GatBwdWs gat_bwd_ws(int64_t n_rows, int64_t n_edges, int32_t H, in
   w.total = at;
   return w;
 }
-
-static void gat_fill_walk(GatWalk& W, int32_t H, int32_t C, float slope, int32_t self_loops) {
-  const GatGeom q = gat_geom(H * C);
-  W.H = H, W.C = C, W.width = H * C, W.G = q.G, W.V = q.V, W.seg = (C + 3) / 4 + 1, W.self_loops = self_loops, W.slope = slope;
-}
-
-#define GAT_DISPATCH(LAUNCH)                                   \
-  do {                                                         \
-    if (S == 2) {                                              \
-      if (vec) { if (small) LAUNCH(2, true, true); else LAUNCH(2, true, false); }      \
-      else { if (small) LAUNCH(2, false, true); else LAUNCH(2, false, false); }        \
-    } else {                                                   \
-      if (vec) { if (small) LAUNCH(1, true, true); else LAUNCH(1, true, false); }      \
-      else { if (small) LAUNCH(1, false, true); else LAUNCH(1, false, false); }        \
-    }                                                          \
-  } while (0)
 
 }  // namespace egc
 

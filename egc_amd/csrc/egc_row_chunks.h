@@ -1,4 +1,4 @@
-// The chunked row walk of the gather kernels (egc_typed_mean.hip, egc_mpnn.hip, egc_gatv2.hip, egc_pna.hip): its index
+// The chunked row walk of the gather kernels (egc_typed_mean.hip, egc_mpnn.hip, egc_gatv2.hip, egc_gat.hip, egc_pna.hip): its index
 // arithmetic, written once.  What is loaded per entry and how it is folded is each kernel's own.
 //
 // Order rule.  A row's entries are cut into consecutive chunks of ROW_CHUNK entries, counted from the row's first entry.  A chunk

@@ -852,6 +852,44 @@ int egc_gatv2_backward_f32(const int32_t* rowptr, const int32_t* col, const int3
                            int32_t ld_out, const float* lse, const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* dxr,
                            int32_t ld_dxr, float* datt, void* workspace, size_t workspace_bytes, egc_stream_t stream);
 
+/* GAT (v1) attention aggregate (egc_gat.hip): PyG GATConv's propagate without an [E, .] array.  H = heads, C = channels per
+ * head, width = H * C <= 512 (any H >= 1, C >= 1).  xl (n_src_rows rows of stride ld_xl) is the lin projection; a_src
+ * (n_src_rows rows of stride ld_a_src, H wide) and a_dst (n_rows rows of stride ld_a_dst, H wide) are the per-node halves of
+ * the additive score, a_src[j, h] = sum_c xl[j, h, c] * att_src[h, c] and a_dst likewise; the three may be column blocks of one
+ * wider array.  For an entry j -> i of the CSR by destination and head h
+ *   s_ij = leaky_relu(a_src[j, h] + a_dst[i, h])                alpha_ij = softmax of s over row i's entries
+ *   out[i, h, :] = sum_j alpha_ij * xl[j, h, :]                  lse[i, h] = log sum_j exp(s_ij)
+ * and out = 0, lse = -inf for a row without entries.  self_loops != 0: the entries whose col equals their row are skipped and
+ * one self entry (j = i) is taken last (needs n_src_rows == n_rows).  One gather pass with an online softmax (the maximum is
+ * subtracted before every exp) and no cross-lane operation per entry; rows longer than EGC_TYPED_MEAN_CHUNK entries are cut
+ * into chunks whose partial states a first launch leaves in `workspace` (egc_gat_forward_workspace_bytes; 16-byte aligned, any
+ * content; 0 when n_edges <= one chunk).  out: n_rows rows of stride ld_out; lse: dense [n_rows, H].  Every element is written
+ * exactly once, no atomics; the order of every sum is fixed by H, C and the row's entries alone (egc_gat.hip's header), so
+ * results are bit-reproducible.  Column indices are clamped to [0, n_src_rows), offsets to [0, n_edges].
+ *
+ * egc_gat_backward_f32 (a square graph): from g = d out, the forward's out and lse, with the scores recomputed.  t_rowptr /
+ * t_col: the transposed CSR (rows = sources, entries = destinations), read for d xl and d a_src.  With D_i = g_i . out_i per
+ * head and w_ij = alpha_ij leaky_relu'(a_src[j] + a_dst[i])
+ *   d xl[j] = sum_i alpha_ij g_i   (the direct term only: the score's share flows through d a_src and d a_dst)
+ *   d a_src[j, h] = sum_i w_ij (g_i . xl_j - D_i)                   d a_dst[i, h] = g_i . (sum_j w_ij xl_j) - D_i sum_j w_ij
+ * Any of d xl (rows of stride ld_dxl), d a_src, d a_dst (H wide, strides ld_d_a_src / ld_d_a_dst; column blocks of one array
+ * are fine) may be NULL.  Workspace: egc_gat_backward_workspace_bytes (always > 0 for n_rows > 0), 16-byte aligned, any content.
+ * EGC_ERR_INVALID: H < 1, C < 1, H * C > 512, a missing pointer, a negative count, a stride smaller than its width (H * C, or
+ * H for the per-head arrays), self_loops with n_src_rows != n_rows; EGC_ERR_UNSUPPORTED: a count >= 2^31; EGC_ERR_WORKSPACE:
+ * workspace missing, misaligned or too small. */
+size_t egc_gat_forward_workspace_bytes(int64_t n_edges, int32_t heads, int32_t channels);
+int egc_gat_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                        const float* xl, int32_t ld_xl, const float* a_src, int32_t ld_a_src, const float* a_dst, int32_t ld_a_dst,
+                        int32_t heads, int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out,
+                        float* lse, void* workspace, size_t workspace_bytes, egc_stream_t stream);
+size_t egc_gat_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32_t heads, int32_t channels);
+int egc_gat_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_rows,
+                         int64_t n_edges, const float* xl, int32_t ld_xl, const float* a_src, int32_t ld_a_src, const float* a_dst,
+                         int32_t ld_a_dst, int32_t heads, int32_t channels, float negative_slope, int32_t self_loops,
+                         const float* out, int32_t ld_out, const float* lse, const float* g, int32_t ld_g, float* dxl,
+                         int32_t ld_dxl, float* d_a_src, int32_t ld_d_a_src, float* d_a_dst, int32_t ld_d_a_dst, void* workspace,
+                         size_t workspace_bytes, egc_stream_t stream);
+
 /* Training form of egc_aggregate_combine_f32: same `out`, plus what the backward needs instead of a second
  * gather.  stats (n_nodes * egc_train_stats_floats(layer) floats, opaque to the caller, handed to the backward
  * as it is) receives every row's raw running aggregates after the self-loop term (those of sum / variance -- as the
