@@ -10,7 +10,14 @@ entries plus exactly one (i, i) per node, taken last; duplicates count each time
 PyG evaluates this through several [E, H, C] and [E, H] arrays that autograd keeps.  The kernel makes one gather pass over xl
 with an online softmax and keeps only lse [N, H]; the backward recomputes the scores (d xr and d att over the CSR, d xl over
 the transposed CSR) and writes d xl and d xr into the two halves of one [N, 2 H C] array.  No [E, .] array, no atomics, every
-element written once, bit-reproducible.  Head mean (``concat=False``) and the bias are torch."""
+element written once, bit-reproducible.  Head mean (``concat=False``) and the bias are torch.
+
+Attention dropout (PyG's ``F.dropout`` on alpha in training: per edge and head, the self loops included) keeps no [E, H] mask
+either: the kernels' DROP instances regenerate it in the forward and in both backward passes from a counter-based generator
+(Philox4x32-10, keyed by one int64 seed on the device, counted by the entry's position in the destination-keyed CSR and the
+head; egc_amd/csrc/egc_gat_dev.h).  ``dropout=p, seed=t`` on the functions below (t: an int64 device tensor of one element);
+the modules draw a seed per training forward with a torch device op, so ``torch.manual_seed`` governs it and nothing
+synchronises."""
 from __future__ import annotations
 
 import math
@@ -33,7 +40,26 @@ def _heads_channels(att):
     return att.contiguous(), att.size(0), att.size(1)
 
 
-def _launch_forward(xl, xr, att, g: CSRGraph, heads, channels, slope, loops, out, lse):
+def _drop_args(dropout, seed, dev):
+    """None for dropout == 0 (the plain kernels); else (p, seed): p in (0, 1) and an int64 tensor of one element on ``dev``."""
+    p = float(dropout)
+    if p == 0.0:
+        return None
+    if not 0.0 < p < 1.0:
+        raise RuntimeError(f"egc_amd: dropout must be in [0, 1) here (got {dropout}); the modules handle dropout >= 1")
+    if seed is None:
+        raise RuntimeError("egc_amd: dropout > 0 needs seed=, an int64 tensor of one element on the inputs' device")
+    if not torch.is_tensor(seed) or seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != dev:
+        raise RuntimeError(f"egc_amd: seed must be an int64 tensor of one element on {dev}")
+    return p, seed
+
+
+def _new_seed(dev):
+    """A fresh seed from torch's generator of ``dev``, by a device op: no synchronisation, fresh in every replay of a captured step."""
+    return torch.empty(1, dtype=torch.int64, device=dev).random_()
+
+
+def _launch_forward(xl, xr, att, g: CSRGraph, heads, channels, slope, loops, out, lse, drop=None):
     lib = _C.load()
     width, dev = heads * channels, xr.device
     ld_xl, ld_xr = _rows2d(xl, "xl", g.n_src_rows, width, dev), _rows2d(xr, "xr", g.n_nodes, width, dev)
@@ -44,13 +70,16 @@ def _launch_forward(xl, xr, att, g: CSRGraph, heads, channels, slope, loops, out
         raise RuntimeError(f"egc_amd: add_self_loops needs a square graph, got [{g.n_nodes}, {g.n_src_rows}]")
     with _device_guard(dev):
         ws, nbytes = _workspace(lib.egc_gatv2_forward_workspace_bytes(g.n_edges, heads, channels), dev)
-        _C.check(lib.egc_gatv2_forward_f32(g.rowptr.data_ptr(), g.col.data_ptr(), g.n_nodes, g.n_edges, g.n_src_rows, xl.data_ptr(),
-                                           ld_xl, xr.data_ptr(), ld_xr, att.data_ptr(), heads, channels, float(slope), int(loops),
-                                           out.data_ptr(), ld_out, lse.data_ptr(), _ptr(ws), nbytes, _stream_ptr(dev)),
-                 "egc_gatv2_forward_f32")
+        args = (g.rowptr.data_ptr(), g.col.data_ptr(), g.n_nodes, g.n_edges, g.n_src_rows, xl.data_ptr(), ld_xl, xr.data_ptr(), ld_xr,
+                att.data_ptr(), heads, channels, float(slope), int(loops), out.data_ptr(), ld_out, lse.data_ptr(), _ptr(ws), nbytes)
+        if drop is None:
+            _C.check(lib.egc_gatv2_forward_f32(*args, _stream_ptr(dev)), "egc_gatv2_forward_f32")
+        else:
+            _C.check(lib.egc_gatv2_forward_dropout_f32(*args, drop[0], drop[1].data_ptr(), _stream_ptr(dev)),
+                     "egc_gatv2_forward_dropout_f32")
 
 
-def _launch_backward(xl, xr, att, g: CSRGraph, heads, channels, slope, loops, out, lse, gout, dxl, dxr, datt):
+def _launch_backward(xl, xr, att, g: CSRGraph, heads, channels, slope, loops, out, lse, gout, dxl, dxr, datt, drop=None):
     """egc_gatv2_backward_f32: d xl, d xr [N, H C] (column blocks are fine) and d att [H C]; any may be None."""
     lib = _C.load()
     width, dev, n = heads * channels, xr.device, g.n_nodes
@@ -63,26 +92,30 @@ def _launch_backward(xl, xr, att, g: CSRGraph, heads, channels, slope, loops, ou
     t = g.transposed() if dxl is not None else None
     with _device_guard(dev):
         ws, nbytes = _workspace(lib.egc_gatv2_backward_workspace_bytes(n, g.n_edges, heads, channels), dev)
-        _C.check(lib.egc_gatv2_backward_f32(
-            g.rowptr.data_ptr(), g.col.data_ptr(), _ptr(t.rowptr if t else None), _ptr(t.col if t else None), n, g.n_edges,
-            xl.data_ptr(), ld_xl, xr.data_ptr(), ld_xr, att.data_ptr(), heads, channels, float(slope), int(loops), out.data_ptr(),
-            ld_out, lse.data_ptr(), gout.data_ptr(), ld_g, _ptr(dxl), ld_dxl, _ptr(dxr), ld_dxr, _ptr(datt), _ptr(ws), nbytes,
-            _stream_ptr(dev)), "egc_gatv2_backward_f32")
+        csr = (g.rowptr.data_ptr(), g.col.data_ptr(), _ptr(t.rowptr if t else None), _ptr(t.col if t else None))
+        args = (n, g.n_edges, xl.data_ptr(), ld_xl, xr.data_ptr(), ld_xr, att.data_ptr(), heads, channels, float(slope), int(loops),
+                out.data_ptr(), ld_out, lse.data_ptr(), gout.data_ptr(), ld_g, _ptr(dxl), ld_dxl, _ptr(dxr), ld_dxr, _ptr(datt),
+                _ptr(ws), nbytes)
+        if drop is None:
+            _C.check(lib.egc_gatv2_backward_f32(*csr, *args, _stream_ptr(dev)), "egc_gatv2_backward_f32")
+        else:
+            _C.check(lib.egc_gatv2_backward_dropout_f32(*csr, _ptr(t.edge_id if t else None), *args, drop[0], drop[1].data_ptr(),
+                                                        _stream_ptr(dev)), "egc_gatv2_backward_dropout_f32")
 
 
-def _forward(xl, xr, att, g, slope, loops):
+def _forward(xl, xr, att, g, slope, loops, drop=None):
     att2, heads, channels = _heads_channels(att)
     _check_f32(xr, "xr")
     n, dev = g.n_nodes, xr.device
     out = torch.empty((n, heads * channels), dtype=torch.float32, device=dev)
     lse = torch.empty((n, heads), dtype=torch.float32, device=dev)
-    _launch_forward(xl, xr, att2, g, heads, channels, slope, loops, out, lse)
+    _launch_forward(xl, xr, att2, g, heads, channels, slope, loops, out, lse, drop)
     return out, lse, att2, heads, channels
 
 
 def _backward(saved, needs, gout):
     """(d xl, d xr, d att) for one saved forward; d xl and d xr are the halves of one [N, 2 H C] array when both are wanted."""
-    xl, xr, att2, g, heads, channels, slope, loops, out, lse, att_shape = saved
+    xl, xr, att2, g, heads, channels, slope, loops, out, lse, att_shape, drop = saved
     width, n, dev = heads * channels, g.n_nodes, gout.device
     gout = _unit_columns(gout)
     both = torch.empty((n, 2 * width), dtype=torch.float32, device=dev) if needs[0] and needs[1] else None
@@ -92,7 +125,7 @@ def _backward(saved, needs, gout):
     if n == 0:
         datt = torch.zeros(width, dtype=torch.float32, device=dev) if needs[2] else None
     else:
-        _launch_backward(xl, xr, att2, g, heads, channels, slope, loops, out, lse, gout, dxl, dxr, datt)
+        _launch_backward(xl, xr, att2, g, heads, channels, slope, loops, out, lse, gout, dxl, dxr, datt, drop)
     return dxl, dxr, (datt.view(att_shape) if datt is not None else None), both
 
 
@@ -100,65 +133,101 @@ class _GatV2Aggregate(torch.autograd.Function):
     """out [N, H C] from xl, xr (separate arrays or column blocks) and att."""
 
     @staticmethod
-    def forward(ctx, xl, xr, att, g, slope, loops):
+    def forward(ctx, xl, xr, att, g, slope, loops, drop=None):
         xl, xr, att = xl.detach(), xr.detach(), att.detach()
-        out, lse, att2, heads, channels = _forward(xl, xr, att, g, slope, loops)
-        ctx.saved = (xl, xr, att2, g, heads, channels, slope, loops, out, lse, att.shape)
+        out, lse, att2, heads, channels = _forward(xl, xr, att, g, slope, loops, drop)
+        ctx.saved = (xl, xr, att2, g, heads, channels, slope, loops, out, lse, att.shape, drop)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         dxl, dxr, datt, _ = _backward(ctx.saved, ctx.needs_input_grad[:3], gout)
-        return dxl, dxr, datt, None, None, None
+        return dxl, dxr, datt, None, None, None, None
 
 
 class _GatV2Fused(torch.autograd.Function):
     """out [N, H C] from lr = [xl | xr] ([N, 2 H C], one dense product): the backward writes both halves of ONE d lr."""
 
     @staticmethod
-    def forward(ctx, lr, att, g, slope, loops):
+    def forward(ctx, lr, att, g, slope, loops, drop=None):
         lr, att = lr.detach(), att.detach()
         width = lr.size(1) // 2
-        out, lse, att2, heads, channels = _forward(lr[:, :width], lr[:, width:], att, g, slope, loops)
-        ctx.saved = (lr[:, :width], lr[:, width:], att2, g, heads, channels, slope, loops, out, lse, att.shape)
+        out, lse, att2, heads, channels = _forward(lr[:, :width], lr[:, width:], att, g, slope, loops, drop)
+        ctx.saved = (lr[:, :width], lr[:, width:], att2, g, heads, channels, slope, loops, out, lse, att.shape, drop)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         need = ctx.needs_input_grad[0]
         _, _, datt, both = _backward(ctx.saved, (need, need, ctx.needs_input_grad[1]), gout)
-        return both, datt, None, None, None
+        return both, datt, None, None, None, None
 
 
-def gatv2_aggregate(xl, xr, att, graph, negative_slope=0.2, add_self_loops=True):
+def gatv2_aggregate(xl, xr, att, graph, negative_slope=0.2, add_self_loops=True, dropout=0.0, seed=None):
     """out [N, H C] of the GATv2 attention aggregate (module docstring) from xl [rows the edges' sources name, H C], xr [N, H C]
     (separate arrays or column blocks of one wider array) and att ([H, C] or [1, H, C]) over ``graph`` (a CSRGraph, SparseTensor,
-    GraphBatch or [2, E] int64 edge_index).  Differentiable with respect to xl, xr and att (the backward needs a square graph)."""
+    GraphBatch or [2, E] int64 edge_index).  Differentiable with respect to xl, xr and att (the backward needs a square graph).
+    ``dropout`` in (0, 1) with ``seed`` (an int64 device tensor of one element): attention dropout under that seed's mask."""
+    drop = _drop_args(dropout, seed, xr.device)
     if xr.dim() != 2:
         raise RuntimeError(f"egc_amd: xr must be [N, H C] (got {tuple(xr.shape)})")
     _heads_channels(att)
     _check_f32(xr, "xr")
-    return _GatV2Aggregate.apply(xl, xr, att, _as_csr(graph, xr.size(0)), float(negative_slope), bool(add_self_loops))
+    return _GatV2Aggregate.apply(xl, xr, att, _as_csr(graph, xr.size(0)), float(negative_slope), bool(add_self_loops), drop)
 
 
-def gatv2_aggregate_lse(xl, xr, att, graph, negative_slope=0.2, add_self_loops=True):
-    """(out [N, H C], lse [N, H]) of the forward kernel: lse is the log-sum-exp of every row's scores, -inf for an empty row.
-    Not differentiable."""
+def gatv2_aggregate_lse(xl, xr, att, graph, negative_slope=0.2, add_self_loops=True, dropout=0.0, seed=None):
+    """(out [N, H C], lse [N, H]) of the forward kernel: lse is the log-sum-exp of every row's scores (dropout does not touch
+    it), -inf for an empty row.  Not differentiable."""
+    drop = _drop_args(dropout, seed, xr.device)
     if xr.dim() != 2:
         raise RuntimeError(f"egc_amd: xr must be [N, H C] (got {tuple(xr.shape)})")
     _heads_channels(att)
     _check_f32(xr, "xr")
     out, lse, _, _, _ = _forward(xl.detach(), xr.detach(), att.detach(), _as_csr(graph, xr.size(0)), float(negative_slope),
-                                 bool(add_self_loops))
+                                 bool(add_self_loops), drop)
     return out, lse
 
 
-def gatv2_aggregate_backward(xl, xr, att, graph, out, lse, gout, negative_slope=0.2, add_self_loops=True):
-    """(d xl, d xr, d att) from d out: the backward kernels on their own (d xl and d xr are the halves of one array)."""
+def gatv2_aggregate_backward(xl, xr, att, graph, out, lse, gout, negative_slope=0.2, add_self_loops=True, dropout=0.0, seed=None):
+    """(d xl, d xr, d att) from d out: the backward kernels on their own (d xl and d xr are the halves of one array).  ``dropout``
+    and ``seed``: those of the forward that produced ``out``."""
     att2, heads, channels = _heads_channels(att)
     saved = (xl, xr, att2, _as_csr(graph, xr.size(0)), heads, channels, float(negative_slope), bool(add_self_loops), out, lse,
-             att.shape)
+             att.shape, _drop_args(dropout, seed, xr.device))
     return _backward(saved, (True, True, True), gout)[:3]
+
+
+def _module_dropout(layer, x):
+    """(drop, all_dropped) of one module forward: (None, False) in eval mode or at dropout == 0; a fresh seed, kept as
+    ``layer.last_dropout_seed``, for 0 < dropout < 1 in training; all_dropped for dropout >= 1 in training.  The layer's dropout
+    is its constructor's: a ``.dropout`` assigned afterwards raises in training as it did before there was a dropout path (a
+    layer built with dropout = 0 keeps exactly its earlier behaviour), and so does a tensor that is not on the device, where the
+    mask would have to be drawn."""
+    if not layer.training:
+        return None, False
+    p, name = float(layer.dropout), type(layer).__name__
+    if p != layer._dropout_built:
+        raise NotImplementedError(f"egc_amd.{name}: attention dropout changed after construction ({layer._dropout_built} -> {p}) is "
+                                  f"not implemented for training; construct the layer with dropout={p} or call .eval()")
+    if p <= 0.0:
+        return None, False
+    if not x.is_cuda:
+        raise NotImplementedError(f"egc_amd.{name}: attention dropout ({p}) is not implemented for tensors on {x.device}: the mask "
+                                  "is generated in the HIP kernels (no CPU fallback)")
+    if p >= 1.0:
+        return None, True
+    layer.last_dropout_seed = _new_seed(x.device)
+    return (p, layer.last_dropout_seed), False
+
+
+def _all_dropped(rows, *params):
+    """The aggregate at dropout >= 1: zeros [N, H C] (F.dropout's result), connected to ``rows`` [N, H C] and to ``params`` so
+    that their gradients are zeros and not None.  No launch."""
+    out = rows * 0.0
+    for q in params:
+        out = out + (q * 0.0).sum()
+    return out
 
 
 def _glorot_(t):
@@ -172,8 +241,11 @@ class GATv2Conv(nn.Module):
     add_self_loops=True, bias=True, share_weights=False)``; ``forward(x, edge_index)`` with edge_index a [2, E] int64 tensor, an
     ``egc_amd.SparseTensor``, a ``CSRGraph`` or a ``GraphBatch``.  Parameters ``lin_l.{weight,bias}``, ``lin_r.{weight,bias}``,
     ``att`` [1, H, C] and ``bias`` ([H C], or [C] for concat=False) as in PyG, so its state dicts load with strict=True (with
-    ``share_weights`` lin_r IS lin_l).  Glorot weights and att, zero biases.  Attention dropout is not implemented: dropout > 0
-    raises in training mode and is ignored in eval mode."""
+    ``share_weights`` lin_r IS lin_l).  Glorot weights and att, zero biases.  ``dropout``: attention dropout in training mode
+    (per edge and head, self loops included, as PyG's; the mask is regenerated in the kernels from ``last_dropout_seed``, the
+    int64 device tensor drawn for the last training forward; module docstring), ignored in eval mode.  The value is the
+    constructor's: a ``.dropout`` assigned afterwards, or a training forward with dropout on a tensor off the device, raises
+    NotImplementedError as before."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
                  bias=True, share_weights=False):
@@ -189,6 +261,7 @@ class GATv2Conv(nn.Module):
             self.bias = nn.Parameter(torch.empty(heads * out_channels if concat else out_channels))
         else:
             self.register_parameter("bias", None)
+        self.last_dropout_seed, self._dropout_built = None, float(dropout)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -202,9 +275,7 @@ class GATv2Conv(nn.Module):
     def forward(self, x, edge_index):
         if x.dim() != 2 or x.size(1) != self.in_channels:
             raise RuntimeError(f"egc_amd.GATv2Conv: x has shape {tuple(x.shape)}, expected (rows, {self.in_channels})")
-        if self.dropout > 0.0 and self.training:
-            raise NotImplementedError(f"egc_amd.GATv2Conv: attention dropout ({self.dropout}) is not implemented for training; "
-                                      "construct the layer with dropout=0.0 (the reference's gat_dropout) or call .eval()")
+        drop, all_dropped = _module_dropout(self, x)
         _check_f32(x, "x")
         g = _as_csr(edge_index, x.size(0))
         if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
@@ -212,10 +283,11 @@ class GATv2Conv(nn.Module):
         slope, loops = float(self.negative_slope), bool(self.add_self_loops)
         if self.share_weights:
             xl = F.linear(x, self.lin_l.weight, self.lin_l.bias)
-            out = _GatV2Aggregate.apply(xl, xl, self.att, g, slope, loops)
+            out = _all_dropped(xl, self.att) if all_dropped else _GatV2Aggregate.apply(xl, xl, self.att, g, slope, loops, drop)
         else:
             lr = F.linear(x, torch.cat([self.lin_l.weight, self.lin_r.weight]), torch.cat([self.lin_l.bias, self.lin_r.bias]))
-            out = _GatV2Fused.apply(lr, self.att, g, slope, loops)
+            out = (_all_dropped(lr[:, :lr.size(1) // 2] + lr[:, lr.size(1) // 2:], self.att) if all_dropped
+                   else _GatV2Fused.apply(lr, self.att, g, slope, loops, drop))
         if not self.concat:
             out = out.view(-1, self.heads, self.out_channels).mean(dim=1)
         return out if self.bias is None else out + self.bias
@@ -250,7 +322,7 @@ def _gat1_shape(xl, a_src, a_dst):
     return heads, xl.size(1) // heads
 
 
-def _gat1_launch_forward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope, loops, out, lse):
+def _gat1_launch_forward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope, loops, out, lse, drop=None):
     lib = _C.load()
     width, dev = heads * channels, a_dst.device
     ld_xl, ld_as = _rows2d(xl, "xl", g.n_src_rows, width, dev), _rows2d(a_src, "a_src", g.n_src_rows, heads, dev)
@@ -261,13 +333,17 @@ def _gat1_launch_forward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope, 
         raise RuntimeError(f"egc_amd: add_self_loops needs a square graph, got [{g.n_nodes}, {g.n_src_rows}]")
     with _device_guard(dev):
         ws, nbytes = _workspace(lib.egc_gat_forward_workspace_bytes(g.n_edges, heads, channels), dev)
-        _C.check(lib.egc_gat_forward_f32(g.rowptr.data_ptr(), g.col.data_ptr(), g.n_nodes, g.n_edges, g.n_src_rows, xl.data_ptr(),
-                                         ld_xl, a_src.data_ptr(), ld_as, a_dst.data_ptr(), ld_ad, heads, channels, float(slope),
-                                         int(loops), out.data_ptr(), ld_out, lse.data_ptr(), _ptr(ws), nbytes, _stream_ptr(dev)),
-                 "egc_gat_forward_f32")
+        args = (g.rowptr.data_ptr(), g.col.data_ptr(), g.n_nodes, g.n_edges, g.n_src_rows, xl.data_ptr(), ld_xl, a_src.data_ptr(),
+                ld_as, a_dst.data_ptr(), ld_ad, heads, channels, float(slope), int(loops), out.data_ptr(), ld_out, lse.data_ptr(),
+                _ptr(ws), nbytes)
+        if drop is None:
+            _C.check(lib.egc_gat_forward_f32(*args, _stream_ptr(dev)), "egc_gat_forward_f32")
+        else:
+            _C.check(lib.egc_gat_forward_dropout_f32(*args, drop[0], drop[1].data_ptr(), _stream_ptr(dev)),
+                     "egc_gat_forward_dropout_f32")
 
 
-def _gat1_launch_backward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope, loops, out, lse, gout, dxl, das, dad):
+def _gat1_launch_backward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope, loops, out, lse, gout, dxl, das, dad, drop=None):
     """egc_gat_backward_f32: d xl [N, H C], d a_src and d a_dst [N, H] (column blocks are fine); any may be None."""
     lib = _C.load()
     width, dev, n = heads * channels, a_dst.device, g.n_nodes
@@ -284,26 +360,30 @@ def _gat1_launch_backward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope,
     t = g.transposed() if dxl is not None or das is not None else None
     with _device_guard(dev):
         ws, nbytes = _workspace(lib.egc_gat_backward_workspace_bytes(n, g.n_edges, heads, channels), dev)
-        _C.check(lib.egc_gat_backward_f32(
-            g.rowptr.data_ptr(), g.col.data_ptr(), _ptr(t.rowptr if t else None), _ptr(t.col if t else None), n, g.n_edges,
-            xl.data_ptr(), ld_xl, a_src.data_ptr(), ld_as, a_dst.data_ptr(), ld_ad, heads, channels, float(slope), int(loops),
-            out.data_ptr(), ld_out, lse.data_ptr(), gout.data_ptr(), ld_g, _ptr(dxl), ld_dxl, _ptr(das), ld_das, _ptr(dad),
-            ld_dad, _ptr(ws), nbytes, _stream_ptr(dev)), "egc_gat_backward_f32")
+        csr = (g.rowptr.data_ptr(), g.col.data_ptr(), _ptr(t.rowptr if t else None), _ptr(t.col if t else None))
+        args = (n, g.n_edges, xl.data_ptr(), ld_xl, a_src.data_ptr(), ld_as, a_dst.data_ptr(), ld_ad, heads, channels, float(slope),
+                int(loops), out.data_ptr(), ld_out, lse.data_ptr(), gout.data_ptr(), ld_g, _ptr(dxl), ld_dxl, _ptr(das), ld_das,
+                _ptr(dad), ld_dad, _ptr(ws), nbytes)
+        if drop is None:
+            _C.check(lib.egc_gat_backward_f32(*csr, *args, _stream_ptr(dev)), "egc_gat_backward_f32")
+        else:
+            _C.check(lib.egc_gat_backward_dropout_f32(*csr, _ptr(t.edge_id if t else None), *args, drop[0], drop[1].data_ptr(),
+                                                      _stream_ptr(dev)), "egc_gat_backward_dropout_f32")
 
 
-def _gat1_forward(xl, a_src, a_dst, g, slope, loops):
+def _gat1_forward(xl, a_src, a_dst, g, slope, loops, drop=None):
     heads, channels = _gat1_shape(xl, a_src, a_dst)
     n, dev = g.n_nodes, a_dst.device
     out = torch.empty((n, heads * channels), dtype=torch.float32, device=dev)
     lse = torch.empty((n, heads), dtype=torch.float32, device=dev)
-    _gat1_launch_forward(xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse)
+    _gat1_launch_forward(xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse, drop)
     return out, lse, heads, channels
 
 
 def _gat1_backward(saved, needs, gout):
     """(d xl, d a_src, d a_dst, ext) for one saved forward: the wanted gradients are the blocks of ONE array ``ext`` in the layout
     [d xl | d a_src | d a_dst | pad]; the blocks nobody wants and the pad columns are zero."""
-    xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse = saved
+    xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse, drop = saved
     width, n, dev = heads * channels, g.n_nodes, gout.device
     gout = _unit_columns(gout)
     ext = torch.empty((n, _ext_width(heads, channels)), dtype=torch.float32, device=dev)
@@ -313,7 +393,7 @@ def _gat1_backward(saved, needs, gout):
             b.zero_()
     wanted = [b if need else None for b, need in zip(blocks, needs)]
     if n > 0 and any(needs):
-        _gat1_launch_backward(xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse, gout, *wanted)
+        _gat1_launch_backward(xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse, gout, *wanted, drop=drop)
     return wanted[0], wanted[1], wanted[2], ext
 
 
@@ -321,16 +401,16 @@ class _GatAggregate(torch.autograd.Function):
     """out [N, H C] from xl, a_src and a_dst (separate arrays or column blocks)."""
 
     @staticmethod
-    def forward(ctx, xl, a_src, a_dst, g, slope, loops):
+    def forward(ctx, xl, a_src, a_dst, g, slope, loops, drop=None):
         xl, a_src, a_dst = xl.detach(), a_src.detach(), a_dst.detach()
-        out, lse, heads, channels = _gat1_forward(xl, a_src, a_dst, g, slope, loops)
-        ctx.saved = (xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse)
+        out, lse, heads, channels = _gat1_forward(xl, a_src, a_dst, g, slope, loops, drop)
+        ctx.saved = (xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse, drop)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         dxl, das, dad, _ = _gat1_backward(ctx.saved, ctx.needs_input_grad[:3], gout)
-        return dxl, das, dad, None, None, None
+        return dxl, das, dad, None, None, None, None
 
 
 class _GatFused(torch.autograd.Function):
@@ -338,44 +418,48 @@ class _GatFused(torch.autograd.Function):
     blocks of ONE d ext of the same layout, the pad columns zero."""
 
     @staticmethod
-    def forward(ctx, ext, heads, channels, g, slope, loops):
+    def forward(ctx, ext, heads, channels, g, slope, loops, drop=None):
         ext = ext.detach()
         w = heads * channels
         if ext.dim() != 2 or ext.size(1) != _ext_width(heads, channels):
             raise RuntimeError(f"egc_amd: [xl | a_src | a_dst | pad] must be [N, {_ext_width(heads, channels)}] (got {tuple(ext.shape)})")
         xl, a_src, a_dst = ext[:, :w], ext[:, w:w + heads], ext[:, w + heads:w + 2 * heads]
-        out, lse, _, _ = _gat1_forward(xl, a_src, a_dst, g, slope, loops)
-        ctx.saved = (xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse)
+        out, lse, _, _ = _gat1_forward(xl, a_src, a_dst, g, slope, loops, drop)
+        ctx.saved = (xl, a_src, a_dst, g, heads, channels, slope, loops, out, lse, drop)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        return _gat1_backward(ctx.saved, (True, True, True), gout)[3], None, None, None, None, None
+        return _gat1_backward(ctx.saved, (True, True, True), gout)[3], None, None, None, None, None, None
 
 
-def gat_aggregate(xl, a_src, a_dst, graph, negative_slope=0.2, add_self_loops=True):
+def gat_aggregate(xl, a_src, a_dst, graph, negative_slope=0.2, add_self_loops=True, dropout=0.0, seed=None):
     """out [N, H C] of the GAT attention aggregate from xl [rows the edges' sources name, H C], a_src [the same rows, H] and
     a_dst [N, H] (separate arrays or column blocks of one wider array) over ``graph`` (a CSRGraph, SparseTensor, GraphBatch or
     [2, E] int64 edge_index): s_ij = leaky_relu(a_src[j] + a_dst[i]), alpha = softmax over i's in-edges, out_i = sum_j alpha_ij
-    xl_j per head.  Differentiable with respect to xl, a_src and a_dst (the backward needs a square graph)."""
+    xl_j per head.  Differentiable with respect to xl, a_src and a_dst (the backward needs a square graph).  ``dropout`` in (0, 1)
+    with ``seed`` (an int64 device tensor of one element): attention dropout under that seed's mask."""
+    drop = _drop_args(dropout, seed, a_dst.device)
     _gat1_shape(xl, a_src, a_dst)
-    return _GatAggregate.apply(xl, a_src, a_dst, _as_csr(graph, a_dst.size(0)), float(negative_slope), bool(add_self_loops))
+    return _GatAggregate.apply(xl, a_src, a_dst, _as_csr(graph, a_dst.size(0)), float(negative_slope), bool(add_self_loops), drop)
 
 
-def gat_aggregate_lse(xl, a_src, a_dst, graph, negative_slope=0.2, add_self_loops=True):
-    """(out [N, H C], lse [N, H]) of the forward kernel: lse is the log-sum-exp of every row's scores, -inf for an empty row.
-    Not differentiable."""
+def gat_aggregate_lse(xl, a_src, a_dst, graph, negative_slope=0.2, add_self_loops=True, dropout=0.0, seed=None):
+    """(out [N, H C], lse [N, H]) of the forward kernel: lse is the log-sum-exp of every row's scores (dropout does not touch
+    it), -inf for an empty row.  Not differentiable."""
+    drop = _drop_args(dropout, seed, a_dst.device)
     _gat1_shape(xl, a_src, a_dst)
     out, lse, _, _ = _gat1_forward(xl.detach(), a_src.detach(), a_dst.detach(), _as_csr(graph, a_dst.size(0)), float(negative_slope),
-                                   bool(add_self_loops))
+                                   bool(add_self_loops), drop)
     return out, lse
 
 
-def gat_aggregate_backward(xl, a_src, a_dst, graph, out, lse, gout, negative_slope=0.2, add_self_loops=True):
+def gat_aggregate_backward(xl, a_src, a_dst, graph, out, lse, gout, negative_slope=0.2, add_self_loops=True, dropout=0.0, seed=None):
     """(d xl, d a_src, d a_dst) from d out: the backward kernels on their own (the three are the column blocks of one array in
-    the layout [d xl | d a_src | d a_dst | pad])."""
+    the layout [d xl | d a_src | d a_dst | pad]).  ``dropout`` and ``seed``: those of the forward that produced ``out``."""
     heads, channels = _gat1_shape(xl, a_src, a_dst)
-    saved = (xl, a_src, a_dst, _as_csr(graph, a_dst.size(0)), heads, channels, float(negative_slope), bool(add_self_loops), out, lse)
+    saved = (xl, a_src, a_dst, _as_csr(graph, a_dst.size(0)), heads, channels, float(negative_slope), bool(add_self_loops), out, lse,
+             _drop_args(dropout, seed, a_dst.device))
     return _gat1_backward(saved, (True, True, True), gout)[:3]
 
 
@@ -386,9 +470,12 @@ class GATConv(nn.Module):
     load with strict=True: ``lin_src.weight`` [H C, F_in] and ``lin_dst.weight`` (lin_dst IS lin_src), ``att_src`` and
     ``att_dst`` [1, H, C], ``bias`` ([H C], or [C] for concat=False); the later layout with a single ``lin.weight`` loads too.
     Glorot weights and att, zero bias.  [xl | a_src | a_dst] is one dense product with the att vectors folded into 2 H extra
-    weight rows; autograd takes d W, d att_src and d att_dst from the one dense gradient.  Attention dropout is not implemented:
-    dropout > 0 raises in training mode and is ignored in eval mode.  Not implemented either: ``edge_dim`` (edge features),
-    bipartite ``in_channels`` (a pair), ``fill_value`` and ``residual``."""
+    weight rows; autograd takes d W, d att_src and d att_dst from the one dense gradient.  ``dropout``: attention dropout in
+    training mode (per edge and head, self loops included, as PyG's; the mask is regenerated in the kernels from
+    ``last_dropout_seed``, the int64 device tensor drawn for the last training forward), ignored in eval mode; the value is the
+    constructor's (a ``.dropout`` assigned afterwards, or a tensor off the device, raises NotImplementedError in training as
+    before).  Not implemented:
+    ``edge_dim`` (edge features), bipartite ``in_channels`` (a pair), ``fill_value`` and ``residual``."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
                  bias=True):
@@ -407,6 +494,7 @@ class GATConv(nn.Module):
             self.bias = nn.Parameter(torch.empty(heads * out_channels if concat else out_channels))
         else:
             self.register_parameter("bias", None)
+        self.last_dropout_seed, self._dropout_built = None, float(dropout)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -435,15 +523,16 @@ class GATConv(nn.Module):
     def forward(self, x, edge_index):
         if x.dim() != 2 or x.size(1) != self.in_channels:
             raise RuntimeError(f"egc_amd.GATConv: x has shape {tuple(x.shape)}, expected (rows, {self.in_channels})")
-        if self.dropout > 0.0 and self.training:
-            raise NotImplementedError(f"egc_amd.GATConv: attention dropout ({self.dropout}) is not implemented for training; "
-                                      "construct the layer with dropout=0.0 (the reference's gat_dropout) or call .eval()")
+        drop, all_dropped = _module_dropout(self, x)
         _check_f32(x, "x")
         g = _as_csr(edge_index, x.size(0))
         if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
             raise RuntimeError(f"egc_amd.GATConv: the graph is [{g.n_nodes}, {g.n_src_rows}], x has {x.size(0)} rows")
         ext = F.linear(x, self.extended_weight())
-        out = _GatFused.apply(ext, self.heads, self.out_channels, g, float(self.negative_slope), bool(self.add_self_loops))
+        if all_dropped:
+            out = _all_dropped(ext[:, :self.heads * self.out_channels])
+        else:
+            out = _GatFused.apply(ext, self.heads, self.out_channels, g, float(self.negative_slope), bool(self.add_self_loops), drop)
         if not self.concat:
             out = out.view(-1, self.heads, self.out_channels).mean(dim=1)
         return out if self.bias is None else out + self.bias

@@ -33,6 +33,17 @@
 // those of chunks 1, 2, ... added in ascending order, the self entry last; then, in the destination pass, the row's head sum
 // and one subtraction.  So the order of every sum is fixed by H, C and the row's entries alone, never by where in the grid the
 // row lands.  -ffp-contract=off.
+//
+// Attention dropout (the *_drop_kernel instances; every (S, VEC, SMALL) form exists with and without): egc_gat_dev.h's mask m'
+// (scale or 0 per entry and head, the self entry included).  out_i = sum_j m'_ij alpha_ij xl_j with alpha and lse those of the
+// unmasked row; D_i = g_i . out_i as before;  d s_ij = w_ij (m'_ij g_i . xl_j - D_i).
+//   destination pass   v_i = sum_j w_ij m'_ij xl_j,  t_i = sum_j w_ij (unmasked),  d a_dst = g_i . v_i - D_i t_i
+//   source pass        d xl_j = sum_i m'_ij alpha_ij g_i,  d a_src[j] = sum_i w_ij (m'_ij g_i . xl_j - D_i); the forward position
+//                      of a transposed entry (the mask's counter) is t_edge_id's, one more 4-byte read per entry of this pass
+// Order rule: every sum above keeps its order.  Forward: egc_gat_dev.h's (dropped terms left out of acc, scale once at the row's
+// end).  Backward: the term of an entry is (w m') xl_j, (alpha m') g_i and w (m' (g_i . xl_j) - D_i), m' applied where written;
+// at scale = 1 and nothing dropped these are the bits of the plain kernels.  A batch's Philox calls follow its gathers in
+// program order (integer work under the loads' latency).
 #include "egc_gat_dev.h"
 
 namespace egc {
@@ -101,9 +112,9 @@ __device__ inline void gat1_batch_rows(int (&j)[N], bool (&live)[N], const Gat1W
 
 // ---------------------------------------------------------------------------------------------------------------- forward
 
-template <int S, bool VEC, bool SMALL, int N, bool FULL>
+template <int S, bool VEC, bool SMALL, int N, bool FULL, class... Mask>
 __device__ inline void gat1_fwd_batch(GatState<S>& st, const Gat1Walk& W, const GatLane<S>& L, const f4 (&ad)[S], int64_t p,
-                                      int64_t p1, int64_t row, bool self) {
+                                      int64_t p1, int64_t row, bool self, const Mask&... mask) {
   int j[N];
   bool live[N];
   gat1_batch_rows<N, FULL>(j, live, W, p, p1, row, self);
@@ -117,84 +128,31 @@ __device__ inline void gat1_fwd_batch(GatState<S>& st, const Gat1Walk& W, const 
   for (int k = 0; k < N; ++k)
 #pragma unroll
     for (int s = 0; s < S; ++s) e[k][s] = gat1_lrelu(e[k][s] + ad[s], W.slope);
-  gat_state_take<S, N>(st, e, v, live);
+  if constexpr (sizeof...(Mask) == 1) {
+    uint32_t keep[N];
+    gat_batch_keep<S, N, FULL>(keep, gat_only(mask...), L, p, p1, row, self);
+    gat_state_take<S, N>(st, e, v, live, keep);
+  } else {
+    gat_state_take<S, N>(st, e, v, live);
+  }
 }
 
-template <int S, bool VEC, bool SMALL>
+template <int S, bool VEC, bool SMALL, class... Mask>
 __device__ inline void gat1_fwd_entries(GatState<S>& st, const Gat1Walk& W, const GatLane<S>& L, const f4 (&ad)[S], int64_t p0,
-                                        int64_t p1, int64_t row) {
+                                        int64_t p1, int64_t row, const Mask&... mask) {
   gat_state_init<S>(st);
   int64_t p = p0;
 #pragma unroll 1
-  for (; p + GAT_AHEAD <= p1; p += GAT_AHEAD) gat1_fwd_batch<S, VEC, SMALL, GAT_AHEAD, true>(st, W, L, ad, p, p1, row, false);
-  if (p < p1) gat1_fwd_batch<S, VEC, SMALL, GAT_AHEAD - 1, false>(st, W, L, ad, p, p1, row, false);
-}
-
-// workspace: per slot and virtual lane three f4: m, l, acc
-template <int S, bool VEC, bool SMALL>
-__global__ void __launch_bounds__(256) gat1_fwd_chunks_kernel(const Gat1Walk W, int64_t slots, float* __restrict__ ws) {
-  int64_t g, row, s0, s1;
-  int c;
-  group_lane(W.G, g, c);
-  if (g >= slots) return;
-  const GatLane<S> L = gat_lane<S>(W, c / 4);
-  if (!slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, s0, s1)) return;
-  f4 ad[S];
-  gat1_heads<S, SMALL>(ad, W.a_dst, row, W.ld_ad, L);
-  GatState<S> st;
-  gat1_fwd_entries<S, VEC, SMALL>(st, W, L, ad, s0, s1, row);
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    f4* o = reinterpret_cast<f4*>(ws) + (g * W.V + L.v[s]) * 3;
-    o[0] = st.m[s], o[1] = st.l[s], o[2] = st.acc[s];
-  }
-}
-
-template <int S, bool VEC, bool SMALL>
-__global__ void __launch_bounds__(256) gat1_fwd_rows_kernel(const Gat1Walk W, float* __restrict__ out, int ld_out,
-                                                            float* __restrict__ lse, const float* __restrict__ ws) {
-  int64_t row, p0, p1;
-  int c;
-  group_lane(W.G, row, c);
-  if (row >= W.n_rows) return;
-  const GatLane<S> L = gat_lane<S>(W, c / 4);
-  row_range(W.rowptr, W.n_edges, row, p0, p1);
-  f4 ad[S];
-  gat1_heads<S, SMALL>(ad, W.a_dst, row, W.ld_ad, L);
-  GatState<S> st;
-  gat1_fwd_entries<S, VEC, SMALL>(st, W, L, ad, p0, min(p0 + ROW_CHUNK, p1), row);
-  int64_t first, n_part;
-  row_partials(p0, p1, first, n_part);
-#pragma unroll 1
-  for (int64_t k = 0; k < n_part; ++k) {
-    f4 m2[S], l2[S], a2[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const f4* o = reinterpret_cast<const f4*>(ws) + ((first + k) * W.V + L.v[s]) * 3;
-      m2[s] = o[0], l2[s] = o[1], a2[s] = o[2];
-    }
-    gat_state_merge<S>(st, m2, l2, a2);
-  }
-  if (W.self_loops) gat1_fwd_batch<S, VEC, SMALL, 1, true>(st, W, L, ad, 0, 0, row, true);
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    f4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const bool any = st.l[s][i] > 0.f;
-      o[i] = any ? st.acc[s][i] / st.l[s][i] : 0.f;
-      if (L.head_first[s][i]) lse[row * W.H + L.hd[s][i]] = any ? st.m[s][i] + logf(st.l[s][i]) : -__builtin_inff();
-    }
-    gat_store<VEC>(out + row * ld_out + L.c[s], L.c[s], W.width, o);
-  }
+  for (; p + GAT_AHEAD <= p1; p += GAT_AHEAD) gat1_fwd_batch<S, VEC, SMALL, GAT_AHEAD, true, Mask...>(st, W, L, ad, p, p1, row, false, mask...);
+  if (p < p1) gat1_fwd_batch<S, VEC, SMALL, GAT_AHEAD - 1, false, Mask...>(st, W, L, ad, p, p1, row, false, mask...);
 }
 
 // --------------------------------------------------------------------------------------------------------------- backward
 
 // destination pass: N entries of row `row` -> v += w xl_j, t += w
-template <int S, bool VEC, bool SMALL, int N, bool FULL>
+template <int S, bool VEC, bool SMALL, int N, bool FULL, class... Mask>
 __device__ inline void gat1_dst_batch(f4 (&va)[S], f4 (&ta)[S], const Gat1Walk& W, const GatLane<S>& L, const f4 (&ad)[S],
-                                      const f4 (&lse)[S], int64_t p, int64_t p1, int64_t row, bool self) {
+                                      const f4 (&lse)[S], int64_t p, int64_t p1, int64_t row, bool self, const Mask&... mask) {
   int j[N];
   bool live[N];
   gat1_batch_rows<N, FULL>(j, live, W, p, p1, row, self);
@@ -204,86 +162,35 @@ __device__ inline void gat1_dst_batch(f4 (&va)[S], f4 (&ta)[S], const Gat1Walk& 
     gat_load_row<S, VEC>(v[k], W.xl, j[k], W.ld_xl, L, W.width);
     gat1_heads<S, SMALL>(as[k], W.a_src, j[k], W.ld_as, L);
   }
+  uint32_t keep[N] = {};
+  if constexpr (sizeof...(Mask) == 1) gat_batch_keep<S, N, FULL>(keep, gat_only(mask...), L, p, p1, row, self);
 #pragma unroll
-  for (int k = 0; k < N; ++k)
+  for (int k = 0; k < N; ++k) {
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       const f4 z = as[k][s] + ad[s];
       f4 w = gat_exp(gat1_lrelu(z, W.slope) - lse[s]) * gat1_dlrelu(z, W.slope);
 #pragma unroll
       for (int i = 0; i < 4; ++i) w[i] = live[k] ? w[i] : 0.f;
-      va[s] = va[s] + w * v[k][s];
+      if constexpr (sizeof...(Mask) == 1) va[s] = va[s] + (w * gat_keep_f4(keep[k], s, gat_only(mask...).scale)) * v[k][s];
+      else va[s] = va[s] + w * v[k][s];
       ta[s] = ta[s] + w;
     }
-}
-
-// CHUNKS: group = slot, the chunk's (v, t) into ws; else group = row: chunk 0, the partials, the self entry; then D into D_out
-// and, when wanted, d a_dst.  Workspace: per slot and virtual lane two f4: v, t.
-template <int S, bool VEC, bool SMALL, bool CHUNKS>
-__global__ void __launch_bounds__(256) gat1_bwd_dst_kernel(const Gat1Walk W, float* __restrict__ d_ad, int ld_d_ad,
-                                                           float* __restrict__ D_out, int64_t slots, float* __restrict__ ws) {
-  int64_t g;
-  int c;
-  group_lane(W.G, g, c);
-  const GatLane<S> L = gat_lane<S>(W, c / 4);
-  int64_t row = g, p0 = 0, p1 = 0;
-  if (CHUNKS) {
-    if (g >= slots || !slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, p0, p1)) return;
-  } else {
-    if (g >= W.n_rows) return;
-    row_range(W.rowptr, W.n_edges, row, p0, p1);
   }
-  f4 ad[S], lse[S], va[S], ta[S];
-  gat1_heads<S, SMALL>(ad, W.a_dst, row, W.ld_ad, L);
-  gat1_heads<S, SMALL>(lse, W.lse, row, W.H, L);
-#pragma unroll
-  for (int s = 0; s < S; ++s) va[s] = f4{0.f, 0.f, 0.f, 0.f}, ta[s] = va[s];
-  const int64_t e1 = CHUNKS ? p1 : min(p0 + ROW_CHUNK, p1);
-  int64_t p = p0;
-#pragma unroll 1
-  for (; p + GAT1_AHEAD_DST <= e1; p += GAT1_AHEAD_DST) gat1_dst_batch<S, VEC, SMALL, GAT1_AHEAD_DST, true>(va, ta, W, L, ad, lse, p, e1, row, false);
-  if (p < e1) gat1_dst_batch<S, VEC, SMALL, GAT1_AHEAD_DST - 1, false>(va, ta, W, L, ad, lse, p, e1, row, false);
-  if (CHUNKS) {
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      f4* o = reinterpret_cast<f4*>(ws) + (g * W.V + L.v[s]) * 2;
-      o[0] = va[s], o[1] = ta[s];
-    }
-    return;
-  }
-  int64_t first, n_part;
-  row_partials(p0, p1, first, n_part);
-#pragma unroll 1
-  for (int64_t k = 0; k < n_part; ++k)
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const f4* o = reinterpret_cast<const f4*>(ws) + ((first + k) * W.V + L.v[s]) * 2;
-      va[s] = va[s] + o[0], ta[s] = ta[s] + o[1];
-    }
-  if (W.self_loops) gat1_dst_batch<S, VEC, SMALL, 1, true>(va, ta, W, L, ad, lse, 0, 0, row, true);
-  f4 gr[S], o[S], u[S], D[S], P[S];
-  gat_load_row<S, VEC>(gr, W.g, row, W.ld_g, L, W.width);
-  gat_load_row<S, VEC>(o, W.out, row, W.ld_out, L, W.width);
-#pragma unroll
-  for (int s = 0; s < S; ++s) u[s] = gr[s] * o[s];
-  gat_head_sums<S, SMALL>(W, L, u, D);
-  gat1_store_heads<S>(D_out, row, W.H, L, D);
-  if (d_ad == nullptr) return;
-#pragma unroll
-  for (int s = 0; s < S; ++s) u[s] = gr[s] * va[s];
-  gat_head_sums<S, SMALL>(W, L, u, P);
-#pragma unroll
-  for (int s = 0; s < S; ++s) P[s] = P[s] - D[s] * ta[s];
-  gat1_store_heads<S>(d_ad, row, ld_d_ad, L, P);
 }
 
 // source pass: N entries (destinations i) of transposed row `row` (= source j) -> d xl += alpha g_i, d a_src += w (g_i . xl_j - D_i)
-template <int S, bool VEC, bool SMALL, int N, bool FULL>
+template <int S, bool VEC, bool SMALL, int N, bool FULL, class... Mask>
 __device__ inline void gat1_src_batch(f4 (&dx)[S], f4 (&sa)[S], const Gat1Walk& W, const GatLane<S>& L, const f4 (&as)[S],
-                                      const f4 (&xl)[S], bool want_das, int64_t p, int64_t p1, int64_t row, bool self) {
+                                      const f4 (&xl)[S], bool want_das, int64_t p, int64_t p1, int64_t row, bool self, const Mask&... mask) {
   int i_[N];
   bool live[N];
   gat1_batch_rows<N, FULL>(i_, live, W, p, p1, row, self);
+  uint32_t pos[N];   // DROP: the entry's forward position (the self entry: its row)
+  if constexpr (sizeof...(Mask) == 1) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) pos[k] = self ? (uint32_t)row : (uint32_t)gat_only(mask...).edge_id[batch_entry<FULL>(p, k, p1)];
+  }
   f4 gr[N][S], ad[N][S], lse[N][S], D[N][S];
 #pragma unroll
   for (int k = 0; k < N; ++k) {
@@ -292,6 +199,8 @@ __device__ inline void gat1_src_batch(f4 (&dx)[S], f4 (&sa)[S], const Gat1Walk& 
     gat1_heads<S, SMALL>(lse[k], W.lse, i_[k], W.H, L);
     gat1_heads<S, SMALL>(D[k], W.D, i_[k], W.H, L);
   }
+  uint32_t keep[N] = {};
+  if constexpr (sizeof...(Mask) == 1) gat_batch_keep_at<S, N>(keep, gat_only(mask...), L, pos, self);
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     f4 u[S], da[S];
@@ -310,64 +219,45 @@ __device__ inline void gat1_src_batch(f4 (&dx)[S], f4 (&sa)[S], const Gat1Walk& 
 #pragma unroll
       for (int i = 0; i < 4; ++i) alpha[i] = live[k] ? alpha[i] : 0.f;
       const f4 w = alpha * gat1_dlrelu(z, W.slope);
-      dx[s] = dx[s] + alpha * gr[k][s];
-      sa[s] = sa[s] + w * (da[s] - D[k][s]);
+      if constexpr (sizeof...(Mask) == 1) {
+        const f4 mk = gat_keep_f4(keep[k], s, gat_only(mask...).scale);
+        dx[s] = dx[s] + (alpha * mk) * gr[k][s];
+        sa[s] = sa[s] + w * (mk * da[s] - D[k][s]);
+      } else {
+        dx[s] = dx[s] + alpha * gr[k][s];
+        sa[s] = sa[s] + w * (da[s] - D[k][s]);
+      }
     }
   }
 }
 
-// workspace: per slot and virtual lane two f4: d xl, d a_src (the head's value in every column of the head)
-template <int S, bool VEC, bool SMALL, bool CHUNKS>
-__global__ void __launch_bounds__(256) gat1_bwd_src_kernel(const Gat1Walk W, float* __restrict__ dxl, int ld_dxl,
-                                                           float* __restrict__ d_as, int ld_d_as, int want_das_, int64_t slots,
-                                                           float* __restrict__ ws) {
-  int64_t g;
-  int c;
-  group_lane(W.G, g, c);
-  const GatLane<S> L = gat_lane<S>(W, c / 4);
-  const bool want_das = want_das_ != 0;
-  int64_t row = g, p0 = 0, p1 = 0;
-  if (CHUNKS) {
-    if (g >= slots || !slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, p0, p1)) return;
-  } else {
-    if (g >= W.n_rows) return;
-    row_range(W.rowptr, W.n_edges, row, p0, p1);
-  }
-  f4 as[S], xl[S], dx[S], sa[S];
-  gat1_heads<S, SMALL>(as, W.a_src, row, W.ld_as, L);
-  gat_load_row<S, VEC>(xl, W.xl, row, W.ld_xl, L, W.width);
-#pragma unroll
-  for (int s = 0; s < S; ++s) dx[s] = f4{0.f, 0.f, 0.f, 0.f}, sa[s] = dx[s];
-  const int64_t e1 = CHUNKS ? p1 : min(p0 + ROW_CHUNK, p1);
-  int64_t p = p0;
-#pragma unroll 1
-  for (; p + GAT1_AHEAD_SRC <= e1; p += GAT1_AHEAD_SRC)
-    gat1_src_batch<S, VEC, SMALL, GAT1_AHEAD_SRC, true>(dx, sa, W, L, as, xl, want_das, p, e1, row, false);
-  if (p < e1) gat1_src_batch<S, VEC, SMALL, GAT1_AHEAD_SRC - 1, false>(dx, sa, W, L, as, xl, want_das, p, e1, row, false);
-  if (CHUNKS) {
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      f4* o = reinterpret_cast<f4*>(ws) + (g * W.V + L.v[s]) * 2;
-      o[0] = dx[s], o[1] = sa[s];
-    }
-    return;
-  }
-  int64_t first, n_part;
-  row_partials(p0, p1, first, n_part);
-#pragma unroll 1
-  for (int64_t k = 0; k < n_part; ++k)
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const f4* o = reinterpret_cast<const f4*>(ws) + ((first + k) * W.V + L.v[s]) * 2;
-      dx[s] = dx[s] + o[0], sa[s] = sa[s] + o[1];
-    }
-  if (W.self_loops) gat1_src_batch<S, VEC, SMALL, 1, true>(dx, sa, W, L, as, xl, want_das, 0, 0, row, true);
-  if (dxl != nullptr) {
-#pragma unroll
-    for (int s = 0; s < S; ++s) gat_store<VEC>(dxl + row * ld_dxl + L.c[s], L.c[s], W.width, dx[s]);
-  }
-  if (d_as != nullptr) gat1_store_heads<S>(d_as, row, ld_d_as, L, sa);
-}
+// ---------------------------------------------------------------------------------------------------------------- kernels
+
+// plain: NAME_kernel, no mask argument anywhere
+#define GAT_KERNEL(name) name##_kernel
+#define GAT_DROP_PARAM
+#define GAT_DROP_SETUP
+#define GAT_MASK
+#define GAT_SCALED(x) x
+#include "egc_gat_kernels.inc"
+#undef GAT_KERNEL
+#undef GAT_DROP_PARAM
+#undef GAT_DROP_SETUP
+#undef GAT_MASK
+#undef GAT_SCALED
+
+// DROP: NAME_drop_kernel(walk, ..., GatDrop R, ...), the mask X handed on as the device functions' last argument
+#define GAT_KERNEL(name) name##_drop_kernel
+#define GAT_DROP_PARAM const GatDrop R,
+#define GAT_DROP_SETUP const GatMask X = gat_mask(R)
+#define GAT_MASK , X
+#define GAT_SCALED(x) (x) * X.scale
+#include "egc_gat_kernels.inc"
+#undef GAT_KERNEL
+#undef GAT_DROP_PARAM
+#undef GAT_DROP_SETUP
+#undef GAT_MASK
+#undef GAT_SCALED
 
 // ------------------------------------------------------------------------------------------------------------------- host
 
@@ -404,10 +294,11 @@ size_t egc_gat_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32_t
   return gat1_bwd_ws(n_rows, n_edges, heads, channels).total * sizeof(float);
 }
 
-int egc_gat_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+// drop == NULL: the plain instances; else the DROP ones with *drop
+static int gat1_forward(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
                         const float* xl, int32_t ld_xl, const float* a_src, int32_t ld_a_src, const float* a_dst, int32_t ld_a_dst,
                         int32_t heads, int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out,
-                        float* lse, void* workspace, size_t workspace_bytes, egc_stream_t stream_) {
+                        float* lse, void* workspace, size_t workspace_bytes, egc_stream_t stream_, const GatDrop* drop) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0 || n_src_rows < 0) return EGC_ERR_INVALID;
   const int32_t width = heads * channels;
@@ -432,25 +323,50 @@ int egc_gat_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_row
     unsigned blocks;
     if (grid_blocks(slots, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
 #define GAT1_FWD_CHUNKS(S_, V_, M_) gat1_fwd_chunks_kernel<S_, V_, M_><<<blocks, 256, 0, stream>>>(W, slots, ws)
-    GAT_DISPATCH(GAT1_FWD_CHUNKS);
+#define GAT1_FWD_CHUNKS_DROP(S_, V_, M_) gat1_fwd_chunks_drop_kernel<S_, V_, M_><<<blocks, 256, 0, stream>>>(W, *drop, slots, ws)
+    if (drop == nullptr) GAT_DISPATCH(GAT1_FWD_CHUNKS);
+    else GAT_DISPATCH(GAT1_FWD_CHUNKS_DROP);
 #undef GAT1_FWD_CHUNKS
+#undef GAT1_FWD_CHUNKS_DROP
     EGC_LAUNCH_CHECK("gat1_fwd_chunks_kernel");
   }
   unsigned blocks;
   if (grid_blocks(n_rows, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
 #define GAT1_FWD_ROWS(S_, V_, M_) gat1_fwd_rows_kernel<S_, V_, M_><<<blocks, 256, 0, stream>>>(W, out, ld_out, lse, ws)
-  GAT_DISPATCH(GAT1_FWD_ROWS);
+#define GAT1_FWD_ROWS_DROP(S_, V_, M_) gat1_fwd_rows_drop_kernel<S_, V_, M_><<<blocks, 256, 0, stream>>>(W, *drop, out, ld_out, lse, ws)
+  if (drop == nullptr) GAT_DISPATCH(GAT1_FWD_ROWS);
+  else GAT_DISPATCH(GAT1_FWD_ROWS_DROP);
 #undef GAT1_FWD_ROWS
+#undef GAT1_FWD_ROWS_DROP
   EGC_LAUNCH_CHECK("gat1_fwd_rows_kernel");
   return EGC_OK;
 }
 
-int egc_gat_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_rows,
+int egc_gat_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                        const float* xl, int32_t ld_xl, const float* a_src, int32_t ld_a_src, const float* a_dst, int32_t ld_a_dst,
+                        int32_t heads, int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out,
+                        float* lse, void* workspace, size_t workspace_bytes, egc_stream_t stream) {
+  return gat1_forward(rowptr, col, n_rows, n_edges, n_src_rows, xl, ld_xl, a_src, ld_a_src, a_dst, ld_a_dst, heads, channels,
+                      negative_slope, self_loops, out, ld_out, lse, workspace, workspace_bytes, stream, nullptr);
+}
+
+int egc_gat_forward_dropout_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                                const float* xl, int32_t ld_xl, const float* a_src, int32_t ld_a_src, const float* a_dst,
+                                int32_t ld_a_dst, int32_t heads, int32_t channels, float negative_slope, int32_t self_loops,
+                                float* out, int32_t ld_out, float* lse, void* workspace, size_t workspace_bytes, double p,
+                                const int64_t* seed, egc_stream_t stream) {
+  GatDrop R = {};
+  if (!gat_fill_drop(R, p, seed, nullptr)) return EGC_ERR_INVALID;
+  return gat1_forward(rowptr, col, n_rows, n_edges, n_src_rows, xl, ld_xl, a_src, ld_a_src, a_dst, ld_a_dst, heads, channels,
+                      negative_slope, self_loops, out, ld_out, lse, workspace, workspace_bytes, stream, &R);
+}
+
+static int gat1_backward(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_rows,
                          int64_t n_edges, const float* xl, int32_t ld_xl, const float* a_src, int32_t ld_a_src, const float* a_dst,
                          int32_t ld_a_dst, int32_t heads, int32_t channels, float negative_slope, int32_t self_loops,
                          const float* out, int32_t ld_out, const float* lse, const float* g, int32_t ld_g, float* dxl,
                          int32_t ld_dxl, float* d_a_src, int32_t ld_d_a_src, float* d_a_dst, int32_t ld_d_a_dst, void* workspace,
-                         size_t workspace_bytes, egc_stream_t stream_) {
+                         size_t workspace_bytes, egc_stream_t stream_, const GatDrop* drop) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0) return EGC_ERR_INVALID;
   const int32_t width = heads * channels;
@@ -482,16 +398,24 @@ int egc_gat_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_
     if (L.slots > 0 && d_a_dst != nullptr) {
 #define GAT1_DST_CHUNKS(S_, V_, M_) \
   gat1_bwd_dst_kernel<S_, V_, M_, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(W, nullptr, 0, nullptr, L.slots, ws + L.part_dst)
-      GAT_DISPATCH(GAT1_DST_CHUNKS);
+#define GAT1_DST_CHUNKS_DROP(S_, V_, M_) \
+  gat1_bwd_dst_drop_kernel<S_, V_, M_, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(W, *drop, nullptr, 0, nullptr, L.slots, ws + L.part_dst)
+      if (drop == nullptr) GAT_DISPATCH(GAT1_DST_CHUNKS);
+      else GAT_DISPATCH(GAT1_DST_CHUNKS_DROP);
 #undef GAT1_DST_CHUNKS
+#undef GAT1_DST_CHUNKS_DROP
       EGC_LAUNCH_CHECK("gat1_bwd_dst_kernel(chunks)");
     }
     Gat1Walk Wr = W;
     if (d_a_dst == nullptr) Wr.n_edges = 0, Wr.self_loops = 0;   // only D is wanted: no entries, no self entry
 #define GAT1_DST_ROWS(S_, V_, M_) \
   gat1_bwd_dst_kernel<S_, V_, M_, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(Wr, d_a_dst, ld_d_a_dst, ws + L.D, L.slots, ws + L.part_dst)
-    GAT_DISPATCH(GAT1_DST_ROWS);
+#define GAT1_DST_ROWS_DROP(S_, V_, M_) \
+  gat1_bwd_dst_drop_kernel<S_, V_, M_, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(Wr, *drop, d_a_dst, ld_d_a_dst, ws + L.D, L.slots, ws + L.part_dst)
+    if (drop == nullptr) GAT_DISPATCH(GAT1_DST_ROWS);
+    else GAT_DISPATCH(GAT1_DST_ROWS_DROP);
 #undef GAT1_DST_ROWS
+#undef GAT1_DST_ROWS_DROP
     EGC_LAUNCH_CHECK("gat1_bwd_dst_kernel(rows)");
   }
   if (src_pass) {
@@ -501,15 +425,48 @@ int egc_gat_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_
     if (L.slots > 0) {
 #define GAT1_SRC_CHUNKS(S_, V_, M_) \
   gat1_bwd_src_kernel<S_, V_, M_, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(T, nullptr, 0, nullptr, 0, want_das, L.slots, ws + L.part_src)
-      GAT_DISPATCH(GAT1_SRC_CHUNKS);
+#define GAT1_SRC_CHUNKS_DROP(S_, V_, M_) \
+  gat1_bwd_src_drop_kernel<S_, V_, M_, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(T, *drop, nullptr, 0, nullptr, 0, want_das, L.slots, ws + L.part_src)
+      if (drop == nullptr) GAT_DISPATCH(GAT1_SRC_CHUNKS);
+      else GAT_DISPATCH(GAT1_SRC_CHUNKS_DROP);
 #undef GAT1_SRC_CHUNKS
+#undef GAT1_SRC_CHUNKS_DROP
       EGC_LAUNCH_CHECK("gat1_bwd_src_kernel(chunks)");
     }
 #define GAT1_SRC_ROWS(S_, V_, M_) \
   gat1_bwd_src_kernel<S_, V_, M_, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(T, dxl, ld_dxl, d_a_src, ld_d_a_src, want_das, L.slots, ws + L.part_src)
-    GAT_DISPATCH(GAT1_SRC_ROWS);
+#define GAT1_SRC_ROWS_DROP(S_, V_, M_) \
+  gat1_bwd_src_drop_kernel<S_, V_, M_, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(T, *drop, dxl, ld_dxl, d_a_src, ld_d_a_src, want_das, L.slots, ws + L.part_src)
+    if (drop == nullptr) GAT_DISPATCH(GAT1_SRC_ROWS);
+    else GAT_DISPATCH(GAT1_SRC_ROWS_DROP);
 #undef GAT1_SRC_ROWS
+#undef GAT1_SRC_ROWS_DROP
     EGC_LAUNCH_CHECK("gat1_bwd_src_kernel(rows)");
   }
   return EGC_OK;
+}
+
+int egc_gat_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_rows,
+                         int64_t n_edges, const float* xl, int32_t ld_xl, const float* a_src, int32_t ld_a_src, const float* a_dst,
+                         int32_t ld_a_dst, int32_t heads, int32_t channels, float negative_slope, int32_t self_loops,
+                         const float* out, int32_t ld_out, const float* lse, const float* g, int32_t ld_g, float* dxl,
+                         int32_t ld_dxl, float* d_a_src, int32_t ld_d_a_src, float* d_a_dst, int32_t ld_d_a_dst, void* workspace,
+                         size_t workspace_bytes, egc_stream_t stream) {
+  return gat1_backward(rowptr, col, t_rowptr, t_col, n_rows, n_edges, xl, ld_xl, a_src, ld_a_src, a_dst, ld_a_dst, heads, channels,
+                       negative_slope, self_loops, out, ld_out, lse, g, ld_g, dxl, ld_dxl, d_a_src, ld_d_a_src, d_a_dst, ld_d_a_dst,
+                       workspace, workspace_bytes, stream, nullptr);
+}
+
+int egc_gat_backward_dropout_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col,
+                                 const int32_t* t_edge_id, int64_t n_rows, int64_t n_edges, const float* xl, int32_t ld_xl,
+                                 const float* a_src, int32_t ld_a_src, const float* a_dst, int32_t ld_a_dst, int32_t heads,
+                                 int32_t channels, float negative_slope, int32_t self_loops, const float* out, int32_t ld_out,
+                                 const float* lse, const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* d_a_src,
+                                 int32_t ld_d_a_src, float* d_a_dst, int32_t ld_d_a_dst, void* workspace, size_t workspace_bytes,
+                                 double p, const int64_t* seed, egc_stream_t stream) {
+  GatDrop R = {};
+  if (!gat_fill_drop(R, p, seed, t_edge_id) || (t_rowptr != nullptr && t_edge_id == nullptr)) return EGC_ERR_INVALID;
+  return gat1_backward(rowptr, col, t_rowptr, t_col, n_rows, n_edges, xl, ld_xl, a_src, ld_a_src, a_dst, ld_a_dst, heads, channels,
+                       negative_slope, self_loops, out, ld_out, lse, g, ld_g, dxl, ld_dxl, d_a_src, ld_d_a_src, d_a_dst, ld_d_a_dst,
+                       workspace, workspace_bytes, stream, &R);
 }

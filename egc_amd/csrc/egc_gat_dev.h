@@ -18,7 +18,19 @@
 // bm = max(m, the live scores in entry order); l = l * r + sum in entry order of exp(s_k - bm), acc likewise with
 // exp(s_k - bm) * v_k, r = exp(m - bm) (1 when m == bm); m = bm.  Two states merge as M = max(m1, m2);
 // l = l1 exp(m1 - M) + l2 exp(m2 - M), acc likewise.
+//
+// Attention dropout (the DROP instances of both files' kernels; PyG's F.dropout on alpha, per entry and head, the self entry
+// included).  The mask is a pure function of (seed, entry, head): Philox4x32-10 (egc_philox.h) under the key (low, high 32 bits
+// of the int64 seed, read on the device), counter (p, h >> 2, 0, 0) for the entry at position p of the FORWARD CSR and
+// (i, h >> 2, 1, 0) for row i's self entry; head h takes output word h & 3 and is dropped iff word < threshold
+// (= floor(p 2^32)).  A lane's quad of columns lies in at most two groups of four heads: one Philox call per slot, a second
+// one only where the quad's first and last column fall into different groups (gat_keep_bits); no lane talks to another.
+// Skipped entries keep their position.  Order rule with the mask: m, l and lse are those of the unmasked row, term for term;
+// a dropped (entry, head) leaves out its term of acc and nothing else, the kept terms stay in entry order, and the forward
+// multiplies by scale = 1 / (1 - p) ONCE, at the row's end: out = (acc / l) * scale.  The backward sums take the factor per
+// entry, m' = scale or 0 (gat_keep_f4), as a factor of the term they add, in the order they had.
 #pragma once
+#include "egc_philox.h"
 #include "egc_row_chunks.h"
 
 namespace egc {
@@ -189,6 +201,12 @@ __device__ inline void gat_load_heads(f4 (&v)[S], const float* __restrict__ a, i
 
 __device__ inline f4 gat_exp(f4 x) { return f4{expf(x[0]), expf(x[1]), expf(x[2]), expf(x[3])}; }
 
+// The DROP forms of the device functions take ONE more argument at the end (the mask's GatMask; a batch's keep bits) and the
+// plain forms none: a parameter pack that is empty or holds that one argument.  So the plain instantiations are, token for
+// token, what they were before there was a mask.  gat_only: the pack's one element.
+template <class T>
+__device__ inline const T& gat_only(const T& t) { return t; }
+
 template <int S>
 struct GatState {
   f4 m[S], l[S], acc[S];
@@ -201,9 +219,11 @@ __device__ inline void gat_state_init(GatState<S>& st) {
   for (int s = 0; s < S; ++s) st.m[s] = f4{ninf, ninf, ninf, ninf}, st.l[s] = f4{0.f, 0.f, 0.f, 0.f}, st.acc[s] = st.l[s];
 }
 
-// one batch of N entries with scores e and rows v folded into the state (file header)
-template <int S, int N>
-__device__ inline void gat_state_take(GatState<S>& st, const f4 (&e)[N][S], const f4 (&v)[N][S], const bool (&live)[N]) {
+// one batch of N entries with scores e and rows v folded into the state (file header).  With one more argument, keep[N] (DROP):
+// bit 4 s + j of keep[k] clear = entry k adds nothing to acc of column j of slot s; m and l never look at it.
+template <int S, int N, class... Keep>
+__device__ inline void gat_state_take(GatState<S>& st, const f4 (&e)[N][S], const f4 (&v)[N][S], const bool (&live)[N],
+                                      const Keep&... keep) {
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     f4 bm = st.m[s];
@@ -221,7 +241,14 @@ __device__ inline void gat_state_take(GatState<S>& st, const f4 (&e)[N][S], cons
 #pragma unroll
       for (int i = 0; i < 4; ++i) w[i] = live[k] ? w[i] : 0.f;
       l = l + w;
-      acc = acc + w * v[k][s];
+      if constexpr (sizeof...(Keep) == 0) {
+        acc = acc + w * v[k][s];
+      } else {
+        const uint32_t bits = gat_only(keep...)[k];
+        const f4 t = acc + w * v[k][s];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = (bits >> (4 * s + i)) & 1u ? t[i] : acc[i];
+      }
     }
     st.m[s] = bm, st.l[s] = l, st.acc[s] = acc;
   }
@@ -241,6 +268,93 @@ __device__ inline void gat_state_merge(GatState<S>& st, const f4 (&m2)[S], const
     st.acc[s] = st.acc[s] * r1 + acc2[s] * r2;
     st.m[s] = bm;
   }
+}
+
+// ------------------------------------------------------------------------------------------------------ attention dropout
+
+struct GatDrop {
+  const int64_t* seed;      // device scalar: the Philox key
+  const int32_t* edge_id;   // source pass: the forward position of every entry of the transposed CSR
+  uint32_t threshold;       // dropped iff word < threshold
+  float scale;              // 1 / (1 - p)
+};
+
+// what the kernels hold of it: the key read, the rest copied
+struct GatMask {
+  uint32_t k0, k1, threshold;
+  float scale;
+  const int32_t* edge_id;
+};
+
+__device__ inline GatMask gat_mask(const GatDrop& R) {
+  const uint64_t s = (uint64_t)*R.seed;
+  return GatMask{(uint32_t)s, (uint32_t)(s >> 32), R.threshold, R.scale, R.edge_id};
+}
+
+// Bit 4 s + j: column c[s] + j of this lane keeps the entry of counter (c0, ., c2, 0) -- c0 = the entry's forward position and
+// c2 = 0, or c0 = the row and c2 = 1 for the self entry.  The heads of a quad span at most two groups of four (file header).
+template <int S>
+__device__ inline uint32_t gat_keep_bits(const GatMask& X, const GatLane<S>& L, uint32_t c0, uint32_t c2) {
+  uint32_t bits = 0;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int g0 = L.hd[s][0] >> 2, g1 = L.hd[s][3] >> 2;
+    uint32_t w0[4], w1[4];
+    philox4x32_10(c0, (uint32_t)g0, c2, 0u, X.k0, X.k1, w0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w1[i] = w0[i];
+    if (g1 != g0) philox4x32_10(c0, (uint32_t)g1, c2, 0u, X.k0, X.k1, w1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int h = L.hd[s][j], i = h & 3;
+      const bool first = (h >> 2) == g0;
+      const uint32_t a = i == 0 ? w0[0] : i == 1 ? w0[1] : i == 2 ? w0[2] : w0[3];
+      const uint32_t b = i == 0 ? w1[0] : i == 1 ? w1[1] : i == 2 ? w1[2] : w1[3];
+      bits |= ((first ? a : b) >= X.threshold ? 1u : 0u) << (4 * s + j);
+    }
+  }
+  return bits;
+}
+
+// keep[k] = gat_keep_bits of entry k of the batch that starts at forward position p (self: the self entry of `row`), one entry
+// after the other in a loop that is NOT unrolled: unrolled, the N independent Philox chains hold their registers at once
+// (60 to 90 VGPRs more than the plain instance, a wave per SIMD less), and the integer work is not what the kernel waits for.
+template <int S, int N, bool FULL>
+__device__ inline void gat_batch_keep(uint32_t (&keep)[N], const GatMask& X, const GatLane<S>& L, int64_t p, int64_t p1, int64_t row,
+                                      bool self) {
+  static_assert(8 * N <= 64 && S <= 2, "eight bits per entry in one 64-bit word");
+  uint64_t packed = 0;
+#pragma unroll 1
+  for (int k = 0; k < N; ++k) {
+    const uint32_t c0 = (uint32_t)(self ? row : batch_entry<FULL>(p, k, p1));
+    packed |= (uint64_t)gat_keep_bits<S>(X, L, c0, self ? 1u : 0u) << (8 * k);
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) keep[k] = (uint32_t)(packed >> (8 * k)) & 0xffu;
+}
+
+// the same for entries whose counters are pos[k] (the source pass: forward positions read from t_edge_id; self: c2 = 1)
+template <int S, int N>
+__device__ inline void gat_batch_keep_at(uint32_t (&keep)[N], const GatMask& X, const GatLane<S>& L, const uint32_t (&pos)[N], bool self) {
+  static_assert(8 * N <= 64 && S <= 2, "eight bits per entry in one 64-bit word");
+  uint64_t packed = 0;
+#pragma unroll 1
+  for (int k = 0; k < N; ++k) {
+    uint32_t c0 = pos[0];
+#pragma unroll
+    for (int i = 1; i < N; ++i) c0 = k == i ? pos[i] : c0;
+    packed |= (uint64_t)gat_keep_bits<S>(X, L, c0, self ? 1u : 0u) << (8 * k);
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) keep[k] = (uint32_t)(packed >> (8 * k)) & 0xffu;
+}
+
+// m' of slot s: scale where kept, 0 where dropped
+__device__ inline f4 gat_keep_f4(uint32_t bits, int s, float scale) {
+  f4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = (bits >> (4 * s + i)) & 1u ? scale : 0.f;
+  return r;
 }
 
 // ------------------------------------------------------------------------------------------------------------------- host
@@ -267,6 +381,15 @@ static inline bool gat_shape_ok(int32_t H, int32_t C) { return H >= 1 && C >= 1 
 static void gat_fill_walk(GatWalk& W, int32_t H, int32_t C, float slope, int32_t self_loops) {
   const GatGeom q = gat_geom(H * C);
   W.H = H, W.C = C, W.width = H * C, W.G = q.G, W.V = q.V, W.seg = (C + 3) / 4 + 1, W.self_loops = self_loops, W.slope = slope;
+}
+
+// p in (0, 1) and a seed: threshold = floor(p 2^32) and scale = 1 / (1 - p), both from p in double
+static inline bool gat_fill_drop(GatDrop& R, double p, const int64_t* seed, const int32_t* edge_id) {
+  if (!(p > 0.0 && p < 1.0) || seed == nullptr) return false;
+  R.seed = seed, R.edge_id = edge_id;
+  R.threshold = (uint32_t)(uint64_t)(p * 4294967296.0);
+  R.scale = (float)(1.0 / (1.0 - p));
+  return true;
 }
 
 #define GAT_DISPATCH(LAUNCH)                                   \

@@ -34,6 +34,15 @@
 // with those of chunks 1, 2, ... added in ascending order, the self entry last.  d att: a lane's sum over its row (entry order,
 // chunk by chunk), the workgroup's groups added in ascending order, the workgroups' partials (row workgroups, then chunk
 // workgroups) added in ascending order in blocks of 64, and those block sums again, until one is left.  -ffp-contract=off.
+//
+// Attention dropout (the *_drop_kernel instances; every (S, VEC, SMALL) form exists with and without): egc_gat_dev.h's mask m'
+// (scale or 0 per entry and head, the self entry included).  out_i = sum_j m'_ij alpha_ij xl_j with alpha and lse those of the
+// unmasked row; D_i = g_i . out_i as before; d s = alpha (m' g_i . xl_j - D_i) in d xr, d att and d xl's chain part, and
+// (alpha m') g_i for d xl's direct term.  The source pass reads the forward position of a transposed entry (the mask's counter)
+// from t_edge_id: one more 4-byte read per entry of that pass.  Order rule: every sum above keeps its order; forward:
+// egc_gat_dev.h's (dropped terms left out of acc, scale once at the row's end); backward: m' is a factor of the entry's term
+// where written, so at scale = 1 and nothing dropped the bits are those of the plain kernels.  A batch's Philox calls follow its
+// gathers in program order.
 #include "egc_gat_dev.h"
 
 namespace egc {
@@ -58,9 +67,9 @@ struct GatV2Score {
 
 // ---------------------------------------------------------------------------------------------------------------- forward
 
-template <int S, bool VEC, bool SMALL, class Score, bool FULL>
+template <int S, bool VEC, bool SMALL, class Score, bool FULL, class... Mask>
 __device__ inline void gat_fwd_batch(GatState<S>& st, const GatWalk& W, const GatLane<S>& L, const Score& sc, const f4 (&xr)[S],
-                                     const f4 (&att)[S], int64_t p, int64_t p1, int64_t row) {
+                                     const f4 (&att)[S], int64_t p, int64_t p1, int64_t row, const Mask&... mask) {
   constexpr int N = FULL ? GAT_AHEAD : GAT_AHEAD - 1;
   const int last_in = (int)W.n_in_rows - 1;
   int j[N];
@@ -81,95 +90,32 @@ __device__ inline void gat_fwd_batch(GatState<S>& st, const GatWalk& W, const Ga
     for (int s = 0; s < S; ++s) t[s] = att[s] * sc.act(v[k][s] + xr[s]);
     gat_head_sums<S, SMALL>(W, L, t, e[k]);
   }
-  gat_state_take<S, N>(st, e, v, live);
+  if constexpr (sizeof...(Mask) == 1) {
+    uint32_t keep[N];
+    gat_batch_keep<S, N, FULL>(keep, gat_only(mask...), L, p, p1, row, false);
+    gat_state_take<S, N>(st, e, v, live, keep);
+  } else {
+    gat_state_take<S, N>(st, e, v, live);
+  }
 }
 
-template <int S, bool VEC, bool SMALL, class Score>
+template <int S, bool VEC, bool SMALL, class Score, class... Mask>
 __device__ inline void gat_fwd_entries(GatState<S>& st, const GatWalk& W, const GatLane<S>& L, const Score& sc, const f4 (&xr)[S],
-                                       const f4 (&att)[S], int64_t p0, int64_t p1, int64_t row) {
+                                       const f4 (&att)[S], int64_t p0, int64_t p1, int64_t row, const Mask&... mask) {
   gat_state_init<S>(st);
   int64_t p = p0;
 #pragma unroll 1
-  for (; p + GAT_AHEAD <= p1; p += GAT_AHEAD) gat_fwd_batch<S, VEC, SMALL, Score, true>(st, W, L, sc, xr, att, p, p1, row);
-  if (p < p1) gat_fwd_batch<S, VEC, SMALL, Score, false>(st, W, L, sc, xr, att, p, p1, row);
-}
-
-// workspace: per slot and virtual lane three f4: m, l, acc
-template <int S, bool VEC, bool SMALL, class Score>
-__global__ void __launch_bounds__(256) gat_fwd_chunks_kernel(const GatWalk W, const Score sc, int64_t slots, float* __restrict__ ws) {
-  int64_t g, row, s0, s1;
-  int c;
-  group_lane(W.G, g, c);
-  if (g >= slots) return;
-  const GatLane<S> L = gat_lane<S>(W, c / 4);
-  if (!slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, s0, s1)) return;
-  f4 xr[S], att[S];
-  gat_load_row<S, VEC>(xr, W.xr, row, W.ld_xr, L, W.width);
-  gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
-  GatState<S> st;
-  gat_fwd_entries<S, VEC, SMALL, Score>(st, W, L, sc, xr, att, s0, s1, row);
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    f4* o = reinterpret_cast<f4*>(ws) + (g * W.V + L.v[s]) * 3;
-    o[0] = st.m[s], o[1] = st.l[s], o[2] = st.acc[s];
-  }
-}
-
-template <int S, bool VEC, bool SMALL, class Score>
-__global__ void __launch_bounds__(256) gat_fwd_rows_kernel(const GatWalk W, const Score sc, float* __restrict__ out, int ld_out,
-                                                           float* __restrict__ lse, int64_t slots, const float* __restrict__ ws) {
-  int64_t row, p0, p1;
-  int c;
-  group_lane(W.G, row, c);
-  if (row >= W.n_rows) return;
-  const GatLane<S> L = gat_lane<S>(W, c / 4);
-  row_range(W.rowptr, W.n_edges, row, p0, p1);
-  f4 xr[S], att[S];
-  gat_load_row<S, VEC>(xr, W.xr, row, W.ld_xr, L, W.width);
-  gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
-  GatState<S> st;
-  gat_fwd_entries<S, VEC, SMALL, Score>(st, W, L, sc, xr, att, p0, min(p0 + ROW_CHUNK, p1), row);
-  int64_t first, n_part;
-  row_partials(p0, p1, first, n_part);
-#pragma unroll 1
-  for (int64_t k = 0; k < n_part; ++k) {
-    f4 m2[S], l2[S], a2[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const f4* o = reinterpret_cast<const f4*>(ws) + ((first + k) * W.V + L.v[s]) * 3;
-      m2[s] = o[0], l2[s] = o[1], a2[s] = o[2];
-    }
-    gat_state_merge<S>(st, m2, l2, a2);
-  }
-  if (W.self_loops) {
-    f4 v[1][S], e[1][S], tt[S];
-    const bool live[1] = {true};
-    gat_load_row<S, VEC>(v[0], W.xl, min(row, W.n_in_rows - 1), W.ld_xl, L, W.width);
-#pragma unroll
-    for (int s = 0; s < S; ++s) tt[s] = att[s] * sc.act(v[0][s] + xr[s]);
-    gat_head_sums<S, SMALL>(W, L, tt, e[0]);
-    gat_state_take<S, 1>(st, e, v, live);
-  }
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    f4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const bool any = st.l[s][i] > 0.f;
-      o[i] = any ? st.acc[s][i] / st.l[s][i] : 0.f;
-      if (L.head_first[s][i]) lse[row * W.H + L.hd[s][i]] = any ? st.m[s][i] + logf(st.l[s][i]) : -__builtin_inff();
-    }
-    gat_store<VEC>(out + row * ld_out + L.c[s], L.c[s], W.width, o);
-  }
+  for (; p + GAT_AHEAD <= p1; p += GAT_AHEAD) gat_fwd_batch<S, VEC, SMALL, Score, true, Mask...>(st, W, L, sc, xr, att, p, p1, row, mask...);
+  if (p < p1) gat_fwd_batch<S, VEC, SMALL, Score, false, Mask...>(st, W, L, sc, xr, att, p, p1, row, mask...);
 }
 
 // --------------------------------------------------------------------------------------------------------------- backward
 
 // destination pass: N entries of row `row` -> d xr and d att partial sums
-template <int S, bool VEC, bool SMALL, class Score, int N, bool FULL>
+template <int S, bool VEC, bool SMALL, class Score, int N, bool FULL, class... Mask>
 __device__ inline void gat_dst_batch(f4 (&dxr)[S], f4 (&datt)[S], const GatWalk& W, const GatLane<S>& L, const Score& sc,
                                      const f4 (&xr)[S], const f4 (&att)[S], const f4 (&g)[S], const f4 (&lse)[S], const f4 (&D)[S],
-                                     int64_t p, int64_t p1, int64_t row, bool self) {
+                                     int64_t p, int64_t p1, int64_t row, bool self, const Mask&... mask) {
   const int last_in = (int)W.n_in_rows - 1;
   int j[N];
   bool live[N];
@@ -182,6 +128,8 @@ __device__ inline void gat_dst_batch(f4 (&dxr)[S], f4 (&datt)[S], const GatWalk&
   f4 v[N][S];
 #pragma unroll
   for (int k = 0; k < N; ++k) gat_load_row<S, VEC>(v[k], W.xl, j[k], W.ld_xl, L, W.width);
+  uint32_t keep[N] = {};
+  if constexpr (sizeof...(Mask) == 1) gat_batch_keep<S, N, FULL>(keep, gat_only(mask...), L, p, p1, row, self);
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     f4 z[S], lz[S], t[S], u[S], e[S], da[S];
@@ -194,6 +142,7 @@ __device__ inline void gat_dst_batch(f4 (&dxr)[S], f4 (&datt)[S], const GatWalk&
       f4 alpha = gat_exp(e[s] - lse[s]);
 #pragma unroll
       for (int i = 0; i < 4; ++i) alpha[i] = live[k] ? alpha[i] : 0.f;
+      if constexpr (sizeof...(Mask) == 1) da[s] = gat_keep_f4(keep[k], s, gat_only(mask...).scale) * da[s];
       const f4 ds = alpha * (da[s] - D[s]);
       dxr[s] = dxr[s] + ds * att[s] * sc.dact(z[s]);
       datt[s] = datt[s] + ds * lz[s];
@@ -217,72 +166,10 @@ __device__ inline void gat_block_datt(const f4 (&datt)[S], const GatWalk& W, con
   }
 }
 
-// CHUNKS: group = slot, the chunk's d xr sum into ws_xr; else group = row: chunk 0, the partials, the self entry; d xr and D
-// stored.  Both: the workgroup's d att partial (part == NULL: not wanted).  No thread leaves before the barrier.
-template <int S, bool VEC, bool SMALL, class Score, bool CHUNKS>
-__global__ void __launch_bounds__(256) gat_bwd_dst_kernel(const GatWalk W, const Score sc, float* __restrict__ dxr_out, int ld_dxr,
-                                                          float* __restrict__ D_out, int64_t slots, float* __restrict__ ws_xr,
-                                                          float* __restrict__ part) {
-  int64_t g;
-  int c;
-  group_lane(W.G, g, c);
-  const GatLane<S> L = gat_lane<S>(W, c / 4);
-  int64_t row = g, p0 = 0, p1 = 0;
-  bool active;
-  if (CHUNKS) {
-    active = g < slots && slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, p0, p1);
-  } else {
-    active = g < W.n_rows;
-    if (active) {
-      row_range(W.rowptr, W.n_edges, row, p0, p1);
-    }
-  }
-  f4 dxr[S], datt[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) dxr[s] = f4{0.f, 0.f, 0.f, 0.f}, datt[s] = dxr[s];
-  if (active) {
-    f4 xr[S], att[S], gr[S], o[S], lse[S], D[S], u[S];
-    gat_load_row<S, VEC>(xr, W.xr, row, W.ld_xr, L, W.width);
-    gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
-    gat_load_row<S, VEC>(gr, W.g, row, W.ld_g, L, W.width);
-    gat_load_row<S, VEC>(o, W.out, row, W.ld_out, L, W.width);
-    gat_load_heads<S>(lse, W.lse, row, W, L);
-#pragma unroll
-    for (int s = 0; s < S; ++s) u[s] = gr[s] * o[s];
-    gat_head_sums<S, SMALL>(W, L, u, D);
-    const int64_t e1 = CHUNKS ? p1 : min(p0 + ROW_CHUNK, p1);
-    int64_t p = p0;
-#pragma unroll 1
-    for (; p + GAT_AHEAD_BWD <= e1; p += GAT_AHEAD_BWD)
-      gat_dst_batch<S, VEC, SMALL, Score, GAT_AHEAD_BWD, true>(dxr, datt, W, L, sc, xr, att, gr, lse, D, p, e1, row, false);
-    if (p < e1) gat_dst_batch<S, VEC, SMALL, Score, GAT_AHEAD_BWD - 1, false>(dxr, datt, W, L, sc, xr, att, gr, lse, D, p, e1, row, false);
-    if (CHUNKS) {
-#pragma unroll
-      for (int s = 0; s < S; ++s) *reinterpret_cast<f4*>(ws_xr + (g * W.V + L.v[s]) * 4) = dxr[s];
-    } else {
-      int64_t first, n_part;
-      row_partials(p0, p1, first, n_part);
-#pragma unroll 1
-      for (int64_t k = 0; k < n_part; ++k)
-#pragma unroll
-        for (int s = 0; s < S; ++s) dxr[s] = dxr[s] + *reinterpret_cast<const f4*>(ws_xr + ((first + k) * W.V + L.v[s]) * 4);
-      if (W.self_loops) gat_dst_batch<S, VEC, SMALL, Score, 1, true>(dxr, datt, W, L, sc, xr, att, gr, lse, D, 0, 0, row, true);
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        if (dxr_out != nullptr) gat_store<VEC>(dxr_out + row * ld_dxr + L.c[s], L.c[s], W.width, dxr[s]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (L.head_first[s][i]) D_out[row * W.H + L.hd[s][i]] = D[s][i];
-      }
-    }
-  }
-  if (part != nullptr) gat_block_datt<S>(datt, W, L, part);
-}
-
 // source pass: N entries (destinations i) of transposed row `row` (= source j) -> d xl partial sum
-template <int S, bool VEC, bool SMALL, class Score, int N, bool FULL>
+template <int S, bool VEC, bool SMALL, class Score, int N, bool FULL, class... Mask>
 __device__ inline void gat_src_batch(f4 (&acc)[S], const GatWalk& W, const GatLane<S>& L, const Score& sc, const f4 (&xl)[S],
-                                     const f4 (&att)[S], int64_t p, int64_t p1, int64_t row, bool self) {
+                                     const f4 (&att)[S], int64_t p, int64_t p1, int64_t row, bool self, const Mask&... mask) {
   const int last_in = (int)W.n_in_rows - 1;
   int i_[N];
   bool live[N];
@@ -291,6 +178,11 @@ __device__ inline void gat_src_batch(f4 (&acc)[S], const GatWalk& W, const GatLa
     const int raw = self ? (int)row : W.col[batch_entry<FULL>(p, k, p1)];
     i_[k] = clamp_index(raw, last_in);
     live[k] = self || ((FULL || p + k < p1) && !(W.self_loops && raw == (int)row));
+  }
+  uint32_t pos[N];   // DROP: the entry's forward position (the self entry: its row)
+  if constexpr (sizeof...(Mask) == 1) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) pos[k] = self ? (uint32_t)row : (uint32_t)gat_only(mask...).edge_id[batch_entry<FULL>(p, k, p1)];
   }
   f4 xr[N][S], gr[N][S], lse[N][S], D[N][S];
 #pragma unroll
@@ -303,6 +195,8 @@ __device__ inline void gat_src_batch(f4 (&acc)[S], const GatWalk& W, const GatLa
     gat_load_heads<S>(lse[k], W.lse, i_[k], W, L);
     gat_load_heads<S>(D[k], W.D, i_[k], W, L);
   }
+  uint32_t keep[N] = {};
+  if constexpr (sizeof...(Mask) == 1) gat_batch_keep_at<S, N>(keep, gat_only(mask...), L, pos, self);
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     f4 z[S], t[S], u[S], e[S], da[S];
@@ -315,51 +209,16 @@ __device__ inline void gat_src_batch(f4 (&acc)[S], const GatWalk& W, const GatLa
       f4 alpha = gat_exp(e[s] - lse[k][s]);
 #pragma unroll
       for (int i = 0; i < 4; ++i) alpha[i] = live[k] ? alpha[i] : 0.f;
-      const f4 ds = alpha * (da[s] - D[k][s]);
-      acc[s] = acc[s] + (alpha * gr[k][s] + ds * att[s] * sc.dact(z[s]));
+      if constexpr (sizeof...(Mask) == 1) {
+        const f4 mk = gat_keep_f4(keep[k], s, gat_only(mask...).scale);
+        const f4 ds = alpha * (mk * da[s] - D[k][s]);
+        acc[s] = acc[s] + ((alpha * mk) * gr[k][s] + ds * att[s] * sc.dact(z[s]));
+      } else {
+        const f4 ds = alpha * (da[s] - D[k][s]);
+        acc[s] = acc[s] + (alpha * gr[k][s] + ds * att[s] * sc.dact(z[s]));
+      }
     }
   }
-}
-
-template <int S, bool VEC, bool SMALL, class Score, bool CHUNKS>
-__global__ void __launch_bounds__(256) gat_bwd_src_kernel(const GatWalk W, const Score sc, float* __restrict__ dxl, int ld_dxl,
-                                                          int64_t slots, float* __restrict__ ws) {
-  int64_t g;
-  int c;
-  group_lane(W.G, g, c);
-  const GatLane<S> L = gat_lane<S>(W, c / 4);
-  int64_t row = g, p0 = 0, p1 = 0;
-  if (CHUNKS) {
-    if (g >= slots || !slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, p0, p1)) return;
-  } else {
-    if (g >= W.n_rows) return;
-    row_range(W.rowptr, W.n_edges, row, p0, p1);
-  }
-  f4 xl[S], att[S], acc[S];
-  gat_load_row<S, VEC>(xl, W.xl, row, W.ld_xl, L, W.width);
-  gat_load_row<S, false>(att, W.att, 0, 0, L, W.width);
-#pragma unroll
-  for (int s = 0; s < S; ++s) acc[s] = f4{0.f, 0.f, 0.f, 0.f};
-  const int64_t e1 = CHUNKS ? p1 : min(p0 + ROW_CHUNK, p1);
-  int64_t p = p0;
-#pragma unroll 1
-  for (; p + GAT_AHEAD_BWD <= e1; p += GAT_AHEAD_BWD)
-    gat_src_batch<S, VEC, SMALL, Score, GAT_AHEAD_BWD, true>(acc, W, L, sc, xl, att, p, e1, row, false);
-  if (p < e1) gat_src_batch<S, VEC, SMALL, Score, GAT_AHEAD_BWD - 1, false>(acc, W, L, sc, xl, att, p, e1, row, false);
-  if (CHUNKS) {
-#pragma unroll
-    for (int s = 0; s < S; ++s) *reinterpret_cast<f4*>(ws + (g * W.V + L.v[s]) * 4) = acc[s];
-    return;
-  }
-  int64_t first, n_part;
-  row_partials(p0, p1, first, n_part);
-#pragma unroll 1
-  for (int64_t k = 0; k < n_part; ++k)
-#pragma unroll
-    for (int s = 0; s < S; ++s) acc[s] = acc[s] + *reinterpret_cast<const f4*>(ws + ((first + k) * W.V + L.v[s]) * 4);
-  if (W.self_loops) gat_src_batch<S, VEC, SMALL, Score, 1, true>(acc, W, L, sc, xl, att, 0, 0, row, true);
-#pragma unroll
-  for (int s = 0; s < S; ++s) gat_store<VEC>(dxl + row * ld_dxl + L.c[s], L.c[s], W.width, acc[s]);
 }
 
 // out[b, c] = in[b * 64, c] + in[b * 64 + 1, c] + ... (ascending, from 0)
@@ -372,6 +231,42 @@ __global__ void __launch_bounds__(256) gat_sum_rows_kernel(const float* __restri
   for (int64_t r = r0; r < r1; ++r) sum += in[r * width + c];
   out[(int64_t)blockIdx.x * width + c] = sum;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- kernels
+
+// plain: NAME_kernel, no mask argument anywhere
+#define GAT_KERNEL(name) name##_kernel
+#define GAT_DROP_PARAM
+#define GAT_DROP_SETUP
+#define GAT_MASK
+#define GAT_SCALED(x) x
+#define GAT_SELF_KEEP_SETUP
+#define GAT_SELF_KEEP
+#include "egc_gatv2_kernels.inc"
+#undef GAT_KERNEL
+#undef GAT_DROP_PARAM
+#undef GAT_DROP_SETUP
+#undef GAT_MASK
+#undef GAT_SCALED
+#undef GAT_SELF_KEEP_SETUP
+#undef GAT_SELF_KEEP
+
+// DROP: NAME_drop_kernel(walk, ..., GatDrop R, ...), the mask X handed on as the device functions' last argument
+#define GAT_KERNEL(name) name##_drop_kernel
+#define GAT_DROP_PARAM const GatDrop R,
+#define GAT_DROP_SETUP const GatMask X = gat_mask(R)
+#define GAT_MASK , X
+#define GAT_SCALED(x) (x) * X.scale
+#define GAT_SELF_KEEP_SETUP const uint32_t keep[1] = {gat_keep_bits<S>(X, L, (uint32_t)row, 1u)}
+#define GAT_SELF_KEEP , keep
+#include "egc_gatv2_kernels.inc"
+#undef GAT_KERNEL
+#undef GAT_DROP_PARAM
+#undef GAT_DROP_SETUP
+#undef GAT_MASK
+#undef GAT_SCALED
+#undef GAT_SELF_KEEP_SETUP
+#undef GAT_SELF_KEEP
 
 // ------------------------------------------------------------------------------------------------------------------- host
 
@@ -413,10 +308,11 @@ size_t egc_gatv2_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32
   return gat_bwd_ws(n_rows, n_edges, heads, channels).total * sizeof(float);
 }
 
-int egc_gatv2_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
-                          const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att, int32_t heads,
-                          int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out, float* lse,
-                          void* workspace, size_t workspace_bytes, egc_stream_t stream_) {
+// drop == NULL: the plain instances; else the DROP ones with *drop
+static int gat2_forward(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                        const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att, int32_t heads,
+                        int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out, float* lse,
+                        void* workspace, size_t workspace_bytes, egc_stream_t stream_, const GatDrop* drop) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0 || n_src_rows < 0) return EGC_ERR_INVALID;
   const int32_t width = heads * channels;
@@ -442,25 +338,53 @@ int egc_gatv2_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_r
     unsigned blocks;
     if (grid_blocks(slots, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
 #define GAT_FWD_CHUNKS(S_, V_, M_) gat_fwd_chunks_kernel<S_, V_, M_, GatV2Score><<<blocks, 256, 0, stream>>>(W, sc, slots, ws)
-    GAT_DISPATCH(GAT_FWD_CHUNKS);
+#define GAT_FWD_CHUNKS_DROP(S_, V_, M_) \
+  gat_fwd_chunks_drop_kernel<S_, V_, M_, GatV2Score><<<blocks, 256, 0, stream>>>(W, sc, *drop, slots, ws)
+    if (drop == nullptr) GAT_DISPATCH(GAT_FWD_CHUNKS);
+    else GAT_DISPATCH(GAT_FWD_CHUNKS_DROP);
 #undef GAT_FWD_CHUNKS
+#undef GAT_FWD_CHUNKS_DROP
     EGC_LAUNCH_CHECK("gat_fwd_chunks_kernel");
   }
   unsigned blocks;
   if (grid_blocks(n_rows, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
 #define GAT_FWD_ROWS(S_, V_, M_) \
   gat_fwd_rows_kernel<S_, V_, M_, GatV2Score><<<blocks, 256, 0, stream>>>(W, sc, out, ld_out, lse, slots, ws)
-  GAT_DISPATCH(GAT_FWD_ROWS);
+#define GAT_FWD_ROWS_DROP(S_, V_, M_) \
+  gat_fwd_rows_drop_kernel<S_, V_, M_, GatV2Score><<<blocks, 256, 0, stream>>>(W, sc, *drop, out, ld_out, lse, slots, ws)
+  if (drop == nullptr) GAT_DISPATCH(GAT_FWD_ROWS);
+  else GAT_DISPATCH(GAT_FWD_ROWS_DROP);
 #undef GAT_FWD_ROWS
+#undef GAT_FWD_ROWS_DROP
   EGC_LAUNCH_CHECK("gat_fwd_rows_kernel");
   return EGC_OK;
 }
 
-int egc_gatv2_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_rows,
-                           int64_t n_edges, const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att,
-                           int32_t heads, int32_t channels, float negative_slope, int32_t self_loops, const float* out,
-                           int32_t ld_out, const float* lse, const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* dxr,
-                           int32_t ld_dxr, float* datt, void* workspace, size_t workspace_bytes, egc_stream_t stream_) {
+int egc_gatv2_forward_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                          const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att, int32_t heads,
+                          int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out, float* lse,
+                          void* workspace, size_t workspace_bytes, egc_stream_t stream) {
+  return gat2_forward(rowptr, col, n_rows, n_edges, n_src_rows, xl, ld_xl, xr, ld_xr, att, heads, channels, negative_slope,
+                      self_loops, out, ld_out, lse, workspace, workspace_bytes, stream, nullptr);
+}
+
+int egc_gatv2_forward_dropout_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                                  const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att, int32_t heads,
+                                  int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out,
+                                  float* lse, void* workspace, size_t workspace_bytes, double p, const int64_t* seed,
+                                  egc_stream_t stream) {
+  GatDrop R = {};
+  if (!gat_fill_drop(R, p, seed, nullptr)) return EGC_ERR_INVALID;
+  return gat2_forward(rowptr, col, n_rows, n_edges, n_src_rows, xl, ld_xl, xr, ld_xr, att, heads, channels, negative_slope,
+                      self_loops, out, ld_out, lse, workspace, workspace_bytes, stream, &R);
+}
+
+static int gat2_backward(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_rows,
+                         int64_t n_edges, const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att,
+                         int32_t heads, int32_t channels, float negative_slope, int32_t self_loops, const float* out,
+                         int32_t ld_out, const float* lse, const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* dxr,
+                         int32_t ld_dxr, float* datt, void* workspace, size_t workspace_bytes, egc_stream_t stream_,
+                         const GatDrop* drop) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0) return EGC_ERR_INVALID;
   const int32_t width = heads * channels;
@@ -493,8 +417,13 @@ int egc_gatv2_backward_f32(const int32_t* rowptr, const int32_t* col, const int3
 #define GAT_DST_CHUNKS(S_, V_, M_)                                                                               \
   gat_bwd_dst_kernel<S_, V_, M_, GatV2Score, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(W, sc, nullptr, 0, nullptr, L.slots, \
                                                                                                  ws + L.part_xr, cpart)
-    GAT_DISPATCH(GAT_DST_CHUNKS);
+#define GAT_DST_CHUNKS_DROP(S_, V_, M_)                                                                                    \
+  gat_bwd_dst_drop_kernel<S_, V_, M_, GatV2Score, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(W, sc, *drop, nullptr, 0, nullptr, \
+                                                                                                      L.slots, ws + L.part_xr, cpart)
+    if (drop == nullptr) GAT_DISPATCH(GAT_DST_CHUNKS);
+    else GAT_DISPATCH(GAT_DST_CHUNKS_DROP);
 #undef GAT_DST_CHUNKS
+#undef GAT_DST_CHUNKS_DROP
     EGC_LAUNCH_CHECK("gat_bwd_dst_kernel(chunks)");
   }
   {
@@ -504,8 +433,13 @@ int egc_gatv2_backward_f32(const int32_t* rowptr, const int32_t* col, const int3
 #define GAT_DST_ROWS(S_, V_, M_)                                                                                                   \
   gat_bwd_dst_kernel<S_, V_, M_, GatV2Score, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(Wr, sc, dxr, ld_dxr, ws + L.D, L.slots, \
                                                                                                 ws + L.part_xr, part)
-    GAT_DISPATCH(GAT_DST_ROWS);
+#define GAT_DST_ROWS_DROP(S_, V_, M_)                                                                                          \
+  gat_bwd_dst_drop_kernel<S_, V_, M_, GatV2Score, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(Wr, sc, *drop, dxr, ld_dxr, ws + L.D, \
+                                                                                                     L.slots, ws + L.part_xr, part)
+    if (drop == nullptr) GAT_DISPATCH(GAT_DST_ROWS);
+    else GAT_DISPATCH(GAT_DST_ROWS_DROP);
 #undef GAT_DST_ROWS
+#undef GAT_DST_ROWS_DROP
     EGC_LAUNCH_CHECK("gat_bwd_dst_kernel(rows)");
   }
   if (datt != nullptr) {
@@ -529,15 +463,45 @@ int egc_gatv2_backward_f32(const int32_t* rowptr, const int32_t* col, const int3
     if (L.slots > 0) {
 #define GAT_SRC_CHUNKS(S_, V_, M_) \
   gat_bwd_src_kernel<S_, V_, M_, GatV2Score, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(T, sc, nullptr, 0, L.slots, ws + L.part_xl)
-      GAT_DISPATCH(GAT_SRC_CHUNKS);
+#define GAT_SRC_CHUNKS_DROP(S_, V_, M_) \
+  gat_bwd_src_drop_kernel<S_, V_, M_, GatV2Score, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(T, sc, *drop, nullptr, 0, L.slots, ws + L.part_xl)
+      if (drop == nullptr) GAT_DISPATCH(GAT_SRC_CHUNKS);
+      else GAT_DISPATCH(GAT_SRC_CHUNKS_DROP);
 #undef GAT_SRC_CHUNKS
+#undef GAT_SRC_CHUNKS_DROP
       EGC_LAUNCH_CHECK("gat_bwd_src_kernel(chunks)");
     }
 #define GAT_SRC_ROWS(S_, V_, M_) \
   gat_bwd_src_kernel<S_, V_, M_, GatV2Score, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(T, sc, dxl, ld_dxl, L.slots, ws + L.part_xl)
-    GAT_DISPATCH(GAT_SRC_ROWS);
+#define GAT_SRC_ROWS_DROP(S_, V_, M_) \
+  gat_bwd_src_drop_kernel<S_, V_, M_, GatV2Score, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(T, sc, *drop, dxl, ld_dxl, L.slots, ws + L.part_xl)
+    if (drop == nullptr) GAT_DISPATCH(GAT_SRC_ROWS);
+    else GAT_DISPATCH(GAT_SRC_ROWS_DROP);
 #undef GAT_SRC_ROWS
+#undef GAT_SRC_ROWS_DROP
     EGC_LAUNCH_CHECK("gat_bwd_src_kernel(rows)");
   }
   return EGC_OK;
+}
+
+int egc_gatv2_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t n_rows,
+                           int64_t n_edges, const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att,
+                           int32_t heads, int32_t channels, float negative_slope, int32_t self_loops, const float* out,
+                           int32_t ld_out, const float* lse, const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* dxr,
+                           int32_t ld_dxr, float* datt, void* workspace, size_t workspace_bytes, egc_stream_t stream) {
+  return gat2_backward(rowptr, col, t_rowptr, t_col, n_rows, n_edges, xl, ld_xl, xr, ld_xr, att, heads, channels, negative_slope,
+                       self_loops, out, ld_out, lse, g, ld_g, dxl, ld_dxl, dxr, ld_dxr, datt, workspace, workspace_bytes, stream,
+                       nullptr);
+}
+
+int egc_gatv2_backward_dropout_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col,
+                                   const int32_t* t_edge_id, int64_t n_rows, int64_t n_edges, const float* xl, int32_t ld_xl,
+                                   const float* xr, int32_t ld_xr, const float* att, int32_t heads, int32_t channels,
+                                   float negative_slope, int32_t self_loops, const float* out, int32_t ld_out, const float* lse,
+                                   const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* dxr, int32_t ld_dxr, float* datt,
+                                   void* workspace, size_t workspace_bytes, double p, const int64_t* seed, egc_stream_t stream) {
+  GatDrop R = {};
+  if (!gat_fill_drop(R, p, seed, t_edge_id) || (t_rowptr != nullptr && t_edge_id == nullptr)) return EGC_ERR_INVALID;
+  return gat2_backward(rowptr, col, t_rowptr, t_col, n_rows, n_edges, xl, ld_xl, xr, ld_xr, att, heads, channels, negative_slope,
+                       self_loops, out, ld_out, lse, g, ld_g, dxl, ld_dxl, dxr, ld_dxr, datt, workspace, workspace_bytes, stream, &R);
 }

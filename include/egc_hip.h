@@ -890,6 +890,41 @@ int egc_gat_backward_f32(const int32_t* rowptr, const int32_t* col, const int32_
                          int32_t ld_dxl, float* d_a_src, int32_t ld_d_a_src, float* d_a_dst, int32_t ld_d_a_dst, void* workspace,
                          size_t workspace_bytes, egc_stream_t stream);
 
+/* Attention dropout in training for the two attention aggregates (PyG's F.dropout on alpha after the softmax: per entry and per
+ * head, the self entry included).  The *_dropout_f32 entry points take the arguments of their plain counterparts, compute the
+ * same alpha and lse (over ALL of a row's entries, unmasked) and, with m'_ij^h = 0 (dropped) or 1 / (1 - p) (kept),
+ *   out[i, h, :] = sum_j m'_ij alpha_ij xl[j, h, :]        d s_ij = alpha_ij (m'_ij g_i . xl_j - g_i . out_i)
+ * and m' alpha for alpha in the direct term of d xl.  The mask is a pure function of (seed, entry, head), the same in the forward
+ * and in both backward passes: Philox4x32-10 (egc_amd/csrc/egc_philox.h) under the key (low, high 32 bits of *seed), counter
+ * (q, h >> 2, 0, 0) for the entry at position q of the FORWARD CSR and (i, h >> 2, 1, 0) for row i's self entry; head h takes
+ * output word h & 3 and is dropped iff word < (uint32) floor(p * 2^32).  Entries skipped for self_loops keep their position.
+ * `seed` is a DEVICE int64 scalar read by the kernels (no synchronisation); t_edge_id[k] is the forward position of entry k of
+ * the transposed CSR (CSRGraph.transposed().edge_id).  Workspaces: those of the plain entry points.  Further EGC_ERR_INVALID
+ * (nothing is launched): p not in (0, 1), seed NULL, t_rowptr given without t_edge_id. */
+int egc_gat_forward_dropout_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                                const float* xl, int32_t ld_xl, const float* a_src, int32_t ld_a_src, const float* a_dst,
+                                int32_t ld_a_dst, int32_t heads, int32_t channels, float negative_slope, int32_t self_loops,
+                                float* out, int32_t ld_out, float* lse, void* workspace, size_t workspace_bytes, double p,
+                                const int64_t* seed, egc_stream_t stream);
+int egc_gat_backward_dropout_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col,
+                                 const int32_t* t_edge_id, int64_t n_rows, int64_t n_edges, const float* xl, int32_t ld_xl,
+                                 const float* a_src, int32_t ld_a_src, const float* a_dst, int32_t ld_a_dst, int32_t heads,
+                                 int32_t channels, float negative_slope, int32_t self_loops, const float* out, int32_t ld_out,
+                                 const float* lse, const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* d_a_src,
+                                 int32_t ld_d_a_src, float* d_a_dst, int32_t ld_d_a_dst, void* workspace, size_t workspace_bytes,
+                                 double p, const int64_t* seed, egc_stream_t stream);
+int egc_gatv2_forward_dropout_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows,
+                                  const float* xl, int32_t ld_xl, const float* xr, int32_t ld_xr, const float* att, int32_t heads,
+                                  int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out,
+                                  float* lse, void* workspace, size_t workspace_bytes, double p, const int64_t* seed,
+                                  egc_stream_t stream);
+int egc_gatv2_backward_dropout_f32(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col,
+                                   const int32_t* t_edge_id, int64_t n_rows, int64_t n_edges, const float* xl, int32_t ld_xl,
+                                   const float* xr, int32_t ld_xr, const float* att, int32_t heads, int32_t channels,
+                                   float negative_slope, int32_t self_loops, const float* out, int32_t ld_out, const float* lse,
+                                   const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* dxr, int32_t ld_dxr, float* datt,
+                                   void* workspace, size_t workspace_bytes, double p, const int64_t* seed, egc_stream_t stream);
+
 /* Training form of egc_aggregate_combine_f32: same `out`, plus what the backward needs instead of a second
  * gather.  stats (n_nodes * egc_train_stats_floats(layer) floats, opaque to the caller, handed to the backward
  * as it is) receives every row's raw running aggregates after the self-loop term (those of sum / variance -- as the

@@ -24,7 +24,13 @@ model of the v1 launches (d = H C, E' = entries with the self loops, N = nodes; 
   forward                        E' (4 d + 4 H + 4) + N (4 d + 8 H + 4)     xl_j, a_src[j], index | a_dst, out, lse, offset
   backward, destination pass     E' (4 d + 4 H + 4) + N (8 d + 16 H + 4)    the same | g, out, a_dst, lse, D, d a_dst, offset
   backward, source pass          E' (4 d + 12 H + 4) + N (8 d + 8 H + 4)    g_i, a_dst[i], lse_i, D_i, index | xl, d xl, a_src,
-                                                                            d a_src, offset"""
+                                                                            d a_src, offset
+
+``--dropout P`` (with either ``--layer``) times attention dropout in training instead, on the same shapes: the DROP launches
+(forward; backward) against the same run's p = 0 launches on the same operands, in the order p = 0, P, p = 0, P inside every
+repetition; then the layer's training forward (no_grad) and forward + backward against the per-edge composition with F.dropout
+on alpha, with peak memory.  The byte model of the DROP launches is that of the plain ones plus 4 E' in the source pass (the
+forward position of every transposed entry); the mask itself costs integer work, no bytes."""
 import argparse
 import json
 import os
@@ -67,6 +73,18 @@ def compare(what, new, ref, iters, reps):
     return rec
 
 
+def versus(what, new, base, iters, reps):
+    """`new` against `base` (the p = 0 launches), two series of each."""
+    for fn in (base, new):
+        fn()
+    torch.cuda.synchronize()
+    b1, n1, b2, n2 = series([base, new, base, new], iters, reps)
+    rec = dict(what=what, new_us=[round(n1, 1), round(n2, 1)], p0_us=[round(b1, 1), round(b2, 1)],
+               spread_us=round(max(abs(b1 - b2), abs(n1 - n2)), 1), ratio_to_p0=round((n1 + n2) / (b1 + b2), 3))
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def kernel(what, fn, nbytes, iters, reps):
     fn()
     torch.cuda.synchronize()
@@ -100,7 +118,7 @@ class TorchGATv2(torch.nn.Module):
         top = torch.full((n, h), -float("inf"), device=x.device).scatter_reduce(0, idx, s.detach(), "amax", include_self=True)
         ex = torch.exp(s - top.index_select(0, dst))
         den = torch.zeros((n, h), device=x.device).index_add(0, dst, ex)
-        alpha = ex / den.index_select(0, dst)
+        alpha = torch.nn.functional.dropout(ex / den.index_select(0, dst), la.dropout, la.training)
         out = torch.zeros((n, h, c), device=x.device).index_add(0, dst, alpha.unsqueeze(-1) * xj)
         out = out.reshape(n, h * c) if la.concat else out.mean(dim=1)
         return out + la.bias
@@ -128,7 +146,7 @@ class TorchGAT(torch.nn.Module):
         top = torch.full((n, h), -float("inf"), device=x.device).scatter_reduce(0, idx, s.detach(), "amax", include_self=True)
         ex = torch.exp(s - top.index_select(0, dst))
         den = torch.zeros((n, h), device=x.device).index_add(0, dst, ex)
-        alpha = ex / den.index_select(0, dst)
+        alpha = torch.nn.functional.dropout(ex / den.index_select(0, dst), la.dropout, la.training)
         out = torch.zeros((n, h, c), device=x.device).index_add(0, dst, alpha.unsqueeze(-1) * xl.index_select(0, src))
         out = out.reshape(n, h * c) if la.concat else out.mean(dim=1)
         return out + la.bias
@@ -206,12 +224,86 @@ def main_gat(args, dev):
     return records
 
 
+def main_dropout(args, dev):
+    """--dropout P: the DROP launches against the p = 0 launches, and the training layer against the composition with F.dropout
+    on alpha (module docstring)."""
+    from egc_amd._gat import gat_aggregate_backward, gat_aggregate_lse
+    v1 = args.layer == "gat"
+    if v1:
+        shapes = [("arxiv_h8", lambda: wl.arxiv_like(seed=0)[:2], 8, 19), ("arxiv_h1", lambda: wl.arxiv_like(seed=0)[:2], 1, 152),
+                  ("molhiv_h8", lambda: wl.molecule_batch(seed=0)[:2], 8, 30)]
+    else:
+        shapes = [("arxiv_h8", lambda: wl.arxiv_like(seed=0)[:2], 8, 14), ("arxiv_h1", lambda: wl.arxiv_like(seed=0)[:2], 1, 112),
+                  ("zinc_h8", lambda: wl.zinc_like_batch(seed=0)[1:3], 8, 13)]
+    p, records = args.dropout, []
+    for name, make, h, c in shapes:
+        if args.only and name not in args.only:
+            continue
+        ei, n = make()
+        ei = ei.to(dev)
+        e, d = int(ei.size(1)), h * c
+        graph = egc_amd.CSRGraph.from_edge_index(ei, n)
+        graph.transposed()
+        e_eff = int((ei[0] != ei[1]).sum()) + n
+        print(json.dumps(dict(shape=name, layer=args.layer, dropout=p, nodes=n, edges=e, entries_with_self_loops=e_eff, heads=h,
+                              channels=c)), flush=True)
+        torch.manual_seed(0)
+        layer = (egc_amd.GATConv if v1 else egc_amd.GATv2Conv)(d, c, heads=h, dropout=p).to(dev)
+        comp = (TorchGAT if v1 else TorchGATv2)(layer)
+        x = torch.randn(n, d, device=dev)
+        seed = torch.empty(1, dtype=torch.int64, device=dev).random_()
+        kw = dict(dropout=p, seed=seed)
+        tag = f"{name} H={h} C={c} p={p}"
+        with torch.no_grad():
+            gout = torch.randn(n, d, device=dev)
+            if v1:
+                ext = 0.3 * torch.randn(n, (d + 2 * h + 3) // 4 * 4, device=dev)
+                ops = (ext[:, :d], ext[:, d:d + h], ext[:, d + h:d + 2 * h])
+                fwd_fn, bwd_fn = gat_aggregate_lse, gat_aggregate_backward
+            else:
+                lr = 0.3 * torch.randn(n, 2 * d, device=dev)
+                ops = (lr[:, :d], lr[:, d:], layer.att.detach()[0].contiguous())
+                fwd_fn, bwd_fn = gatv2_aggregate_lse, gatv2_aggregate_backward
+            out0, lse0 = fwd_fn(*ops, graph)
+            out1, lse1 = fwd_fn(*ops, graph, **kw)
+            print(json.dumps(dict(what=f"{tag}: lse of the DROP forward is the plain forward's, bit for bit",
+                                  value=bool(torch.equal(lse0, lse1)))), flush=True)
+            records.append(versus(f"{tag}: forward launch", lambda: fwd_fn(*ops, graph, **kw), lambda: fwd_fn(*ops, graph),
+                                  args.iters, args.reps))
+            records.append(versus(f"{tag}: backward launches", lambda: bwd_fn(*ops, graph, out1, lse1, gout, **kw),
+                                  lambda: bwd_fn(*ops, graph, out0, lse0, gout), args.iters, args.reps))
+            del ops, gout, out0, lse0, out1, lse1
+
+        def fwd(f, g):
+            def run():
+                with torch.no_grad():
+                    f(x, g)
+            return run
+        layer.train()
+        records.append(compare(f"{tag}: training forward", fwd(layer, graph), fwd(comp, ei), args.iters, args.reps))
+        xg = x.clone().requires_grad_(True)
+
+        def step(f, g):
+            def run():
+                layer.zero_grad(set_to_none=True)
+                xg.grad = None
+                f(xg, g).sum().backward()
+            return run
+        rec = compare(f"{tag}: training forward + backward", step(layer, graph), step(comp, ei), args.iters, args.reps)
+        rec.update(new_peak_bytes=peak_of(step(layer, graph)), torch_peak_bytes=peak_of(step(comp, ei)), one_edge_array_bytes=4 * e_eff * d)
+        print(json.dumps(rec), flush=True)
+        records.append(rec)
+        del layer, comp, xg, x, graph
+        torch.cuda.empty_cache()
+    return records
+
+
 def table(records):
-    print(f"\n{'what':<52}{'new us':>20}{'torch us':>22}{'x':>7}{'floor us':>10}{'of 8 TB/s':>11}{'peak MB new / torch':>24}")
+    print(f"\n{'what':<58}{'new us':>20}{'torch | p = 0 us':>22}{'x':>7}{'floor us':>10}{'of 8 TB/s':>11}{'peak MB new / torch':>24}")
     for r in records:
         share = f"{100 * r['share_of_8TBps']:.1f}%" if "share_of_8TBps" in r else ""
         peak = f"{r['new_peak_bytes'] / 1e6:.0f} / {r['torch_peak_bytes'] / 1e6:.0f}" if "new_peak_bytes" in r else ""
-        print(f"{r['what']:<52}{str(r['new_us']):>20}{str(r.get('torch_us', '')):>22}{str(r.get('speedup', '')):>7}"
+        print(f"{r['what']:<58}{str(r['new_us']):>20}{str(r.get('torch_us', r.get('p0_us', ''))):>22}{str(r.get('speedup', r.get('ratio_to_p0', ''))):>7}"
               f"{str(r.get('floor_us', '')):>10}{share:>11}{peak:>24}")
 
 
@@ -232,10 +324,17 @@ def main():
     ap.add_argument("--only", nargs="*", default=None, help="shape names to run (arxiv_h8 arxiv_h1 zinc_h8; molhiv_h8 with --layer gat)")
     ap.add_argument("--layer", choices=("gatv2", "gat"), default="gatv2", help="gatv2: GATv2Conv (the default); gat: GATConv, with "
                     "GATv2's launches at the same width and graph next to it")
+    ap.add_argument("--dropout", type=float, default=0.0, help="P in (0, 1): time attention dropout in training instead (the DROP "
+                    "launches against the p = 0 launches, the training layer against the composition with F.dropout on alpha)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("gat_time.py needs the GPU: a timing taken anywhere else says nothing")
     dev = torch.device("cuda:0")
+    if args.dropout != 0.0:
+        if not 0.0 < args.dropout < 1.0:
+            sys.exit("--dropout wants P in (0, 1)")
+        table(main_dropout(args, dev))
+        return
     if args.layer == "gat":
         table(main_gat(args, dev))
         return
