@@ -20,6 +20,7 @@ the modules draw a seed per training forward with a torch device op, so ``torch.
 synchronises."""
 from __future__ import annotations
 
+import functools
 import math
 
 import torch
@@ -59,48 +60,64 @@ def _new_seed(dev):
     return torch.empty(1, dtype=torch.int64, device=dev).random_()
 
 
+@functools.lru_cache(maxsize=None)
+def _entry(lib, name, dropout):
+    """(launch entry, its name, workspace query) of egc_<name>[_dropout]_f32 in ``lib``, looked up once."""
+    entry = f"egc_{name}_dropout_f32" if dropout else f"egc_{name}_f32"
+    return getattr(lib, entry), entry, getattr(lib, f"egc_{name}_workspace_bytes")
+
+
+def _lib_call(name, dev, g, heads, channels, args, drop, src_pass=None):
+    """egc_<name>_f32(CSR pointers, *args, workspace, bytes, stream) under the device guard, the workspace sized by
+    egc_<name>_workspace_bytes.  A forward (``src_pass`` None) names rowptr and col; a backward also the transposed graph's, NULL
+    unless a gradient of the source pass is wanted (``src_pass``).  With ``drop`` = (p, seed): egc_<name>_dropout_f32, which takes
+    (p, seed pointer) after the workspace and, in a backward, the transposed entries' forward positions after the CSR pointers."""
+    launch, entry, ws_bytes = _entry(_C.load(), name, drop is not None)
+    csr, query = (g.rowptr.data_ptr(), g.col.data_ptr()), (g.n_edges, heads, channels)
+    if src_pass is not None:
+        t = g.transposed() if src_pass else None
+        csr += (_ptr(t.rowptr if t else None), _ptr(t.col if t else None)) + (() if drop is None else (_ptr(t.edge_id if t else None),))
+        query = (g.n_nodes,) + query
+    with _device_guard(dev):
+        ws, nbytes = _workspace(ws_bytes(*query), dev)
+        tail = () if drop is None else (drop[0], drop[1].data_ptr())
+        _C.check(launch(*csr, *args, _ptr(ws), nbytes, *tail, _stream_ptr(dev)), entry)
+
+
+def _check_graph(g, dev, loops=False, operands=None, att=None, backward=None):
+    """A launch's graph checks.  A forward (``operands``: the message's words for them): the graph, and ``att``, on the
+    operands' device, square under add_self_loops.  A backward (``backward``: the flavour's name): a square graph."""
+    if backward is not None and g.n_src_rows != g.n_nodes:
+        raise RuntimeError(f"egc_amd: the {backward} backward needs a square graph, got [{g.n_nodes}, {g.n_src_rows}]")
+    if operands is not None and (g.device != dev or (att is not None and att.device != dev)):
+        where = operands if att is None else f"att on {att.device}, {operands}"
+        raise RuntimeError(f"egc_amd: the graph is on {g.device}, {where} on {dev}")
+    if loops and g.n_src_rows != g.n_nodes:
+        raise RuntimeError(f"egc_amd: add_self_loops needs a square graph, got [{g.n_nodes}, {g.n_src_rows}]")
+
+
 def _launch_forward(xl, xr, att, g: CSRGraph, heads, channels, slope, loops, out, lse, drop=None):
-    lib = _C.load()
     width, dev = heads * channels, xr.device
     ld_xl, ld_xr = _rows2d(xl, "xl", g.n_src_rows, width, dev), _rows2d(xr, "xr", g.n_nodes, width, dev)
     ld_out = _rows2d(out, "out", g.n_nodes, width, dev)
-    if g.device != dev or att.device != dev:
-        raise RuntimeError(f"egc_amd: the graph is on {g.device}, att on {att.device}, xl and xr on {dev}")
-    if loops and g.n_src_rows != g.n_nodes:
-        raise RuntimeError(f"egc_amd: add_self_loops needs a square graph, got [{g.n_nodes}, {g.n_src_rows}]")
-    with _device_guard(dev):
-        ws, nbytes = _workspace(lib.egc_gatv2_forward_workspace_bytes(g.n_edges, heads, channels), dev)
-        args = (g.rowptr.data_ptr(), g.col.data_ptr(), g.n_nodes, g.n_edges, g.n_src_rows, xl.data_ptr(), ld_xl, xr.data_ptr(), ld_xr,
-                att.data_ptr(), heads, channels, float(slope), int(loops), out.data_ptr(), ld_out, lse.data_ptr(), _ptr(ws), nbytes)
-        if drop is None:
-            _C.check(lib.egc_gatv2_forward_f32(*args, _stream_ptr(dev)), "egc_gatv2_forward_f32")
-        else:
-            _C.check(lib.egc_gatv2_forward_dropout_f32(*args, drop[0], drop[1].data_ptr(), _stream_ptr(dev)),
-                     "egc_gatv2_forward_dropout_f32")
+    _check_graph(g, dev, loops, "xl and xr", att)
+    _lib_call("gatv2_forward", dev, g, heads, channels,
+              (g.n_nodes, g.n_edges, g.n_src_rows, xl.data_ptr(), ld_xl, xr.data_ptr(), ld_xr, att.data_ptr(), heads, channels,
+               float(slope), int(loops), out.data_ptr(), ld_out, lse.data_ptr()), drop)
 
 
 def _launch_backward(xl, xr, att, g: CSRGraph, heads, channels, slope, loops, out, lse, gout, dxl, dxr, datt, drop=None):
     """egc_gatv2_backward_f32: d xl, d xr [N, H C] (column blocks are fine) and d att [H C]; any may be None."""
-    lib = _C.load()
     width, dev, n = heads * channels, xr.device, g.n_nodes
-    if g.n_src_rows != n:
-        raise RuntimeError(f"egc_amd: the GATv2 backward needs a square graph, got [{n}, {g.n_src_rows}]")
+    _check_graph(g, dev, backward="GATv2")
     ld_xl, ld_xr = _rows2d(xl, "xl", n, width, dev), _rows2d(xr, "xr", n, width, dev)
     ld_out, ld_g = _rows2d(out, "out", n, width, dev), _rows2d(gout, "d out", n, width, dev)
     ld_dxl = _rows2d(dxl, "d xl", n, width, dev) if dxl is not None else 0
     ld_dxr = _rows2d(dxr, "d xr", n, width, dev) if dxr is not None else 0
-    t = g.transposed() if dxl is not None else None
-    with _device_guard(dev):
-        ws, nbytes = _workspace(lib.egc_gatv2_backward_workspace_bytes(n, g.n_edges, heads, channels), dev)
-        csr = (g.rowptr.data_ptr(), g.col.data_ptr(), _ptr(t.rowptr if t else None), _ptr(t.col if t else None))
-        args = (n, g.n_edges, xl.data_ptr(), ld_xl, xr.data_ptr(), ld_xr, att.data_ptr(), heads, channels, float(slope), int(loops),
-                out.data_ptr(), ld_out, lse.data_ptr(), gout.data_ptr(), ld_g, _ptr(dxl), ld_dxl, _ptr(dxr), ld_dxr, _ptr(datt),
-                _ptr(ws), nbytes)
-        if drop is None:
-            _C.check(lib.egc_gatv2_backward_f32(*csr, *args, _stream_ptr(dev)), "egc_gatv2_backward_f32")
-        else:
-            _C.check(lib.egc_gatv2_backward_dropout_f32(*csr, _ptr(t.edge_id if t else None), *args, drop[0], drop[1].data_ptr(),
-                                                        _stream_ptr(dev)), "egc_gatv2_backward_dropout_f32")
+    _lib_call("gatv2_backward", dev, g, heads, channels,
+              (n, g.n_edges, xl.data_ptr(), ld_xl, xr.data_ptr(), ld_xr, att.data_ptr(), heads, channels, float(slope), int(loops),
+               out.data_ptr(), ld_out, lse.data_ptr(), gout.data_ptr(), ld_g, _ptr(dxl), ld_dxl, _ptr(dxr), ld_dxr, _ptr(datt)),
+              drop, src_pass=dxl is not None)
 
 
 def _forward(xl, xr, att, g, slope, loops, drop=None):
@@ -236,7 +253,44 @@ def _glorot_(t):
         return t.uniform_(-bound, bound)
 
 
-class GATv2Conv(nn.Module):
+class _AttentionConv(nn.Module):
+    """What GATv2Conv and GATConv share: the width check and the attributes, the bias (registered last, after the flavour's own
+    parameters: ``_finish``), the dropout bookkeeping, and of ``forward`` the input, dropout and graph checks, the head mean and
+    the bias.  A flavour builds its parameters, resets them and turns x into the aggregate [N, H C] (``_aggregate``)."""
+
+    def __init__(self, in_channels, out_channels, heads, concat, negative_slope, dropout, add_self_loops):
+        super().__init__()
+        if heads < 1 or out_channels < 1 or heads * out_channels > 512:
+            raise ValueError(f"egc_amd.{type(self).__name__}: heads * out_channels must be in 1..512, got {heads} * {out_channels}")
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
+        self.negative_slope, self.dropout, self.add_self_loops = negative_slope, dropout, add_self_loops
+        self.last_dropout_seed, self._dropout_built = None, float(dropout)
+
+    def _finish(self, bias):
+        if bias:
+            self.bias = nn.Parameter(torch.empty(self.heads * self.out_channels if self.concat else self.out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def forward(self, x, edge_index):
+        if x.dim() != 2 or x.size(1) != self.in_channels:
+            raise RuntimeError(f"egc_amd.{type(self).__name__}: x has shape {tuple(x.shape)}, expected (rows, {self.in_channels})")
+        drop, all_dropped = _module_dropout(self, x)
+        _check_f32(x, "x")
+        g = _as_csr(edge_index, x.size(0))
+        if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
+            raise RuntimeError(f"egc_amd.{type(self).__name__}: the graph is [{g.n_nodes}, {g.n_src_rows}], x has {x.size(0)} rows")
+        out = self._aggregate(x, g, float(self.negative_slope), bool(self.add_self_loops), drop, all_dropped)
+        if not self.concat:
+            out = out.view(-1, self.heads, self.out_channels).mean(dim=1)
+        return out if self.bias is None else out + self.bias
+
+    def extra_repr(self):
+        return f"{self.in_channels}, {self.out_channels}, heads={self.heads}, concat={self.concat}"
+
+
+class GATv2Conv(_AttentionConv):
     """PyG 2.x ``GATv2Conv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0,
     add_self_loops=True, bias=True, share_weights=False)``; ``forward(x, edge_index)`` with edge_index a [2, E] int64 tensor, an
     ``egc_amd.SparseTensor``, a ``CSRGraph`` or a ``GraphBatch``.  Parameters ``lin_l.{weight,bias}``, ``lin_r.{weight,bias}``,
@@ -249,20 +303,12 @@ class GATv2Conv(nn.Module):
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
                  bias=True, share_weights=False):
-        super().__init__()
-        if heads < 1 or out_channels < 1 or heads * out_channels > 512:
-            raise ValueError(f"egc_amd.GATv2Conv: heads * out_channels must be in 1..512, got {heads} * {out_channels}")
-        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
-        self.negative_slope, self.dropout, self.add_self_loops, self.share_weights = negative_slope, dropout, add_self_loops, share_weights
+        super().__init__(in_channels, out_channels, heads, concat, negative_slope, dropout, add_self_loops)
+        self.share_weights = share_weights
         self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=True)
         self.lin_r = self.lin_l if share_weights else nn.Linear(in_channels, heads * out_channels, bias=True)
         self.att = nn.Parameter(torch.empty(1, heads, out_channels))
-        if bias:
-            self.bias = nn.Parameter(torch.empty(heads * out_channels if concat else out_channels))
-        else:
-            self.register_parameter("bias", None)
-        self.last_dropout_seed, self._dropout_built = None, float(dropout)
-        self.reset_parameters()
+        self._finish(bias)
 
     def reset_parameters(self):
         for lin in (self.lin_l, self.lin_r):
@@ -272,28 +318,14 @@ class GATv2Conv(nn.Module):
         if self.bias is not None:
             nn.init.zeros_(self.bias)
 
-    def forward(self, x, edge_index):
-        if x.dim() != 2 or x.size(1) != self.in_channels:
-            raise RuntimeError(f"egc_amd.GATv2Conv: x has shape {tuple(x.shape)}, expected (rows, {self.in_channels})")
-        drop, all_dropped = _module_dropout(self, x)
-        _check_f32(x, "x")
-        g = _as_csr(edge_index, x.size(0))
-        if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
-            raise RuntimeError(f"egc_amd.GATv2Conv: the graph is [{g.n_nodes}, {g.n_src_rows}], x has {x.size(0)} rows")
-        slope, loops = float(self.negative_slope), bool(self.add_self_loops)
+    def _aggregate(self, x, g, slope, loops, drop, all_dropped):
         if self.share_weights:
             xl = F.linear(x, self.lin_l.weight, self.lin_l.bias)
-            out = _all_dropped(xl, self.att) if all_dropped else _GatV2Aggregate.apply(xl, xl, self.att, g, slope, loops, drop)
-        else:
-            lr = F.linear(x, torch.cat([self.lin_l.weight, self.lin_r.weight]), torch.cat([self.lin_l.bias, self.lin_r.bias]))
-            out = (_all_dropped(lr[:, :lr.size(1) // 2] + lr[:, lr.size(1) // 2:], self.att) if all_dropped
-                   else _GatV2Fused.apply(lr, self.att, g, slope, loops, drop))
-        if not self.concat:
-            out = out.view(-1, self.heads, self.out_channels).mean(dim=1)
-        return out if self.bias is None else out + self.bias
-
-    def extra_repr(self):
-        return f"{self.in_channels}, {self.out_channels}, heads={self.heads}, concat={self.concat}"
+            return _all_dropped(xl, self.att) if all_dropped else _GatV2Aggregate.apply(xl, xl, self.att, g, slope, loops, drop)
+        lr = F.linear(x, torch.cat([self.lin_l.weight, self.lin_r.weight]), torch.cat([self.lin_l.bias, self.lin_r.bias]))
+        if all_dropped:
+            return _all_dropped(lr[:, :lr.size(1) // 2] + lr[:, lr.size(1) // 2:], self.att)
+        return _GatV2Fused.apply(lr, self.att, g, slope, loops, drop)
 
 
 # ------------------------------------------------------------------------------------------------------------------ GAT v1
@@ -323,32 +355,19 @@ def _gat1_shape(xl, a_src, a_dst):
 
 
 def _gat1_launch_forward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope, loops, out, lse, drop=None):
-    lib = _C.load()
     width, dev = heads * channels, a_dst.device
     ld_xl, ld_as = _rows2d(xl, "xl", g.n_src_rows, width, dev), _rows2d(a_src, "a_src", g.n_src_rows, heads, dev)
     ld_ad, ld_out = _rows2d(a_dst, "a_dst", g.n_nodes, heads, dev), _rows2d(out, "out", g.n_nodes, width, dev)
-    if g.device != dev:
-        raise RuntimeError(f"egc_amd: the graph is on {g.device}, xl, a_src and a_dst on {dev}")
-    if loops and g.n_src_rows != g.n_nodes:
-        raise RuntimeError(f"egc_amd: add_self_loops needs a square graph, got [{g.n_nodes}, {g.n_src_rows}]")
-    with _device_guard(dev):
-        ws, nbytes = _workspace(lib.egc_gat_forward_workspace_bytes(g.n_edges, heads, channels), dev)
-        args = (g.rowptr.data_ptr(), g.col.data_ptr(), g.n_nodes, g.n_edges, g.n_src_rows, xl.data_ptr(), ld_xl, a_src.data_ptr(),
-                ld_as, a_dst.data_ptr(), ld_ad, heads, channels, float(slope), int(loops), out.data_ptr(), ld_out, lse.data_ptr(),
-                _ptr(ws), nbytes)
-        if drop is None:
-            _C.check(lib.egc_gat_forward_f32(*args, _stream_ptr(dev)), "egc_gat_forward_f32")
-        else:
-            _C.check(lib.egc_gat_forward_dropout_f32(*args, drop[0], drop[1].data_ptr(), _stream_ptr(dev)),
-                     "egc_gat_forward_dropout_f32")
+    _check_graph(g, dev, loops, "xl, a_src and a_dst")
+    _lib_call("gat_forward", dev, g, heads, channels,
+              (g.n_nodes, g.n_edges, g.n_src_rows, xl.data_ptr(), ld_xl, a_src.data_ptr(), ld_as, a_dst.data_ptr(), ld_ad, heads,
+               channels, float(slope), int(loops), out.data_ptr(), ld_out, lse.data_ptr()), drop)
 
 
 def _gat1_launch_backward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope, loops, out, lse, gout, dxl, das, dad, drop=None):
     """egc_gat_backward_f32: d xl [N, H C], d a_src and d a_dst [N, H] (column blocks are fine); any may be None."""
-    lib = _C.load()
     width, dev, n = heads * channels, a_dst.device, g.n_nodes
-    if g.n_src_rows != n:
-        raise RuntimeError(f"egc_amd: the GAT backward needs a square graph, got [{n}, {g.n_src_rows}]")
+    _check_graph(g, dev, backward="GAT")
     ld_xl, ld_as, ld_ad = _rows2d(xl, "xl", n, width, dev), _rows2d(a_src, "a_src", n, heads, dev), _rows2d(a_dst, "a_dst", n, heads, dev)
     ld_out, ld_g = _rows2d(out, "out", n, width, dev), _rows2d(gout, "d out", n, width, dev)
     _check_f32(lse, "lse", (n, heads))
@@ -357,18 +376,10 @@ def _gat1_launch_backward(xl, a_src, a_dst, g: CSRGraph, heads, channels, slope,
     ld_dxl = _rows2d(dxl, "d xl", n, width, dev) if dxl is not None else 0
     ld_das = _rows2d(das, "d a_src", n, heads, dev) if das is not None else 0
     ld_dad = _rows2d(dad, "d a_dst", n, heads, dev) if dad is not None else 0
-    t = g.transposed() if dxl is not None or das is not None else None
-    with _device_guard(dev):
-        ws, nbytes = _workspace(lib.egc_gat_backward_workspace_bytes(n, g.n_edges, heads, channels), dev)
-        csr = (g.rowptr.data_ptr(), g.col.data_ptr(), _ptr(t.rowptr if t else None), _ptr(t.col if t else None))
-        args = (n, g.n_edges, xl.data_ptr(), ld_xl, a_src.data_ptr(), ld_as, a_dst.data_ptr(), ld_ad, heads, channels, float(slope),
-                int(loops), out.data_ptr(), ld_out, lse.data_ptr(), gout.data_ptr(), ld_g, _ptr(dxl), ld_dxl, _ptr(das), ld_das,
-                _ptr(dad), ld_dad, _ptr(ws), nbytes)
-        if drop is None:
-            _C.check(lib.egc_gat_backward_f32(*csr, *args, _stream_ptr(dev)), "egc_gat_backward_f32")
-        else:
-            _C.check(lib.egc_gat_backward_dropout_f32(*csr, _ptr(t.edge_id if t else None), *args, drop[0], drop[1].data_ptr(),
-                                                      _stream_ptr(dev)), "egc_gat_backward_dropout_f32")
+    _lib_call("gat_backward", dev, g, heads, channels,
+              (n, g.n_edges, xl.data_ptr(), ld_xl, a_src.data_ptr(), ld_as, a_dst.data_ptr(), ld_ad, heads, channels, float(slope),
+               int(loops), out.data_ptr(), ld_out, lse.data_ptr(), gout.data_ptr(), ld_g, _ptr(dxl), ld_dxl, _ptr(das), ld_das,
+               _ptr(dad), ld_dad), drop, src_pass=dxl is not None or das is not None)
 
 
 def _gat1_forward(xl, a_src, a_dst, g, slope, loops, drop=None):
@@ -463,7 +474,7 @@ def gat_aggregate_backward(xl, a_src, a_dst, graph, out, lse, gout, negative_slo
     return _gat1_backward(saved, (True, True, True), gout)[:3]
 
 
-class GATConv(nn.Module):
+class GATConv(_AttentionConv):
     """PyG ``GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
     bias=True)``, non-bipartite (``in_channels`` an int); ``forward(x, edge_index)`` with edge_index a [2, E] int64 tensor, an
     ``egc_amd.SparseTensor``, a ``CSRGraph`` or a ``GraphBatch``.  State dict in the PyG 2.0 - 2.2 layout, so such state dicts
@@ -479,23 +490,14 @@ class GATConv(nn.Module):
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
                  bias=True):
-        super().__init__()
         if not isinstance(in_channels, int):
             raise ValueError(f"egc_amd.GATConv: in_channels must be an int (bipartite inputs are not implemented), got {in_channels!r}")
-        if heads < 1 or out_channels < 1 or heads * out_channels > 512:
-            raise ValueError(f"egc_amd.GATConv: heads * out_channels must be in 1..512, got {heads} * {out_channels}")
-        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
-        self.negative_slope, self.dropout, self.add_self_loops = negative_slope, dropout, add_self_loops
+        super().__init__(in_channels, out_channels, heads, concat, negative_slope, dropout, add_self_loops)
         self.lin_src = nn.Linear(in_channels, heads * out_channels, bias=False)
         self.lin_dst = self.lin_src
         self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
         self.att_dst = nn.Parameter(torch.empty(1, heads, out_channels))
-        if bias:
-            self.bias = nn.Parameter(torch.empty(heads * out_channels if concat else out_channels))
-        else:
-            self.register_parameter("bias", None)
-        self.last_dropout_seed, self._dropout_built = None, float(dropout)
-        self.reset_parameters()
+        self._finish(bias)
 
     def reset_parameters(self):
         _glorot_(self.lin_src.weight)
@@ -520,22 +522,8 @@ class GATConv(nn.Module):
             rows.append(w.new_zeros((pad, self.in_channels)))
         return torch.cat(rows)
 
-    def forward(self, x, edge_index):
-        if x.dim() != 2 or x.size(1) != self.in_channels:
-            raise RuntimeError(f"egc_amd.GATConv: x has shape {tuple(x.shape)}, expected (rows, {self.in_channels})")
-        drop, all_dropped = _module_dropout(self, x)
-        _check_f32(x, "x")
-        g = _as_csr(edge_index, x.size(0))
-        if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
-            raise RuntimeError(f"egc_amd.GATConv: the graph is [{g.n_nodes}, {g.n_src_rows}], x has {x.size(0)} rows")
+    def _aggregate(self, x, g, slope, loops, drop, all_dropped):
         ext = F.linear(x, self.extended_weight())
         if all_dropped:
-            out = _all_dropped(ext[:, :self.heads * self.out_channels])
-        else:
-            out = _GatFused.apply(ext, self.heads, self.out_channels, g, float(self.negative_slope), bool(self.add_self_loops), drop)
-        if not self.concat:
-            out = out.view(-1, self.heads, self.out_channels).mean(dim=1)
-        return out if self.bias is None else out + self.bias
-
-    def extra_repr(self):
-        return f"{self.in_channels}, {self.out_channels}, heads={self.heads}, concat={self.concat}"
+            return _all_dropped(ext[:, :self.heads * self.out_channels])
+        return _GatFused.apply(ext, self.heads, self.out_channels, g, slope, loops, drop)

@@ -44,7 +44,7 @@
 // end).  Backward: the term of an entry is (w m') xl_j, (alpha m') g_i and w (m' (g_i . xl_j) - D_i), m' applied where written;
 // at scale = 1 and nothing dropped these are the bits of the plain kernels.  A batch's Philox calls follow its gathers in
 // program order (integer work under the loads' latency).
-#include "egc_gat_dev.h"
+#include "egc_gat_host.h"
 
 namespace egc {
 
@@ -56,20 +56,6 @@ struct Gat1Walk : GatWalk {
   const float* a_dst;   // forward / destination pass: the row's own; source pass: gathered
   int32_t ld_as, ld_ad;
 };
-
-__device__ inline f4 gat1_lrelu(f4 z, float slope) {
-  f4 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) r[i] = z[i] > 0.f ? z[i] : slope * z[i];
-  return r;
-}
-
-__device__ inline f4 gat1_dlrelu(f4 z, float slope) {
-  f4 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) r[i] = z[i] > 0.f ? 1.f : slope;
-  return r;
-}
 
 // a[row, head] of every column of the lane, rows of stride ld.  C >= 4: a quad lies in at most two heads, two loads.
 template <int S, bool SMALL>
@@ -127,7 +113,7 @@ __device__ inline void gat1_fwd_batch(GatState<S>& st, const Gat1Walk& W, const 
 #pragma unroll
   for (int k = 0; k < N; ++k)
 #pragma unroll
-    for (int s = 0; s < S; ++s) e[k][s] = gat1_lrelu(e[k][s] + ad[s], W.slope);
+    for (int s = 0; s < S; ++s) e[k][s] = gat_lrelu(e[k][s] + ad[s], W.slope);
   if constexpr (sizeof...(Mask) == 1) {
     uint32_t keep[N];
     gat_batch_keep<S, N, FULL>(keep, gat_only(mask...), L, p, p1, row, self);
@@ -169,7 +155,7 @@ __device__ inline void gat1_dst_batch(f4 (&va)[S], f4 (&ta)[S], const Gat1Walk& 
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       const f4 z = as[k][s] + ad[s];
-      f4 w = gat_exp(gat1_lrelu(z, W.slope) - lse[s]) * gat1_dlrelu(z, W.slope);
+      f4 w = gat_exp(gat_lrelu(z, W.slope) - lse[s]) * gat_dlrelu(z, W.slope);
 #pragma unroll
       for (int i = 0; i < 4; ++i) w[i] = live[k] ? w[i] : 0.f;
       if constexpr (sizeof...(Mask) == 1) va[s] = va[s] + (w * gat_keep_f4(keep[k], s, gat_only(mask...).scale)) * v[k][s];
@@ -215,10 +201,10 @@ __device__ inline void gat1_src_batch(f4 (&dx)[S], f4 (&sa)[S], const Gat1Walk& 
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       const f4 z = as[s] + ad[k][s];
-      f4 alpha = gat_exp(gat1_lrelu(z, W.slope) - lse[k][s]);
+      f4 alpha = gat_exp(gat_lrelu(z, W.slope) - lse[k][s]);
 #pragma unroll
       for (int i = 0; i < 4; ++i) alpha[i] = live[k] ? alpha[i] : 0.f;
-      const f4 w = alpha * gat1_dlrelu(z, W.slope);
+      const f4 w = alpha * gat_dlrelu(z, W.slope);
       if constexpr (sizeof...(Mask) == 1) {
         const f4 mk = gat_keep_f4(keep[k], s, gat_only(mask...).scale);
         dx[s] = dx[s] + (alpha * mk) * gr[k][s];
@@ -264,14 +250,13 @@ __device__ inline void gat1_src_batch(f4 (&dx)[S], f4 (&sa)[S], const Gat1Walk& 
 // backward workspace, in floats
 struct Gat1BwdWs {
   size_t D, part_dst, part_src, total;
-  int64_t slots, row_blocks, chunk_blocks;
+  int64_t slots;
 };
 
 static inline Gat1BwdWs gat1_bwd_ws(int64_t n_rows, int64_t n_edges, int32_t H, int32_t C) {
   const GatGeom q = gat_geom(H * C);
   Gat1BwdWs w;
   w.slots = chunk_slots(n_edges);
-  w.row_blocks = gat_blocks(n_rows, q.G), w.chunk_blocks = gat_blocks(w.slots, q.G);
   size_t at = 0;
   w.D = at, at += gat_align((size_t)n_rows * H);
   w.part_dst = at, at += (size_t)w.slots * q.V * 2 * 4;
@@ -285,8 +270,7 @@ static inline Gat1BwdWs gat1_bwd_ws(int64_t n_rows, int64_t n_edges, int32_t H, 
 using namespace egc;
 
 size_t egc_gat_forward_workspace_bytes(int64_t n_edges, int32_t heads, int32_t channels) {
-  if (n_edges <= 0 || !gat_shape_ok(heads, channels)) return 0;
-  return (size_t)chunk_slots(n_edges) * (size_t)gat_geom(heads * channels).V * 3 * 16;
+  return gat_fwd_ws_bytes(n_edges, heads, channels);
 }
 
 size_t egc_gat_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32_t heads, int32_t channels) {
@@ -300,44 +284,28 @@ static int gat1_forward(const int32_t* rowptr, const int32_t* col, int64_t n_row
                         int32_t heads, int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out,
                         float* lse, void* workspace, size_t workspace_bytes, egc_stream_t stream_, const GatDrop* drop) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0 || n_src_rows < 0) return EGC_ERR_INVALID;
-  const int32_t width = heads * channels;
-  if (ld_xl < width || ld_out < width || ld_a_src < heads || ld_a_dst < heads) return EGC_ERR_INVALID;
-  if (self_loops && n_src_rows != n_rows) return EGC_ERR_INVALID;
-  if (n_rows == 0) return EGC_OK;
-  if (rowptr == nullptr || a_dst == nullptr || out == nullptr || lse == nullptr) return EGC_ERR_INVALID;
-  if ((n_edges > 0 || self_loops) && (xl == nullptr || a_src == nullptr)) return EGC_ERR_INVALID;
-  if (n_edges > 0 && (col == nullptr || n_src_rows == 0)) return EGC_ERR_INVALID;
-  if (!counts_fit_int32(n_rows, n_edges, n_src_rows)) return EGC_ERR_UNSUPPORTED;
+  const int rc = gat_forward_args(rowptr, col, n_rows, n_edges, n_src_rows, heads, channels, self_loops, xl, ld_xl, out, ld_out, lse,
+                                  workspace, workspace_bytes, ld_a_src >= heads && ld_a_dst >= heads,
+                                  a_dst != nullptr && (!(n_edges > 0 || self_loops) || a_src != nullptr));
+  if (rc != GAT_RUN) return rc;
   Gat1Walk W = {};
   W.rowptr = rowptr, W.col = col, W.xl = xl, W.a_src = a_src, W.a_dst = a_dst;
   W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_src_rows, W.ld_xl = ld_xl, W.ld_as = ld_a_src, W.ld_ad = ld_a_dst;
   gat_fill_walk(W, heads, channels, negative_slope, self_loops ? 1 : 0);
-  const int S = gat_geom(width).S;
-  const bool small = channels < 4;
-  const bool vec = all_mult4(width, ld_xl, ld_out) && all_aligned16(xl, out);
+  const GatForm form = gat_form(heads, channels, {ld_xl, ld_out}, {xl, out});
   const int64_t slots = chunk_slots(n_edges);
   float* ws = static_cast<float*>(workspace);
   if (slots > 0) {
-    if (!workspace_ok(ws, workspace_bytes, egc_gat_forward_workspace_bytes(n_edges, heads, channels))) return EGC_ERR_WORKSPACE;
-    unsigned blocks;
-    if (grid_blocks(slots, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
-#define GAT1_FWD_CHUNKS(S_, V_, M_) gat1_fwd_chunks_kernel<S_, V_, M_><<<blocks, 256, 0, stream>>>(W, slots, ws)
-#define GAT1_FWD_CHUNKS_DROP(S_, V_, M_) gat1_fwd_chunks_drop_kernel<S_, V_, M_><<<blocks, 256, 0, stream>>>(W, *drop, slots, ws)
-    if (drop == nullptr) GAT_DISPATCH(GAT1_FWD_CHUNKS);
-    else GAT_DISPATCH(GAT1_FWD_CHUNKS_DROP);
-#undef GAT1_FWD_CHUNKS
-#undef GAT1_FWD_CHUNKS_DROP
+    gat_dispatch(form, [&](auto f) {
+      if (drop == nullptr) gat1_fwd_chunks_kernel<f.S, f.VEC, f.SMALL><<<gat_grid(slots, W.G), 256, 0, stream>>>(W, slots, ws);
+      else gat1_fwd_chunks_drop_kernel<f.S, f.VEC, f.SMALL><<<gat_grid(slots, W.G), 256, 0, stream>>>(W, *drop, slots, ws);
+    });
     EGC_LAUNCH_CHECK("gat1_fwd_chunks_kernel");
   }
-  unsigned blocks;
-  if (grid_blocks(n_rows, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
-#define GAT1_FWD_ROWS(S_, V_, M_) gat1_fwd_rows_kernel<S_, V_, M_><<<blocks, 256, 0, stream>>>(W, out, ld_out, lse, ws)
-#define GAT1_FWD_ROWS_DROP(S_, V_, M_) gat1_fwd_rows_drop_kernel<S_, V_, M_><<<blocks, 256, 0, stream>>>(W, *drop, out, ld_out, lse, ws)
-  if (drop == nullptr) GAT_DISPATCH(GAT1_FWD_ROWS);
-  else GAT_DISPATCH(GAT1_FWD_ROWS_DROP);
-#undef GAT1_FWD_ROWS
-#undef GAT1_FWD_ROWS_DROP
+  gat_dispatch(form, [&](auto f) {
+    if (drop == nullptr) gat1_fwd_rows_kernel<f.S, f.VEC, f.SMALL><<<gat_grid(n_rows, W.G), 256, 0, stream>>>(W, out, ld_out, lse, ws);
+    else gat1_fwd_rows_drop_kernel<f.S, f.VEC, f.SMALL><<<gat_grid(n_rows, W.G), 256, 0, stream>>>(W, *drop, out, ld_out, lse, ws);
+  });
   EGC_LAUNCH_CHECK("gat1_fwd_rows_kernel");
   return EGC_OK;
 }
@@ -356,7 +324,7 @@ int egc_gat_forward_dropout_f32(const int32_t* rowptr, const int32_t* col, int64
                                 float* out, int32_t ld_out, float* lse, void* workspace, size_t workspace_bytes, double p,
                                 const int64_t* seed, egc_stream_t stream) {
   GatDrop R = {};
-  if (!gat_fill_drop(R, p, seed, nullptr)) return EGC_ERR_INVALID;
+  if (!gat_fill_drop(R, p, seed, nullptr, nullptr)) return EGC_ERR_INVALID;
   return gat1_forward(rowptr, col, n_rows, n_edges, n_src_rows, xl, ld_xl, a_src, ld_a_src, a_dst, ld_a_dst, heads, channels,
                       negative_slope, self_loops, out, ld_out, lse, workspace, workspace_bytes, stream, &R);
 }
@@ -368,79 +336,57 @@ static int gat1_backward(const int32_t* rowptr, const int32_t* col, const int32_
                          int32_t ld_dxl, float* d_a_src, int32_t ld_d_a_src, float* d_a_dst, int32_t ld_d_a_dst, void* workspace,
                          size_t workspace_bytes, egc_stream_t stream_, const GatDrop* drop) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0) return EGC_ERR_INVALID;
-  const int32_t width = heads * channels;
-  if (ld_xl < width || ld_out < width || ld_g < width || ld_a_src < heads || ld_a_dst < heads) return EGC_ERR_INVALID;
-  if ((dxl != nullptr && ld_dxl < width) || (d_a_src != nullptr && ld_d_a_src < heads) || (d_a_dst != nullptr && ld_d_a_dst < heads))
-    return EGC_ERR_INVALID;
-  if (dxl == nullptr && d_a_src == nullptr && d_a_dst == nullptr) return EGC_OK;
-  if (n_rows == 0) return EGC_OK;
-  if (rowptr == nullptr || xl == nullptr || a_src == nullptr || a_dst == nullptr || out == nullptr || lse == nullptr || g == nullptr)
-    return EGC_ERR_INVALID;
-  if (n_edges > 0 && col == nullptr) return EGC_ERR_INVALID;
   const bool src_pass = dxl != nullptr || d_a_src != nullptr;
-  if (src_pass && (t_rowptr == nullptr || (n_edges > 0 && t_col == nullptr))) return EGC_ERR_INVALID;
-  if (!counts_fit_int32(n_rows, n_edges)) return EGC_ERR_UNSUPPORTED;
+  const int rc = gat_backward_args(
+      rowptr, col, t_rowptr, t_col, n_rows, n_edges, heads, channels, xl, ld_xl, out, ld_out, lse, g, ld_g, dxl, ld_dxl, workspace,
+      workspace_bytes, egc_gat_backward_workspace_bytes,
+      ld_a_src >= heads && ld_a_dst >= heads && (d_a_src == nullptr || ld_d_a_src >= heads) && (d_a_dst == nullptr || ld_d_a_dst >= heads),
+      src_pass || d_a_dst != nullptr, EGC_OK, a_src != nullptr && a_dst != nullptr, src_pass);
+  if (rc != GAT_RUN) return rc;
   const Gat1BwdWs L = gat1_bwd_ws(n_rows, n_edges, heads, channels);
   float* ws = static_cast<float*>(workspace);
-  if (!workspace_ok(ws, workspace_bytes, L.total * sizeof(float))) return EGC_ERR_WORKSPACE;
-  if (!counts_fit_int32(L.row_blocks, L.chunk_blocks)) return EGC_ERR_UNSUPPORTED;
   Gat1Walk W = {};
   W.rowptr = rowptr, W.col = col, W.xl = xl, W.a_src = a_src, W.a_dst = a_dst, W.g = g, W.out = out, W.lse = lse, W.D = ws + L.D;
   W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_rows;
   W.ld_xl = ld_xl, W.ld_as = ld_a_src, W.ld_ad = ld_a_dst, W.ld_g = ld_g, W.ld_out = ld_out;
   gat_fill_walk(W, heads, channels, negative_slope, self_loops ? 1 : 0);
-  const int S = gat_geom(width).S;
-  const bool small = channels < 4;
-  const bool vec = all_mult4(width, ld_xl, ld_out, ld_g, ld_dxl) && all_aligned16(xl, out, g, dxl);
+  const GatForm form = gat_form(heads, channels, {ld_xl, ld_out, ld_g, ld_dxl}, {xl, out, g, dxl});
+  const unsigned chunk_grid = gat_grid(L.slots, W.G), row_grid = gat_grid(n_rows, W.G);
   // destination pass: chunks (only when d a_dst is wanted), then rows (d a_dst, and D, which the source pass reads for d a_src)
   if (d_a_dst != nullptr || d_a_src != nullptr) {
+    float* part = ws + L.part_dst;
     if (L.slots > 0 && d_a_dst != nullptr) {
-#define GAT1_DST_CHUNKS(S_, V_, M_) \
-  gat1_bwd_dst_kernel<S_, V_, M_, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(W, nullptr, 0, nullptr, L.slots, ws + L.part_dst)
-#define GAT1_DST_CHUNKS_DROP(S_, V_, M_) \
-  gat1_bwd_dst_drop_kernel<S_, V_, M_, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(W, *drop, nullptr, 0, nullptr, L.slots, ws + L.part_dst)
-      if (drop == nullptr) GAT_DISPATCH(GAT1_DST_CHUNKS);
-      else GAT_DISPATCH(GAT1_DST_CHUNKS_DROP);
-#undef GAT1_DST_CHUNKS
-#undef GAT1_DST_CHUNKS_DROP
+      gat_dispatch(form, [&](auto f) {
+        if (drop == nullptr) gat1_bwd_dst_kernel<f.S, f.VEC, f.SMALL, true><<<chunk_grid, 256, 0, stream>>>(W, nullptr, 0, nullptr, L.slots, part);
+        else gat1_bwd_dst_drop_kernel<f.S, f.VEC, f.SMALL, true><<<chunk_grid, 256, 0, stream>>>(W, *drop, nullptr, 0, nullptr, L.slots, part);
+      });
       EGC_LAUNCH_CHECK("gat1_bwd_dst_kernel(chunks)");
     }
-    Gat1Walk Wr = W;
-    if (d_a_dst == nullptr) Wr.n_edges = 0, Wr.self_loops = 0;   // only D is wanted: no entries, no self entry
-#define GAT1_DST_ROWS(S_, V_, M_) \
-  gat1_bwd_dst_kernel<S_, V_, M_, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(Wr, d_a_dst, ld_d_a_dst, ws + L.D, L.slots, ws + L.part_dst)
-#define GAT1_DST_ROWS_DROP(S_, V_, M_) \
-  gat1_bwd_dst_drop_kernel<S_, V_, M_, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(Wr, *drop, d_a_dst, ld_d_a_dst, ws + L.D, L.slots, ws + L.part_dst)
-    if (drop == nullptr) GAT_DISPATCH(GAT1_DST_ROWS);
-    else GAT_DISPATCH(GAT1_DST_ROWS_DROP);
-#undef GAT1_DST_ROWS
-#undef GAT1_DST_ROWS_DROP
+    const Gat1Walk Wr = d_a_dst != nullptr ? W : gat_walk_only_D(W);
+    gat_dispatch(form, [&](auto f) {
+      if (drop == nullptr) gat1_bwd_dst_kernel<f.S, f.VEC, f.SMALL, false><<<row_grid, 256, 0, stream>>>(Wr, d_a_dst, ld_d_a_dst, ws + L.D, L.slots, part);
+      else gat1_bwd_dst_drop_kernel<f.S, f.VEC, f.SMALL, false><<<row_grid, 256, 0, stream>>>(Wr, *drop, d_a_dst, ld_d_a_dst, ws + L.D, L.slots, part);
+    });
     EGC_LAUNCH_CHECK("gat1_bwd_dst_kernel(rows)");
   }
   if (src_pass) {
     Gat1Walk T = W;
     T.rowptr = t_rowptr, T.col = t_col;
     const int want_das = d_a_src != nullptr ? 1 : 0;
+    float* part = ws + L.part_src;
     if (L.slots > 0) {
-#define GAT1_SRC_CHUNKS(S_, V_, M_) \
-  gat1_bwd_src_kernel<S_, V_, M_, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(T, nullptr, 0, nullptr, 0, want_das, L.slots, ws + L.part_src)
-#define GAT1_SRC_CHUNKS_DROP(S_, V_, M_) \
-  gat1_bwd_src_drop_kernel<S_, V_, M_, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(T, *drop, nullptr, 0, nullptr, 0, want_das, L.slots, ws + L.part_src)
-      if (drop == nullptr) GAT_DISPATCH(GAT1_SRC_CHUNKS);
-      else GAT_DISPATCH(GAT1_SRC_CHUNKS_DROP);
-#undef GAT1_SRC_CHUNKS
-#undef GAT1_SRC_CHUNKS_DROP
+      gat_dispatch(form, [&](auto f) {
+        if (drop == nullptr) gat1_bwd_src_kernel<f.S, f.VEC, f.SMALL, true><<<chunk_grid, 256, 0, stream>>>(T, nullptr, 0, nullptr, 0, want_das, L.slots, part);
+        else gat1_bwd_src_drop_kernel<f.S, f.VEC, f.SMALL, true><<<chunk_grid, 256, 0, stream>>>(T, *drop, nullptr, 0, nullptr, 0, want_das, L.slots, part);
+      });
       EGC_LAUNCH_CHECK("gat1_bwd_src_kernel(chunks)");
     }
-#define GAT1_SRC_ROWS(S_, V_, M_) \
-  gat1_bwd_src_kernel<S_, V_, M_, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(T, dxl, ld_dxl, d_a_src, ld_d_a_src, want_das, L.slots, ws + L.part_src)
-#define GAT1_SRC_ROWS_DROP(S_, V_, M_) \
-  gat1_bwd_src_drop_kernel<S_, V_, M_, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(T, *drop, dxl, ld_dxl, d_a_src, ld_d_a_src, want_das, L.slots, ws + L.part_src)
-    if (drop == nullptr) GAT_DISPATCH(GAT1_SRC_ROWS);
-    else GAT_DISPATCH(GAT1_SRC_ROWS_DROP);
-#undef GAT1_SRC_ROWS
-#undef GAT1_SRC_ROWS_DROP
+    gat_dispatch(form, [&](auto f) {
+      if (drop == nullptr) gat1_bwd_src_kernel<f.S, f.VEC, f.SMALL, false><<<row_grid, 256, 0, stream>>>(
+          T, dxl, ld_dxl, d_a_src, ld_d_a_src, want_das, L.slots, part);
+      else gat1_bwd_src_drop_kernel<f.S, f.VEC, f.SMALL, false><<<row_grid, 256, 0, stream>>>(
+          T, *drop, dxl, ld_dxl, d_a_src, ld_d_a_src, want_das, L.slots, part);
+    });
     EGC_LAUNCH_CHECK("gat1_bwd_src_kernel(rows)");
   }
   return EGC_OK;
@@ -465,7 +411,7 @@ int egc_gat_backward_dropout_f32(const int32_t* rowptr, const int32_t* col, cons
                                  int32_t ld_d_a_src, float* d_a_dst, int32_t ld_d_a_dst, void* workspace, size_t workspace_bytes,
                                  double p, const int64_t* seed, egc_stream_t stream) {
   GatDrop R = {};
-  if (!gat_fill_drop(R, p, seed, t_edge_id) || (t_rowptr != nullptr && t_edge_id == nullptr)) return EGC_ERR_INVALID;
+  if (!gat_fill_drop(R, p, seed, t_rowptr, t_edge_id)) return EGC_ERR_INVALID;
   return gat1_backward(rowptr, col, t_rowptr, t_col, n_rows, n_edges, xl, ld_xl, a_src, ld_a_src, a_dst, ld_a_dst, heads, channels,
                        negative_slope, self_loops, out, ld_out, lse, g, ld_g, dxl, ld_dxl, d_a_src, ld_d_a_src, d_a_dst, ld_d_a_dst,
                        workspace, workspace_bytes, stream, &R);

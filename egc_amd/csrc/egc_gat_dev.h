@@ -1,6 +1,6 @@
-// Device and host pieces that the attention kernels (egc_gatv2.hip, egc_gat.hip) share: the padded-group row mapping and its
-// lane bookkeeping, the per-head sum across a group's lanes, the row loads and stores, the online-softmax state, the launch
-// geometry and the (S, VEC, SMALL) dispatch.
+// Device pieces that the attention kernels (egc_gatv2.hip, egc_gat.hip) share: the padded-group row mapping and its lane
+// bookkeeping, the per-head sum across a group's lanes, the row loads and stores, the online-softmax state and the dropout
+// mask.  Their host side (launch geometry, argument checks, the (S, VEC, SMALL) dispatch): egc_gat_host.h.
 //
 // Mapping: egc_row_chunks.h's, with the group padded.  A row's group is G = the power of two >= ceil(H C / 4) lanes, at most 64,
 // so it lies inside one wavefront; for H C > 256 the group is a whole wavefront and a lane owns two quads of columns (S = 2
@@ -201,6 +201,21 @@ __device__ inline void gat_load_heads(f4 (&v)[S], const float* __restrict__ a, i
 
 __device__ inline f4 gat_exp(f4 x) { return f4{expf(x[0]), expf(x[1]), expf(x[2]), expf(x[3])}; }
 
+// the score's activation and its derivative, per column
+__device__ inline f4 gat_lrelu(f4 z, float slope) {
+  f4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = z[i] > 0.f ? z[i] : slope * z[i];
+  return r;
+}
+
+__device__ inline f4 gat_dlrelu(f4 z, float slope) {
+  f4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = z[i] > 0.f ? 1.f : slope;
+  return r;
+}
+
 // The DROP forms of the device functions take ONE more argument at the end (the mask's GatMask; a batch's keep bits) and the
 // plain forms none: a parameter pack that is empty or holds that one argument.  So the plain instantiations are, token for
 // token, what they were before there was a mask.  gat_only: the pack's one element.
@@ -356,51 +371,5 @@ __device__ inline f4 gat_keep_f4(uint32_t bits, int s, float scale) {
   for (int i = 0; i < 4; ++i) r[i] = (bits >> (4 * s + i)) & 1u ? scale : 0.f;
   return r;
 }
-
-// ------------------------------------------------------------------------------------------------------------------- host
-
-struct GatGeom {
-  int32_t S, G, V;
-};
-
-static inline GatGeom gat_geom(int32_t width) {
-  const int lanes = (width + 3) / 4;
-  GatGeom q;
-  q.S = lanes > 64 ? 2 : 1;
-  int G = 1;
-  while (G < lanes && G < 64) G <<= 1;
-  q.G = G, q.V = q.S * G;
-  return q;
-}
-
-static inline int64_t gat_blocks(int64_t groups, int32_t G) { return ceil_div(groups, 256 / G); }
-static inline size_t gat_align(size_t floats) { return (floats + 3) & ~(size_t)3; }
-
-static inline bool gat_shape_ok(int32_t H, int32_t C) { return H >= 1 && C >= 1 && (int64_t)H * C <= 512; }
-
-static void gat_fill_walk(GatWalk& W, int32_t H, int32_t C, float slope, int32_t self_loops) {
-  const GatGeom q = gat_geom(H * C);
-  W.H = H, W.C = C, W.width = H * C, W.G = q.G, W.V = q.V, W.seg = (C + 3) / 4 + 1, W.self_loops = self_loops, W.slope = slope;
-}
-
-// p in (0, 1) and a seed: threshold = floor(p 2^32) and scale = 1 / (1 - p), both from p in double
-static inline bool gat_fill_drop(GatDrop& R, double p, const int64_t* seed, const int32_t* edge_id) {
-  if (!(p > 0.0 && p < 1.0) || seed == nullptr) return false;
-  R.seed = seed, R.edge_id = edge_id;
-  R.threshold = (uint32_t)(uint64_t)(p * 4294967296.0);
-  R.scale = (float)(1.0 / (1.0 - p));
-  return true;
-}
-
-#define GAT_DISPATCH(LAUNCH)                                   \
-  do {                                                         \
-    if (S == 2) {                                              \
-      if (vec) { if (small) LAUNCH(2, true, true); else LAUNCH(2, true, false); }      \
-      else { if (small) LAUNCH(2, false, true); else LAUNCH(2, false, false); }        \
-    } else {                                                   \
-      if (vec) { if (small) LAUNCH(1, true, true); else LAUNCH(1, true, false); }      \
-      else { if (small) LAUNCH(1, false, true); else LAUNCH(1, false, false); }        \
-    }                                                          \
-  } while (0)
 
 }  // namespace egc

@@ -13,18 +13,9 @@
 //   source pass (transposed CSR)         d xl_j = sum_i (alpha_ij g_i + d z_ij)
 // Every output element is written exactly once: no zero fill, no atomics.
 //
-// Mapping: egc_row_chunks.h's, with the group padded.  A row's group is G = the power of two >= ceil(H C / 4) lanes, at most 64,
-// so it lies inside one wavefront; for H C > 256 the group is a whole wavefront and a lane owns two quads of columns (S = 2
-// slots, 256 columns apart).  "Virtual lane" v = lane + G * slot owns columns 4 v .. 4 v + 3.
-//
-// Order rule of a per-head sum over the head's C columns (the score, d alpha, D).  It depends on H and C only, never on where in
-// the grid the row lands.
-//   C >= 4: per virtual lane, a = its columns of the head of its FIRST column added in ascending column order, b = its later
-//   columns (they belong to the next head) likewise.  The first virtual lane of a head's segment (the lanes whose first column
-//   lies in the head) takes a = b(v - 1) + a when the head starts inside lane v - 1.  Then a Hillis-Steele inclusive scan over
-//   the segment: for d = 1, 2, 4, ... < ceil(C / 4) + 1, a(v) = a(v) + a(v - d) where v - d is still in the segment (all lanes
-//   read before any writes).  The head's sum is a of the segment's last lane.
-//   C < 4: a head lies within virtual lanes v - 1 .. v + 1; every column adds the head's columns in ascending column order.
+// Mapping, and the order rule of a per-head sum over the head's C columns (the score, d alpha, D): egc_gat_dev.h's (a lane owns
+// four adjacent columns, a row's group lies inside one wavefront; gat_head_sums depends on H and C only, never on where in the
+// grid the row lands).
 // Order rule of a row: egc_row_chunks.h's chunks (skipped entries keep their place).  Inside a chunk, batches of AHEAD entries
 // (8 forward, 4 backward) from the chunk's start.
 // Forward, per batch: bm = max(m, the live scores in entry order); l = l * r + sum in entry order of exp(s_k - bm), acc likewise
@@ -43,7 +34,7 @@
 // egc_gat_dev.h's (dropped terms left out of acc, scale once at the row's end); backward: m' is a factor of the entry's term
 // where written, so at scale = 1 and nothing dropped the bits are those of the plain kernels.  A batch's Philox calls follow its
 // gathers in program order.
-#include "egc_gat_dev.h"
+#include "egc_gat_host.h"
 
 namespace egc {
 
@@ -51,18 +42,8 @@ namespace egc {
 // per-node scalars per head and needs no per-entry head sum: it has a kernel of its own, egc_gat.hip, on egc_gat_dev.h's mapping.)
 struct GatV2Score {
   float slope;
-  __device__ inline f4 act(f4 z) const {
-    f4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = z[i] > 0.f ? z[i] : slope * z[i];
-    return r;
-  }
-  __device__ inline f4 dact(f4 z) const {
-    f4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = z[i] > 0.f ? 1.f : slope;
-    return r;
-  }
+  __device__ inline f4 act(f4 z) const { return gat_lrelu(z, slope); }
+  __device__ inline f4 dact(f4 z) const { return gat_dlrelu(z, slope); }
 };
 
 // ---------------------------------------------------------------------------------------------------------------- forward
@@ -299,8 +280,7 @@ static inline GatBwdWs gat_bwd_ws(int64_t n_rows, int64_t n_edges, int32_t H, in
 using namespace egc;
 
 size_t egc_gatv2_forward_workspace_bytes(int64_t n_edges, int32_t heads, int32_t channels) {
-  if (n_edges <= 0 || !gat_shape_ok(heads, channels)) return 0;
-  return (size_t)chunk_slots(n_edges) * (size_t)gat_geom(heads * channels).V * 3 * 16;
+  return gat_fwd_ws_bytes(n_edges, heads, channels);
 }
 
 size_t egc_gatv2_backward_workspace_bytes(int64_t n_rows, int64_t n_edges, int32_t heads, int32_t channels) {
@@ -314,48 +294,28 @@ static int gat2_forward(const int32_t* rowptr, const int32_t* col, int64_t n_row
                         int32_t channels, float negative_slope, int32_t self_loops, float* out, int32_t ld_out, float* lse,
                         void* workspace, size_t workspace_bytes, egc_stream_t stream_, const GatDrop* drop) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0 || n_src_rows < 0) return EGC_ERR_INVALID;
-  const int32_t width = heads * channels;
-  if (ld_xl < width || ld_xr < width || ld_out < width) return EGC_ERR_INVALID;
-  if (self_loops && n_src_rows != n_rows) return EGC_ERR_INVALID;
-  if (n_rows == 0) return EGC_OK;
-  if (rowptr == nullptr || xr == nullptr || att == nullptr || out == nullptr || lse == nullptr) return EGC_ERR_INVALID;
-  if ((n_edges > 0 || self_loops) && xl == nullptr) return EGC_ERR_INVALID;
-  if (n_edges > 0 && (col == nullptr || n_src_rows == 0)) return EGC_ERR_INVALID;
-  if (!counts_fit_int32(n_rows, n_edges, n_src_rows)) return EGC_ERR_UNSUPPORTED;
+  const int rc = gat_forward_args(rowptr, col, n_rows, n_edges, n_src_rows, heads, channels, self_loops, xl, ld_xl, out, ld_out, lse,
+                                  workspace, workspace_bytes, ld_xr >= (int64_t)heads * channels, xr != nullptr && att != nullptr);
+  if (rc != GAT_RUN) return rc;
   GatWalk W = {};
   W.rowptr = rowptr, W.col = col, W.xl = xl, W.xr = xr, W.att = att;
   W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_src_rows, W.ld_xl = ld_xl, W.ld_xr = ld_xr;
   gat_fill_walk(W, heads, channels, negative_slope, self_loops ? 1 : 0);
   const GatV2Score sc = {negative_slope};
-  const int S = gat_geom(width).S;
-  const bool small = channels < 4;
-  const bool vec = all_mult4(width, ld_xl, ld_xr, ld_out) && all_aligned16(xl, xr, out);
+  const GatForm form = gat_form(heads, channels, {ld_xl, ld_xr, ld_out}, {xl, xr, out});
   const int64_t slots = chunk_slots(n_edges);
   float* ws = static_cast<float*>(workspace);
   if (slots > 0) {
-    if (!workspace_ok(ws, workspace_bytes, egc_gatv2_forward_workspace_bytes(n_edges, heads, channels))) return EGC_ERR_WORKSPACE;
-    unsigned blocks;
-    if (grid_blocks(slots, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
-#define GAT_FWD_CHUNKS(S_, V_, M_) gat_fwd_chunks_kernel<S_, V_, M_, GatV2Score><<<blocks, 256, 0, stream>>>(W, sc, slots, ws)
-#define GAT_FWD_CHUNKS_DROP(S_, V_, M_) \
-  gat_fwd_chunks_drop_kernel<S_, V_, M_, GatV2Score><<<blocks, 256, 0, stream>>>(W, sc, *drop, slots, ws)
-    if (drop == nullptr) GAT_DISPATCH(GAT_FWD_CHUNKS);
-    else GAT_DISPATCH(GAT_FWD_CHUNKS_DROP);
-#undef GAT_FWD_CHUNKS
-#undef GAT_FWD_CHUNKS_DROP
+    gat_dispatch(form, [&](auto f) {
+      if (drop == nullptr) gat_fwd_chunks_kernel<f.S, f.VEC, f.SMALL, GatV2Score><<<gat_grid(slots, W.G), 256, 0, stream>>>(W, sc, slots, ws);
+      else gat_fwd_chunks_drop_kernel<f.S, f.VEC, f.SMALL, GatV2Score><<<gat_grid(slots, W.G), 256, 0, stream>>>(W, sc, *drop, slots, ws);
+    });
     EGC_LAUNCH_CHECK("gat_fwd_chunks_kernel");
   }
-  unsigned blocks;
-  if (grid_blocks(n_rows, 256 / W.G, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
-#define GAT_FWD_ROWS(S_, V_, M_) \
-  gat_fwd_rows_kernel<S_, V_, M_, GatV2Score><<<blocks, 256, 0, stream>>>(W, sc, out, ld_out, lse, slots, ws)
-#define GAT_FWD_ROWS_DROP(S_, V_, M_) \
-  gat_fwd_rows_drop_kernel<S_, V_, M_, GatV2Score><<<blocks, 256, 0, stream>>>(W, sc, *drop, out, ld_out, lse, slots, ws)
-  if (drop == nullptr) GAT_DISPATCH(GAT_FWD_ROWS);
-  else GAT_DISPATCH(GAT_FWD_ROWS_DROP);
-#undef GAT_FWD_ROWS
-#undef GAT_FWD_ROWS_DROP
+  gat_dispatch(form, [&](auto f) {
+    if (drop == nullptr) gat_fwd_rows_kernel<f.S, f.VEC, f.SMALL, GatV2Score><<<gat_grid(n_rows, W.G), 256, 0, stream>>>(W, sc, out, ld_out, lse, slots, ws);
+    else gat_fwd_rows_drop_kernel<f.S, f.VEC, f.SMALL, GatV2Score><<<gat_grid(n_rows, W.G), 256, 0, stream>>>(W, sc, *drop, out, ld_out, lse, slots, ws);
+  });
   EGC_LAUNCH_CHECK("gat_fwd_rows_kernel");
   return EGC_OK;
 }
@@ -374,7 +334,7 @@ int egc_gatv2_forward_dropout_f32(const int32_t* rowptr, const int32_t* col, int
                                   float* lse, void* workspace, size_t workspace_bytes, double p, const int64_t* seed,
                                   egc_stream_t stream) {
   GatDrop R = {};
-  if (!gat_fill_drop(R, p, seed, nullptr)) return EGC_ERR_INVALID;
+  if (!gat_fill_drop(R, p, seed, nullptr, nullptr)) return EGC_ERR_INVALID;
   return gat2_forward(rowptr, col, n_rows, n_edges, n_src_rows, xl, ld_xl, xr, ld_xr, att, heads, channels, negative_slope,
                       self_loops, out, ld_out, lse, workspace, workspace_bytes, stream, &R);
 }
@@ -386,60 +346,44 @@ static int gat2_backward(const int32_t* rowptr, const int32_t* col, const int32_
                          int32_t ld_dxr, float* datt, void* workspace, size_t workspace_bytes, egc_stream_t stream_,
                          const GatDrop* drop) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!gat_shape_ok(heads, channels) || n_rows < 0 || n_edges < 0) return EGC_ERR_INVALID;
-  const int32_t width = heads * channels;
-  if (ld_xl < width || ld_xr < width || ld_out < width || ld_g < width) return EGC_ERR_INVALID;
-  if ((dxl != nullptr && ld_dxl < width) || (dxr != nullptr && ld_dxr < width)) return EGC_ERR_INVALID;
-  if (dxl == nullptr && dxr == nullptr && datt == nullptr) return EGC_OK;
-  if (n_rows == 0) return datt == nullptr ? EGC_OK : EGC_ERR_INVALID;   // (d att of nothing is the caller's zero)
-  if (rowptr == nullptr || xl == nullptr || xr == nullptr || att == nullptr || out == nullptr || lse == nullptr || g == nullptr)
-    return EGC_ERR_INVALID;
-  if (n_edges > 0 && col == nullptr) return EGC_ERR_INVALID;
-  if (dxl != nullptr && (t_rowptr == nullptr || (n_edges > 0 && t_col == nullptr))) return EGC_ERR_INVALID;
-  if (!counts_fit_int32(n_rows, n_edges)) return EGC_ERR_UNSUPPORTED;
+  const int64_t width = (int64_t)heads * channels;
+  const int rc = gat_backward_args(rowptr, col, t_rowptr, t_col, n_rows, n_edges, heads, channels, xl, ld_xl, out, ld_out, lse, g, ld_g,
+                                   dxl, ld_dxl, workspace, workspace_bytes, egc_gatv2_backward_workspace_bytes,
+                                   ld_xr >= width && (dxr == nullptr || ld_dxr >= width), dxl != nullptr || dxr != nullptr || datt != nullptr,
+                                   datt == nullptr ? EGC_OK : EGC_ERR_INVALID,   // (d att of nothing is the caller's zero)
+                                   xr != nullptr && att != nullptr, dxl != nullptr);
+  if (rc != GAT_RUN) return rc;
   const GatBwdWs L = gat_bwd_ws(n_rows, n_edges, heads, channels);
   float* ws = static_cast<float*>(workspace);
-  if (!workspace_ok(ws, workspace_bytes, L.total * sizeof(float))) return EGC_ERR_WORKSPACE;
   GatWalk W = {};
   W.rowptr = rowptr, W.col = col, W.xl = xl, W.xr = xr, W.att = att, W.g = g, W.out = out, W.lse = lse, W.D = ws + L.D;
   W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_rows;
   W.ld_xl = ld_xl, W.ld_xr = ld_xr, W.ld_g = ld_g, W.ld_out = ld_out;
   gat_fill_walk(W, heads, channels, negative_slope, self_loops ? 1 : 0);
   const GatV2Score sc = {negative_slope};
-  const int S = gat_geom(width).S;
-  const bool small = channels < 4;
-  const bool vec = all_mult4(width, ld_xl, ld_xr, ld_out, ld_g, ld_dxl, ld_dxr) && all_aligned16(xl, xr, out, g, dxl, dxr);
-  if (!counts_fit_int32(L.row_blocks, L.chunk_blocks)) return EGC_ERR_UNSUPPORTED;
+  const GatForm form = gat_form(heads, channels, {ld_xl, ld_xr, ld_out, ld_g, ld_dxl, ld_dxr}, {xl, xr, out, g, dxl, dxr});
+  const unsigned chunk_grid = gat_grid(L.slots, W.G), row_grid = gat_grid(n_rows, W.G);
   float* part = datt != nullptr ? ws + L.part_att : nullptr;
   // destination pass: chunks (only when something they produce is wanted), then rows (always: the source pass reads D)
-  if (L.slots > 0 && (dxr != nullptr || datt != nullptr)) {
+  const bool dst_sums = dxr != nullptr || datt != nullptr;
+  if (L.slots > 0 && dst_sums) {
     float* cpart = part != nullptr ? part + (size_t)L.row_blocks * width : nullptr;
-#define GAT_DST_CHUNKS(S_, V_, M_)                                                                               \
-  gat_bwd_dst_kernel<S_, V_, M_, GatV2Score, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(W, sc, nullptr, 0, nullptr, L.slots, \
-                                                                                                 ws + L.part_xr, cpart)
-#define GAT_DST_CHUNKS_DROP(S_, V_, M_)                                                                                    \
-  gat_bwd_dst_drop_kernel<S_, V_, M_, GatV2Score, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(W, sc, *drop, nullptr, 0, nullptr, \
-                                                                                                      L.slots, ws + L.part_xr, cpart)
-    if (drop == nullptr) GAT_DISPATCH(GAT_DST_CHUNKS);
-    else GAT_DISPATCH(GAT_DST_CHUNKS_DROP);
-#undef GAT_DST_CHUNKS
-#undef GAT_DST_CHUNKS_DROP
+    gat_dispatch(form, [&](auto f) {
+      if (drop == nullptr) gat_bwd_dst_kernel<f.S, f.VEC, f.SMALL, GatV2Score, true><<<chunk_grid, 256, 0, stream>>>(
+          W, sc, nullptr, 0, nullptr, L.slots, ws + L.part_xr, cpart);
+      else gat_bwd_dst_drop_kernel<f.S, f.VEC, f.SMALL, GatV2Score, true><<<chunk_grid, 256, 0, stream>>>(
+          W, sc, *drop, nullptr, 0, nullptr, L.slots, ws + L.part_xr, cpart);
+    });
     EGC_LAUNCH_CHECK("gat_bwd_dst_kernel(chunks)");
   }
   {
-    GatWalk Wr = W;
-    if (dxr == nullptr && datt == nullptr) Wr.n_edges = 0;   // only D is wanted: no entries, and the self entry's sums are unused
-    if (dxr == nullptr && datt == nullptr) Wr.self_loops = 0;
-#define GAT_DST_ROWS(S_, V_, M_)                                                                                                   \
-  gat_bwd_dst_kernel<S_, V_, M_, GatV2Score, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(Wr, sc, dxr, ld_dxr, ws + L.D, L.slots, \
-                                                                                                ws + L.part_xr, part)
-#define GAT_DST_ROWS_DROP(S_, V_, M_)                                                                                          \
-  gat_bwd_dst_drop_kernel<S_, V_, M_, GatV2Score, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(Wr, sc, *drop, dxr, ld_dxr, ws + L.D, \
-                                                                                                     L.slots, ws + L.part_xr, part)
-    if (drop == nullptr) GAT_DISPATCH(GAT_DST_ROWS);
-    else GAT_DISPATCH(GAT_DST_ROWS_DROP);
-#undef GAT_DST_ROWS
-#undef GAT_DST_ROWS_DROP
+    const GatWalk Wr = dst_sums ? W : gat_walk_only_D(W);   // (only D: the self entry's sums are unused too)
+    gat_dispatch(form, [&](auto f) {
+      if (drop == nullptr) gat_bwd_dst_kernel<f.S, f.VEC, f.SMALL, GatV2Score, false><<<row_grid, 256, 0, stream>>>(
+          Wr, sc, dxr, ld_dxr, ws + L.D, L.slots, ws + L.part_xr, part);
+      else gat_bwd_dst_drop_kernel<f.S, f.VEC, f.SMALL, GatV2Score, false><<<row_grid, 256, 0, stream>>>(
+          Wr, sc, *drop, dxr, ld_dxr, ws + L.D, L.slots, ws + L.part_xr, part);
+    });
     EGC_LAUNCH_CHECK("gat_bwd_dst_kernel(rows)");
   }
   if (datt != nullptr) {
@@ -461,24 +405,16 @@ static int gat2_backward(const int32_t* rowptr, const int32_t* col, const int32_
     GatWalk T = W;
     T.rowptr = t_rowptr, T.col = t_col;
     if (L.slots > 0) {
-#define GAT_SRC_CHUNKS(S_, V_, M_) \
-  gat_bwd_src_kernel<S_, V_, M_, GatV2Score, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(T, sc, nullptr, 0, L.slots, ws + L.part_xl)
-#define GAT_SRC_CHUNKS_DROP(S_, V_, M_) \
-  gat_bwd_src_drop_kernel<S_, V_, M_, GatV2Score, true><<<(unsigned)L.chunk_blocks, 256, 0, stream>>>(T, sc, *drop, nullptr, 0, L.slots, ws + L.part_xl)
-      if (drop == nullptr) GAT_DISPATCH(GAT_SRC_CHUNKS);
-      else GAT_DISPATCH(GAT_SRC_CHUNKS_DROP);
-#undef GAT_SRC_CHUNKS
-#undef GAT_SRC_CHUNKS_DROP
+      gat_dispatch(form, [&](auto f) {
+        if (drop == nullptr) gat_bwd_src_kernel<f.S, f.VEC, f.SMALL, GatV2Score, true><<<chunk_grid, 256, 0, stream>>>(T, sc, nullptr, 0, L.slots, ws + L.part_xl);
+        else gat_bwd_src_drop_kernel<f.S, f.VEC, f.SMALL, GatV2Score, true><<<chunk_grid, 256, 0, stream>>>(T, sc, *drop, nullptr, 0, L.slots, ws + L.part_xl);
+      });
       EGC_LAUNCH_CHECK("gat_bwd_src_kernel(chunks)");
     }
-#define GAT_SRC_ROWS(S_, V_, M_) \
-  gat_bwd_src_kernel<S_, V_, M_, GatV2Score, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(T, sc, dxl, ld_dxl, L.slots, ws + L.part_xl)
-#define GAT_SRC_ROWS_DROP(S_, V_, M_) \
-  gat_bwd_src_drop_kernel<S_, V_, M_, GatV2Score, false><<<(unsigned)L.row_blocks, 256, 0, stream>>>(T, sc, *drop, dxl, ld_dxl, L.slots, ws + L.part_xl)
-    if (drop == nullptr) GAT_DISPATCH(GAT_SRC_ROWS);
-    else GAT_DISPATCH(GAT_SRC_ROWS_DROP);
-#undef GAT_SRC_ROWS
-#undef GAT_SRC_ROWS_DROP
+    gat_dispatch(form, [&](auto f) {
+      if (drop == nullptr) gat_bwd_src_kernel<f.S, f.VEC, f.SMALL, GatV2Score, false><<<row_grid, 256, 0, stream>>>(T, sc, dxl, ld_dxl, L.slots, ws + L.part_xl);
+      else gat_bwd_src_drop_kernel<f.S, f.VEC, f.SMALL, GatV2Score, false><<<row_grid, 256, 0, stream>>>(T, sc, *drop, dxl, ld_dxl, L.slots, ws + L.part_xl);
+    });
     EGC_LAUNCH_CHECK("gat_bwd_src_kernel(rows)");
   }
   return EGC_OK;
@@ -501,7 +437,7 @@ int egc_gatv2_backward_dropout_f32(const int32_t* rowptr, const int32_t* col, co
                                    const float* g, int32_t ld_g, float* dxl, int32_t ld_dxl, float* dxr, int32_t ld_dxr, float* datt,
                                    void* workspace, size_t workspace_bytes, double p, const int64_t* seed, egc_stream_t stream) {
   GatDrop R = {};
-  if (!gat_fill_drop(R, p, seed, t_edge_id) || (t_rowptr != nullptr && t_edge_id == nullptr)) return EGC_ERR_INVALID;
+  if (!gat_fill_drop(R, p, seed, t_rowptr, t_edge_id)) return EGC_ERR_INVALID;
   return gat2_backward(rowptr, col, t_rowptr, t_col, n_rows, n_edges, xl, ld_xl, xr, ld_xr, att, heads, channels, negative_slope,
                        self_loops, out, ld_out, lse, g, ld_g, dxl, ld_dxl, dxr, ld_dxr, datt, workspace, workspace_bytes, stream, &R);
 }
