@@ -46,6 +46,8 @@ CODES = {"sum": _C.AGGR_SUM, "mean": _C.AGGR_MEAN, "max": _C.AGGR_MAX, "min": _C
 ACTS = {"none": _C.ACT_NONE, "softmax": _C.ACT_SOFTMAX, "sigmoid": _C.ACT_SIGMOID, "hardtanh": _C.ACT_HARDTANH}
 # (set of every aggregator but symnorm, set of symnorm): EGConv without / with self loops, EfficientGraphConv with them
 SETS = {"raw": (_C.SET_RAW, _C.SET_RAW), "looped": (_C.SET_LOOPED, _C.SET_LOOPED), "lay": (_C.SET_RAW, _C.SET_LOOPED)}
+# ... and the pair neither layer class produces but the C ABI accepts (tests/forward_ref.py): what the restatement looks a name up in
+ALL_SETS = dict(SETS, xl=(_C.SET_LOOPED, _C.SET_RAW))
 
 
 class Case(NamedTuple):
@@ -65,9 +67,10 @@ class Case(NamedTuple):
 
 
 def geometry(case):
-    """(L, Ls, ldb, slots, A, W) of a case, with the basis stride the layers choose."""
+    """(L, Ls, ldb, slots, A, W) of a case, with the basis stride the layers choose -- or the case's own ``stride``, where it
+    has one (tests/forward_ref.py: an unpadded basis whose length is no multiple of 4)."""
     L = case.out // case.H
-    Ls = padded_basis_stride(case.out, case.H, case.B)
+    Ls = getattr(case, "stride", 0) or padded_basis_stride(case.out, case.H, case.B)
     ldb = (case.B * Ls + 3) & ~3
     return L, Ls, ldb, ldb // 4, len(case.aggrs), case.H * case.B * len(case.aggrs)
 
@@ -83,17 +86,20 @@ def stdvar(case):
 # ------------------------------------------------------------------------------------------------------------------------------
 # the operand-level restatement
 
-def edge_sets(ei, n, sets):
-    """{set code: (edge list [2, E'], the raw edge every entry is -- E for an appended self loop)} for the two sets of ``sets``."""
+def edge_sets(ei, n, sets, n_loop=None):
+    """{set code: (edge list [2, E'], the raw edge every entry is -- E for an appended self loop)} for the two sets of ``sets``.
+    ``n_loop``: a LOOPED set appends self loops to rows < n_loop only (a layer without ``loops_all_nodes``: 1 + the largest index
+    of the edge list, as add_remaining_self_loops infers the node count); every row by default."""
     ei = np.asarray(ei, dtype=np.int64)
     e = ei.shape[1]
+    n_loop = n if n_loop is None else n_loop
     got = {}
-    for code in set(SETS[sets]):
+    for code in set(ALL_SETS[sets]):
         if code == _C.SET_RAW:
             got[code] = (ei, np.arange(e, dtype=np.int64))
         else:            # add_remaining_self_loops: existing loops dropped, one per node appended behind the remaining edges
-            looped, _ = orc.add_remaining_self_loops(ei, None, 1.0, n)
-            got[code] = (looped, np.concatenate([np.nonzero(ei[0] != ei[1])[0], np.full(n, e, dtype=np.int64)]))
+            looped, _ = orc.add_remaining_self_loops(ei, None, 1.0, n_loop)
+            got[code] = (looped, np.concatenate([np.nonzero(ei[0] != ei[1])[0], np.full(n_loop, e, dtype=np.int64)]))
     return got
 
 
@@ -121,14 +127,15 @@ def activate(w, H, act):
     return w
 
 
-def aggregate_combine(bases, weightings, ei, n, case):
-    """out [n, H L]; torch tensors of one dtype on the CPU, differentiable with respect to ``bases`` and ``weightings``."""
+def aggregate_combine(bases, weightings, ei, n, case, n_loop=None):
+    """out [n, H L]; torch tensors of one dtype on the CPU, differentiable with respect to ``bases`` and ``weightings``.
+    ``n_loop``: see ``edge_sets``."""
     L, Ls, ldb, _, A, W = geometry(case)
     assert bases.shape[1] == ldb and weightings.shape == (n, W)
     H, B = case.H, case.B
     xb = real_columns(bases, B, L, Ls)
-    sets = edge_sets(ei, n, case.sets)
-    agg_code, sym_code = SETS[case.sets]
+    sets = edge_sets(ei, n, case.sets, n_loop)
+    agg_code, sym_code = ALL_SETS[case.sets]
     aggs = []
     for a in case.aggrs:
         edges = sets[sym_code if a == "symnorm" else agg_code][0]
@@ -140,22 +147,22 @@ def aggregate_combine(bases, weightings, ei, n, case):
     return torch.einsum("nhba,nabl->nhl", w, agg).reshape(n, H * L)
 
 
-def gradients(bases, weightings, gout, ei, n, case, dtype):
+def gradients(bases, weightings, gout, ei, n, case, dtype, n_loop=None):
     """(out, d_bases [n_src, ldb], d_weightings [n, W]) as numpy, evaluated in ``dtype`` from float32 inputs."""
     b = torch.from_numpy(bases).to(dtype).requires_grad_(True)
     w = torch.from_numpy(weightings).to(dtype).requires_grad_(True)
-    out = aggregate_combine(b, w, ei, n, case)
+    out = aggregate_combine(b, w, ei, n, case, n_loop)
     out.backward(torch.from_numpy(gout).to(dtype))
     return out.detach().numpy(), b.grad.numpy(), w.grad.numpy()
 
 
-def arg_positions(bases, ei, n, case, which):
+def arg_positions(bases, ei, n, case, which, n_loop=None):
     """[n, B L] int64: the raw edge (position in ``ei``) the maximum (``which`` = "max") or minimum of every (row, real column)
     goes to -- the first entry of the aggregators' edge set attaining it, in edge order, the appended self loop last; E for that
     self loop, -1 for a row without entries."""
     L, Ls, _, _, _, _ = geometry(case)
     xb = real_columns(np.asarray(bases, dtype=np.float32), case.B, L, Ls)
-    edges, raw = edge_sets(ei, n, case.sets)[SETS[case.sets][0]]
+    edges, raw = edge_sets(ei, n, case.sets, n_loop)[ALL_SETS[case.sets][0]]
     _, arg = orc.scatter(xb[edges[0]], edges[1], n, which)
     return np.where(arg >= edges.shape[1], -1, raw[np.minimum(arg, edges.shape[1] - 1)])
 
