@@ -28,6 +28,9 @@ ACT_NONE, ACT_SOFTMAX, ACT_SIGMOID, ACT_HARDTANH = range(4)
 READOUT_SUM, READOUT_MEAN, READOUT_MAX = range(3)
 SOFTMAX_MAX_CLASSES = 1024   # EGC_SOFTMAX_MAX_CLASSES
 TYPED_MAX_RELATIONS = 8      # EGC_TYPED_MAX_RELATIONS
+TOKEN_HEAD_MAX_SEQ = 8       # EGC_TOKEN_HEAD_MAX_SEQ
+TOKEN_HEAD_SLAB = 64         # EGC_TOKEN_HEAD_SLAB: vocabulary columns of one workgroup step
+TOKEN_HEAD_MAX_IN = 384      # widest in_features of the token head's kernels
 # EGC_MPNN_*
 MPNN_ADD, MPNN_MEAN, MPNN_MAX = range(3)
 # EGC_PNA_* aggregators and scalers
@@ -194,6 +197,13 @@ SYMBOLS = {
                                                   C.c_void_p]),
     "egc_nll_log_softmax_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "egc_token_head_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "egc_token_head_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p]),
+    "egc_token_head_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_void_p]),
     "egc_typed_mean_chunk": (C.c_int32, []),
     "egc_typed_mean_workspace_bytes": (C.c_size_t, [C.POINTER(EgcTypedRel), C.c_int32, C.c_int32]),
     "egc_typed_mean_f32": (C.c_int, [C.POINTER(EgcTypedRel), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,

@@ -42,6 +42,9 @@ Public surface (mirrors the reference's layer API):
                        the output head and loss of the classification nets on the full-width logits: the row
                        log-softmax (+ arg-max) in one read, and ``F.nll_loss(x[:, :C].log_softmax(-1)[idx], y[idx])`` as
                        one read of the selected rows forward and one read plus one write of the gradient backward
+  TokenHead(in_features, num_classes, seq_len), token_head_loss / token_head_argmax
+                       the token predictors of the ogbg-code net (state-dict compatible) fused with their loss: the Linear
+                       maps, the mean cross-entropy over the positions, the arg-max and the backward without a logits array
   SparseTensor         minimal adj_t container (torch_sparse is not required)
   CSRGraph             device CSR + degree statistics + long-row plan
   GraphBatch           a PyG-style batch of small graphs (edge_index + graph offsets) for the tile kernels: the CSR of
@@ -62,6 +65,7 @@ from ._nbr import GCNConv, GINConv, SAGEConv, neighbor_sum  # noqa: F401
 from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean_pool, readout  # noqa: F401
 from .encoders import ASTNodeEncoder, AtomEncoder, Embedding, NodeEncoder  # noqa: F401
 from ._softmax import RowSelection, cross_entropy, log_softmax, nll_log_softmax  # noqa: F401
+from ._token_head import TokenHead, token_head_argmax, token_head_loss  # noqa: F401
 from .hipgraph import GraphedStep  # noqa: F401
 from . import ops  # noqa: F401  (registers torch.ops.egc_amd.*)
 

@@ -553,7 +553,7 @@ int egc_encoder_backward_f32(const float* d_out, const uint8_t* keep, float keep
  * ceil(n_classes / 4), at most 64; a lane adds its columns ascending, then the lanes combine over the xor distances
  * G/2, .., 1 -- a function of n_classes alone, so every call gives the same bits.
  * EGC_ERR_INVALID: a missing pointer, n_rows < 0, n_classes <= 0, ld < n_classes; EGC_ERR_UNSUPPORTED: n_classes >
- * EGC_SOFTMAX_MAX_CLASSES (the 5,002-wide token heads of ogbg-code stay with the caller), n_rows >= 2^38.  n_rows == 0 is
+ * EGC_SOFTMAX_MAX_CLASSES (the 5,002-wide token heads of ogbg-code have egc_token_head_forward_f32), n_rows >= 2^38.  n_rows == 0 is
  * fine.  16-byte accesses need the row strides % 4 == 0 and 16-byte aligned pointers; any other shape takes 4-byte ones.
  *
  * egc_log_softmax_forward_f32    out [n_rows, n_classes] dense: out[r, c] = x[r, c] - lse[r], lse[r] = m_r + log(sum_c
@@ -599,6 +599,52 @@ int egc_nll_log_softmax_forward_f32(const float* x, const int64_t* y, const int3
 int egc_nll_log_softmax_backward_f32(const float* x, const int64_t* y, const int32_t* cnt, const int64_t* total,
                                      const float* lse, const float* grad_loss, int64_t n_rows, int32_t n_classes, int32_t ld,
                                      int32_t mean, float* d_x, egc_stream_t stream);
+
+/* The token head of the reference's ogbg-code net fused with its loss (egc_token_head.hip): seq_len Linear maps of the pooled
+ * rows onto a vocabulary, the mean cross-entropy over the positions and the arg-max of every position,
+ *   preds = [Linear_t(x)];  loss = sum_t F.cross_entropy(preds[t], y[:, t]) / seq_len;  pred = argmax(preds[t], 1)
+ * (code/models.py:95-98, 121-125 with code/configs.py:63-66, 94), and what autograd derives from it.  Nothing of size
+ * [n_rows, n_classes] is written: with logit[g, t, c] = b_t[c] + sum_k x[g, k] W_t[c, k],
+ *   lse[g, t]    = m + log(sum_c exp(logit[g, t, c] - m)), m the maximum over c,
+ *   argmax[g, t] = the FIRST maximal column (ties go to the smaller column),
+ *   *loss        = (sum over g, t of (lse[g, t] - logit[g, t, y[g, t]])) / float(n_rows * seq_len),
+ *   grad         = grad_loss / float(n_rows * seq_len) * (exp(logit - lse) - [c == y[g, t]])       (never stored),
+ *   d_W_t = grad_t^T x,   d_b_t[c] = sum_g grad[g, t, c],   d_x = sum over t, c of grad[g, t, c] W_t[c, :].
+ * x [n_rows, in_features] float32; weights / biases / d_weights / d_biases: HOST arrays of seq_len device pointers to
+ * W_t [n_classes, in_features] and b_t [n_classes] (e.g. the parameters of seq_len nn.Linear and their gradients); y
+ * [n_rows, seq_len] int64 row-major; lse [n_rows, seq_len]; argmax [n_rows, seq_len] int32.
+ * Forward: y == NULL is the evaluation form (argmax only; loss, lse may be NULL); with y, argmax may be NULL.  A label
+ * outside [0, n_classes) is never used as an address: its term adds 0, its gradient is 0 and *host_flag = 1 is stored (may
+ * be NULL; the sticky word of egc_coo_to_csr_checked).  n_rows == 0 gives *loss = NaN, as torch's mean does.
+ * Backward: from the forward's lse and *grad_loss (device scalar).  d_x, d_weights, d_biases may each be NULL: that product
+ * is skipped.  Every element of every gradient is written (no zero fill by the caller).
+ * Order.  A logit is ONE float32 fma chain over a fixed permutation of k, the same for every row and column (the four k of
+ * MFMA e of step s are 16 s + e + {0, 4, 8, 12}), then one add of the bias: exact products, equal weights give equal bits.
+ * The columns of a position are cut into slabs of EGC_TOKEN_HEAD_SLAB; a slab's sum of exp(logit - slab max) adds a lane's four
+ * columns 16 apart ascending, then the 16 lanes over the xor distances 1, 2, 4, 8; lse adds the slabs' sums, each scaled by
+ * exp(slab max - m), in ascending slab order.  The loss adds term[i = g * seq_len + t]: thread i % 256 takes its terms
+ * ascending, the 256 thread sums are added four adjacent ones at a time, ascending, then over the xor distances 32 .. 1: the
+ * longest chain is ceil(n_rows seq_len / 256) + 3 + 6 adds.  Rows are walked in blocks of 128.  d_W_t: a block's rows in the
+ * order 16 (s / 4) + s % 4 + {0, 4, 8, 12}, s = 0 .. 31, one fma chain; the first block is written, each later block's sum is
+ * added to it (n_rows <= 128: every element written exactly once).  d_b_t: a block's rows ascending, blocks as d_W_t.  d_x:
+ * inside a workgroup one fma chain over its slabs ascending, a slab's columns in the order 16 (s / 4) + s % 4 + {0, 4, 8, 12},
+ * s = 0 .. 15; then the workgroups' partial arrays are added ascending.  No float atomics: two calls give the same bits.
+ * workspace: egc_token_head_workspace_bytes(n_rows, in_features, n_classes, seq_len) bytes (one size for both calls; 0
+ * outside the limits), 16-byte aligned, any content; EGC_ERR_WORKSPACE if smaller.  Forward: three launches (two without
+ * y), backward: two (one without d_x).
+ * EGC_ERR_INVALID: a missing pointer, n_rows < 0, in_features, n_classes or seq_len <= 0; EGC_ERR_UNSUPPORTED: in_features % 4
+ * != 0 or > 384, seq_len > EGC_TOKEN_HEAD_MAX_SEQ, n_classes or n_rows > 2^30, x / W_t / d_x / d_W_t not 16-byte aligned. */
+#define EGC_TOKEN_HEAD_MAX_SEQ 8
+#define EGC_TOKEN_HEAD_SLAB 64
+size_t egc_token_head_workspace_bytes(int64_t n_rows, int32_t in_features, int32_t n_classes, int32_t seq_len);
+int egc_token_head_forward_f32(const float* x, const float* const* weights, const float* const* biases, const int64_t* y,
+                               int64_t n_rows, int32_t in_features, int32_t n_classes, int32_t seq_len, float* loss, float* lse,
+                               int32_t* argmax, void* workspace, size_t workspace_bytes, int32_t* host_flag,
+                               egc_stream_t stream);
+int egc_token_head_backward_f32(const float* x, const float* const* weights, const float* const* biases, const int64_t* y,
+                                const float* lse, const float* grad_loss, int64_t n_rows, int32_t in_features, int32_t n_classes,
+                                int32_t seq_len, float* d_x, float* const* d_weights, float* const* d_biases, void* workspace,
+                                size_t workspace_bytes, egc_stream_t stream);
 
 /* Typed mean aggregation (egc_typed_mean.hip): the sparse part of the reference's R-GCN baseline layer,
  * `self.rel_lins[key](adj_t.matmul(x_dict[src], reduce="mean"))` per relation (rmag/models.py:61-72), and of what autograd
