@@ -41,6 +41,27 @@ def _as_csr(graph, n: int) -> CSRGraph:
     return g.csr() if isinstance(g, GraphBatch) else g
 
 
+def _layer_graph(x, edge_index, in_channels, who):
+    """The CSR of a layer's ``forward(x, edge_index)``: x is float32 [rows, in_channels] and the graph [rows, rows]."""
+    if x.dim() != 2 or x.size(1) != in_channels:
+        raise RuntimeError(f"egc_amd.{who}: x has shape {tuple(x.shape)}, expected (rows, {in_channels})")
+    _check_f32(x, "x")
+    g = _as_csr(edge_index, x.size(0))
+    if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
+        raise RuntimeError(f"egc_amd.{who}: the graph is [{g.n_nodes}, {g.n_src_rows}], x has {x.size(0)} rows")
+    return g
+
+
+def _out_block(out, out_col, width, who, grads):
+    """The ``out=`` inference form: columns out_col .. out_col + width of ``out``, the block the kernel writes.  It cannot
+    carry a gradient, so none of ``grads`` (the differentiable operands; None entries skipped) may require one."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in grads):
+        raise RuntimeError(f"egc_amd.{who}: out= is the inference form; call it under no_grad or without out")
+    if out.dim() != 2 or out_col < 0 or out_col + width > out.size(1):
+        raise RuntimeError(f"egc_amd: out must be [N, >= {out_col + width}] (got {tuple(out.shape)})")
+    return out[:, out_col:out_col + width]
+
+
 def _unit_columns(t):
     """``t`` [rows, columns] with unit column stride: itself when it has one (or is empty), else a dense copy."""
     return t.contiguous() if t.stride(1) != 1 and t.numel() > 0 else t

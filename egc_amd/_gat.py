@@ -28,7 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _C
-from ._args import _as_csr, _check_f32, _ptr, _rows2d, _unit_columns, _workspace
+from ._args import _as_csr, _check_f32, _layer_graph, _ptr, _rows2d, _unit_columns, _workspace
 from .graph import CSRGraph, _device_guard, _stream_ptr
 
 
@@ -274,13 +274,8 @@ class _AttentionConv(nn.Module):
         self.reset_parameters()
 
     def forward(self, x, edge_index):
-        if x.dim() != 2 or x.size(1) != self.in_channels:
-            raise RuntimeError(f"egc_amd.{type(self).__name__}: x has shape {tuple(x.shape)}, expected (rows, {self.in_channels})")
-        drop, all_dropped = _module_dropout(self, x)
-        _check_f32(x, "x")
-        g = _as_csr(edge_index, x.size(0))
-        if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
-            raise RuntimeError(f"egc_amd.{type(self).__name__}: the graph is [{g.n_nodes}, {g.n_src_rows}], x has {x.size(0)} rows")
+        drop, all_dropped = _module_dropout(self, x)   # (ahead of the device check: its message names the dropout)
+        g = _layer_graph(x, edge_index, self.in_channels, type(self).__name__)
         out = self._aggregate(x, g, float(self.negative_slope), bool(self.add_self_loops), drop, all_dropped)
         if not self.concat:
             out = out.view(-1, self.heads, self.out_channels).mean(dim=1)

@@ -18,7 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _C
-from ._args import _as_csr, _check_f32, _ptr, _rows2d, _unit_columns, _workspace
+from ._args import _as_csr, _check_f32, _layer_graph, _out_block, _ptr, _rows2d, _unit_columns, _workspace
 from .graph import CSRGraph, _device_guard, _stream_ptr
 
 _OP = {"add": _C.MPNN_ADD, "mean": _C.MPNN_MEAN, "max": _C.MPNN_MAX}
@@ -127,12 +127,7 @@ def mpnn_message(P, Q, graph, aggr, out=None, out_col=0):
     g = _as_csr(graph, Q.size(0))
     if out is None:
         return _MpnnMessage.apply(P, Q, g, op)
-    if torch.is_grad_enabled() and (P.requires_grad or Q.requires_grad):
-        raise RuntimeError("egc_amd.mpnn_message: out= is the inference form; call it under no_grad or without out")
-    d = Q.size(1)
-    if out.dim() != 2 or out_col < 0 or out_col + d > out.size(1):
-        raise RuntimeError(f"egc_amd: out must be [N, >= {out_col + d}] (got {tuple(out.shape)})")
-    block = out[:, out_col:out_col + d]
+    block = _out_block(out, out_col, Q.size(1), "mpnn_message", (P, Q))
     _launch_forward(P.detach(), Q.detach(), g, op, block, None)
     return block
 
@@ -211,12 +206,7 @@ class Mpnn(nn.Module):
         if self.in_dim != self.out_dim:
             raise RuntimeError(f"egc_amd.Mpnn: in_dim ({self.in_dim}) != out_dim ({self.out_dim}): the reference's update() "
                                "reshapes the aggregated messages by in_dim // towers and only works when they are equal")
-        if x.dim() != 2 or x.size(1) != self.in_dim:
-            raise RuntimeError(f"egc_amd.Mpnn: x has shape {tuple(x.shape)}, expected (rows, {self.in_dim})")
-        _check_f32(x, "x")
-        g = _as_csr(edge_index, x.size(0))
-        if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
-            raise RuntimeError(f"egc_amd.Mpnn: the graph is [{g.n_nodes}, {g.n_src_rows}], x has {x.size(0)} rows")
+        g = _layer_graph(x, edge_index, self.in_dim, "Mpnn")
         w_pq, b_pq, w_out, b_out = self._weights()
         pq = F.linear(x, w_pq, b_pq)                                         # layers.py:251-258, both halves of every tower
         a = _MpnnOperand.apply(pq, x, g, _OP[self.aggr])                     # aggregate + the [inputs | x_init] of update()

@@ -22,7 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _C
-from ._args import _as_csr, _check_f32, _ptr, _rows2d, _unit_columns, _workspace
+from ._args import _as_csr, _check_f32, _layer_graph, _out_block, _ptr, _rows2d, _unit_columns, _workspace
 from .graph import CSRGraph, _device_guard, _stream_ptr
 
 _FORM = {"sum": _C.NBR_SUM, "add": _C.NBR_SUM, "mean": _C.NBR_MEAN, "mean_t": _C.NBR_MEAN_T, "sym": _C.NBR_SYM}
@@ -149,12 +149,7 @@ def neighbor_sum(x, graph, form, x_self=None, self_scale=1.0, eps=None, skip_sel
     shared = x_self is x
     if out is None:
         return _NeighborSum.apply(x, None if shared else x_self, eps, g, code, skip, float(self_scale), scale, edge_scale, shared)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, x_self, eps)):
-        raise RuntimeError("egc_amd.neighbor_sum: out= is the inference form; call it under no_grad or without out")
-    d = x.size(1)
-    if out.dim() != 2 or out_col < 0 or out_col + d > out.size(1):
-        raise RuntimeError(f"egc_amd: out must be [N, >= {out_col + d}] (got {tuple(out.shape)})")
-    block = out[:, out_col:out_col + d]
+    block = _out_block(out, out_col, x.size(1), "neighbor_sum", (x, x_self, eps))
     xd = _unit_columns(x.detach())
     sd = xd if shared else (_unit_columns(x_self.detach()) if x_self is not None else None)
     _launch(g, False, xd, sd, code, skip, float(self_scale), eps.detach() if eps is not None else None, scale, edge_scale, block)
@@ -182,16 +177,6 @@ class _NbrOperand(torch.autograd.Function):
         dx = torch.empty((g.n_src_rows, d), dtype=torch.float32, device=da.device)
         _launch(g, True, da[:, :d], da[:, d:], _TRANSPOSE[ctx.form], False, 1.0, None, None, None, dx)
         return dx, None, None
-
-
-def _layer_graph(x, edge_index, in_channels, who):
-    if x.dim() != 2 or x.size(1) != in_channels:
-        raise RuntimeError(f"egc_amd.{who}: x has shape {tuple(x.shape)}, expected (rows, {in_channels})")
-    _check_f32(x, "x")
-    g = _as_csr(edge_index, x.size(0))
-    if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
-        raise RuntimeError(f"egc_amd.{who}: the graph is [{g.n_nodes}, {g.n_src_rows}], x has {x.size(0)} rows")
-    return g
 
 
 class GCNConv(nn.Module):

@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _C
-from ._args import _as_csr, _check_f32, _ptr, _rows2d, _unit_columns, _workspace
+from ._args import _as_csr, _check_f32, _layer_graph, _out_block, _ptr, _rows2d, _unit_columns, _workspace
 from .graph import CSRGraph, GraphBatch, SparseTensor, _device_guard, _stream_ptr
 
 AGGREGATORS = {"sum": _C.PNA_SUM, "mean": _C.PNA_MEAN, "min": _C.PNA_MIN, "max": _C.PNA_MAX, "var": _C.PNA_VAR, "std": _C.PNA_STD}
@@ -239,12 +239,7 @@ def pna_aggregate(P, Q, graph, aggregators, out=None, out_col=0):
     g = _q_and_graph(Q, graph)
     if out is None:
         return _PnaAggregate.apply(P, Q, g, codes)
-    if torch.is_grad_enabled() and (P.requires_grad or Q.requires_grad):
-        raise RuntimeError("egc_amd.pna_aggregate: out= is the inference form; call it under no_grad or without out")
-    wide = len(codes) * Q.size(1)
-    if out.dim() != 2 or out_col < 0 or out_col + wide > out.size(1):
-        raise RuntimeError(f"egc_amd: out must be [N, >= {out_col + wide}] (got {tuple(out.shape)})")
-    block = out[:, out_col:out_col + wide]
+    block = _out_block(out, out_col, len(codes) * Q.size(1), "pna_aggregate", (P, Q))
     _launch_aggregate(P.detach(), Q.detach(), g, codes, block)
     return block
 
@@ -378,12 +373,7 @@ class PNAConv(nn.Module):
         return self._fold
 
     def forward(self, x, edge_index):
-        if x.dim() != 2 or x.size(1) != self.in_channels:
-            raise RuntimeError(f"egc_amd.PNAConv: x has shape {tuple(x.shape)}, expected (rows, {self.in_channels})")
-        _check_f32(x, "x")
-        g = _as_csr(edge_index, x.size(0))
-        if g.n_nodes != x.size(0) or g.n_src_rows != x.size(0):
-            raise RuntimeError(f"egc_amd.PNAConv: the graph is [{g.n_nodes}, {g.n_src_rows}], x has {x.size(0)} rows")
+        g = _layer_graph(x, edge_index, self.in_channels, "PNAConv")
         w_pq, b_pq, w_y, w_base, b_base = self._weights()
         pq = F.linear(x, w_pq, b_pq)                                          # both halves of every tower's pre-transform
         agg = _PnaAggregatePQ.apply(pq, g, self._codes)                       # every aggregator, one gather pass

@@ -17,29 +17,14 @@
 // Order rule and mapping: egc_row_chunks.h.  A chunk's sum is ((0 + t0) + t1) + ... in entry order, the row's sum is chunk 0's
 // with the sums of chunks 1, 2, ... added in ascending order; the term's product or division, then the finish's division,
 // products and additions are one IEEE operation each (-ffp-contract=off).  Every element named is written exactly once: no
-// zero fill, no atomics, nothing read back.  A batch is NS_AHEAD entries; the scale and degree lookups of a batch are
-// requested with its rows, at clamped indices.
-#include "egc_row_chunks.h"
+// zero fill, no atomics, nothing read back.  The terms (GS_PLAIN, GS_DIV_DEG, GS_EDGE_SCALE, GS_SRC_SCALE), their fold, the
+// chunk kernel and the merge of the partials are egc_gather_sum.h's; this file holds the finish and the forms compiled.
+#include "egc_gather_sum.h"
 
 namespace egc {
 
-constexpr int NS_AHEAD = 8;
-
-// what an entry contributes: the row it names; that row over the named row's degree; that row times the entry's / the named row's scale
-enum { NS_PLAIN = 0, NS_DIV_DEG = 1, NS_EDGE_SCALE = 2, NS_SRC_SCALE = 3 };
 // how a row ends: agg (+ s * x_self); agg / deg (+ s * x_self); r * agg or r * (agg + r * x_self)
 enum { NS_FIN_SUM = 0, NS_FIN_MEAN = 1, NS_FIN_SYM = 2 };
-
-struct NsWalk {
-  const int32_t* rowptr;       // the CSR walked: n_rows + 1 offsets
-  const int32_t* col;          // n_edges entries: rows of `in`
-  const int32_t* deg_rowptr;   // NS_DIV_DEG: n_in_rows + 1 offsets
-  const float* src_scale;      // NS_SRC_SCALE: n_in_rows factors
-  const float* edge_scale;     // NS_EDGE_SCALE: n_edges factors
-  const float* in;             // n_in_rows rows of ld_in floats
-  int64_t n_rows, n_edges, n_in_rows;
-  int32_t ld_in, width, lanes;
-};
 
 struct NsFinish {
   const float* x_self;      // n_rows rows of ld_self floats (SELF forms)
@@ -50,70 +35,9 @@ struct NsFinish {
   int32_t ld_self, ld_out;
 };
 
-// NS_AHEAD consecutive entries of row `row` from p on (FULL: all of them exist; else those before p1, the others load entry
-// p1 - 1 again and are not taken) folded into acc in entry order
-template <bool VEC, int TERM, bool SKIP, bool FULL>
-__device__ inline void ns_take_batch(f4& acc, const NsWalk& W, int row, int64_t p, int64_t p1, int c) {
-  constexpr int N = FULL ? NS_AHEAD : NS_AHEAD - 1;
-  const int last_in = (int)W.n_in_rows - 1;   // (< 2^31: the entries are int32)
-  int j[N];
-  batch_rows<N, FULL>(j, W.col, p, p1, last_in);
-  float e[N];
-  if (TERM == NS_DIV_DEG) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) e[k] = (float)max(W.deg_rowptr[j[k] + 1] - W.deg_rowptr[j[k]], 1);
-  }
-  if (TERM == NS_EDGE_SCALE) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) e[k] = W.edge_scale[batch_entry<FULL>(p, k, p1)];
-  }
-  if (TERM == NS_SRC_SCALE) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) e[k] = W.src_scale[j[k]];
-  }
-  f4 v[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = tm_load<VEC>(W.in + (int64_t)j[k] * W.ld_in + c, c, W.width);
-  if (TERM == NS_DIV_DEG) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] /= e[k];
-  }
-  if (TERM == NS_EDGE_SCALE || TERM == NS_SRC_SCALE) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = e[k] * v[k];
-  }
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const bool live = (FULL || p + k < p1) && !(SKIP && j[k] == row);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = live ? acc[i] + v[k][i] : acc[i];
-  }
-}
-
-// the entries [p0, p1), p0 < p1, of row `row` in order: ((0 + t[p0]) + t[p0 + 1]) + ...
-template <bool VEC, int TERM, bool SKIP>
-__device__ inline f4 ns_reduce_entries(const NsWalk& W, int row, int64_t p0, int64_t p1, int c) {
-  f4 acc = f4{0.f, 0.f, 0.f, 0.f};
-  int64_t p = p0;
-#pragma unroll 1
-  for (; p + NS_AHEAD <= p1; p += NS_AHEAD) ns_take_batch<VEC, TERM, SKIP, true>(acc, W, row, p, p1, c);
-  if (p < p1) ns_take_batch<VEC, TERM, SKIP, false>(acc, W, row, p, p1, c);
-  return acc;
-}
-
-// workspace: [slots][lanes] f4 chunk sums
-template <bool VEC, int TERM, bool SKIP>
-__global__ void __launch_bounds__(256) nbr_sum_chunks_kernel(const NsWalk W, int64_t slots, float* __restrict__ ws) {
-  int64_t g, row, s0, s1;
-  int c;
-  group_lane(W.lanes, g, c);
-  if (g >= slots || !slot_chunk(W.rowptr, W.n_rows, W.n_edges, g, row, s0, s1)) return;
-  *reinterpret_cast<f4*>(ws + (g * W.lanes) * 4 + c) = ns_reduce_entries<VEC, TERM, SKIP>(W, (int)row, s0, s1, c);
-}
-
 // one group per row: chunk 0 here, chunks 1, 2, ... from the workspace in ascending order, the finish, the store
 template <bool VEC, int TERM, bool SKIP, int FIN, bool SELF>
-__global__ void __launch_bounds__(256) nbr_sum_rows_kernel(const NsWalk W, const NsFinish F, const float* __restrict__ ws) {
+__global__ void __launch_bounds__(256) nbr_sum_rows_kernel(const GsWalk W, const NsFinish F, const float* __restrict__ ws) {
   int64_t row, p0, p1;
   int c;
   group_lane(W.lanes, row, c);
@@ -121,11 +45,7 @@ __global__ void __launch_bounds__(256) nbr_sum_rows_kernel(const NsWalk W, const
   row_range(W.rowptr, W.n_edges, row, p0, p1);
   f4 agg = f4{0.f, 0.f, 0.f, 0.f};
   if (p1 > p0) {
-    agg = ns_reduce_entries<VEC, TERM, SKIP>(W, (int)row, p0, min(p0 + ROW_CHUNK, p1), c);
-    int64_t first, n_part;
-    row_partials(p0, p1, first, n_part);
-#pragma unroll 4
-    for (int64_t k = 0; k < n_part; ++k) agg += *reinterpret_cast<const f4*>(ws + ((first + k) * W.lanes) * 4 + c);
+    agg = gs_sum_row<VEC, TERM, SKIP>(W, (int)row, p0, p1, c, ws);
     if (FIN == NS_FIN_MEAN) agg = agg / (float)(p1 - p0);
   }
   if (FIN == NS_FIN_SYM) {
@@ -139,25 +59,11 @@ __global__ void __launch_bounds__(256) nbr_sum_rows_kernel(const NsWalk W, const
   tm_store<VEC>(F.out + row * F.ld_out + c, c, W.width, agg);
 }
 
-static inline size_t ns_workspace_bytes(int64_t n_edges, int32_t width) {
-  if (n_edges <= 0 || width <= 0) return 0;
-  return (size_t)chunk_slots(n_edges) * (size_t)((width + 3) / 4) * 16;
-}
-
 template <int TERM, bool SKIP, int FIN, bool SELF>
-static int ns_launch(const NsWalk& W, const NsFinish& F, bool vec, int64_t slots, float* ws, hipStream_t stream) {
-  unsigned blocks;
-  if (slots > 0) {
-    if (grid_blocks(slots * W.lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
-    if (vec) nbr_sum_chunks_kernel<true, TERM, SKIP><<<blocks, 256, 0, stream>>>(W, slots, ws);
-    else nbr_sum_chunks_kernel<false, TERM, SKIP><<<blocks, 256, 0, stream>>>(W, slots, ws);
-    EGC_LAUNCH_CHECK("nbr_sum_chunks_kernel");
-  }
-  if (grid_blocks(W.n_rows * W.lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
-  if (vec) nbr_sum_rows_kernel<true, TERM, SKIP, FIN, SELF><<<blocks, 256, 0, stream>>>(W, F, ws);
-  else nbr_sum_rows_kernel<false, TERM, SKIP, FIN, SELF><<<blocks, 256, 0, stream>>>(W, F, ws);
-  EGC_LAUNCH_CHECK("nbr_sum_rows_kernel");
-  return EGC_OK;
+static int ns_launch(const GsWalk& W, const NsFinish& F, bool vec, int64_t slots, float* ws, hipStream_t stream) {
+  const int st = gs_launch_chunks<TERM, SKIP>(W, vec, slots, ws, stream);
+  if (st != EGC_OK) return st;
+  return launch_lanes(vec, W.n_rows * W.lanes, stream, EGC_VEC_PAIR(nbr_sum_rows_kernel, TERM, SKIP, FIN, SELF), W, F, ws);
 }
 
 // The forms compiled: what GCNConv, SAGEConv and GINConv launch, forward and backward.
@@ -180,7 +86,7 @@ static bool ns_compiled(int form, bool skip, bool self) {
 
 using namespace egc;
 
-size_t egc_nbr_sum_workspace_bytes(int64_t n_edges, int32_t width) { return ns_workspace_bytes(n_edges, width); }
+size_t egc_nbr_sum_workspace_bytes(int64_t n_edges, int32_t width) { return gs_workspace_bytes(chunk_slots(n_edges), width); }
 
 int egc_nbr_sum_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_edges, int64_t n_src_rows, const float* x,
                     int32_t ld_x, const float* x_self, int32_t ld_self, int32_t width, int32_t form, int32_t skip_self_entries,
@@ -199,7 +105,7 @@ int egc_nbr_sum_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, i
   if (rowptr == nullptr || out == nullptr) return EGC_ERR_INVALID;
   if (n_edges > 0 && (col == nullptr || x == nullptr || n_src_rows == 0)) return EGC_ERR_INVALID;
   if (!counts_fit_int32(n_rows, n_edges, n_src_rows)) return EGC_ERR_UNSUPPORTED;
-  NsWalk W = {};
+  GsWalk W = {};
   W.rowptr = rowptr, W.col = col, W.deg_rowptr = deg_rowptr, W.src_scale = src_scale, W.edge_scale = edge_scale, W.in = x;
   W.n_rows = n_rows, W.n_edges = n_edges, W.n_in_rows = n_src_rows;
   W.ld_in = ld_x, W.width = width, W.lanes = (width + 3) / 4;
@@ -209,25 +115,25 @@ int egc_nbr_sum_f32(const int32_t* rowptr, const int32_t* col, int64_t n_rows, i
   const bool vec = all_mult4(width, ld_x, ld_out, self ? ld_self : 0) && all_aligned16(x, x_self, out);
   const int64_t slots = chunk_slots(n_edges);
   float* ws = static_cast<float*>(workspace);
-  if (slots > 0 && !workspace_ok(ws, workspace_bytes, ns_workspace_bytes(n_edges, width))) return EGC_ERR_WORKSPACE;
+  if (slots > 0 && !workspace_ok(ws, workspace_bytes, gs_workspace_bytes(slots, width))) return EGC_ERR_WORKSPACE;
 #define EGC_NBR(T, S, FI, X) return ns_launch<T, S, FI, X>(W, F, vec, slots, ws, stream)
   switch (form) {
     case EGC_NBR_SUM:
-      if (skip) EGC_NBR(NS_PLAIN, true, NS_FIN_SUM, true);
-      if (self) EGC_NBR(NS_PLAIN, false, NS_FIN_SUM, true);
-      EGC_NBR(NS_PLAIN, false, NS_FIN_SUM, false);
+      if (skip) EGC_NBR(GS_PLAIN, true, NS_FIN_SUM, true);
+      if (self) EGC_NBR(GS_PLAIN, false, NS_FIN_SUM, true);
+      EGC_NBR(GS_PLAIN, false, NS_FIN_SUM, false);
     case EGC_NBR_MEAN:
-      EGC_NBR(NS_PLAIN, false, NS_FIN_MEAN, false);
+      EGC_NBR(GS_PLAIN, false, NS_FIN_MEAN, false);
     case EGC_NBR_MEAN_T:
-      if (self) EGC_NBR(NS_DIV_DEG, false, NS_FIN_SUM, true);
-      EGC_NBR(NS_DIV_DEG, false, NS_FIN_SUM, false);
+      if (self) EGC_NBR(GS_DIV_DEG, false, NS_FIN_SUM, true);
+      EGC_NBR(GS_DIV_DEG, false, NS_FIN_SUM, false);
     default:   // EGC_NBR_SYM
       if (edge_scale != nullptr) {
-        if (skip) EGC_NBR(NS_EDGE_SCALE, true, NS_FIN_SYM, true);
-        EGC_NBR(NS_EDGE_SCALE, false, NS_FIN_SYM, false);
+        if (skip) EGC_NBR(GS_EDGE_SCALE, true, NS_FIN_SYM, true);
+        EGC_NBR(GS_EDGE_SCALE, false, NS_FIN_SYM, false);
       }
-      if (skip) EGC_NBR(NS_SRC_SCALE, true, NS_FIN_SYM, true);
-      EGC_NBR(NS_SRC_SCALE, false, NS_FIN_SYM, false);
+      if (skip) EGC_NBR(GS_SRC_SCALE, true, NS_FIN_SYM, true);
+      EGC_NBR(GS_SRC_SCALE, false, NS_FIN_SYM, false);
   }
 #undef EGC_NBR
 }

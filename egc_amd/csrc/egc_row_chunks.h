@@ -1,5 +1,6 @@
 // The chunked row walk of the gather kernels (egc_typed_mean.hip, egc_mpnn.hip, egc_gatv2.hip, egc_gat.hip, egc_pna.hip): its index
-// arithmetic, written once.  What is loaded per entry and how it is folded is each kernel's own.
+// arithmetic, written once.  What is loaded per entry and how it is folded is each kernel's own, except the float32 gather-sum
+// of the first two and egc_nbr_sum.hip, which is egc_gather_sum.h's.
 //
 // Order rule.  A row's entries are cut into consecutive chunks of ROW_CHUNK entries, counted from the row's first entry.  A chunk
 // is reduced from a fresh accumulator in entry order; the row's value is chunk 0's with the values of chunks 1, 2, ... merged in

@@ -15,12 +15,11 @@
 // Order rule and mapping: egc_row_chunks.h.  A chunk's sum is ((0 + v0) + v1) + ... in entry order, one IEEE add each
 // (-ffp-contract=off), v = pre * in (one multiply) where there is a pre; the row's sum is the sum of chunk 0 with the sums of
 // chunks 1, 2, ... added in ascending order; then post.  Every relation whose n_edges exceed one chunk has its own run of
-// workspace slots (TypedTable::slot0).  A batch is TM_AHEAD entries.
-#include "egc_row_chunks.h"
+// workspace slots (TypedTable::slot0).  The fold, the walk of an entry range, the merge of the partials and the launches are
+// egc_gather_sum.h's, which says why the term is not.
+#include "egc_gather_sum.h"
 
 namespace egc {
-
-constexpr int TM_AHEAD = 8;
 
 struct TypedTable {
   egc_typed_rel rel[EGC_TYPED_MAX_RELATIONS];
@@ -28,12 +27,12 @@ struct TypedTable {
   int32_t n_rels;
 };
 
-// TM_AHEAD consecutive entries from p on (FULL: all of them exist; else those before p1, the others load entry p1 - 1 again
-// and are not taken) added to acc in entry order
+// the terms v = pre * in of the GS_BATCH<FULL> entries from p on and the rows j they name (stage 1 of egc_gather_sum.h)
 template <bool VEC, bool FULL>
-__device__ inline void take_batch(f4& acc, const egc_typed_rel& R, int64_t p, int64_t p1, int c, int width) {
-  constexpr int N = FULL ? TM_AHEAD : TM_AHEAD - 1;
+__device__ inline GsTerms<FULL> batch_terms(const egc_typed_rel& R, int64_t p, int64_t p1, int c, int width) {
+  constexpr int N = GS_BATCH<FULL>;
   const int last_in = (int)R.n_in_rows - 1;   // (n_in_rows < 2^31: the entries are int32)
+  f4 v[N];
   int j[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) {
@@ -45,29 +44,26 @@ __device__ inline void take_batch(f4& acc, const egc_typed_rel& R, int64_t p, in
 #pragma unroll
     for (int k = 0; k < N; ++k) s[k] = 1.0f / (float)max(R.pre_rowptr[j[k] + 1] - R.pre_rowptr[j[k]], 1);
   }
-  f4 v[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) v[k] = tm_load<VEC>(R.in + (int64_t)j[k] * R.ld_in + c, c, width);
   if (R.pre_rowptr != nullptr) {
 #pragma unroll
     for (int k = 0; k < N; ++k) v[k] *= s[k];
   }
+  GsTerms<FULL> t;
 #pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const bool live = FULL || p + k < p1;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = live ? acc[i] + v[k][i] : acc[i];
-  }
+  for (int k = 0; k < N; ++k) t.v[k] = v[k], t.j[k] = j[k];
+  return t;
 }
 
 // ((0 + v[p0]) + v[p0 + 1]) + ... over the entries [p0, p1)
 template <bool VEC>
 __device__ inline f4 sum_entries(const egc_typed_rel& R, int64_t p0, int64_t p1, int c, int width) {
   f4 acc = f4{0.f, 0.f, 0.f, 0.f};
-  int64_t p = p0;
-#pragma unroll 1
-  for (; p + TM_AHEAD <= p1; p += TM_AHEAD) take_batch<VEC, true>(acc, R, p, p1, c, width);
-  if (p < p1) take_batch<VEC, false>(acc, R, p, p1, c, width);
+  gs_for_batches(p0, p1, [&](int64_t p, auto full) {
+    constexpr bool FULL = decltype(full)::value;
+    gs_fold_sum<false, FULL>(acc, batch_terms<VEC, FULL>(R, p, p1, c, width), 0, p, p1);
+  });
   return acc;
 }
 
@@ -115,11 +111,7 @@ __global__ void __launch_bounds__(256) typed_mean_rows_kernel(const TypedTable T
     int64_t p0, p1;
     row_range(R, row, p0, p1);
     f4 acc = sum_entries<VEC>(R, p0, min(p0 + ROW_CHUNK, p1), c, width);
-    int64_t first, n_part;   // chunks 1, 2, ...: their sums wait in the workspace, added in ascending order
-    row_partials(p0, p1, first, n_part);
-    const float* part = ws + ((T.slot0[r] + first) * lanes) * 4 + c;
-#pragma unroll 4
-    for (int64_t k = 0; k < n_part; ++k) acc += *reinterpret_cast<const f4*>(part + k * lanes * 4);
+    gs_add_partials(acc, ws, T.slot0[r], p0, p1, lanes, c);   // chunks 1, 2, ...: their sums wait in the workspace
     if (R.post_mean) {
       const float deg = (float)(p1 - p0);
       acc = p1 > p0 ? acc / deg : f4{0.f, 0.f, 0.f, 0.f};
@@ -144,7 +136,7 @@ size_t egc_typed_mean_workspace_bytes(const egc_typed_rel* rels, int32_t n_rels,
   if (rels == nullptr || n_rels <= 0 || n_rels > EGC_TYPED_MAX_RELATIONS || width <= 0) return 0;
   int64_t slots = 0;
   for (int r = 0; r < n_rels; ++r) slots += tm_slots(rels[r]);
-  return (size_t)slots * (size_t)((width + 3) / 4) * 16;
+  return gs_workspace_bytes(slots, width);
 }
 
 int egc_typed_mean_f32(const egc_typed_rel* rels, int32_t n_rels, int64_t n_rows, int32_t width, int32_t accumulate,
@@ -174,25 +166,14 @@ int egc_typed_mean_f32(const egc_typed_rel* rels, int32_t n_rels, int64_t n_rows
   }
   if (ld_out < cols_end) return EGC_ERR_INVALID;
   const int64_t slots = T.slot0[n_rels];
+  float* ws = static_cast<float*>(workspace);
   if (slots > 0) {
-    if (!workspace_ok(workspace, workspace_bytes, (size_t)slots * lanes * 16)) return EGC_ERR_WORKSPACE;
-    unsigned blocks;
-    if (grid_blocks(slots * lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
-    float* ws = static_cast<float*>(workspace);
-    if (vec) typed_mean_chunks_kernel<true><<<blocks, 256, 0, stream>>>(T, n_rows, width, lanes, ws);
-    else typed_mean_chunks_kernel<false><<<blocks, 256, 0, stream>>>(T, n_rows, width, lanes, ws);
-    EGC_LAUNCH_CHECK("typed_mean_chunks_kernel");
+    if (!workspace_ok(ws, workspace_bytes, gs_workspace_bytes(slots, width))) return EGC_ERR_WORKSPACE;
+    const int st = launch_lanes(vec, slots * lanes, stream, EGC_VEC_PAIR(typed_mean_chunks_kernel), T, n_rows, width, lanes, ws);
+    if (st != EGC_OK) return st;
   }
-  unsigned blocks;
-  if (grid_blocks((accumulate ? n_rows : n_rows * n_rels) * lanes, 256, blocks) != EGC_OK) return EGC_ERR_UNSUPPORTED;
-  const float* ws = static_cast<const float*>(workspace);
-#define EGC_TYPED_ROWS(V, A) \
-  typed_mean_rows_kernel<V, A><<<blocks, 256, 0, stream>>>(T, n_rows, width, lanes, out, ld_out, ws)
-  if (vec && accumulate) EGC_TYPED_ROWS(true, true);
-  else if (vec) EGC_TYPED_ROWS(true, false);
-  else if (accumulate) EGC_TYPED_ROWS(false, true);
-  else EGC_TYPED_ROWS(false, false);
+#define EGC_TYPED_ROWS(A, groups) \
+  launch_lanes(vec, (groups) * lanes, stream, EGC_VEC_PAIR(typed_mean_rows_kernel, A), T, n_rows, width, lanes, out, ld_out, ws)
+  return accumulate ? EGC_TYPED_ROWS(true, n_rows) : EGC_TYPED_ROWS(false, n_rows * n_rels);
 #undef EGC_TYPED_ROWS
-  EGC_LAUNCH_CHECK("typed_mean_rows_kernel");
-  return EGC_OK;
 }
