@@ -38,6 +38,10 @@ PNA_SUM, PNA_MEAN, PNA_MIN, PNA_MAX, PNA_VAR, PNA_STD = range(6)
 PNA_IDENTITY, PNA_AMPLIFICATION, PNA_ATTENUATION, PNA_LINEAR, PNA_INVERSE_LINEAR = range(5)
 # EGC_NBR_*
 NBR_SUM, NBR_MEAN, NBR_MEAN_T, NBR_SYM = range(4)
+# EGC_GP_*: header words of a gather plan, its forms
+GP_HEADER_INTS = 16
+GP_FORM, GP_COL_BITS, GP_TABLE_SIZE = range(3)
+GP_PACKED, GP_UNFIT = 1, 2
 
 _STATUS = {1: "EGC_ERR_INVALID", 2: "EGC_ERR_WORKSPACE", 3: "EGC_ERR_HIP", 4: "EGC_ERR_UNSUPPORTED"}
 
@@ -49,6 +53,8 @@ class EgcGraph(C.Structure):
         ("dis_raw", C.c_void_p), ("dis_looped", C.c_void_p),
         ("max_index", C.c_void_p), ("plan", C.c_void_p), ("n_chunks", C.c_int64),
         ("n_src_rows", C.c_int64), ("edge_dis_raw", C.c_void_p), ("edge_dis_looped", C.c_void_p),
+        ("gather_plan_raw", C.c_void_p), ("gather_plan_looped", C.c_void_p),
+        ("gather_plan_form_raw", C.c_int32), ("gather_plan_form_looped", C.c_int32),
     ]
 
 
@@ -98,6 +104,13 @@ SYMBOLS = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "egc_csr_edge_dis": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egc_gather_plan_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "egc_gather_plan_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "egc_gather_plan_offset": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "egc_gather_plan_form": (C.c_int32, [C.c_int64, C.c_int64, C.c_int32]),
+    "egc_gather_plan_build": (C.c_int, [C.POINTER(EgcGraph), C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
+    "egc_gather_plan_launches": (C.c_int64, []),
     "egc_csr_prepare": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "egc_bases_ld": (C.c_int32, [C.POINTER(EgcLayer)]),

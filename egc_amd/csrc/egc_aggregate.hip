@@ -647,6 +647,12 @@ int egc_aggregate_combine_train_rows_f32(const egc_graph* graph, const egc_layer
   return egc::arg_extrema(graph, layer, bases, ldb, stats, cnt, arg_max, arg_min, a8max, a8min, (hipStream_t)stream);
 }
 
+// EGC_NO_GATHER_PLAN set to anything but "" / "0": a static graph's gather plan is left alone
+static bool gather_plan_off() {
+  const char* v = getenv("EGC_NO_GATHER_PLAN");
+  return v != nullptr && v[0] != '\0' && !(v[0] == '0' && v[1] == '\0');
+}
+
 static int aggregate_combine_impl(const egc_graph* graph, const egc_layer* layer, const float* bases, int32_t ldb,
                                   const float* weightings, const float* bias, const egc_post* post, float* out,
                                   float* stats, int32_t* cnt_out, int64_t row_begin, int64_t row_end, void* workspace,
@@ -681,6 +687,23 @@ static int aggregate_combine_impl(const egc_graph* graph, const egc_layer* layer
   }
   a.max_index = graph->max_index;
   if (layer->loops_all_nodes == 0 && graph->max_index == nullptr) return EGC_ERR_INVALID;
+  // The gather plan of a static graph (egc_gather_plan_build), for a whole-graph inference launch on a square graph: the plan of
+  // the symnorm edge set (a layer without symnorm never looks at a plan's dis values: either plan serves it).
+  a.gp_form = a.gp_cb = 0;
+  a.gp_ent = nullptr;
+  a.gp_table = nullptr;
+  if (stats == nullptr && arg_max == nullptr && arg_min == nullptr && row_begin == 0 && (row_end < 0 || row_end == n) && n_src == n &&
+      !gather_plan_off()) {
+    const bool looped = layer_uses_symnorm(layer) ? layer->sym_set == EGC_SET_LOOPED : graph->gather_plan_looped != nullptr;
+    const int32_t* gp = looped ? graph->gather_plan_looped : graph->gather_plan_raw;
+    const int form = looped ? graph->gather_plan_form_looped : graph->gather_plan_form_raw;
+    if (gp != nullptr && (form & 0xff) == EGC_GP_PACKED) {
+      a.gp_form = EGC_GP_PACKED;
+      a.gp_cb = (form >> 8) & 0xff;
+      a.gp_table = reinterpret_cast<const float*>(gp + egc_gather_plan_offset(n, e, 0));
+      a.gp_ent = reinterpret_cast<const unsigned*>(gp + egc_gather_plan_offset(n, e, 1));
+    }
+  }
   a.plan = graph->plan;
   a.bases = bases;
   a.weightings = weightings;

@@ -100,6 +100,10 @@ struct AggArgs {
   int n_chunks_hint;       // host-known number of long-row chunks, or -1 (launch for the capacity)
   int l4_off;              // two-slots-per-lane kernel: first slot (inside a basis) of the set being finished (else 0)
   int wide_p0, wide_p1;    // two-slots-per-lane kernel: slots per basis of the lane's first / second set (P0 + P1 = Ls / 4)
+  // gather plan of a static graph (egc_gather_plan.hip; the fast kernel's PLAN form): gp_form = EGC_GP_PACKED, or 0 = no plan
+  int gp_form, gp_cb;        // gp_cb: bits of a packed entry that hold the source id (both from egc_graph.gather_plan_form_*)
+  const unsigned* gp_ent;    // [n_edges] col[p] | index of edge_dis[p] in gp_table << gp_cb
+  const float* gp_table;     // the distinct dis values
   int w_lds_stride;        // floats between the per-group weight strips in LDS
   int bias_lds_floats;     // floats of the per-wavefront bias strip in LDS
   // training forward only (egc_aggregate_combine_train_f32): the row's raw running aggregates, after the
@@ -200,6 +204,7 @@ __device__ inline __amdgpu_buffer_rsrc_t bases_rsrc(const AggArgs& a) {
 // Returns EGC_OK, an error, or EGC_ERR_UNSUPPORTED when the generic path must be used instead.
 bool fast_path_supported(const AggArgs& a, int layout, int chunks);
 int launch_fast(AggArgs a, int64_t n_nodes, const PlanCaps& caps, hipStream_t stream);
+void gather_plan_launched();   // egc_gather_plan.hip: counts the PLAN-form launches (egc_gather_plan_launches)
 // rows of 65..128 slots (the two ogbg-code nets): two slots per lane, short rows only (egc_aggregate_fast.hip)
 bool wide_path_supported(const AggArgs& a, int layout);
 int launch_wide_rows(AggArgs a, const PlanCaps& caps, hipStream_t stream);   // short rows AND long-row chunks: one launch

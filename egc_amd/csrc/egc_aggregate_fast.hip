@@ -42,7 +42,11 @@ namespace egc {
 // ---------------------------------------------------------------------------------------------
 // kernel
 // ---------------------------------------------------------------------------------------------
-template <int LPR_LOG2, int HPB, int NEED, class C>
+// PLAN (the inference instances without optional aggregates, on a static graph with a gather plan -- egc_gather_plan.hip): the
+// short-row role streams ONE word per entry, col[p] in its low a.gp_cb bits and above them the index of edge_dis[p] in the table
+// of the distinct dis values, where it streams col[p] and edge_dis[p] otherwise.  Rows are found through rowptr either way; the
+// table lookup feeds only the fold, not the gathers' addresses.
+template <int LPR_LOG2, int HPB, int NEED, class C, bool PLAN = false>
 // Inference variants (NEED == 0) fit 80 VGPRs without spilling when asked to, which buys the sixth wavefront per
 // SIMD; the variants carrying more running aggregates are left to the register allocator.
 #ifndef EGC_AGG_WAVES_SQ
@@ -101,6 +105,8 @@ agg_fast_kernel(AggArgs a) {
   const int n_end = a.row_end;
   if (r0 >= n_end) return;
   const int rp = a.rowptr[min(r0 + lane, a.n_nodes)];  // lanes 0..Q*G hold this wavefront's row pointers
+  const int* ent = PLAN ? reinterpret_cast<const int*>(a.gp_ent) : a.col;  // the entry stream: packed words / source ids
+  auto src_of = [&](int word) { return PLAN ? (int)((unsigned)word & ((1u << a.gp_cb) - 1u)) : word; };
   const int grp_addr = (g << LPR_LOG2) << 2;            // ds_bpermute byte address of the group's lane 0
   // stage the first row group's column indices (lane q of group g <- entry q of row r0 + g)
   int start_n = bperm(g << 2, rp);
@@ -109,7 +115,7 @@ agg_fast_kernel(AggArgs a) {
     const int deg = bperm((g + 1) << 2, rp) - start_n;
     nd_n = (r0 + g < n_end && deg <= EGC_LONG_ROW_THRESHOLD) ? deg : 0;
   }
-  int jj_n = q < nd_n ? a.col[start_n + q] : 0;
+  int jj_n = q < nd_n ? ent[start_n + q] : 0;
   for (int k = 0; k < Q; ++k) {
     const int rbase = r0 + k * G;
     if (rbase >= n_end) break;
@@ -121,7 +127,7 @@ agg_fast_kernel(AggArgs a) {
       start_n = bperm(((k + 1) * G + g) << 2, rp);
       const int deg = bperm(((k + 1) * G + g + 1) << 2, rp) - start_n;
       nd_n = (rbase + G + g < n_end && deg <= EGC_LONG_ROW_THRESHOLD) ? deg : 0;
-      jj_n = q < nd_n ? a.col[start_n + q] : 0;
+      jj_n = q < nd_n ? ent[start_n + q] : 0;
     }
     // wave-uniform trip count: entries still valid in any group
     int maxd = nd;
@@ -136,24 +142,30 @@ agg_fast_kernel(AggArgs a) {
 
     FAcc<NEED> acc;
     acc.init();
+    int jc = src_of(jj);   // the staged source ids (jj itself without a plan)
     if constexpr (NEED & NEED_SQ) {   // the variance's shift: the row's first entry (lane 0 of the group staged its column), also
       // when the layer's x-part excludes that entry (a self-entry under add_self_loops: its value is as good a shift, and 0 --
       // what the masked gather returns for it -- is none: tiny graphs full of self-entries, tools/tile_fuzz.py seed 77)
-      const int first = bperm(grp_addr, jj);
+      const int first = bperm(grp_addr, jc);
       acc.sh = load_slot(R.bases, (lane_live && nd > 0) ? (unsigned)first * row_bytes + slot_off : OOB);
     }
     int nself = 0;
     for (int ts = 0; ts < maxd; ts += LPR) {
-      if (ts > 0) jj = (ts + q < nd) ? a.col[start + ts + q] : 0;  // rows of more than LPR entries
+      if (ts > 0) {  // rows of more than LPR entries
+        jj = (ts + q < nd) ? ent[start + ts + q] : 0;
+        jc = src_of(jj);
+      }
       const bool pv = ts + q < nd;
-      const float dd = !pv ? 0.f : a.edis != nullptr ? a.edis[start + ts + q] : a.dis != nullptr ? a.dis[jj] : 0.f;
+      float dd;
+      if constexpr (PLAN) dd = (pv && a.dis != nullptr) ? a.gp_table[(unsigned)jj >> a.gp_cb] : 0.f;
+      else dd = !pv ? 0.f : a.edis != nullptr ? a.edis[start + ts + q] : a.dis != nullptr ? a.dis[jj] : 0.f;
       if (looped_any) {  // self-entries are excluded from LOOPED sets: count them per group
-        const unsigned long long sb = __ballot(pv && jj == row);
+        const unsigned long long sb = __ballot(pv && jc == row);
         nself += __popcll((sb >> (g << LPR_LOG2)) & ((LPR == 64) ? ~0ull : ((1ull << LPR) - 1ull)));
       }
       const int cnt = min(LPR, maxd - ts);  // wave-uniform
       for (int t0 = 0; t0 < cnt; t0 += FU)
-        gather_batch<NEED, C>(a, R, acc, grp_addr + (t0 << 2), 4, row, jj, dd, dis_i, lane_live ? nd : 0, ts + t0, 1, row_bytes,
+        gather_batch<NEED, C>(a, R, acc, grp_addr + (t0 << 2), 4, row, jc, dd, dis_i, lane_live ? nd : 0, ts + t0, 1, row_bytes,
                               slot_off, start);
     }
     // Opaque copy of the lane id: keeps the compiler from hoisting the epilogue's lane arithmetic out
@@ -509,6 +521,14 @@ bool fast_path_supported(const AggArgs& a, int layout, int chunks) {
 
 template <int LPR_LOG2, int HPB, int NEED, class C>
 static int launch_one(const AggArgs& a, unsigned grid, size_t lds, hipStream_t stream) {
+  if constexpr (NEED == 0) {   // every inference instance without optional aggregates has the PLAN form (a.gp_form: aggregate_combine_impl
+    if (a.gp_form == EGC_GP_PACKED) {   // offers a plan only to a whole-graph inference launch)
+      agg_fast_kernel<LPR_LOG2, HPB, NEED, C, true><<<grid, 256, lds, stream>>>(a);
+      EGC_LAUNCH_CHECK("agg_fast_kernel");
+      gather_plan_launched();
+      return EGC_OK;
+    }
+  }
   agg_fast_kernel<LPR_LOG2, HPB, NEED, C><<<grid, 256, lds, stream>>>(a);
   EGC_LAUNCH_CHECK("agg_fast_kernel");
   return EGC_OK;

@@ -95,6 +95,7 @@ class CSRGraph:
         self.edge_dis_raw = self.edge_dis_looped = None  # dis_*[col[p]] per entry (refresh_edge_dis)
         self._workspaces = {}
         self._n_chunks = None  # host copy of plan[1]; -1 = not read back (see c_struct)
+        self.gather_plans = {}  # "raw" / "looped" -> (plan tensor, host copy of its header): static graphs (trim_launches)
 
     # -- construction ---------------------------------------------------------------------
     @classmethod
@@ -274,7 +275,8 @@ class CSRGraph:
 
     def refresh_edge_dis(self):
         """(Re)build the per-entry copies of the source-side deg^-1/2 (egc_csr_edge_dis): the aggregate kernel then
-        streams them instead of gathering dis[col[p]].  Call again whenever dis_raw / dis_looped change."""
+        streams them instead of gathering dis[col[p]].  Call again whenever dis_raw / dis_looped change; the gather plans of
+        a static graph hold the same values and are rebuilt here with them."""
         lib = _C.load()
         dev = self.device
         e = self.n_edges
@@ -285,6 +287,8 @@ class CSRGraph:
             _C.check(lib.egc_csr_edge_dis(e, self.col.data_ptr(), self.dis_raw.data_ptr(), self.dis_looped.data_ptr(),
                                           self.edge_dis_raw.data_ptr(), self.edge_dis_looped.data_ptr(),
                                           _stream_ptr(dev)), "egc_csr_edge_dis")
+        if self.gather_plans:
+            self.rebuild_gather_plans()
 
     def transposed(self) -> "CSRGraph":
         """The transposed graph as a CSRGraph (rows = SOURCES, entries = destinations, with its own long-row
@@ -302,7 +306,7 @@ class CSRGraph:
                                                           _stream_ptr(dev)), "egc_csr_transposed_coo")
                 self._transposed = CSRGraph.from_edge_index(coo, ns, max(n, 1), _poll=False)   # (derived, not user input)
         if self._n_chunks is not None and self._n_chunks >= 0:   # a static graph: its transpose is one too
-            self._transposed.trim_launches()
+            self._transposed.trim_launches(gather_plan=False)   # (the backward walks it: no inference aggregate reads it)
         return self._transposed
 
     def workspace(self, nbytes: int, zero_bytes: int | None = None) -> torch.Tensor:
@@ -334,11 +338,25 @@ class CSRGraph:
                            self.edge_id.data_ptr(), self.dis_raw.data_ptr(), self.dis_looped.data_ptr(),
                            self.max_index.data_ptr(), self.plan.data_ptr(), self._n_chunks, self.n_src_rows,
                            self.edge_dis_raw.data_ptr() if self.edge_dis_raw is not None else None,
-                           self.edge_dis_looped.data_ptr() if self.edge_dis_looped is not None else None)
+                           self.edge_dis_looped.data_ptr() if self.edge_dis_looped is not None else None,
+                           *self._gather_plan_fields())
+
+    def _gather_plan_fields(self):
+        """(plan_raw, plan_looped, form_raw, form_looped) of the C view: pointers (None = no plan) and the host copies of
+        the header words FORM | COL_BITS << 8."""
+        if not self.gather_plans:          # (per-batch graphs pass here on every layer call)
+            return None, None, 0, 0
+        ptrs, forms = [], []
+        for name in ("raw", "looped"):
+            hit = self.gather_plans.get(name)
+            ptrs.append(hit[0].data_ptr() if hit is not None else None)
+            forms.append((hit[1][_C.GP_FORM] | (hit[1][_C.GP_COL_BITS] << 8)) if hit is not None else 0)
+        return (*ptrs, *forms)
 
     def tensors(self) -> list:
         """The device tensors the C view points into (what a compiled autograd node keeps alive next to its copy of the struct)."""
         ts = [self.rowptr, self.col, self.edge_id, self.dis_raw, self.dis_looped, self.max_index, self.plan]
+        ts += [p for p, _ in self.gather_plans.values()]
         return ts + [t for t in (self.edge_dis_raw, self.edge_dis_looped) if t is not None]
 
     def c_addr(self) -> int:
@@ -369,13 +387,60 @@ class CSRGraph:
             cache.setdefault("_keep", []).append(spec)      # id(spec) stays unique while the entry lives
         return ws
 
-    def trim_launches(self) -> "CSRGraph":
-        """Read the long-row chunk count back to the host (ONE synchronisation) so that later launches carry only
-        the chunk workgroups that exist instead of the plan's capacity -- for a graph that is built once and used
-        many times (``cached=True`` layers, full-graph training); about 4 us per launch at ogbn-arxiv size."""
+    def trim_launches(self, gather_plan: bool = True) -> "CSRGraph":
+        """Declare the graph STATIC (``cached=True`` layers, full-graph training; built once, used many times).  Reads the
+        long-row chunk count back to the host so that later launches carry only the chunk workgroups that exist instead of the
+        plan's capacity -- about 4 us per launch at ogbn-arxiv size -- and builds the gather plans (egc_gather_plan_build: col
+        and edge_dis of every entry in one word, which the inference aggregate then streams); their headers come back in the
+        same read: ONE synchronisation.  A partition (``halo`` set) or a rectangular adjacency gets no plan;
+        ``gather_plan=False`` is for a graph no inference aggregate will read."""
         if self._n_chunks is None or self._n_chunks < 0:
-            self._n_chunks = int(self.plan[1].item())
+            built = self._launch_gather_plan_builds() if gather_plan else {}
+            words = torch.cat([self.plan[1:2]] + [p[:_C.GP_HEADER_INTS] for p in built.values()]).cpu().tolist()
+            self._n_chunks = int(words[0])
+            self._keep_gather_plans(built, words[1:])
             self.check_indices()
+        return self
+
+    def _launch_gather_plan_builds(self, min_col_bits: int = 0) -> dict:
+        """Issue egc_gather_plan_build for both edge sets (raw / looped deg^-1/2 table); nothing is read back here."""
+        if self.halo is not None or self.n_src_rows != self.n_nodes or self.n_nodes <= 0 or self.dis_raw is None:
+            return {}
+        lib = _C.load()
+        dev = self.device
+        n, e = self.n_nodes, self.n_edges
+        built = {}
+        with _device_guard(dev):
+            words = int(lib.egc_gather_plan_bytes(n, e)) // 4
+            # (scratch in whole 2 MiB units: the block it leaves in the caching allocator is then one a later request of any
+            # size either fits to within the allocator's own rounding or splits)
+            ws_bytes = (int(lib.egc_gather_plan_workspace_bytes(n, e)) + (1 << 21) - 1) & ~((1 << 21) - 1)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            g = self.c_struct()
+            for name, edge_set in (("raw", _C.SET_RAW), ("looped", _C.SET_LOOPED)):
+                plan = torch.empty(words, dtype=torch.int32, device=dev)
+                _C.check(lib.egc_gather_plan_build(C.byref(g), edge_set, min_col_bits, plan.data_ptr(), plan.numel() * 4,
+                                                   ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "egc_gather_plan_build")
+                built[name] = plan
+        return built
+
+    def _keep_gather_plans(self, built: dict, header_words: list):
+        """Keep the plans whose header (host copy in ``header_words``, one after the other) says PACKED: a graph whose
+        distinct deg^-1/2 values do not fit the spare bits runs the path it ran."""
+        self.gather_plans = {}
+        for k, (name, plan) in enumerate(built.items()):
+            header = header_words[k * _C.GP_HEADER_INTS:(k + 1) * _C.GP_HEADER_INTS]
+            if header[_C.GP_FORM] == _C.GP_PACKED:
+                self.gather_plans[name] = (plan, header)
+        self._c_cached = None
+
+    def rebuild_gather_plans(self, min_col_bits: int = 0) -> "CSRGraph":
+        """Build the gather plans again (synchronises): after the deg^-1/2 tables of a static graph have changed."""
+        self.gather_plans = {}
+        self._c_cached = None
+        built = self._launch_gather_plan_builds(min_col_bits)
+        if built:
+            self._keep_gather_plans(built, torch.cat([p[:_C.GP_HEADER_INTS] for p in built.values()]).cpu().tolist())
         return self
 
     def long_row_stats(self):
@@ -384,7 +449,7 @@ class CSRGraph:
         return int(h[0]), int(h[1])
 
 
-_FAST_BUILD_MAX_EDGES = 4_000_000   # beyond: always the radix-sort pipeline (full graphs: built once; never measured on the fast build)
+_FAST_BUILD_MAX_EDGES = 4_000_000  # beyond: always the radix-sort pipeline (full graphs: built once; never measured on the fast build)
 _FAST_BUILD_SMALL = 262_144         # up to here the fast build wins whatever the edge order (launch-bound either way)
 _BUILD_WS: "dict[tuple, torch.Tensor]" = {}
 

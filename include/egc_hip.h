@@ -94,6 +94,14 @@ typedef struct {
                                  kernel streams it instead of gathering 4 bytes per entry; the weight itself,
                                  dis[src] * dis[dst], is still formed in the kernel */
   const float* edge_dis_looped; /* [n_edges] the same for dis_looped, or NULL */
+  const int32_t* gather_plan_raw;    /* egc_gather_plan_build(EGC_SET_RAW) of a STATIC graph, or NULL = no plan: col and
+                                        edge_dis_raw of every entry in ONE word, which the inference aggregate streams instead */
+  const int32_t* gather_plan_looped; /* the same for EGC_SET_LOOPED, or NULL */
+  int32_t gather_plan_form_raw;      /* HOST copies of two header words of the plans, read back once by the caller:
+                                        header[EGC_GP_FORM] | header[EGC_GP_COL_BITS] << 8; 0 = no plan */
+  int32_t gather_plan_form_looped;
+  /* The library reads every field of this struct: a caller ZERO-INITIALISES it (egc_graph g = {0};) and then fills in what it
+   * has, so that fields it does not know -- the trailing ones a newer header adds -- mean "absent". */
 } egc_graph;
 
 /* int32 words the caller must allocate for egc_graph.plan. */
@@ -166,6 +174,35 @@ int egc_csr_transposed_coo(int64_t n_nodes, int64_t n_edges, const int32_t* rowp
  * dis_* arrays are final (on a vertex partition: after their halo entries have arrived).  Either pair may be NULL. */
 int egc_csr_edge_dis(int64_t n_edges, const int32_t* col, const float* dis_raw, const float* dis_looped,
                      float* edge_dis_raw, float* edge_dis_looped, egc_stream_t stream);
+
+/* Gather plan of a STATIC graph (egc_graph.gather_plan_*): per CSR entry the inference aggregate streams col (4 B) and
+ * edge_dis (4 B), yet edge_dis[p] = dis[col[p]] is one of a few hundred distinct floats.  The plan holds both in one word per
+ * entry, at the entry's CSR position (rows are found through rowptr as ever) -- built once per graph and edge set, on the
+ * device, no synchronisation:
+ *   header   EGC_GP_HEADER_INTS words (EGC_GP_* below)
+ *   table    the distinct values of the edge set's deg^-1/2 table, ascending by bit pattern: table[index] IS dis[source]
+ *   entries  [n_edges] words: bits [0, cb) = col[p], the bits above = index of dis[col[p]] in `table`
+ * cb = max(ceil(log2(n_nodes)), 1, min_col_bits) (min_col_bits > 0 only widens it: tests).  Where the distinct values do not
+ * fit the 32 - cb spare bits the header says EGC_GP_UNFIT, `entries` is not written, and a launch given that form walks col
+ * and edge_dis as it does without a plan.  Requires a square graph (n_src_rows == n_nodes) whose dis table of `edge_set` is
+ * final: rebuild the plan whenever that table changes. */
+#define EGC_GP_HEADER_INTS 16
+#define EGC_GP_FORM 0            /* EGC_GP_PACKED / EGC_GP_UNFIT */
+#define EGC_GP_COL_BITS 1        /* cb */
+#define EGC_GP_TABLE_SIZE 2      /* distinct dis values */
+#define EGC_GP_PACKED 1
+#define EGC_GP_UNFIT 2
+size_t egc_gather_plan_bytes(int64_t n_nodes, int64_t n_edges);
+size_t egc_gather_plan_workspace_bytes(int64_t n_nodes, int64_t n_edges);
+int egc_gather_plan_build(const egc_graph* graph, int32_t edge_set, int32_t min_col_bits, int32_t* plan, size_t plan_bytes,
+                          void* workspace, size_t workspace_bytes, egc_stream_t stream);
+/* The builder's decision as a host function: header[EGC_GP_FORM] | header[EGC_GP_COL_BITS] << 8 of a plan over n_nodes sources
+ * whose dis table has n_table distinct values: packed iff cb < 32 and n_table <= 2^(32 - cb). */
+int32_t egc_gather_plan_form(int64_t n_nodes, int64_t n_table, int32_t min_col_bits);
+/* int32 offset of a part of the plan (0 table, 1 entries; 2 = the plan's end): a function of the sizes alone */
+int64_t egc_gather_plan_offset(int64_t n_nodes, int64_t n_edges, int32_t part);
+/* Launches of the aggregate's PLAN form issued by this process so far (a diagnostic: tests assert that a launch took the form). */
+int64_t egc_gather_plan_launches(void);
 
 /* Vertex-partitioned runs (the reference is single-device, so there is no call site to cite beyond the
  * gather of MessagePassing.propagate this distributes): out[k][0..width) = table[idx[k]][0..width) -- the SEND PACK of
