@@ -21,7 +21,10 @@ two-slots-per-lane kernel, launch_all<1..4> with the wavefronts-per-block rule a
 under the switches EGC_FORCE_GENERIC, EGC_NO_STATIC_CFG and EGC_NO_WIDE.  ``static_rows`` reads the compiled-in configurations out
 of egc_aggregate_fast.hip, so that a row added there without a case here is noticed.
 
-``CASES`` is the table: every cell of the rule at the smallest shape that reaches it."""
+``CASES`` is the table: every cell of the rule at the smallest shape that reaches it.
+
+``plan_form`` / ``plan_instances`` add the gather plan of a static graph to the rule: which calls take agg_fast_kernel's PLAN form
+on a trimmed graph, and which PLAN kernels the library compiles (tests/test_forward_plan_cpu.py, tests/test_forward_plan_gpu.py)."""
 import functools
 import re
 from typing import NamedTuple
@@ -499,3 +502,30 @@ def family(case, n=32, env=()):
 
 
 FAMILIES = ("reg contig", "reg padded", "wide", "lds one chunk", "lds chunks")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the gather plan of a static graph as part of the rule
+
+PLAN_SWITCH = "EGC_NO_GATHER_PLAN"
+PLAN_FORMS = ((), ("EGC_NO_STATIC_CFG",))      # a compiled-in configuration and its rt<...,0> fallback are two compiled PLAN kernels
+
+
+def plan_form(case, kind, rows=None, env=()):
+    """True exactly when the call ``dispatch(case, n, ...)`` describes -- ``n`` the rows of the graph key ``kind``, ``rows`` a row
+    range or None -- takes the PLAN form of agg_fast_kernel on a TRIMMED graph (CSRGraph.trim_launches(), whose plan the small
+    graphs here always keep).  launch_one gives the form to every register instance without optional aggregates; aggregate_combine_impl
+    offers a plan to a whole-graph inference launch on a square graph unless EGC_NO_GATHER_PLAN is set."""
+    ei, n, n_src = edges(*graph_key(case, kind, False))
+    whole = rows is None or tuple(rows) == (0, n)
+    return (dispatch(case, n if rows is None else rows[1] - rows[0], False, env).family == "reg" and need_of(case) == "0"
+            and n_src == n and whole and PLAN_SWITCH not in env)
+
+
+def plan_instances(source=None):
+    """The PLAN instances the library compiles, by name: every EGC_STATIC_CFG row of need 0 and the need-0 column of the RtCfg ladder."""
+    return ({r.name for r in static_rows(source) if r.kind == "reg" and r.need == "0"}
+            | {f"rt<{lg},{hpb},0>" for lg in (4, 5, 6) for hpb in (1, 2, 4)})
+
+
+PLAN_CASES = tuple(c for c in CASES if plan_form(c, home(c)))

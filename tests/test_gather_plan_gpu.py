@@ -10,7 +10,9 @@ Two properties, on small graphs that hit every edge the builder and the kernel h
     forward, which folds mean into sum), one run-time configuration each at 32- and 64-lane groups, and the ogbn-mag layer
     (44 slots: one row per wavefront) on a graph of more than 32768 rows, where a wavefront takes four row groups in turn.
 Graphs: 1, 3, 5 and 67 rows; empty rows; rows of exactly 64 and 65 entries; self entries; a hub of a few hundred entries next to
-short rows; sources of one degree only; more distinct degrees than the spare bits hold (min_col_bits)."""
+short rows; sources of one degree only; more distinct degrees than the spare bits hold (min_col_bits); exactly as many as they hold
+(a path: two degrees at 31 source-id bits, the index in bit 31 of the word) and one more; exactly 64 and 65 rows, most entries
+reading the highest-numbered rows."""
 import functools
 import os
 
@@ -74,7 +76,33 @@ def _big_graph():
     return np.stack([src, dst]).astype(np.int64), n
 
 
+def _path_graph(n=40, three_at=None):
+    """A path: the end rows have one entry, the inner rows two -- two distinct degrees in either edge set, exactly what ONE spare
+    bit holds.  ``three_at``: that row gets a third entry, and the graph a third degree."""
+    r = np.arange(n)
+    src, dst = np.concatenate([r[:-1], r[1:]]), np.concatenate([r[1:], r[:-1]])
+    if three_at is not None:
+        src, dst = np.append(src, (three_at + 7) % n), np.append(dst, three_at)
+    return np.stack([src, dst]).astype(np.int64), n
+
+
+def _top_source_graph(n):
+    """Exactly ``n`` rows (64: six source-id bits, 65: seven); most entries read row 63 (and row 64 where there is one), whose own
+    single entry gives it the largest deg^-1/2, the LAST table index: an all-ones source id next to a non-zero index."""
+    rng = np.random.default_rng(n)
+    deg = rng.integers(0, 9, n)
+    deg[5], deg[63:] = 40, 1
+    dst = np.repeat(np.arange(n), deg)
+    hot = rng.integers(63, n, dst.size)
+    src = np.where(rng.random(dst.size) < 0.6, hot, rng.integers(0, n, dst.size))
+    return np.stack([src, dst]).astype(np.int64), n
+
+
 GRAPHS = {
+    "two_degree": _path_graph,
+    "three_degree": lambda: _path_graph(three_at=11),
+    "n64": lambda: _top_source_graph(64),
+    "n65": lambda: _top_source_graph(65),
     "n1": lambda: (np.array([[0, 0], [0, 0]], dtype=np.int64), 1),
     "n3": lambda: _random_graph(3, 7, 1),
     "n5_empty_rows": lambda: _random_graph(5, 12, 2, empty_every=2),
@@ -86,6 +114,10 @@ GRAPHS = {
 # (graph, min_col_bits): 31 leaves one spare bit -- two table values -- to graphs with more distinct degrees: no plan is kept
 SMALL = [("n1", 0), ("n3", 0), ("n5_empty_rows", 0), ("n67", 0), ("threshold_and_hub", 0), ("one_degree", 0), ("one_degree", 31)]
 UNFIT = [("n67", 31), ("threshold_and_hub", 31)]
+# the exact fit n_table == 1 << (32 - cb) on a BUILT plan: two values at 31 source-id bits put the index in bit 31 of the word;
+# three values there keep no plan.  64 / 65 rows: the source-id field full of ones, and one bit wider
+SMALL += [("two_degree", 31), ("n64", 0), ("n65", 0)]
+UNFIT += [("three_degree", 31)]
 IDS = dict(ids=lambda p: f"{p[0]}-cb{p[1]}")
 
 
@@ -149,6 +181,50 @@ def test_cases_reach_what_they_name():
     assert {64, 65} <= set(deg.tolist()) and deg.max() >= 300
     big = np.diff(static_graph("big").rowptr.cpu().numpy())
     assert big.size >= 32768 and big.max() >= 500 and (big == 0).any() and ((big > 64) & (big < 256)).any()
+
+
+def _read_back(g, edge_set):
+    """(header, table, entry words) of a kept plan"""
+    lib = _C.load()
+    plan, header = g.gather_plans[edge_set]
+    p = plan.cpu().numpy()
+    off = [int(lib.egc_gather_plan_offset(g.n_nodes, g.n_edges, k)) for k in range(2)]
+    return header, p[off[0]:off[0] + header[_C.GP_TABLE_SIZE]].view(np.uint32), p[off[1]:off[1] + g.n_edges].view(np.uint32)
+
+
+@pytest.mark.parametrize("edge_set", ["raw", "looped"])
+def test_the_exact_fit_puts_the_index_in_bit_31(edge_set):
+    """two values at 31 source-id bits: n_table == 1 << (32 - cb), the plan is kept and its index bit is the word's sign bit"""
+    g = static_graph("two_degree", 31)
+    header, table, words = _read_back(g, edge_set)
+    assert (header[_C.GP_FORM], header[_C.GP_COL_BITS], header[_C.GP_TABLE_SIZE]) == (_C.GP_PACKED, 31, 2) and len(table) == 2
+    assert header[_C.GP_TABLE_SIZE] == 1 << (32 - header[_C.GP_COL_BITS])
+    assert int(_C.load().egc_gather_plan_form(g.n_nodes, 3, 31)) & 0xff == _C.GP_UNFIT
+    top = (words >> np.uint32(31)).astype(bool)
+    assert top.any() and not top.all()
+    check_plan(g, edge_set, 31)
+    deg = np.diff(g.rowptr.cpu().numpy()[:g.n_nodes + 1])
+    assert sorted(set(deg.tolist())) == [1, 2] and (deg[[0, -1]] == 1).all()
+    three = np.diff(static_graph("three_degree", 31).rowptr.cpu().numpy()[:g.n_nodes + 1])
+    assert sorted(set(three.tolist())) == [1, 2, 3] and (three == 3).sum() == 1
+
+
+@pytest.mark.parametrize("layer", ["northstar_folded", "rt_32_lanes", "mag_44_slots"])
+def test_aggregate_bit_identical_with_the_index_in_bit_31(layer):
+    """16-, 32- and 64-lane groups; the raw plan (rt_32_lanes) and the looped one"""
+    aggregate_case(static_graph("two_degree", 31), layer, 1)
+
+
+@pytest.mark.parametrize("rows", [64, 65])
+@pytest.mark.parametrize("edge_set", ["raw", "looped"])
+def test_the_source_field_full_of_ones_next_to_an_index(rows, edge_set):
+    g = static_graph(f"n{rows}")
+    header, table, words = _read_back(g, edge_set)
+    cb = header[_C.GP_COL_BITS]
+    assert g.n_nodes == rows and cb == {64: 6, 65: 7}[rows] and len(table) > 2
+    src, idx = words & np.uint32((1 << cb) - 1), words >> np.uint32(cb)
+    hot = src >= 63
+    assert 2 * hot.sum() > words.size and (idx[hot] != 0).all() and (src == rows - 1).any() and (src == 63).any()
 
 
 # ---- the kernel: bit-identical with and without the plan, and the PLAN form did launch ----------------------------------------
