@@ -31,6 +31,13 @@ TYPED_MAX_RELATIONS = 8      # EGC_TYPED_MAX_RELATIONS
 TOKEN_HEAD_MAX_SEQ = 8       # EGC_TOKEN_HEAD_MAX_SEQ
 TOKEN_HEAD_SLAB = 64         # EGC_TOKEN_HEAD_SLAB: vocabulary columns of one workgroup step
 TOKEN_HEAD_MAX_IN = 384      # widest in_features of the token head's kernels
+# EGC_HEAD_*: the envelope of the graph-level MLP head's kernels, its row tile and its fused losses
+HEAD_MAX_LINEARS = 4
+HEAD_MAX_WIDTH = 384
+HEAD_MAX_OUT = 64
+HEAD_MAX_ROWS = 65536
+HEAD_ROW_TILE = 16
+HEAD_LOSS_NONE, HEAD_LOSS_L1, HEAD_LOSS_BCE_MASKED = range(3)
 # EGC_MPNN_*
 MPNN_ADD, MPNN_MEAN, MPNN_MAX = range(3)
 # EGC_PNA_* aggregators and scalers
@@ -88,6 +95,14 @@ class EgcTypedRel(C.Structure):
     _fields_ = [("rowptr", C.c_void_p), ("col", C.c_void_p), ("pre_rowptr", C.c_void_p), ("in_", C.c_void_p),
                 ("n_edges", C.c_int64), ("n_in_rows", C.c_int64), ("ld_in", C.c_int32), ("out_col", C.c_int32),
                 ("post_mean", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EgcHead(C.Structure):
+    _fields_ = ([("n_linears", C.c_int32), ("sizes", C.c_int32 * (HEAD_MAX_LINEARS + 1))]
+                + [(name, C.c_void_p * HEAD_MAX_LINEARS)
+                   for name in ("weight", "bias", "gamma", "beta", "running_mean", "running_var", "num_batches_tracked")]
+                + [("eps", C.c_double * HEAD_MAX_LINEARS), ("momentum", C.c_double * HEAD_MAX_LINEARS)]
+                + [(name, C.c_void_p * HEAD_MAX_LINEARS) for name in ("z", "stats", "affine", "dz", "g", "coef", "d_weight", "d_bias")])
 
 
 # name -> (restype, argtypes): exactly the symbols include/egc_hip.h declares
@@ -217,6 +232,17 @@ SYMBOLS = {
     "egc_token_head_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_size_t, C.c_void_p]),
+    "egc_head_workspace_bytes": (C.c_size_t, [C.POINTER(EgcHead), C.c_int64]),
+    "egc_head_forward_train_f32": (C.c_int, [C.POINTER(EgcHead), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "egc_head_forward_eval_f32": (C.c_int, [C.POINTER(EgcHead), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "egc_head_backward_f32": (C.c_int, [C.POINTER(EgcHead), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "egc_l1_loss_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "egc_l1_loss_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "egc_bce_masked_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "egc_bce_masked_backward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "egc_head_launches": (C.c_int64, []),
     "egc_typed_mean_chunk": (C.c_int32, []),
     "egc_typed_mean_workspace_bytes": (C.c_size_t, [C.POINTER(EgcTypedRel), C.c_int32, C.c_int32]),
     "egc_typed_mean_f32": (C.c_int, [C.POINTER(EgcTypedRel), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,

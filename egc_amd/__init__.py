@@ -45,6 +45,10 @@ Public surface (mirrors the reference's layer API):
   TokenHead(in_features, num_classes, seq_len), token_head_loss / token_head_argmax
                        the token predictors of the ogbg-code net (state-dict compatible) fused with their loss: the Linear
                        maps, the mean cross-entropy over the positions, the arg-max and the backward without a logits array
+  GraphHead(sizes, act, dropout), l1_loss / masked_bce_with_logits
+                       the graph-level MLP head of the batched nets (experiments.utils.mlp, state-dict compatible) with
+                       the L1 / NaN-masked BCE loss fused into its last launch: one launch per Linear forward (one in all
+                       in evaluation), one row pass per Linear and one parameter-gradient launch backward
   SparseTensor         minimal adj_t container (torch_sparse is not required)
   CSRGraph             device CSR + degree statistics + long-row plan
   GraphBatch           a PyG-style batch of small graphs (edge_index + graph offsets) for the tile kernels: the CSR of
@@ -66,6 +70,7 @@ from .fusion import FusedEGCBlock, global_add_pool, global_max_pool, global_mean
 from .encoders import ASTNodeEncoder, AtomEncoder, Embedding, NodeEncoder  # noqa: F401
 from ._softmax import RowSelection, cross_entropy, log_softmax, nll_log_softmax  # noqa: F401
 from ._token_head import TokenHead, token_head_argmax, token_head_loss  # noqa: F401
+from ._head import GraphHead, l1_loss, masked_bce_with_logits  # noqa: F401
 from .hipgraph import GraphedStep  # noqa: F401
 from . import ops  # noqa: F401  (registers torch.ops.egc_amd.*)
 

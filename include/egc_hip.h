@@ -683,6 +683,103 @@ int egc_token_head_backward_f32(const float* x, const float* const* weights, con
                                 int32_t seq_len, float* d_x, float* const* d_weights, float* const* d_biases, void* workspace,
                                 size_t workspace_bytes, egc_stream_t stream);
 
+/* The graph-level MLP head of the reference's batched nets fused with its loss (egc_head.hip):
+ *   pool -> mlp([K0, K1, .., K_{L-1}, OUT]) -> loss,  mlp = [Linear -> BatchNorm1d -> ReLU -> Dropout(0)] x (L - 1), Linear
+ * (experiments/utils.py:30-40; zinc/configs.py:48-50 F.l1_loss, mol/configs.py:64-68 BCE-with-logits over the labelled entries),
+ * and what autograd derives from it.  With a_0 = x [n_rows, K0] and, for l = 1 .. L,
+ *   z_l = a_{l-1} W_l^T + b_l                              W_l [K_l, K_{l-1}] (nn.Linear.weight), K_L = OUT
+ *   stats_l = {mean, biased variance, 1 / sqrt(variance + eps)} of the columns of z_l (training), float64 [3][K_l]
+ *   affine_l = {scale = gamma rstd, shift = beta - mean gamma rstd} rounded once from float64, float32 [2][K_l]
+ *   a_l = relu(z_l scale + shift), the ReLU decision being the float32 expression fl(fl(z * scale) + shift) > 0 in the forward
+ *         and in the backward alike (it is formed again from z_l and affine_l; no mask is stored)
+ *   out = z_L [n_rows, OUT]
+ *   EGC_HEAD_LOSS_L1          loss = mean |out - y| over all n_rows OUT entries; d out = sign(out - y) grad_loss / (n_rows OUT),
+ *                             sign(0) = 0
+ *   EGC_HEAD_LOSS_BCE_MASKED  loss = mean over {y == y} of max(o, 0) - o y + log1p(exp(-|o|)); a NaN target adds nothing and
+ *                             has a zero gradient; the divisor is the labelled count, taken on the device; no labelled entry:
+ *                             loss = NaN; d out = (sigmoid(o) - y) grad_loss / count
+ *   EGC_HEAD_LOSS_NONE        out only; the backward takes the caller's d out
+ * The loss terms and d out are evaluated in float64 from the float32 out and y and rounded ONCE; loss2 = {loss, count} (float32;
+ * count = n_rows OUT for L1).  In evaluation the running statistics take the place of the batch's: scale / shift from
+ * running_mean / running_var by the same float64 expressions.
+ * Backward of a hidden layer, with g = d a * [pre > 0]: coef_l [5][K_l] = {d gamma = sum g z_hat, d beta = sum g, c_g, c_h, c_1}
+ * (float64 sums, rounded once) and dz_l = fl(fl(fl(c_g g) + fl(c_h z)) + c_1) -- egc_bn_backward_finalize's coefficients;
+ * d a_{l-1} = dz_l W_l, d W_l = dz_l^T a_{l-1}, d b_l = column sums of dz_l, d x = dz_1 W_1.
+ * Envelope: 1 <= L <= EGC_HEAD_MAX_LINEARS; any positive widths K_0 .. K_{L-1} <= EGC_HEAD_MAX_WIDTH (no multiple-of-4
+ * requirement), OUT <= EGC_HEAD_MAX_OUT, n_rows <= EGC_HEAD_MAX_ROWS; float32; dense row-major arrays, no alignment beyond
+ * their element's (the workspace: 8 bytes).  Training needs n_rows >= 2 when L > 1 (nn.BatchNorm1d raises on one row) and
+ * n_rows >= 1 otherwise; evaluation with n_rows == 0 launches nothing.
+ * Launches: training forward L (one per Linear; a hidden layer's launch also produces stats_l, affine_l, the running
+ * statistics and num_batches_tracked + 1 in its last block -- the arrival counter of egc_bn_forward_stats_f32; the final
+ * launch also produces loss2); evaluation forward 1; backward L row passes from the top layer down (the top pass is skipped
+ * when it has nothing to form: EGC_HEAD_LOSS_NONE without a layer or d_x below) and 1 launch for every d W_l and d b_l
+ * (want_params).  No grid barrier, no spin wait, no cooperative launch, no float atomics; nothing reads back from the device.
+ * Order (two calls give the same bits).  Every product element is ONE float32 fma chain over the reduction index ascending
+ * (exact products), then one add of the bias (forward).  Column sums are float64: a block of EGC_HEAD_ROW_TILE rows adds its
+ * rows ascending; the last block adds the blocks' partials, lane j = 0 .. 7 taking the partials j, j + 8, .. ascending, then the
+ * eight lane sums ascending.  Loss (float64): a row block adds, per column, its rows ascending, then its columns ascending; the
+ * last block: lane j = 0 .. 63 takes the blocks j, j + 64, .. ascending, then the lane sums ascending; loss = float(sum / count).
+ * d W_l and d b_l: one fma chain (one chain of adds) over all rows ascending.  The stand-alone losses: thread j = 0 .. 255 takes
+ * the elements j, j + 256, .. ascending, then the thread sums ascending.
+ * egc_head: n_linears = L, sizes[0 .. L]; weight / bias [l] of Linear l + 1; gamma / beta (either may be NULL: 1 / 0),
+ * running_mean / running_var (both NULL: no running statistics), num_batches_tracked (int64 scalar; may be NULL with a
+ * momentum), eps, momentum (< 0: the cumulative average 1 / num_batches_tracked) [l] of the BatchNorm behind Linear l + 1; the
+ * per-call arrays z [n_rows, K_{l+1}], stats, affine (written by the training forward, read by the backward), dz
+ * [n_rows, K_{l+1}] (dz[L - 1] is unused with EGC_HEAD_LOSS_NONE), g [n_rows, K_{l+1}] (hidden layers) and coef (written by the
+ * backward), d_weight / d_bias (written
+ * when want_params).  d gamma_l = coef_l[0], d beta_l = coef_l[1].
+ * grad: the device scalar grad_loss, or with EGC_HEAD_LOSS_NONE the caller's d out [n_rows, OUT].  d_x may be NULL.
+ * workspace: egc_head_workspace_bytes(head, n_rows) bytes (0 outside the envelope), any content; sync: a device int32 that is
+ * zero on entry and zero again on exit.
+ * EGC_ERR_INVALID: a missing pointer, a width < 1, n_linears < 1, too few rows, an unknown loss, evaluation without running
+ * statistics; EGC_ERR_UNSUPPORTED: outside the envelope -- both before any launch.
+ * egc_l1_loss_* / egc_bce_masked_*: the two losses alone on n = n_rows OUT elements (n <= EGC_HEAD_MAX_ROWS EGC_HEAD_MAX_OUT),
+ * one launch each way; the backward reads the forward's loss2.
+ * egc_head_launches: host-only, the number of kernel launches the entry points of this section have issued in this process. */
+#define EGC_HEAD_MAX_LINEARS 4
+#define EGC_HEAD_MAX_WIDTH 384
+#define EGC_HEAD_MAX_OUT 64
+#define EGC_HEAD_MAX_ROWS 65536
+#define EGC_HEAD_ROW_TILE 16
+#define EGC_HEAD_LOSS_NONE 0
+#define EGC_HEAD_LOSS_L1 1
+#define EGC_HEAD_LOSS_BCE_MASKED 2
+typedef struct egc_head {
+  int32_t n_linears;
+  int32_t sizes[EGC_HEAD_MAX_LINEARS + 1];
+  const float* weight[EGC_HEAD_MAX_LINEARS];
+  const float* bias[EGC_HEAD_MAX_LINEARS];
+  const float* gamma[EGC_HEAD_MAX_LINEARS];
+  const float* beta[EGC_HEAD_MAX_LINEARS];
+  float* running_mean[EGC_HEAD_MAX_LINEARS];
+  float* running_var[EGC_HEAD_MAX_LINEARS];
+  int64_t* num_batches_tracked[EGC_HEAD_MAX_LINEARS];
+  double eps[EGC_HEAD_MAX_LINEARS];
+  double momentum[EGC_HEAD_MAX_LINEARS];
+  float* z[EGC_HEAD_MAX_LINEARS];
+  double* stats[EGC_HEAD_MAX_LINEARS];
+  float* affine[EGC_HEAD_MAX_LINEARS];
+  float* dz[EGC_HEAD_MAX_LINEARS];
+  float* g[EGC_HEAD_MAX_LINEARS];
+  float* coef[EGC_HEAD_MAX_LINEARS];
+  float* d_weight[EGC_HEAD_MAX_LINEARS];
+  float* d_bias[EGC_HEAD_MAX_LINEARS];
+} egc_head;
+size_t egc_head_workspace_bytes(const egc_head* head, int64_t n_rows);
+int egc_head_forward_train_f32(const egc_head* head, const float* x, int64_t n_rows, int32_t loss_kind, const float* y, float* out,
+                               float* loss2, void* workspace, size_t workspace_bytes, int32_t* sync, egc_stream_t stream);
+int egc_head_forward_eval_f32(const egc_head* head, const float* x, int64_t n_rows, float* out, egc_stream_t stream);
+int egc_head_backward_f32(const egc_head* head, const float* x, int64_t n_rows, int32_t loss_kind, const float* y, const float* out,
+                          const float* loss2, const float* grad, float* d_x, int32_t want_params, void* workspace,
+                          size_t workspace_bytes, int32_t* sync, egc_stream_t stream);
+int egc_l1_loss_forward_f32(const float* out, const float* y, int64_t n, float* loss2, egc_stream_t stream);
+int egc_l1_loss_backward_f32(const float* out, const float* y, const float* grad_loss, const float* loss2, int64_t n, float* d_out,
+                             egc_stream_t stream);
+int egc_bce_masked_forward_f32(const float* out, const float* y, int64_t n, float* loss2, egc_stream_t stream);
+int egc_bce_masked_backward_f32(const float* out, const float* y, const float* grad_loss, const float* loss2, int64_t n,
+                                float* d_out, egc_stream_t stream);
+int64_t egc_head_launches(void);
+
 /* Typed mean aggregation (egc_typed_mean.hip): the sparse part of the reference's R-GCN baseline layer,
  * `self.rel_lins[key](adj_t.matmul(x_dict[src], reduce="mean"))` per relation (rmag/models.py:61-72), and of what autograd
  * derives from it, over a LIST of relations in one call:
