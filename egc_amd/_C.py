@@ -38,6 +38,10 @@ HEAD_MAX_OUT = 64
 HEAD_MAX_ROWS = 65536
 HEAD_ROW_TILE = 16
 HEAD_LOSS_NONE, HEAD_LOSS_L1, HEAD_LOSS_BCE_MASKED = range(3)
+# EGC_COLLATE_*: fields of each kind, graphs per batch, bytes per field row of the device-side collation
+COLLATE_MAX_FIELDS = 8
+COLLATE_MAX_GRAPHS = 4096
+COLLATE_MAX_ROW_BYTES = 4096
 # EGC_MPNN_*
 MPNN_ADD, MPNN_MEAN, MPNN_MAX = range(3)
 # EGC_PNA_* aggregators and scalers
@@ -103,6 +107,26 @@ class EgcHead(C.Structure):
                    for name in ("weight", "bias", "gamma", "beta", "running_mean", "running_var", "num_batches_tracked")]
                 + [("eps", C.c_double * HEAD_MAX_LINEARS), ("momentum", C.c_double * HEAD_MAX_LINEARS)]
                 + [(name, C.c_void_p * HEAD_MAX_LINEARS) for name in ("z", "stats", "affine", "dz", "g", "coef", "d_weight", "d_bias")])
+
+
+class EgcCollateField(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int32), ("elem_bytes", C.c_int32),
+                ("fill_bits", C.c_uint64)]
+
+
+class EgcCollateFields(C.Structure):
+    _fields_ = [("n_node", C.c_int32), ("n_graph", C.c_int32), ("node", EgcCollateField * COLLATE_MAX_FIELDS),
+                ("graph", EgcCollateField * COLLATE_MAX_FIELDS)]
+
+
+class EgcCollateStore(C.Structure):
+    _fields_ = [("node_ptr", C.c_void_p), ("edge_ptr", C.c_void_p), ("edge_index", C.c_void_p), ("n_graphs", C.c_int64),
+                ("n_edges_all", C.c_int64)]
+
+
+class EgcCollateOut(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("edge_index", "batch", "ptr", "edge_ptr", "n_valid", "e_valid", "g_valid",
+                                                "counts", "graph_mask", "inv_g", "status")]
 
 
 # name -> (restype, argtypes): exactly the symbols include/egc_hip.h declares
@@ -347,6 +371,10 @@ SYMBOLS = {
                                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egc_collate_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "egc_collate": (C.c_int, [C.POINTER(EgcCollateStore), C.POINTER(EgcCollateFields), C.POINTER(EgcCollateOut), C.c_void_p,
+                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                              C.c_size_t, C.c_void_p, C.c_void_p]),
     "egc_last_error": (C.c_char_p, []),
     "egc_version": (C.c_char_p, []),
 }

@@ -56,6 +56,16 @@ Public surface (mirrors the reference's layer API):
   egc_layer_forward    operator-level call into libegc_hip.so
   ops                  the same call as torch.library operators (torch.ops.egc_amd.layer_forward / _train / _backward)
   GraphedStep          a whole training / inference step (graph build included) recorded as one hipGraph
+  GraphStore(node_ptr, edge_ptr, edge_index, node_fields, graph_fields)
+                       a dataset of small graphs that lives on the device: M graphs back to back, node ids local to their
+                       graph, named per-node and per-graph arrays (nothing is copied)
+  BatchCollator(store, batch_size, n_pad, e_pad, graph_fill)
+                       the input side of a recorded step, in place of PyG's DataLoader + ``batch.to(device)``: owns the static
+                       padded buffers of one batch (fields, edge_index, batch, ptr, edge_ptr, n_valid / e_valid / g_valid,
+                       counts, graph_mask, inv_g) and fills ALL of them in two launches without host work --
+                       ``collate(ids)``, or ``set_epoch(perm)`` + ``next()`` with cursor and permutation read on the device, so
+                       that ``next()`` recorded inside a GraphedStep makes one replay the whole iteration; malformed batches
+                       are clamped, flagged and named by ``check()``
 """
 from .graph import CSRGraph, GraphBatch, SparseTensor, GLOBAL_GRAPH_CACHE  # noqa: F401
 from .functional import egc_layer_forward, make_spec, LayerSpec  # noqa: F401
@@ -72,6 +82,7 @@ from ._softmax import RowSelection, cross_entropy, log_softmax, nll_log_softmax 
 from ._token_head import TokenHead, token_head_argmax, token_head_loss  # noqa: F401
 from ._head import GraphHead, l1_loss, masked_bce_with_logits  # noqa: F401
 from .hipgraph import GraphedStep  # noqa: F401
+from ._collate import EGC_COLLATE_MAX_FIELDS, BatchCollator, GraphStore  # noqa: F401
 from . import ops  # noqa: F401  (registers torch.ops.egc_amd.*)
 
 __version__ = "0.1.0"

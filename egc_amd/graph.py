@@ -71,7 +71,8 @@ class _IndexFlag:
                                "[0, num_nodes): index out of range (those edges were dropped) -- or, for a GraphBatch, edges that "
                                "leave their graph / a graph larger than max_nodes (its rows were written as zeros; "
                                "GraphBatch.check() tells which) -- or, for a node encoder, an index outside its embedding table (that "
-                               "table contributed a zero row)")
+                               "table contributed a zero row) -- or, for a BatchCollator, a graph id outside the store (an empty "
+                               "slot) / a batch over its n_pad or e_pad (cut short; BatchCollator.check() tells which)")
 
 
 def _require_cuda(t: torch.Tensor, what: str):

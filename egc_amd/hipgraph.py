@@ -27,6 +27,26 @@ recording serves every batch up to the padded size (tests/test_hipgraph_gpu.py).
         graphed()                            # .grad of every parameter now holds this batch's gradient
         optimizer.step()
 
+With the dataset on the device the input side goes into the recording as well: ``egc_amd.BatchCollator`` owns the padded
+static buffers (padding as described above: zero rows in a spare last graph, self-loops on the last row) and ``next()``
+writes the epoch's next batch into them in two launches, cursor and permutation read on the device -- one replay is then
+the entire iteration, and an epoch a loop of replays with no host work (_collate.py, DESIGN.md section 3.31)::
+
+    store = egc_amd.GraphStore(node_ptr, edge_ptr, edge_index, node_fields={"x": x_all}, graph_fields={"y": y_all})
+    col = egc_amd.BatchCollator(store, batch_size=G)           # n_pad, e_pad: store.capacity(G)
+    def step():
+        col.next()                                               # batch perm[cursor * G : (cursor + 1) * G]; cursor += 1
+        h = model(col.fields["x"], col.edge_index, n_valid=col.n_valid)
+        out = head(egc_amd.global_mean_pool(h, col.batch, size=G + 1))
+        (((out - col.fields["y"]) ** 2 * col.graph_mask).sum() * col.inv_g).backward()
+        optimizer.step(); optimizer.zero_grad(set_to_none=False)
+    graphed = egc_amd.GraphedStep(step, params=model.parameters())   # (its warm-up runs are real steps and advance the cursor)
+    for epoch in range(epochs):
+        col.set_epoch(torch.randperm(M, device=dev))             # re-shuffling does not invalidate the recording
+        for _ in range(col.batches_per_epoch()):
+            graphed()
+    col.check()                                                  # synchronises; names a malformed batch, if there was one
+
 The reference has no counterpart (PyTorch eager throughout, experiments/*/main.py); this is the CDNA-side answer to its
 launch-bound small-batch regime (task statement: "capture launch-bound inner loops in hipGraphs").
 """

@@ -1311,6 +1311,81 @@ int egc_aggregate_combine_backward_f32(const egc_graph* graph, const egc_graph* 
                                        int32_t ld_d_bases, float* d_weightings, int32_t ld_d_weightings,
                                        void* workspace, size_t workspace_bytes, egc_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mini-batch collation on the device (egc_collate.hip).  The reference's batched nets take their batches from PyG's
+ * DataLoader: per-graph collation in Python on the CPU, then `batch.to(device)` (zinc/configs.py:53-67,
+ * mol/configs.py:52-70, cifar/configs.py:66-82, code/configs.py:47-69).  Here the dataset lives on the device
+ * (egc_collate_store: M graphs back to back, node ids of edge_index LOCAL to their graph, a graph's edges contiguous) and
+ * one call writes a batch of up to batch_size = G graphs into static buffers padded to n_pad rows and e_pad edges -- the
+ * convention of a recorded step (egc_amd/hipgraph.py): zero feature rows, padding rows in a spare last graph G, padding
+ * edges as self-loops on row n_pad - 1.  Slot i of the batch is graph ids[i], i < n_ids (1 <= n_ids <= G, repeats allowed);
+ * or, with ids == NULL, graph perm[c G + i] of batch c = *cursor of an epoch of floor(*perm_len / G) full batches -- cursor
+ * and perm_len are DEVICE words read by the kernel, a cursor outside the epoch counts as 0, and c + 1 is stored back, so
+ * the same recorded launch serves successive batches and wraps.  perm has room for store->n_graphs entries.
+ * With g_valid graphs kept, n_valid rows and e_valid edges, EVERY element of every output is written by every call:
+ *   node field dst [n_pad, row]   rows of the kept graphs in batch order; rows >= n_valid all-zero bytes
+ *   out->edge_index [2, e_pad]    local id + the slot's row offset; columns >= e_valid (n_pad - 1, n_pad - 1)
+ *   out->batch [n_pad]            the slot of each row; rows >= n_valid hold G
+ *   out->ptr, edge_ptr [G + 2]    row / edge offset of slots 0 .. G (slots >= g_valid repeat n_valid / e_valid); last n_pad / e_pad
+ *   out->n_valid, e_valid, g_valid   int64 scalars
+ *   out->counts [G + 1] float     rows of the slot; 1 for a slot without rows and for the spare graph
+ *   out->graph_mask [G + 1] float 1 for slots < g_valid, else 0;  out->inv_g = (float)(1.0 / max(g_valid, 1))
+ *   graph field dst [G + 1, row]  the graph's row; the field's fill element (fill_bits, low elem_bytes bytes) in slots that hold no
+ *                                 graph: slots >= g_valid, the spare graph, and a slot whose id is out of range
+ * Malformed input never addresses anything and is always reported: an id outside [0, n_graphs) is an empty slot (status bit
+ * 1); the first graph with which the rows would exceed n_pad - 1 (bit 2) or the edges e_pad (bit 4), and every graph after
+ * it, are dropped.  The bits are OR-ed into *out->status (device, cleared by the caller) and *host_flag = 1 is stored (may
+ * be NULL; the sticky host-visible word of egc_coo_to_csr_checked).
+ * Fields: at most EGC_COLLATE_MAX_FIELDS of each kind, elements of 4 or 8 bytes, contiguous rows of at most
+ * EGC_COLLATE_MAX_ROW_BYTES bytes, pointers aligned to the element; 16- and 8-byte accesses where the row size and both
+ * base addresses are multiples of 16 / 8.  The structs are read during the call and travel in the kernel arguments.
+ * workspace: egc_collate_workspace_bytes(batch_size) bytes (0 outside 1 .. EGC_COLLATE_MAX_GRAPHS), 8-byte aligned, any
+ * content.  Two launches whatever the fields; launch sizes depend on batch_size, n_pad, e_pad alone.
+ * EGC_ERR_INVALID: a missing pointer, n_ids outside 1 .. batch_size, n_pad or e_pad < 1, a row size that is no multiple of
+ * its element, a misaligned field; EGC_ERR_UNSUPPORTED: batch_size > EGC_COLLATE_MAX_GRAPHS, n_pad or e_pad >= 2^31, too
+ * many fields, an element size other than 4 / 8, a row over the limit; EGC_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------ */
+#define EGC_COLLATE_MAX_FIELDS 8
+#define EGC_COLLATE_MAX_GRAPHS 4096
+#define EGC_COLLATE_MAX_ROW_BYTES 4096
+typedef struct {
+  const void* src;     /* [rows of the store, row_bytes] */
+  void* dst;           /* [n_pad or G + 1, row_bytes] */
+  int32_t row_bytes;
+  int32_t elem_bytes;  /* 4 or 8 */
+  uint64_t fill_bits;  /* graph fields: bit pattern of the fill element (low 32 bits for 4-byte elements); node fields: unused */
+} egc_collate_field;
+typedef struct {
+  int32_t n_node, n_graph;
+  egc_collate_field node[EGC_COLLATE_MAX_FIELDS];
+  egc_collate_field graph[EGC_COLLATE_MAX_FIELDS];
+} egc_collate_fields;
+typedef struct {
+  const int64_t* node_ptr;    /* [n_graphs + 1] non-decreasing */
+  const int64_t* edge_ptr;    /* [n_graphs + 1] non-decreasing */
+  const int64_t* edge_index;  /* [2, n_edges_all] node ids local to their graph */
+  int64_t n_graphs;
+  int64_t n_edges_all;
+} egc_collate_store;
+typedef struct {
+  int64_t* edge_index;
+  int64_t* batch;
+  int64_t* ptr;
+  int64_t* edge_ptr;
+  int64_t* n_valid;
+  int64_t* e_valid;
+  int64_t* g_valid;
+  float* counts;
+  float* graph_mask;
+  float* inv_g;
+  int32_t* status;
+} egc_collate_out;
+size_t egc_collate_workspace_bytes(int32_t batch_size);
+int egc_collate(const egc_collate_store* store, const egc_collate_fields* fields, const egc_collate_out* out,
+                const int64_t* ids, int64_t n_ids, const int64_t* perm, const int64_t* perm_len, int64_t* cursor,
+                int32_t batch_size, int64_t n_pad, int64_t e_pad, void* workspace, size_t workspace_bytes,
+                int32_t* host_flag, egc_stream_t stream);
+
 /* Human-readable text of the last HIP failure seen on the calling thread ("" if none). */
 const char* egc_last_error(void);
 
