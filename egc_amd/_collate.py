@@ -125,8 +125,12 @@ class BatchCollator:
                             slots that hold no graph: slots >= g_valid, the spare graph, a slot whose id is out of range
 
     Every element of every buffer is written by every collate.  ``n_pad`` / ``e_pad`` default to ``store.capacity(G)``; at
-    most n_pad - 1 rows are real.  ``FusedEGCBlock(..., n_valid=)``, ``global_*_pool(x, batch, size=G + 1)``, the encoders
-    and the loss heads take the buffers as they are.
+    most n_pad - 1 rows are real.  The encoders (and a Linear embedding) take the node fields as they are,
+    ``FusedEGCBlock(..., n_valid=)`` -- around an EGC layer or ``egc_amd.Mpnn`` -- the activations, ``edge_index`` and
+    ``n_valid``, ``global_*_pool(x, batch, size=G + 1)`` the batch vector; the loss heads (``GraphHead``, ``TokenHead``,
+    ``cross_entropy``) take the first G pooled rows and the first G rows of the label field (a full batch; NaN-filled labels
+    of empty slots drop out of the masked BCE).  Every row of every intermediate array stays finite, padding included
+    (tests/test_batched_nets_golden.py runs the reference's molhiv, CIFAR and ogbg-code nets this way).
 
     Malformed input never writes out of bounds and never goes unreported: a graph id outside [0, M) is an empty slot
     (status bit 1); the first graph with which the rows would exceed n_pad - 1 (bit 2) or the edges e_pad (bit 4), and

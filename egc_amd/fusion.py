@@ -25,7 +25,9 @@ from .graph import GraphBatch, graph_from_input
 class FusedEGCBlock(nn.Module):
     """conv -> BatchNorm1d -> ReLU (-> dropout) (-> + input) as one module; ``conv`` is an ``egc_amd.EfficientGraphConv``
     or ``egc_amd.EGConv``, ``bn`` the ``nn.BatchNorm1d`` that follows it in the reference nets (shared, not copied:
-    state dicts keep their keys), ``dropout`` the probability of the arxiv net's ``F.dropout(x, p, self.training)``
+    state dicts keep their keys); another layer with ``forward(x, edge_index)`` (``egc_amd.Mpnn``) may stand in for
+    ``conv``: it runs by itself, in training the fused tail (with ``n_valid``) follows it, in evaluation torch's
+    operators do.  ``dropout`` the probability of the arxiv net's ``F.dropout(x, p, self.training)``
     (0 for the other nets).  The dropout mask is drawn from torch's generator on the input's device (one byte per
     element), so ``torch.manual_seed`` reproduces a run; the mask of the last training forward stays in
     ``last_keep_mask`` for inspection."""
@@ -131,7 +133,8 @@ class FusedEGCBlock(nn.Module):
             return self._plain(x, edge_index, identity)
         fusable = not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())
                                                     or (identity is not None and identity.requires_grad)))
-        if not fusable:
+        # the tail folds into the store of the EGC layers' own kernel; another conv (egc_amd.Mpnn) runs by itself
+        if not fusable or not hasattr(self.conv, "_packed_weights"):
             return self._plain(x, edge_index, identity)
         identity = x if identity is None else identity
         conv = self.conv

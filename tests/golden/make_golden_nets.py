@@ -130,7 +130,8 @@ def _run(net, call, gout, dtype, state):
     return out_eval, out.detach().clone(), grads, gx
 
 
-def _save(name, meta, inputs, state, gout, r32, r64, manifest):
+def _collect(meta, inputs, state, gout, r32, r64):
+    """(arrays, meta) of one fixture: what _save writes (make_golden_batched_nets.py adds to it before writing)."""
     arrays = {f"in:{k}": v for k, v in inputs.items()}
     arrays.update({f"param:{k}": v.numpy() for k, v in state.items()})
     arrays["gout"] = gout.numpy()
@@ -152,10 +153,16 @@ def _save(name, meta, inputs, state, gout, r32, r64, manifest):
     d_out = float((r32[1].double() - r64[1]).abs().max() / max(1.0, float(r64[1].abs().max())))
     meta = dict(meta, f32_vs_f64_out_train=d_out, f32_vs_f64_grad_max=max(dist.values()), f32_vs_f64_grad=dist,
                 grad_scale=gscale)
+    return arrays, meta
+
+
+def _save(name, meta, inputs, state, gout, r32, r64, manifest):
+    arrays, meta = _collect(meta, inputs, state, gout, r32, r64)
     arrays["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
     np.savez_compressed(os.path.join(HERE, f"{name}.npz"), **arrays)
     manifest[name] = {k: v for k, v in meta.items() if k != "f32_vs_f64_grad"}
-    print(f"{name:26s} out f32-vs-f64 {d_out:.2e}   worst gradient f32-vs-f64 {max(dist.values()):.2e}")
+    print(f"{name:26s} out f32-vs-f64 {meta['f32_vs_f64_out_train']:.2e}   "
+          f"worst gradient f32-vs-f64 {meta['f32_vs_f64_grad_max']:.2e}")
 
 
 def zinc_cases(manifest):
