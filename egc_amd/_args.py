@@ -67,9 +67,12 @@ def _unit_columns(t):
     return t.contiguous() if t.stride(1) != 1 and t.numel() > 0 else t
 
 
-def _workspace(nbytes, dev):
-    """(workspace, nbytes) for a size the library gave: no tensor when it asks for none."""
+def _workspace(nbytes, dev, what=None):
+    """(workspace, nbytes) for a size the library gave: no tensor when it asks for none.  ``what``: zero is the library's
+    "not this shape" (the heads' size queries), raised with that message."""
     nbytes = int(nbytes)
+    if what is not None and nbytes == 0:
+        raise RuntimeError(what)
     return (torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None), nbytes
 
 

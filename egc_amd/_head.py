@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _C
-from ._args import _ptr
+from ._args import _ptr, _workspace
 from .graph import _device_guard, _stream_ptr
 
 LOSS_NONE, LOSS_L1, LOSS_BCE = _C.HEAD_LOSS_NONE, _C.HEAD_LOSS_L1, _C.HEAD_LOSS_BCE_MASKED
@@ -123,6 +123,10 @@ class _HeadFunction(torch.autograd.Function):
         return (None, dx, None, None, *[g if n else None for g, n in zip(grads, need[4:])])
 
 
+def _head_workspace(lib, d, g, dev):
+    return _workspace(lib.egc_head_workspace_bytes(C.byref(d), g), dev, "egc_amd: the head's kernels do not take this shape")
+
+
 class GraphHead(nn.Sequential):
     """``experiments.utils.mlp(sizes, act, dropout)``: the same children (``mlp.*`` state dicts of the reference load with
     ``strict=True``; parameter order and ``repr`` match), on the head kernels:
@@ -219,13 +223,6 @@ class GraphHead(nn.Sequential):
                 self._sync[dev] = w
         return w
 
-    @staticmethod
-    def _workspace(lib, d, g, dev):
-        nbytes = int(lib.egc_head_workspace_bytes(C.byref(d), g))
-        if nbytes == 0:
-            raise RuntimeError("egc_amd: the head's kernels do not take this shape")
-        return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
-
     def _launch_train(self, x, y, kind):
         """The training forward: L launches.  Returns what the backward needs."""
         lib = _C.load()
@@ -239,7 +236,7 @@ class GraphHead(nn.Sequential):
                   "loss2": torch.empty(2, dtype=torch.float32, device=dev) if kind != LOSS_NONE else None}
             for i in range(len(s) - 2):
                 d.z[i], d.stats[i], d.affine[i] = st["z"][i].data_ptr(), st["stats"][i].data_ptr(), st["affine"][i].data_ptr()
-            ws, nbytes = self._workspace(lib, d, g, dev)
+            ws, nbytes = _head_workspace(lib, d, g, dev)
             _C.check(lib.egc_head_forward_train_f32(C.byref(d), x.data_ptr(), g, kind, _ptr(y), st["out"].data_ptr(),
                                                     _ptr(st["loss2"]), ws.data_ptr(), nbytes, self._sync_word(dev).data_ptr(),
                                                     _stream_ptr(dev)), "egc_head_forward_train_f32")
@@ -267,7 +264,7 @@ class GraphHead(nn.Sequential):
                 d.dz[i] = _ptr(dz[i])
                 if want_params:
                     d.d_weight[i], d.d_bias[i] = dw[i].data_ptr(), db[i].data_ptr()
-            ws, nbytes = self._workspace(lib, d, g, dev)
+            ws, nbytes = _head_workspace(lib, d, g, dev)
             _C.check(lib.egc_head_backward_f32(C.byref(d), x.data_ptr(), g, kind, _ptr(y), st["out"].data_ptr(), _ptr(st["loss2"]),
                                                grad.data_ptr(), _ptr(dx), int(want_params), ws.data_ptr(), nbytes,
                                                self._sync_word(dev).data_ptr(), _stream_ptr(dev)), "egc_head_backward_f32")

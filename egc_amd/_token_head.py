@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _C
-from ._args import _ptr
+from ._args import _ptr, _workspace
 from .graph import _IndexFlag, _device_guard, _stream_ptr
 
 
@@ -67,11 +67,9 @@ def _pointers(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-def _workspace(lib, g, k, v, t, dev):
-    nbytes = int(lib.egc_token_head_workspace_bytes(g, k, v, t))
-    if nbytes == 0:
-        raise RuntimeError(f"egc_amd: the token head's kernels do not take [{g}, {k}] x {t} x [{v}, {k}]")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+def _head_workspace(lib, g, k, v, t, dev):
+    return _workspace(lib.egc_token_head_workspace_bytes(g, k, v, t), dev,
+                      f"egc_amd: the token head's kernels do not take [{g}, {k}] x {t} x [{v}, {k}]")
 
 
 def head_forward(x, weights, biases, y, want_argmax: bool):
@@ -84,7 +82,7 @@ def head_forward(x, weights, biases, y, want_argmax: bool):
         loss = torch.empty((), dtype=torch.float32, device=dev) if y is not None else None
         lse = torch.empty((g, t), dtype=torch.float32, device=dev) if y is not None else None
         arg = torch.empty((g, t), dtype=torch.int32, device=dev) if want_argmax else None
-        ws, nbytes = _workspace(lib, g, k, v, t, dev)
+        ws, nbytes = _head_workspace(lib, g, k, v, t, dev)
         _C.check(lib.egc_token_head_forward_f32(x.data_ptr(), _pointers(weights), _pointers(biases), _ptr(y), g, k, v, t,
                                                 _ptr(loss), _ptr(lse), _ptr(arg), ws.data_ptr(), nbytes, _IndexFlag.ptr(),
                                                 _stream_ptr(dev)), "egc_token_head_forward_f32")
@@ -101,7 +99,7 @@ def head_backward(grad_loss, x, weights, biases, y, lse, want_dx: bool, want_dw:
         dx = torch.empty_like(x) if want_dx else None
         dw = [torch.empty_like(w) for w in weights] if want_dw else None
         db = [torch.empty_like(b) for b in biases] if want_db else None
-        ws, nbytes = _workspace(lib, g, k, v, t, dev)
+        ws, nbytes = _head_workspace(lib, g, k, v, t, dev)
         _C.check(lib.egc_token_head_backward_f32(x.data_ptr(), _pointers(weights), _pointers(biases), y.data_ptr(),
                                                  lse.data_ptr(), grad_loss.data_ptr(), g, k, v, t, _ptr(dx),
                                                  _pointers(dw) if want_dw else None, _pointers(db) if want_db else None,

@@ -537,8 +537,7 @@ int egc_column_sums_f32(const float* x, int64_t n_rows, int32_t ld, int32_t cols
                         egc_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (n_rows < 0 || cols <= 0 || ld < cols || partials == nullptr || n_partials <= 0) return EGC_ERR_INVALID;
-  if ((cols & 3) != 0 || (ld & 3) != 0 || cols > 1024 || (reinterpret_cast<uintptr_t>(x) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(partials) & 15) != 0)
+  if ((cols & 3) != 0 || (ld & 3) != 0 || cols > 1024 || !aligned16(x) || !aligned16(partials))
     return EGC_ERR_UNSUPPORTED;
   if (n_rows > 0 && x == nullptr) return EGC_ERR_INVALID;
   const int rows_per_block = (int)std::max<int64_t>(ceil_div(n_rows, (int64_t)n_partials), 1);  // empty blocks write zeros
@@ -668,7 +667,7 @@ static int aggregate_combine_impl(const egc_graph* graph, const egc_layer* layer
   if (graph->rowptr == nullptr || graph->plan == nullptr || (e > 0 && graph->col == nullptr)) return EGC_ERR_INVALID;
   if (bases == nullptr || weightings == nullptr || out == nullptr) return EGC_ERR_INVALID;
   if (ldb != egc_bases_ld(layer)) return EGC_ERR_INVALID;
-  if ((reinterpret_cast<uintptr_t>(bases) & 15) != 0) return EGC_ERR_INVALID;
+  if (!aligned16(bases)) return EGC_ERR_INVALID;
   const int64_t n_src = graph->n_src_rows > 0 ? graph->n_src_rows : n;  // owned rows + halo rows
   // a rectangular adjacency (relation between two node types; fewer sources than rows is possible) has no
   // self loops and no symmetric normalisation: nothing then indexes the source tables by a ROW id
@@ -718,7 +717,7 @@ static int aggregate_combine_impl(const egc_graph* graph, const egc_layer* layer
   if (a.row_begin >= a.row_end) return EGC_OK;
   agg_layer_fields(layer, a);   // (ldb == egc_bases_ld(layer): checked above)
   if (ldw > 0) a.ldw = ldw;     // row stride of `weightings` (a column block of a wider array when > W)
-  if (a.ldw != a.W && (a.ldw < a.W || (a.ldw & 3) != 0 || (reinterpret_cast<uintptr_t>(weightings) & 15) != 0))
+  if (a.ldw != a.W && (a.ldw < a.W || (a.ldw & 3) != 0 || !aligned16(weightings)))
     return EGC_ERR_INVALID;
   a.magic_L = a.L > 1 ? agg_magic(a.L) : 0u;  // L == 1: h = o in-kernel
   a.bases_bytes = (unsigned)((uint64_t)n_src * ldb * 4ull);
@@ -884,7 +883,7 @@ static int fused_batch_args(AggArgs& a, const egc_layer* layer, const int64_t* g
   if (n_nodes == 0 || n_graphs == 0) return EGC_OK;
   if (graph_ptr == nullptr || x == nullptr || packed == nullptr || status == nullptr || !own_ok) return EGC_ERR_INVALID;
   if (n_edges > 0 && (src == nullptr || dst == nullptr)) return EGC_ERR_INVALID;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(packed) & 15) != 0) return EGC_ERR_INVALID;
+  if (!aligned16(x) || !aligned16(packed)) return EGC_ERR_INVALID;
   if (!a.loops_all && max_index == nullptr) return EGC_ERR_INVALID;
   if ((uint64_t)n_nodes * (uint64_t)a.F_out * 4ull > (uint64_t)OOB) return EGC_ERR_UNSUPPORTED;
   batch_rows(a, layer, n_nodes, x);
@@ -925,13 +924,13 @@ int egc_aggregate_combine_batch_f32(const int32_t* tiles, const int32_t* n_tiles
   if (n_nodes == 0 || n_tiles_bound == 0) return EGC_OK;
   if (tiles == nullptr || n_tiles == nullptr || bases == nullptr || weightings == nullptr || out == nullptr || status == nullptr)
     return EGC_ERR_INVALID;
-  if (ldb != a.ldb || (reinterpret_cast<uintptr_t>(bases) & 15) != 0) return EGC_ERR_INVALID;
+  if (ldb != a.ldb || !aligned16(bases)) return EGC_ERR_INVALID;
   if (post != nullptr && ((post->scale == nullptr) != (post->shift == nullptr))) return EGC_ERR_INVALID;
   if (!a.loops_all && max_index == nullptr) return EGC_ERR_INVALID;
   if ((uint64_t)n_nodes * (uint64_t)ldb * 4ull > (uint64_t)OOB) return EGC_ERR_UNSUPPORTED;
   if ((uint64_t)n_nodes * (uint64_t)a.F_out * 4ull > (uint64_t)OOB) return EGC_ERR_UNSUPPORTED;   // out / residual descriptors
   a.ldw = ldw > 0 ? ldw : a.W;
-  if (a.ldw != a.W && (a.ldw < a.W || (a.ldw & 3) != 0 || (reinterpret_cast<uintptr_t>(weightings) & 15) != 0)) return EGC_ERR_INVALID;
+  if (a.ldw != a.W && (a.ldw < a.W || (a.ldw & 3) != 0 || !aligned16(weightings))) return EGC_ERR_INVALID;
   batch_rows(a, layer, n_nodes, bases);
   a.bases = bases;
   a.weightings = weightings;
@@ -1085,9 +1084,9 @@ int egc_layer_backward_batch_fused_f32(const int64_t* graph_ptr, const int64_t* 
   int st = tile_layer_args(layer, a);
   if (st != EGC_OK) return st;
   const bool own_ok =
-      packed_t != nullptr && grad_out != nullptr && d_x != nullptr && (reinterpret_cast<uintptr_t>(packed_t) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(grad_out) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_x_add) & 3) == 0 &&
-      (d_cat == nullptr || (ld_dcat >= a.ldb + a.W && (ld_dcat & 3) == 0 && (reinterpret_cast<uintptr_t>(d_cat) & 15) == 0));
+      packed_t != nullptr && grad_out != nullptr && d_x != nullptr && aligned16(packed_t) && aligned16(grad_out) &&
+      aligned_to(d_x_add, 4) &&
+      (d_cat == nullptr || (ld_dcat >= a.ldb + a.W && (ld_dcat & 3) == 0 && aligned16(d_cat)));
   bool go;
   st = fused_batch_args(a, layer, graph_ptr, n_graphs, src, dst, n_edges, n_nodes, max_index, x, packed, status, own_ok, &go);
   if (!go) return st;

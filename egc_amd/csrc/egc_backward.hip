@@ -1301,7 +1301,7 @@ int egc_aggregate_combine_backward_f32(const egc_graph* graph, const egc_graph* 
   a.ld_db = ld_d_bases > 0 ? ld_d_bases : ldb;
   a.ld_dw = ld_d_weightings > 0 ? ld_d_weightings : p.W;
   // 16-byte row accesses of d_bases; both arrays at least as wide as what is written
-  if (a.ld_db < ldb || (a.ld_db & 3) != 0 || (reinterpret_cast<uintptr_t>(d_bases) & 15) != 0 || a.ld_dw < p.W) return EGC_ERR_INVALID;
+  if (a.ld_db < ldb || (a.ld_db & 3) != 0 || !aligned16(d_bases) || a.ld_dw < p.W) return EGC_ERR_INVALID;
   a.n_nodes = (int)n; a.n_src_rows = (int)n_src; a.n_edges = (int)graph->n_edges;
   a.overwrite_db = n_src == n;
   a.ldb = p.ldb; a.slots = p.slots; a.H = p.H; a.B = p.B; a.A = p.A; a.L = p.L; a.Ls = p.Ls; a.F_g = p.F_g; a.F_out = p.F_out; a.W = p.W;

@@ -246,14 +246,13 @@ __global__ void __launch_bounds__(COL_THREADS) collate_copy_kernel(ColArgs a, in
   }
 }
 
-static inline bool col_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 static int col_check_field(const egc_collate_field& f) {
   if (f.src == nullptr || f.dst == nullptr) return EGC_ERR_INVALID;
   if (f.elem_bytes != 4 && f.elem_bytes != 8) return EGC_ERR_UNSUPPORTED;
   if (f.row_bytes <= 0 || f.row_bytes % f.elem_bytes != 0) return EGC_ERR_INVALID;
   if (f.row_bytes > EGC_COLLATE_MAX_ROW_BYTES) return EGC_ERR_UNSUPPORTED;
-  if (!col_aligned(f.src, (uintptr_t)f.elem_bytes) || !col_aligned(f.dst, (uintptr_t)f.elem_bytes)) return EGC_ERR_INVALID;
+  if (!aligned_to(f.src, (uintptr_t)f.elem_bytes) || !aligned_to(f.dst, (uintptr_t)f.elem_bytes)) return EGC_ERR_INVALID;
   return EGC_OK;
 }
 
@@ -284,7 +283,7 @@ int egc_collate(const egc_collate_store* store, const egc_collate_fields* fields
     return EGC_ERR_INVALID;
   if (fields->n_node < 0 || fields->n_graph < 0) return EGC_ERR_INVALID;
   if (fields->n_node > EGC_COLLATE_MAX_FIELDS || fields->n_graph > EGC_COLLATE_MAX_FIELDS) return EGC_ERR_UNSUPPORTED;
-  if (workspace == nullptr || !col_aligned(workspace, 8) || workspace_bytes < egc_collate_workspace_bytes(batch_size))
+  if (workspace == nullptr || !aligned_to(workspace, 8) || workspace_bytes < egc_collate_workspace_bytes(batch_size))
     return EGC_ERR_WORKSPACE;
   ColArgs a = {};
   a.st = *store;
@@ -306,8 +305,8 @@ int egc_collate(const egc_collate_store* store, const egc_collate_fields* fields
     if (int rc = col_check_field(fd)) return rc;
     a.node[f] = fd;
     int unit = 4;   // the widest access that divides the row and both base addresses: a unit never leaves its row
-    if (fd.row_bytes % 16 == 0 && col_aligned(fd.src, 16) && col_aligned(fd.dst, 16)) unit = 16;
-    else if (fd.row_bytes % 8 == 0 && col_aligned(fd.src, 8) && col_aligned(fd.dst, 8)) unit = 8;
+    if (fd.row_bytes % 16 == 0 && aligned16(fd.src) && aligned16(fd.dst)) unit = 16;
+    else if (fd.row_bytes % 8 == 0 && aligned_to(fd.src, 8) && aligned_to(fd.dst, 8)) unit = 8;
     a.node_unit[f] = unit;
   }
   for (int f = 0; f < fields->n_graph; ++f) {

@@ -64,15 +64,16 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // so lgkmcnt(0) + s_barrier is all that is needed.
 __device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// A lane's four adjacent columns c .. c + 3 of a row of `width` floats (egc_typed_mean.hip, egc_mpnn.hip): one 16-byte access
-// (VEC: width, strides and pointers are multiples of 16 bytes) or 4-byte ones of the columns that exist.
-template <bool VEC>
+// A lane's four adjacent columns c .. c + 3 of a row of `width` floats, p pointing at column c (every kernel that gives a lane
+// four columns: the baseline layers, the encoders, the readouts): one 16-byte access (VEC: width, strides and pointers are
+// multiples of 16 bytes) or 4-byte ones of the columns that exist.  NT: non-temporal loads (data read once: the readouts' x).
+template <bool VEC, bool NT = false>
 __device__ inline f4 tm_load(const float* __restrict__ p, int c, int width) {
-  if (VEC) return *reinterpret_cast<const f4*>(p);
+  if (VEC) return NT ? __builtin_nontemporal_load(reinterpret_cast<const f4*>(p)) : *reinterpret_cast<const f4*>(p);
   f4 v = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    if (c + j < width) v[j] = p[j];
+    if (c + j < width) v[j] = NT ? __builtin_nontemporal_load(p + j) : p[j];
   return v;
 }
 
@@ -110,8 +111,6 @@ __device__ inline void tm_store_i(int32_t* __restrict__ p, int c, int width, i4 
   for (int j = 0; j < 4; ++j)
     if (c + j < width) p[j] = v[j];
 }
-
-static inline bool tm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // egc_backward.hip: CSR positions of the first entries attaining each row's max / min (training forward)
 int arg_extrema(const egc_graph* graph, const egc_layer* layer, const float* bases, int32_t ldb, const float* stats,

@@ -47,29 +47,6 @@ struct EncTables {   // by value in the kernel arguments: nothing to upload, rec
   int32_t slot_offset[EGC_ENCODER_MAX_TABLES + 1];   // prefix sums of min(ENC_CHUNK, rows): partial rows per chunk
 };
 
-template <bool VEC>
-__device__ inline f4 enc_load(const float* __restrict__ x, int64_t r, int width, int c) {
-  const float* p = x + r * width + c;
-  if (VEC) return *reinterpret_cast<const f4*>(p);
-  f4 v = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (c + j < width) v[j] = p[j];
-  return v;
-}
-
-template <bool VEC>
-__device__ inline void enc_store(float* __restrict__ y, int64_t r, int width, int c, f4 v) {
-  float* p = y + r * width + c;
-  if (VEC) {
-    *reinterpret_cast<f4*>(p) = v;
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (c + j < width) p[j] = v[j];
-}
-
 // keep ? v * scale : 0 for a lane's four columns (mask bytes of row r; nullptr: no dropout)
 template <bool VEC>
 __device__ inline f4 enc_drop(f4 v, const uint8_t* __restrict__ keep, float scale, int64_t r, int width, int c) {
@@ -114,7 +91,7 @@ __global__ void __launch_bounds__(256) encoder_forward_kernel(EncTables tb, int 
       const int t = min(t0 + k, n_tables - 1);   // past the last table: the last one again, not taken
       const int key = enc_key(idx, n, n_tables, t, tb.rows[t], tb.clamp[t]);
       bad |= key < 0;
-      v[k] = key >= 0 ? enc_load<VEC>(tb.w[t], key, width, c) : f4{0.f, 0.f, 0.f, 0.f};
+      v[k] = key >= 0 ? tm_load<VEC>(tb.w[t] + (int64_t)key * width + c, c, width) : f4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int k = 0; k < ENC_FWD_BATCH; ++k) {
@@ -125,13 +102,8 @@ __global__ void __launch_bounds__(256) encoder_forward_kernel(EncTables tb, int 
   if (bad && c == 0 && host_flag != nullptr) *(volatile int32_t*)host_flag = 1;   // sticky, host-visible
   acc = enc_drop<VEC>(acc, keep, keep_scale, n, width, c);
   float* p = out + n * width + c;
-  if (VEC) {
-    __builtin_nontemporal_store(acc, reinterpret_cast<f4*>(p));
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (c + j < width) p[j] = acc[j];
-  }
+  if (VEC) __builtin_nontemporal_store(acc, reinterpret_cast<f4*>(p));
+  else tm_store<false>(p, c, width, acc);
 }
 
 // partial rows in front of the rows of workgroup (t, chunk): every table owns n_chunks * min(ENC_CHUNK, rows) of them
@@ -209,7 +181,7 @@ __global__ void __launch_bounds__(ENC_CHUNK) encoder_partial_kernel(EncTables tb
 #pragma unroll
       for (int k = 0; k < ENC_RD_AHEAD; ++k) {   // past the end: the last row again, not taken
         const int64_t r = row0 + s_order[start + min(k0 + k, len - 1)];
-        v[k] = enc_drop<VEC>(enc_load<VEC>(d_out, r, width, c), keep, keep_scale, r, width, c);
+        v[k] = enc_drop<VEC>(tm_load<VEC>(d_out + r * width + c, c, width), keep, keep_scale, r, width, c);
       }
 #pragma unroll
       for (int k = 0; k < ENC_RD_AHEAD; ++k) {
@@ -217,7 +189,7 @@ __global__ void __launch_bounds__(ENC_CHUNK) encoder_partial_kernel(EncTables tb
         else if (k0 + k < len) acc += v[k];
       }
     }
-    enc_store<VEC>(partial, base + l, width, c, acc);
+    tm_store<VEC>(partial + (base + l) * width + c, c, width, acc);
   }
 }
 
@@ -242,7 +214,7 @@ __global__ void __launch_bounds__(256) encoder_reduce_kernel(EncTables tb, int n
     for (int k = 0; k < ENC_RD_AHEAD; ++k) slot[k] = c0 + k < n_chunks ? m[c0 + k] : -1;
 #pragma unroll
     for (int k = 0; k < ENC_RD_AHEAD; ++k)
-      v[k] = slot[k] >= 0 ? enc_load<VEC>(partial, slot[k], width, c) : f4{0.f, 0.f, 0.f, 0.f};
+      v[k] = slot[k] >= 0 ? tm_load<VEC>(partial + (int64_t)slot[k] * width + c, c, width) : f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < ENC_RD_AHEAD; ++k) {
       if (slot[k] >= 0) {
@@ -251,10 +223,8 @@ __global__ void __launch_bounds__(256) encoder_reduce_kernel(EncTables tb, int n
       }
     }
   }
-  enc_store<VEC>(tb.dw[t], d - tb.row_offset[t], width, c, acc);
+  tm_store<VEC>(tb.dw[t] + (d - tb.row_offset[t]) * width + c, c, width, acc);
 }
-
-static inline bool enc_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 static inline int64_t enc_chunks(int64_t n_rows) { return ceil_div(n_rows, ENC_CHUNK); }
 
@@ -303,11 +273,11 @@ int egc_encoder_forward_f32(const float* const* tables, const int32_t* table_row
   int64_t total;
   if (tables == nullptr) return EGC_ERR_INVALID;
   if (int rc = enc_tables(table_rows, clamp, n_tables, width, n_rows, &tb, &total)) return rc;
-  bool vec = (width & 3) == 0 && enc_aligned(out, 16) && enc_aligned(keep, 4);
+  bool vec = (width & 3) == 0 && aligned16(out) && aligned_to(keep, 4);
   for (int t = 0; t < n_tables; ++t) {
     if (tables[t] == nullptr) return EGC_ERR_INVALID;
     tb.w[t] = tables[t];
-    vec = vec && enc_aligned(tables[t], 16);
+    vec = vec && aligned16(tables[t]);
   }
   if (n_rows == 0) return EGC_OK;
   if (idx == nullptr || out == nullptr) return EGC_ERR_INVALID;
@@ -352,7 +322,7 @@ int egc_encoder_backward_f32(const float* d_out, const uint8_t* keep, float keep
     return EGC_OK;
   }
   if (d_out == nullptr || idx == nullptr) return EGC_ERR_INVALID;
-  if (workspace == nullptr || !enc_aligned(workspace, 16) ||
+  if (workspace == nullptr || !aligned16(workspace) ||
       workspace_bytes < egc_encoder_workspace_bytes(n_rows, n_tables, total, width))
     return EGC_ERR_WORKSPACE;
   const int64_t n_chunks = enc_chunks(n_rows);
@@ -360,8 +330,8 @@ int egc_encoder_backward_f32(const float* d_out, const uint8_t* keep, float keep
   float* partial = static_cast<float*>(workspace);
   int32_t* map = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + enc_partial_bytes(n_chunks, slots, width));
   const int lanes = (width + 3) / 4;
-  bool vec = (width & 3) == 0 && enc_aligned(d_out, 16) && enc_aligned(keep, 4);
-  for (int t = 0; t < n_tables; ++t) vec = vec && enc_aligned(d_tables[t], 16);
+  bool vec = (width & 3) == 0 && aligned16(d_out) && aligned_to(keep, 4);
+  for (int t = 0; t < n_tables; ++t) vec = vec && aligned16(d_tables[t]);
   const dim3 grid1((unsigned)n_chunks, (unsigned)n_tables);
   const int64_t blocks2 = ceil_div(total * lanes, 256);
   if (vec) {

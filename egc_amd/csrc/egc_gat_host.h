@@ -72,7 +72,7 @@ struct GatForm {
 static inline GatForm gat_form(int32_t H, int32_t C, std::initializer_list<int32_t> strides, std::initializer_list<const void*> pointers) {
   GatForm f = {gat_geom(H * C).S, all_mult4(H * C), C < 4};
   for (const int32_t ld : strides) f.vec = f.vec && all_mult4(ld);
-  for (const void* p : pointers) f.vec = f.vec && tm_aligned16(p);
+  for (const void* p : pointers) f.vec = f.vec && aligned16(p);
   return f;
 }
 

@@ -124,7 +124,7 @@ extern "C" int egc_basis_transform_f32(const float* x, const float* wcat, const 
   const int nblocks = (int)ceil_div(ldb + w_cols, BN);
   if (mblocks >= ((int64_t)1 << 31)) return EGC_ERR_INVALID;
   dim3 grid((unsigned)mblocks, (unsigned)nblocks);
-  const bool vec4 = (f_in % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  const bool vec4 = (f_in % 4 == 0) && aligned16(x);
   if (vec4)
     basis_gemm_kernel<true><<<grid, 256, 0, stream>>>(x, wcat, bcat, n_nodes, f_in, f_g, w_cols, bases, ldb, weightings);
   else

@@ -581,7 +581,7 @@ int egc_basis_transform_packed_add(const float* x, const void* packed, const flo
   if (p.layout == GEMM_F16X2K) return f16x2k_launch(x, packed, bcat, n_nodes, p, bases, weightings, stream, bases_addend);
   if (bases_addend != nullptr) return EGC_ERR_UNSUPPORTED;   // only the long-k kernels carry the addend
   if (p.layout == GEMM_F16X2) return f16x2_launch(x, packed, bcat, n_nodes, p, bases, weightings, stream);
-  const auto ls = gemm_bf16x3_launches(n_nodes, f_in, p.NV, f_in % 4 == 0 && gemm_aligned16(x));
+  const auto ls = gemm_bf16x3_launches(n_nodes, f_in, p.NV, f_in % 4 == 0 && aligned16(x));
   const u16* pk = (const u16*)packed;
   for (int l = 0; l < ls.n; ++l) {   // as described there: the instances compiled are exactly these
     const GemmBf16x3Launch& g = ls.l[l];

@@ -385,7 +385,7 @@ int f16x2_pack(const float* wcat, int64_t rs, int64_t cs, const GemmPlan& p, voi
 int f16x2_launch(const float* x, const void* packed, const float* bcat, int64_t M, const GemmPlan& p, float* bases,
                  float* weightings, hipStream_t stream, const float* dis, int fold_s, int fold_m) {
   const int K = p.f_in, W = p.w_cols, ldb = p.ldb, NV = p.NV;
-  if (p.layout != GEMM_F16X2 || !gemm_aligned16(x)) return EGC_ERR_UNSUPPORTED;   // (the kernel's shapes: gemm_f16x2_shape)
+  if (p.layout != GEMM_F16X2 || !aligned16(x)) return EGC_ERR_UNSUPPORTED;   // (the kernel's shapes: gemm_f16x2_shape)
   const bool fold = fold_m >= 0;
   if (fold && (dis == nullptr || W % 32 != 0 || fold_m > 3 || fold_s < 0 || fold_s > 3 || fold_s == fold_m)) return EGC_ERR_INVALID;
   const int W_out = fold ? W / 4 * 3 : W;

@@ -595,8 +595,8 @@ static int launch_ks(const GemmLongKLaunch& g, const float* x, const u16* packed
 int f16x2k_launch(const float* x, const void* packed, const float* bcat, int64_t M, const GemmPlan& p, float* bases,
                   float* weightings, hipStream_t stream, const float* addend) {
   const int K = p.f_in, ldb = p.ldb, W = p.w_cols;
-  if (!gemm_aligned16(x) || !gemm_aligned16(bases) || (W > 0 && (W & 3) == 0 && !gemm_aligned16(weightings))) return EGC_ERR_UNSUPPORTED;
-  if (addend != nullptr && (!gemm_aligned16(addend) || (ldb & 3) != 0)) return EGC_ERR_UNSUPPORTED;
+  if (!aligned16(x) || !aligned16(bases) || (W > 0 && (W & 3) == 0 && !aligned16(weightings))) return EGC_ERR_UNSUPPORTED;
+  if (addend != nullptr && (!aligned16(addend) || (ldb & 3) != 0)) return EGC_ERR_UNSUPPORTED;
   const auto ls = gemm_longk_launches(K, p.NT);
   if (ls.status != EGC_OK) return ls.status;
   const KCols c = kcols(p);

@@ -24,7 +24,6 @@ constexpr int XLD = 40;                      // ... LDS row stride in bf16 (80 B
 constexpr int WS_ROWS = 32;                  // weight-stationary bf16x3 kernel: rows per tile
 
 inline int64_t gemm_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline bool gemm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // row tiles of a launch; EGC_ERR_INVALID: more than a 32-bit tile walk (or a grid dimension) holds
 inline int gemm_row_tiles(int64_t M, int rows, int& n_tiles) {
   const int64_t n = gemm_cdiv(M, rows);

@@ -634,9 +634,9 @@ static int weight_grad_impl(const float* x, int64_t ldx, const float* d, int64_t
   hipStream_t stream = (hipStream_t)stream_;
   if (n_rows < 0 || f_in <= 0 || k_cols <= 0 || (out == nullptr && sc == nullptr)) return EGC_ERR_INVALID;
   if (e == nullptr || e_sums == nullptr) { e = nullptr; e_sums = nullptr; e_cols = 0; }
-  if ((f_in % 4) || (k_cols % 4) || (ldx % 4) || (ldd % 4) || ((uintptr_t)x % 16) || ((uintptr_t)d % 16) ||
-      ((uintptr_t)out % 16) || ((uintptr_t)col_sums % 16) || ((uintptr_t)workspace % 16) || (e_cols % 4) || (lde % 4) ||
-      ((uintptr_t)e % 16) || ((uintptr_t)e_sums % 16))
+  if ((f_in % 4) || (k_cols % 4) || (ldx % 4) || (ldd % 4) || !aligned16(x) || !aligned16(d) ||
+      !aligned16(out) || !aligned16(col_sums) || !aligned16(workspace) || (e_cols % 4) || (lde % 4) ||
+      !aligned16(e) || !aligned16(e_sums))
     return EGC_ERR_UNSUPPORTED;
   const bool fp32_only = xt_fp32_only();
   const bool one_tile = !fp32_only && f_in <= X3_TM && k_cols <= X3_TN;
@@ -727,7 +727,7 @@ int egc_sum_partials_f32(const float* partials, int32_t n_partials, int32_t cols
   using namespace egc;
   hipStream_t stream = (hipStream_t)stream_;
   if (n_partials <= 0 || cols <= 0 || partials == nullptr || out == nullptr) return EGC_ERR_INVALID;
-  if ((cols & 3) != 0 || ((uintptr_t)partials & 15) != 0 || ((uintptr_t)out & 15) != 0) return EGC_ERR_UNSUPPORTED;
+  if ((cols & 3) != 0 || !aligned16(partials) || !aligned16(out)) return EGC_ERR_UNSUPPORTED;
   xt_reduce_kernel<<<(unsigned)ceil_div(cols / 4, 16), 256, 0, stream>>>(partials, cols, cols, n_partials, out, nullptr);
   EGC_LAUNCH_CHECK("xt_reduce_kernel");
   return EGC_OK;

@@ -863,7 +863,7 @@ int egc_gather_rows_f32(const float* table, int64_t ld, const int64_t* idx, int6
   if (n_rows < 0 || width <= 0 || (width & 3) != 0 || (ld & 3) != 0 || ld < width) return EGC_ERR_INVALID;
   if (n_rows == 0) return EGC_OK;
   if (table == nullptr || idx == nullptr || out == nullptr) return EGC_ERR_INVALID;
-  if (((uintptr_t)table & 15) != 0 || ((uintptr_t)out & 15) != 0) return EGC_ERR_INVALID;
+  if (!aligned16(table) || !aligned16(out)) return EGC_ERR_INVALID;
   const int64_t pieces = n_rows * (width / 4);
   const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(pieces, (int64_t)256), 256 * 16);
   gather_rows_kernel<<<blocks, 256, 0, stream>>>((const float4*)table, idx, pieces, width / 4, ld / 4, (float4*)out);

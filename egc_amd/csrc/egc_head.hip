@@ -6,7 +6,7 @@
 // positive widths <= EGC_HEAD_MAX_WIDTH (no multiple-of-4 requirement: nothing here moves 16 bytes of global memory at a
 // time), OUT <= EGC_HEAD_MAX_OUT, 2 <= G <= EGC_HEAD_MAX_ROWS rows in training.
 //
-// Launch structure (every dependency on all rows is a launch boundary or the arrival counter of egc_tail.hip: the block whose
+// Launch structure (every dependency on all rows is a launch boundary or the arrival counter of egc_bn_column.h: the block whose
 // agent-scope fetch_add finds all others arrived reads their partials after an acquire fence and re-zeroes the counter; no
 // grid barrier, no spin wait, no cooperative launch, no float atomics):
 //   training forward   L launches of hd_linear_kernel, one per Linear.  Launch l reads its input rows (x, or z_{l-1} with
@@ -43,6 +43,7 @@
 //                 loss = float(sum / count).  The stand-alone losses: thread j = 0 .. 255 takes the elements j, j + 256, ..
 //                 ascending, then the thread sums ascending.
 //   dW, db        one fma chain (db: one chain of adds) over all G rows ascending.
+#include "egc_bn_column.h"
 #include "egc_common.h"
 
 #include <atomic>
@@ -127,23 +128,6 @@ __device__ inline f4 hd_tile_mm(const float* __restrict__ al, const float* __res
   return acc;
 }
 
-// The arrival counter of egc_tail.hip: true in the block that arrives last (all other blocks' agent-scope stores are then
-// visible to its loads), which also re-zeroes the counter.
-__device__ inline bool hd_arrive_last(int* sync, int n_blocks) {
-  __shared__ int last_block;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this block's partials have left
-  __syncthreads();
-  if (threadIdx.x == 0)
-    last_block = __hip_atomic_fetch_add(sync, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == n_blocks - 1;
-  __syncthreads();
-  if (!last_block) return false;
-  if (threadIdx.x == 0) __hip_atomic_store(sync, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  return true;
-}
-
-__device__ inline void hd_store_partial(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // A row block's float64 column sums of a and a * b over the 16 rows ascending, from two LDS tiles [16][HD_PW] (ta, tb):
 // partials[block][0][col] = sum ta, partials[block][1][col] = sum ta * tb
 __device__ inline void hd_block_moments(const float* ta, const float* tb, int c0, int cols, int block, double* partials) {
@@ -155,8 +139,8 @@ __device__ inline void hd_block_moments(const float* ta, const float* tb, int c0
       s1 += a;
       s2 += a * (double)tb[rr * HD_PW + t];
     }
-    hd_store_partial(partials + ((int64_t)block * 2) * cols + c0 + t, s1);
-    hd_store_partial(partials + ((int64_t)block * 2 + 1) * cols + c0 + t, s2);
+    store_partial(partials + ((int64_t)block * 2) * cols + c0 + t, s1);
+    store_partial(partials + ((int64_t)block * 2 + 1) * cols + c0 + t, s2);
   }
 }
 
@@ -196,40 +180,6 @@ __device__ inline void hd_col_totals(const double* __restrict__ partials, int n_
       t1 += red[0][k][cl];
       t2 += red[1][k][cl];
     }
-}
-
-// (egc_tail.hip's bn_forward_column) batch statistics, the affine pair and the module's running statistics of one column
-__device__ inline void hd_bn_forward_column(double s1, double s2, int col, int cols, double n_rows, const float* gamma,
-                                            const float* beta, double eps, double* stats, float* affine, float* running_mean,
-                                            float* running_var, double momentum, double n_tracked) {
-  const double mean = s1 / n_rows;
-  double var = s2 / n_rows - mean * mean;
-  var = var > 0.0 ? var : 0.0;
-  const double rstd = 1.0 / sqrt(var + eps);
-  const double g = gamma != nullptr ? (double)gamma[col] : 1.0, b = beta != nullptr ? (double)beta[col] : 0.0;
-  stats[col] = mean;
-  stats[cols + col] = var;
-  stats[2 * cols + col] = rstd;
-  affine[col] = (float)(g * rstd);
-  affine[cols + col] = (float)(b - mean * g * rstd);
-  if (running_mean != nullptr) {
-    const double m = momentum >= 0.0 ? momentum : 1.0 / n_tracked;
-    running_mean[col] = (float)((1.0 - m) * (double)running_mean[col] + m * mean);
-    running_var[col] = (float)((1.0 - m) * (double)running_var[col] + m * var * (n_rows > 1.0 ? n_rows / (n_rows - 1.0) : 1.0));
-  }
-}
-
-// (egc_tail.hip's bn_backward_column) coef [5][cols] = d gamma, d beta, c_g, c_h, c_1 of dz = c_g g + c_h z + c_1
-__device__ inline void hd_bn_backward_column(double s1, double sgz, int col, int cols, double n_rows, const double* stats,
-                                             const float* gamma, float* coef) {
-  const double mean = stats[col], rstd = stats[2 * cols + col];
-  const double s2 = (sgz - mean * s1) * rstd;   // sum g * z_hat
-  const double a = (gamma != nullptr ? (double)gamma[col] : 1.0) * rstd;
-  coef[col] = (float)s2;
-  coef[cols + col] = (float)s1;
-  coef[2 * cols + col] = (float)a;
-  coef[3 * cols + col] = (float)(-(a / n_rows) * rstd * s2);
-  coef[4 * cols + col] = (float)(-(a / n_rows) * (s1 - mean * rstd * s2));
 }
 
 // one element of a loss in float64: its term and whether it counts
@@ -307,7 +257,7 @@ __global__ void __launch_bounds__(HD_THREADS) hd_linear_kernel(HdLinear a) {
     *reinterpret_cast<f4*>(wl + r * HD_PW + 4 * c4) = z;
     __syncthreads();
     hd_block_moments(wl, wl, c0, a.N, (int)blockIdx.x, a.partials);
-    if (!hd_arrive_last(a.sync, n_blocks)) return;
+    if (!arrive_last(a.sync, n_blocks)) return;
     if (t == 0) {   // nn.BatchNorm1d: the count first, the cumulative average then uses it
       double tracked = 1.0;
       if (a.running_mean != nullptr && a.n_tracked != nullptr) {
@@ -322,7 +272,7 @@ __global__ void __launch_bounds__(HD_THREADS) hd_linear_kernel(HdLinear a) {
       double t1, t2;
       hd_col_totals(a.partials, (int)gridDim.x, a.N, cbase, red, t1, t2);
       if (t < HD_GCOLS && cbase + t < a.N)
-        hd_bn_forward_column(t1, t2, cbase + t, a.N, (double)a.G, a.gamma, a.beta, a.eps, a.stats, a.affine, a.running_mean,
+        bn_forward_column(t1, t2, cbase + t, a.N, (double)a.G, a.gamma, a.beta, a.eps, a.stats, a.affine, a.running_mean,
                              a.running_var, a.momentum, s_tracked);
     }
     return;
@@ -359,10 +309,10 @@ __global__ void __launch_bounds__(HD_THREADS) hd_linear_kernel(HdLinear a) {
       s += dt[k];
       c += ct[k];
     }
-    hd_store_partial(a.lpart + 2 * (int64_t)blockIdx.x, s);
-    hd_store_partial(a.lpart + 2 * (int64_t)blockIdx.x + 1, c);
+    store_partial(a.lpart + 2 * (int64_t)blockIdx.x, s);
+    store_partial(a.lpart + 2 * (int64_t)blockIdx.x + 1, c);
   }
-  if (!hd_arrive_last(a.sync, n_blocks)) return;
+  if (!arrive_last(a.sync, n_blocks)) return;
   s = c = 0.0;
   if (t < 64)
     for (int p = t; p < n_blocks; p += 64) {
@@ -517,12 +467,12 @@ __global__ void __launch_bounds__(HD_THREADS) hd_backward_rows_kernel(HdRows a) 
     hd_block_moments(wl, wl + HD_ROWS * HD_PW, c0, a.Kin, (int)blockIdx.x, a.partials);
   }
   if (a.lower != 2) return;
-  if (!hd_arrive_last(a.sync, (int)gridDim.x)) return;
+  if (!arrive_last(a.sync, (int)gridDim.x)) return;
   for (int cbase = 0; cbase < a.Kin; cbase += HD_GCOLS) {
     double t1, t2;
     hd_col_totals(a.partials, (int)gridDim.x, a.Kin, cbase, red, t1, t2);
     if (t < HD_GCOLS && cbase + t < a.Kin)
-      hd_bn_backward_column(t1, t2, cbase + t, a.Kin, (double)a.G, a.stats_lo, a.gamma_lo, a.coef_lo);
+      bn_backward_column(t1, t2, cbase + t, a.Kin, (double)a.G, a.stats_lo, a.gamma_lo, a.coef_lo, nullptr);
   }
 }
 
@@ -716,7 +666,7 @@ int egc_head_forward_train_f32(const egc_head* h, const float* x, int64_t n_rows
     if (h->z[i] == nullptr || h->stats[i] == nullptr || h->affine[i] == nullptr) return EGC_ERR_INVALID;
     if (h->running_mean[i] != nullptr && h->momentum[i] < 0.0 && h->num_batches_tracked[i] == nullptr) return EGC_ERR_INVALID;
   }
-  if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0 || workspace_bytes < hd_workspace_bytes(h, n_rows))
+  if (workspace == nullptr || !aligned_to(workspace, 8) || workspace_bytes < hd_workspace_bytes(h, n_rows))
     return EGC_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t nb = hd_row_blocks(n_rows);
@@ -804,7 +754,7 @@ int egc_head_backward_f32(const egc_head* h, const float* x, int64_t n_rows, int
   if (want_params)
     for (int i = 0; i < L; ++i)
       if (h->d_weight[i] == nullptr || h->d_bias[i] == nullptr) return EGC_ERR_INVALID;
-  if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0 || workspace_bytes < hd_workspace_bytes(h, n_rows))
+  if (workspace == nullptr || !aligned_to(workspace, 8) || workspace_bytes < hd_workspace_bytes(h, n_rows))
     return EGC_ERR_WORKSPACE;
   if (d_x == nullptr && !want_params) return EGC_OK;
   hipStream_t stream = (hipStream_t)stream_;

@@ -12,6 +12,10 @@ constexpr unsigned OOB = 0xFFFFFFF0u;  // any offset >= num_records makes a buff
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// THE alignment predicate of every launcher (a null pointer counts as aligned); bytes: a power of two
+static inline bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+static inline bool aligned16(const void* p) { return aligned_to(p, 16); }
+
 constexpr int AMAX = 4;     // aggregators supported by the register-resident combine
 
 // floor(2^32 / d) + 1: q / d == umulhi(q, magic) for the q < 2^16 the kernels divide

@@ -30,31 +30,6 @@ namespace egc {
 
 constexpr int RD_AHEAD = 8;   // rows requested before the first add that consumes them (8 x 16 bytes per lane in flight)
 
-template <bool VEC>
-__device__ inline f4 load_cols(const float* __restrict__ x, int64_t r, int width, int c) {
-  const float* p = x + r * width + c;
-  if (VEC) return __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
-  f4 v = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (c + j < width) v[j] = __builtin_nontemporal_load(p + j);
-  return v;
-}
-
-template <bool VEC, typename T, typename V>
-__device__ inline void store_cols(T* __restrict__ y, int64_t r, int width, int c, V v) {
-  T* p = y + r * width + c;
-  if (VEC) {
-    *reinterpret_cast<V*>(p) = v;
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (c + j < width) p[j] = v[j];
-}
-
-typedef int i4 __attribute__((ext_vector_type(4)));
-
 // one row into the running state of a lane's four columns, in input order (`live` false: the state stays as it is)
 template <int OP>
 __device__ inline void take_row(f4& acc, i4& win, f4 v, int64_t r, bool live = true) {
@@ -86,20 +61,20 @@ __global__ void __launch_bounds__(256) segment_reduce_kernel(const float* __rest
   for (; r + RD_AHEAD <= r1; r += RD_AHEAD) {   // (not unrolled further: typical segments are a few batches long)
     f4 v[RD_AHEAD];
 #pragma unroll
-    for (int k = 0; k < RD_AHEAD; ++k) v[k] = load_cols<VEC>(x, r + k, width, c);
+    for (int k = 0; k < RD_AHEAD; ++k) v[k] = tm_load<VEC, true>(x + (r + k) * width + c, c, width);
 #pragma unroll
     for (int k = 0; k < RD_AHEAD; ++k) take_row<OP>(acc, win, v[k], r + k);
   }
   if (r < r1) {   // the last, partial batch: every load issued (past the end: the last row again, not taken), no branch
     f4 v[RD_AHEAD - 1];
 #pragma unroll
-    for (int k = 0; k < RD_AHEAD - 1; ++k) v[k] = load_cols<VEC>(x, min(r + k, r1 - 1), width, c);
+    for (int k = 0; k < RD_AHEAD - 1; ++k) v[k] = tm_load<VEC, true>(x + min(r + k, r1 - 1) * width + c, c, width);
 #pragma unroll
     for (int k = 0; k < RD_AHEAD - 1; ++k) take_row<OP>(acc, win, v[k], r + k, r + k < r1);
   }
   if (OP == EGC_READOUT_MEAN) acc /= (float)(r1 > r0 ? r1 - r0 : 1);   // scatter-mean divides the sum by the count
-  store_cols<VEC>(out, g, width, c, acc);
-  if (OP == EGC_READOUT_MAX && arg != nullptr) store_cols<VEC>(arg, g, width, c, win);
+  tm_store<VEC>(out + g * width + c, c, width, acc);
+  if (OP == EGC_READOUT_MAX && arg != nullptr) tm_store_i<VEC>(arg + g * width + c, c, width, win);
 }
 
 template <int OP, bool VEC>
@@ -118,17 +93,8 @@ __global__ void __launch_bounds__(256) segment_reduce_backward_kernel(const floa
   if (g < n_segments) {
     r0 = min(max(seg_ptr[g], (int64_t)0), n_rows), r1 = min(max(seg_ptr[g + 1], r0), n_rows);
     if (r0 < r1) {
-      if (VEC) {
-        d = *reinterpret_cast<const f4*>(d_out + g * width + c);
-        if (OP == EGC_READOUT_MAX) win = *reinterpret_cast<const i4*>(arg + g * width + c);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (c + j < width) {
-            d[j] = d_out[g * width + c + j];
-            if (OP == EGC_READOUT_MAX) win[j] = arg[g * width + c + j];
-          }
-      }
+      d = tm_load<VEC>(d_out + g * width + c, c, width);
+      if (OP == EGC_READOUT_MAX) win = tm_load_i<VEC>(arg + g * width + c, c, width);
       if (OP == EGC_READOUT_MEAN) d /= (float)(r1 - r0);
     }
   } else if (g == n_segments) {   // rows in front of the first segment
@@ -143,11 +109,9 @@ __global__ void __launch_bounds__(256) segment_reduce_backward_kernel(const floa
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = win[j] == (int)r ? d[j] : 0.f;
     }
-    store_cols<VEC>(d_x, r, width, c, v);
+    tm_store<VEC>(d_x + r * width + c, c, width, v);
   }
 }
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // threads of the grid: one group of ceil(width / 4) lanes per row range
 static inline int64_t readout_blocks(int64_t n_ranges, int lanes) { return ceil_div(n_ranges * lanes, 256); }

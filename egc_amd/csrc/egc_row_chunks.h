@@ -116,7 +116,7 @@ static inline int grid_blocks(int64_t items, int64_t per_block, unsigned& blocks
 }
 
 static inline bool workspace_ok(const void* workspace, size_t workspace_bytes, size_t needed) {
-  return workspace != nullptr && tm_aligned16(workspace) && workspace_bytes >= needed;
+  return workspace != nullptr && aligned16(workspace) && workspace_bytes >= needed;
 }
 
 // the 16-byte access form: every width and stride a multiple of four floats, every pointer 16-byte aligned (NULL counts)
@@ -126,7 +126,7 @@ static inline bool all_mult4(T... n) {
 }
 template <class... T>
 static inline bool all_aligned16(T... p) {
-  return (tm_aligned16(p) && ...);
+  return (aligned16(p) && ...);
 }
 
 }  // namespace egc

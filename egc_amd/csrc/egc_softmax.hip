@@ -313,8 +313,6 @@ __global__ void __launch_bounds__(SM_BLOCK) selection_count_kernel(const int64_t
   if ((threadIdx.x & 63) == 0 && b != 0) atomicAdd(total, (unsigned long long)__popcll(b));
 }
 
-static inline bool sm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 struct SmShape {
   int gl, k;
   int64_t chunks;
@@ -361,7 +359,7 @@ int egc_log_softmax_forward_f32(const float* x, int64_t n_rows, int32_t n_classe
   if (n_rows == 0) return EGC_OK;
   if (x == nullptr || out == nullptr) return EGC_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
-  const bool vec = (ld & 3) == 0 && (n_classes & 3) == 0 && sm_aligned16(x) && sm_aligned16(out);
+  const bool vec = (ld & 3) == 0 && (n_classes & 3) == 0 && aligned16(x) && aligned16(out);
   SM_LAUNCH(log_softmax_forward_kernel, x, n_rows, n_classes, ld, sh.gl, out, lse, argmax);
   return EGC_OK;
 }
@@ -373,7 +371,7 @@ int egc_log_softmax_backward_f32(const float* grad_out, const float* out, int64_
   if (n_rows == 0) return EGC_OK;
   if (grad_out == nullptr || out == nullptr || d_x == nullptr) return EGC_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
-  const bool vec = (ld & 3) == 0 && (n_classes & 3) == 0 && sm_aligned16(grad_out) && sm_aligned16(out) && sm_aligned16(d_x);
+  const bool vec = (ld & 3) == 0 && (n_classes & 3) == 0 && aligned16(grad_out) && aligned16(out) && aligned16(d_x);
   SM_LAUNCH(log_softmax_backward_kernel, grad_out, out, n_rows, n_classes, ld, sh.gl, d_x);
   return EGC_OK;
 }
@@ -407,13 +405,13 @@ int egc_nll_log_softmax_forward_f32(const float* x, const int64_t* y, const int3
   if (int rc = sm_shape(n_rows, n_classes, ld, &sh)) return rc;
   if (loss == nullptr || (cnt != nullptr && total == nullptr)) return EGC_ERR_INVALID;
   if (n_rows > 0 && (x == nullptr || y == nullptr || lse == nullptr)) return EGC_ERR_INVALID;
-  if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 3) != 0 ||
+  if (workspace == nullptr || !aligned_to(workspace, 4) ||
       workspace_bytes < egc_nll_log_softmax_workspace_bytes(n_rows, n_classes))
     return EGC_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   float* partial = static_cast<float*>(workspace);
   if (n_rows > 0) {
-    const bool vec = (ld & 3) == 0 && sm_aligned16(x);
+    const bool vec = (ld & 3) == 0 && aligned16(x);
     SM_LAUNCH(nll_forward_kernel, x, y, cnt, n_rows, n_classes, ld, sh.gl, lse, partial, host_flag);
   }
   nll_finalize_kernel<<<1, SM_BLOCK, 0, stream>>>(partial, sh.chunks, cnt != nullptr ? total : nullptr, n_rows, mean != 0, loss);
@@ -431,7 +429,7 @@ int egc_nll_log_softmax_backward_f32(const float* x, const int64_t* y, const int
       (cnt != nullptr && total == nullptr))
     return EGC_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
-  const bool vec = (ld & 3) == 0 && sm_aligned16(x) && sm_aligned16(d_x);
+  const bool vec = (ld & 3) == 0 && aligned16(x) && aligned16(d_x);
   SM_LAUNCH(nll_backward_kernel, x, y, cnt, cnt != nullptr ? total : nullptr, lse, grad_loss, n_rows, n_classes, ld, sh.gl,
             mean != 0, d_x);
   return EGC_OK;

@@ -11,6 +11,7 @@
 // All four are plain streaming kernels: 16 bytes per lane, channel constants from LDS, HBM-bound.
 #include <algorithm>
 
+#include "egc_bn_column.h"
 #include "egc_common.h"
 #include "egc_pack_map.h"
 
@@ -55,11 +56,6 @@ struct FinArgs {
 template <bool COHERENT>
 __device__ inline void moment_totals(const double* __restrict__ partials, int n_partials, int cols, int col, int pl,
                                      double (&red)[2][4][64 + 1], double& t1, double& t2);
-__device__ inline void bn_forward_column(double s1, double s2, int col, int cols, double n_rows, const float* gamma, const float* beta,
-                                         double eps, double* stats, float* affine, float* running_mean, float* running_var,
-                                         double momentum, double n_tracked);
-__device__ inline void bn_backward_column(double s1, double sgh, int col, int cols, double n_rows, const double* stats,
-                                          const float* gamma, float* outv, float* dh_sums);
 
 template <bool MASKED, int FIN = 0>   // FIN: 0 partials only, 1 + forward finalize, 2 + backward finalize
 __global__ void __launch_bounds__(256) column_moments_kernel(const float* __restrict__ a, const float* __restrict__ b,
@@ -125,8 +121,8 @@ __global__ void __launch_bounds__(256) column_moments_kernel(const float* __rest
     if (FIN != 0) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        __hip_atomic_store(o + 4 * g + i, s1[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(o + cols + 4 * g + i, s2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        store_partial(o + 4 * g + i, s1[i]);
+        store_partial(o + cols + 4 * g + i, s2[i]);
       }
     } else {
       reinterpret_cast<d4*>(o)[g] = s1;
@@ -134,15 +130,7 @@ __global__ void __launch_bounds__(256) column_moments_kernel(const float* __rest
     }
   }
   if constexpr (FIN != 0) {
-    __shared__ int last_block;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this block's partials have left
-    __syncthreads();
-    if (threadIdx.x == 0)
-      last_block = __hip_atomic_fetch_add(fin.sync, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
-    __syncthreads();
-    if (!last_block) return;
-    if (threadIdx.x == 0) __hip_atomic_store(fin.sync, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (!arrive_last(fin.sync, (int)gridDim.x)) return;
     const double nr = fmax((double)n_rows, 1.0);
     // One thread per column; at most 64 partial blocks (host), added in the finalize kernels' order -- eight runs of eight
     // partials, then the eight run totals: the same bits as the two-launch form.  All loads of a column are independent.
@@ -221,43 +209,6 @@ __device__ inline void moment_totals(const double* __restrict__ partials, int n_
   t1 = t2 = 0.0;
   if (pl == 0)
     for (int k = 0; k < 8; ++k) { t1 += red[0][cl][k]; t2 += red[1][cl][k]; }
-}
-
-__device__ inline void bn_forward_column(double s1, double s2, int col, int cols, double n_rows, const float* gamma, const float* beta,
-                                         double eps, double* stats, float* affine, float* running_mean, float* running_var,
-                                         double momentum, double n_tracked) {
-  const double mean = s1 / n_rows;
-  double var = s2 / n_rows - mean * mean;
-  var = var > 0.0 ? var : 0.0;
-  const double rstd = 1.0 / sqrt(var + eps);
-  const double g = gamma != nullptr ? (double)gamma[col] : 1.0, b = beta != nullptr ? (double)beta[col] : 0.0;
-  stats[col] = mean;
-  stats[cols + col] = var;
-  stats[2 * cols + col] = rstd;
-  affine[col] = (float)(g * rstd);
-  affine[cols + col] = (float)(b - mean * g * rstd);
-  if (running_mean != nullptr) {
-    const double m = momentum >= 0.0 ? momentum : 1.0 / n_tracked;
-    running_mean[col] = (float)((1.0 - m) * (double)running_mean[col] + m * mean);
-    running_var[col] = (float)((1.0 - m) * (double)running_var[col] + m * var * (n_rows > 1.0 ? n_rows / (n_rows - 1.0) : 1.0));
-  }
-}
-
-__device__ inline void bn_backward_column(double s1, double sgh, int col, int cols, double n_rows, const double* stats,
-                                          const float* gamma, float* outv, float* dh_sums) {
-  const double mean = stats[col], rstd = stats[2 * cols + col];
-  const double s2 = (sgh - mean * s1) * rstd;                 // sum g * h_hat
-  const double a = (gamma != nullptr ? (double)gamma[col] : 1.0) * rstd;
-  const float cg = (float)a, ch = (float)(-(a / n_rows) * rstd * s2), c1 = (float)(-(a / n_rows) * (s1 - mean * rstd * s2));
-  outv[col] = (float)s2;                                      // d gamma
-  outv[cols + col] = (float)s1;                               // d beta
-  outv[2 * cols + col] = cg;                                  // dh = a g - (a / n) (s1 + (h - mean) rstd s2)
-  outv[3 * cols + col] = ch;
-  outv[4 * cols + col] = c1;
-  // The column sum of the dh the elementwise pass will write (the gradient of a bias in front of the BatchNorm: zero but for
-  // rounding -- autograd's value is the float sum of its own dh): sum_rows (cg g + ch h + c1) with the three coefficients AS
-  // ROUNDED above, from the sums this step already holds (sum g = s1, sum h = n mean) -- no pass over dh.
-  if (dh_sums != nullptr) dh_sums[col] = (float)((double)cg * s1 + (double)ch * (n_rows * mean) + n_rows * (double)c1);
 }
 
 // Everything between the statistics pass and the elementwise pass of the training-mode BatchNorm tail, per column:
@@ -346,8 +297,6 @@ __global__ void __launch_bounds__(256) tail_backward_kernel(const float* __restr
   __builtin_nontemporal_store(r, reinterpret_cast<f4*>(dh) + k);
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // The GEMM operand of a layer from its parameters, and the parameter gradients from the operand's gradient.
 //   wcat [F_in][B Ls + W] = [the B basis matrices side by side, each padded from L to Ls columns | comb_weight^T],
 //   bcat [W] = comb_bias   (W = H B A).  The bases come as ONE [F_in][B L] matrix (EGConv.bases_weight) or as B matrices
@@ -388,12 +337,12 @@ int egc_column_moments_f64(const float* a, const float* b, const float* scale, c
   hipStream_t stream = (hipStream_t)stream_;
   if (n_rows < 0 || cols <= 0 || partials == nullptr || n_partials <= 0) return EGC_ERR_INVALID;
   if ((cols & 3) != 0 || cols > 1024 || !aligned16(a) || !aligned16(b) || !aligned16(scale) || !aligned16(shift) ||
-      (reinterpret_cast<uintptr_t>(partials) & 31) != 0)
+      !aligned_to(partials, 32))
     return EGC_ERR_UNSUPPORTED;
   if (n_rows > 0 && a == nullptr) return EGC_ERR_INVALID;
   const bool masked = b != nullptr;
   if (masked && relu && (scale == nullptr || shift == nullptr)) return EGC_ERR_INVALID;
-  if (keep != nullptr && (!masked || (reinterpret_cast<uintptr_t>(keep) & 3) != 0)) return EGC_ERR_INVALID;
+  if (keep != nullptr && (!masked || !aligned_to(keep, 4))) return EGC_ERR_INVALID;
   const int rows_per_block = (int)std::max<int64_t>(ceil_div(n_rows, (int64_t)n_partials), 1);  // empty blocks write zeros
   if (masked)
     column_moments_kernel<true><<<(unsigned)n_partials, 256, 0, stream>>>(a, b, scale, shift, n_rows, cols,
@@ -421,7 +370,7 @@ int egc_bn_forward_stats_f32(const float* h, int64_t n_rows, int32_t cols, doubl
   }
   if (n_rows <= 0 || cols <= 0 || partials == nullptr || n_partials <= 0 || h == nullptr || stats == nullptr || affine == nullptr)
     return EGC_ERR_INVALID;
-  if ((cols & 3) != 0 || cols > 1024 || !aligned16(h) || (reinterpret_cast<uintptr_t>(partials) & 31) != 0) return EGC_ERR_UNSUPPORTED;
+  if ((cols & 3) != 0 || cols > 1024 || !aligned16(h) || !aligned_to(partials, 32)) return EGC_ERR_UNSUPPORTED;
   if ((running_mean == nullptr) != (running_var == nullptr)) return EGC_ERR_INVALID;
   if (running_mean != nullptr && momentum < 0.0 && n_tracked == nullptr) return EGC_ERR_INVALID;
   if (running_mean != nullptr && n_rows < 2) return EGC_ERR_INVALID;
@@ -468,10 +417,10 @@ int egc_bn_backward_stats_sums_f32(const float* dout, const float* h, const floa
       out5 == nullptr)
     return EGC_ERR_INVALID;
   if ((cols & 3) != 0 || cols > 1024 || !aligned16(dout) || !aligned16(h) || !aligned16(scale) || !aligned16(shift) ||
-      (reinterpret_cast<uintptr_t>(partials) & 31) != 0)
+      !aligned_to(partials, 32))
     return EGC_ERR_UNSUPPORTED;
   if (relu && (scale == nullptr || shift == nullptr)) return EGC_ERR_INVALID;
-  if (keep != nullptr && (reinterpret_cast<uintptr_t>(keep) & 3) != 0) return EGC_ERR_INVALID;
+  if (keep != nullptr && !aligned_to(keep, 4)) return EGC_ERR_INVALID;
   FinArgs f = FinArgs();
   f.sync = sync; f.gamma = gamma; f.bstats = stats; f.outv = out5; f.dh_sums = dh_col_sums;
   const int rows_per_block = (int)std::max<int64_t>(ceil_div(n_rows, (int64_t)n_partials), 1);
@@ -514,7 +463,7 @@ int egc_affine_act_residual_f32(const float* h, const float* scale, const float*
   if (n_rows == 0) return EGC_OK;
   if (h == nullptr || out == nullptr) return EGC_ERR_INVALID;
   const int64_t quads = n_rows * (cols / 4);
-  if ((reinterpret_cast<uintptr_t>(keep) & 3) != 0) return EGC_ERR_UNSUPPORTED;
+  if (!aligned_to(keep, 4)) return EGC_ERR_UNSUPPORTED;
   affine_act_residual_kernel<<<(unsigned)ceil_div(quads, 256), 256, 0, stream>>>(h, scale, shift, residual, relu, quads, cols / 4, out,
                                                                                keep, keep_scale, n_valid);
   EGC_LAUNCH_CHECK("affine_act_residual_kernel");
@@ -535,7 +484,7 @@ int egc_affine_act_backward_f32(const float* dout, const float* h, const float* 
   if (n_rows == 0) return EGC_OK;
   if (dout == nullptr || h == nullptr || dh == nullptr) return EGC_ERR_INVALID;
   const int64_t quads = n_rows * (cols / 4);
-  if ((reinterpret_cast<uintptr_t>(keep) & 3) != 0) return EGC_ERR_UNSUPPORTED;
+  if (!aligned_to(keep, 4)) return EGC_ERR_UNSUPPORTED;
   tail_backward_kernel<<<(unsigned)ceil_div(quads, 256), 256, 0, stream>>>(dout, h, scale, shift, relu, coef_g, coef_h, coef_1, quads,
                                                                          cols / 4, dh, keep, keep_scale, n_valid);
   EGC_LAUNCH_CHECK("tail_backward_kernel");

@@ -400,8 +400,6 @@ __global__ void __launch_bounds__(TH_BLOCK) th_dx_reduce_kernel(const float* __r
   reinterpret_cast<f4*>(dx)[i] = s;
 }
 
-static inline bool th_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 }  // namespace egc
 
@@ -425,13 +423,13 @@ int egc_token_head_forward_f32(const float* x, const float* const* weights, cons
   ThPtrs ptrs = {};
   for (int t = 0; t < seq_len; ++t) {
     if (weights[t] == nullptr || biases[t] == nullptr) return EGC_ERR_INVALID;
-    if (!th_aligned16(weights[t])) return EGC_ERR_UNSUPPORTED;
+    if (!aligned16(weights[t])) return EGC_ERR_UNSUPPORTED;
     ptrs.w[t] = weights[t];
     ptrs.b[t] = biases[t];
   }
   if (n_rows > 0 && x == nullptr) return EGC_ERR_INVALID;
-  if (!th_aligned16(x)) return EGC_ERR_UNSUPPORTED;
-  if (workspace == nullptr || !th_aligned16(workspace) || workspace_bytes < pl.bytes) return EGC_ERR_WORKSPACE;
+  if (!aligned16(x)) return EGC_ERR_UNSUPPORTED;
+  if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < pl.bytes) return EGC_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   float* ws = static_cast<float*>(workspace);
   float* term = ws + pl.off_term;
@@ -465,15 +463,15 @@ int egc_token_head_backward_f32(const float* x, const float* const* weights, con
   for (int t = 0; t < seq_len; ++t) {
     if (weights[t] == nullptr || biases[t] == nullptr) return EGC_ERR_INVALID;
     if ((d_weights != nullptr && d_weights[t] == nullptr) || (d_biases != nullptr && d_biases[t] == nullptr)) return EGC_ERR_INVALID;
-    if (!th_aligned16(weights[t]) || (d_weights != nullptr && !th_aligned16(d_weights[t]))) return EGC_ERR_UNSUPPORTED;
+    if (!aligned16(weights[t]) || (d_weights != nullptr && !aligned16(d_weights[t]))) return EGC_ERR_UNSUPPORTED;
     ptrs.w[t] = weights[t];
     ptrs.b[t] = biases[t];
     ptrs.dw[t] = d_weights != nullptr ? d_weights[t] : nullptr;
     ptrs.db[t] = d_biases != nullptr ? d_biases[t] : nullptr;
   }
   if (n_rows > 0 && (x == nullptr || y == nullptr || lse == nullptr)) return EGC_ERR_INVALID;
-  if (!th_aligned16(x) || !th_aligned16(d_x)) return EGC_ERR_UNSUPPORTED;
-  if (workspace == nullptr || !th_aligned16(workspace) || workspace_bytes < pl.bytes) return EGC_ERR_WORKSPACE;
+  if (!aligned16(x) || !aligned16(d_x)) return EGC_ERR_UNSUPPORTED;
+  if (workspace == nullptr || !aligned16(workspace) || workspace_bytes < pl.bytes) return EGC_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   if (n_rows == 0) {   // no row: the parameters' gradients are zeros, d_x is empty
     for (int t = 0; t < seq_len; ++t) {

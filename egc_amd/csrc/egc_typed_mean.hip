@@ -162,7 +162,7 @@ int egc_typed_mean_f32(const egc_typed_rel* rels, int32_t n_rels, int64_t n_rows
     if (R.rowptr == nullptr) T.rel[r].col = nullptr, T.rel[r].n_edges = 0;
     T.slot0[r + 1] = T.slot0[r] + tm_slots(R);
     if (!accumulate) cols_end = R.out_col + width > cols_end ? R.out_col + width : cols_end;
-    vec = vec && (R.ld_in & 3) == 0 && tm_aligned16(R.in) && (accumulate || (R.out_col & 3) == 0);
+    vec = vec && (R.ld_in & 3) == 0 && aligned16(R.in) && (accumulate || (R.out_col & 3) == 0);
   }
   if (ld_out < cols_end) return EGC_ERR_INVALID;
   const int64_t slots = T.slot0[n_rels];
