@@ -9,6 +9,8 @@ import os
 
 import torch
 
+from . import _C
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _PATH = os.path.join(_HERE, "lib", "libegc_torch_ext.so")
 _OPS = None
@@ -24,8 +26,7 @@ def ops():
     global _OPS, _TRIED
     if not _TRIED:
         _TRIED = True
-        if os.environ.get("EGC_NO_NATIVE_EXT", "0") in ("", "0") and os.path.exists(_PATH):
-            from . import _C
+        if not _C.env_flag("EGC_NO_NATIVE_EXT") and os.path.exists(_PATH):
             _C.load()                      # libegc_hip.so first: the extension links against it
             torch.ops.load_library(_PATH)
             _OPS = torch.ops.egc_amd_native

@@ -33,8 +33,7 @@ namespace egc {
 
 // EGC_STDVAR_REFERENCE set (not "" / "0") and the layer has a var / std aggregator; read on every call
 bool stdvar_reference(const egc_layer* layer) {
-  const char* e = getenv("EGC_STDVAR_REFERENCE");
-  if (layer == nullptr || e == nullptr || e[0] == '\0' || (e[0] == '0' && e[1] == '\0')) return false;
+  if (layer == nullptr || !env_on("EGC_STDVAR_REFERENCE")) return false;
   for (int t = 0; t < layer->num_aggrs && t < EGC_MAX_AGGRS; ++t)
     if (layer->aggrs[t] == EGC_AGGR_VAR || layer->aggrs[t] == EGC_AGGR_STD) return true;
   return false;
@@ -647,10 +646,7 @@ int egc_aggregate_combine_train_rows_f32(const egc_graph* graph, const egc_layer
 }
 
 // EGC_NO_GATHER_PLAN set to anything but "" / "0": a static graph's gather plan is left alone
-static bool gather_plan_off() {
-  const char* v = getenv("EGC_NO_GATHER_PLAN");
-  return v != nullptr && v[0] != '\0' && !(v[0] == '0' && v[1] == '\0');
-}
+static bool gather_plan_off() { return env_on("EGC_NO_GATHER_PLAN"); }
 
 static int aggregate_combine_impl(const egc_graph* graph, const egc_layer* layer, const float* bases, int32_t ldb,
                                   const float* weightings, const float* bias, const egc_post* post, float* out,
@@ -765,7 +761,7 @@ static int aggregate_combine_impl(const egc_graph* graph, const egc_layer* layer
   PlanCaps caps = plan_caps(n, e);
   a.rows_per_wave = 0;
   a.n_chunks_hint = (graph->n_chunks >= 0 && graph->n_chunks <= caps.cap_chunks) ? (int)graph->n_chunks : -1;
-  const bool force_generic = getenv("EGC_FORCE_GENERIC") != nullptr || a.var_ref != 0;
+  const bool force_generic = env_on("EGC_FORCE_GENERIC") || a.var_ref != 0;
   if (!force_generic && fast_path_supported(a, layer->weight_layout, chunks)) {
     if (arg_done != nullptr) *arg_done = true;  // the register-resident kernels track the arg positions themselves
     return launch_fast(a, n, caps, stream);
@@ -774,7 +770,7 @@ static int aggregate_combine_impl(const egc_graph* graph, const egc_layer* layer
   switch (chunks) {
     case 1: return launch_all<1>(a, n, caps, wpb, lds_bytes, stream);
     case 2: return launch_all<2>(a, n, caps, wpb, lds_bytes, stream,
-                                 !force_generic && getenv("EGC_NO_WIDE") == nullptr && wide_path_supported(a, layer->weight_layout));
+                                 !force_generic && !env_on("EGC_NO_WIDE") && wide_path_supported(a, layer->weight_layout));
     case 3: return launch_all<3>(a, n, caps, wpb, lds_bytes, stream);
     case 4: return launch_all<4>(a, n, caps, wpb, lds_bytes, stream);
     default: return EGC_ERR_UNSUPPORTED;
@@ -1101,8 +1097,7 @@ int32_t egc_layer_gemm_flags(const egc_layer* layer) {
   // itself is up to 3.7e-4 off; profiles/r04_stdvar_shift.md).  EGC_GEMM_STDVAR_24BIT=1 brings the old choice back.
   if (layer == nullptr) return 0;
   if (egc::stdvar_reference(layer)) return EGC_GEMM_24BIT;     // (the reference-formula mode: 24-bit operands, no one-launch path)
-  const char* e = getenv("EGC_GEMM_STDVAR_24BIT");
-  if (e == nullptr || e[0] == '\0' || (e[0] == '0' && e[1] == '\0')) return 0;
+  if (!egc::env_on("EGC_GEMM_STDVAR_24BIT")) return 0;
   for (int t = 0; t < layer->num_aggrs && t < EGC_MAX_AGGRS; ++t)
     if (layer->aggrs[t] == EGC_AGGR_VAR || layer->aggrs[t] == EGC_AGGR_STD) return EGC_GEMM_24BIT;
   return 0;

@@ -489,7 +489,7 @@ int launch_wide_rows(AggArgs a, const PlanCaps& caps, hipStream_t stream) {
   const size_t lds = (size_t)4 * a.lds_floats_per_wave * sizeof(float);
   if (lds > 64 * 1024) return EGC_ERR_UNSUPPORTED;
   const unsigned grid = (unsigned)(a.chunk_blocks + ceil_div((int64_t)a.row_end - a.row_begin, (int64_t)4 * a.rows_per_wave));
-  if (getenv("EGC_NO_STATIC_CFG") == nullptr) {
+  if (!env_on("EGC_NO_STATIC_CFG")) {
     int status = EGC_OK;
     constexpr int X = EGC_AGGR_MAX, N = EGC_AGGR_MIN, Y = EGC_AGGR_SYMNORM;
     // the reference's ogbg-code nets (run_pretrained.sh:47-48): EGC-M 300/H4/B4 symadd,min,max and EGC-S 304/H8/B8 symadd
@@ -576,7 +576,7 @@ int launch_fast(AggArgs a, int64_t n_nodes, const PlanCaps& caps, hipStream_t st
   const int64_t row_blocks = ceil_div((int64_t)a.row_end - a.row_begin, (int64_t)4 * a.rows_per_wave * G);
   const unsigned grid = (unsigned)(a.chunk_blocks + row_blocks);
 
-  if (getenv("EGC_NO_STATIC_CFG") == nullptr) {
+  if (!env_on("EGC_NO_STATIC_CFG")) {
     int status = EGC_OK;
     constexpr int S = EGC_AGGR_SUM, M = EGC_AGGR_MEAN, X = EGC_AGGR_MAX, Y = EGC_AGGR_SYMNORM;
     // EGConv / EGC-M north star: d=128, H=8, B=4, sum+mean+max+symnorm, gcn_norm self-loops on every node

@@ -501,7 +501,7 @@ int launch_tile(AggArgs a, TileArgs t, int n_tiles, hipStream_t stream) {
   const unsigned grid = (unsigned)std::min(n_tiles, 256 * TILE_WGS_PER_CU);   // persistent: n_tiles = upper bound of the tile count
   // the d = 128 layer configurations with their constants compiled in (the same idea as EGC_STATIC_CFG of the fast kernel):
   // 16-lane groups, two heads per lane, no optional aggregate
-  if (getenv("EGC_NO_STATIC_CFG") == nullptr) {
+  if (!env_on("EGC_NO_STATIC_CFG")) {
     if (cfg_matches<cfg::EGConvM128>(a)) return launch_tile_one<4, 2, 0, cfg::EGConvM128>(a, t, grid, L.total, stream);
     if (cfg_matches<cfg::EgcM128>(a)) return launch_tile_one<4, 2, 0, cfg::EgcM128>(a, t, grid, L.total, stream);
     if (cfg_matches<cfg::EgcS128>(a)) return launch_tile_one<4, 2, 0, cfg::EgcS128>(a, t, grid, L.total, stream);

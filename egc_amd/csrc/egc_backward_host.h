@@ -101,7 +101,7 @@ struct BwdSwitches {
   bool rec_separate;   // EGC_BWD_REC_SEPARATE: records by bwd_records_kernel also behind the register form
 };
 inline BwdSwitches bwd_switches() {
-  return {getenv("EGC_BWD_GENERIC") != nullptr, getenv("EGC_BWD_NO_REC") != nullptr, getenv("EGC_BWD_REC_SEPARATE") != nullptr};
+  return {env_on("EGC_BWD_GENERIC"), env_on("EGC_BWD_NO_REC"), env_on("EGC_BWD_REC_SEPARATE")};
 }
 
 // The workspace: tables T, S, V, X, N of [n, ldb] floats, then one 64-byte record per entry and extremum (max first).

@@ -225,7 +225,7 @@ struct FtSwitches {
 };
 inline FtSwitches ft_switches() {
   const char* e = getenv("EGC_FT_GRID");
-  return {getenv("EGC_NO_STATIC_CFG") == nullptr, e != nullptr ? std::max(1, atoi(e)) : 256};
+  return {!env_on("EGC_NO_STATIC_CFG"), e != nullptr ? std::max(1, atoi(e)) : 256};
 }
 // one workgroup per CU at most; fewer when the batch is small (a workgroup's share: at least ~16 nodes, at least one graph)
 inline unsigned ft_grid(const FtSwitches& sw, int64_t n_graphs, int64_t n_nodes) {

@@ -535,10 +535,7 @@ constexpr XtShape XT_SHAPES[] = {{1, 1, 4}, {1, 2, 4}, {1, 3, 4}, {2, 1, 4}, {2,
 // instead of the split-bf16 form
 // Read per call (a getenv is nothing next to a launch): the host side decides from the same variables at every call
 // (functional._weight_grads), and a value cached here at first use would disagree with it once the environment changes.
-bool xt_fp32_only() {
-  const char* e = getenv("EGC_GEMM_EXACT");
-  return e != nullptr && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0');
-}
+bool xt_fp32_only() { return env_on("EGC_GEMM_EXACT"); }
 
 XtPlan xt_plan(int64_t n_rows, int F, int K) {
   // Tile shape and row split together, by modelled time: a workgroup's time per row of the reduction is the larger of its tile's MFMA

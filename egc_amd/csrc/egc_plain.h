@@ -3,6 +3,7 @@
 // compiled without HIP) build on it.
 #pragma once
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "egc_hip.h"
 
@@ -15,6 +16,13 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // THE alignment predicate of every launcher (a null pointer counts as aligned); bytes: a power of two
 static inline bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 static inline bool aligned16(const void* p) { return aligned_to(p, 16); }
+
+// THE reading of an on/off switch of the environment: on iff set to anything but "" / "0", as
+// egc_amd._C.env_flag reads it; read on every call
+static inline bool env_on(const char* name) {
+  const char* v = getenv(name);
+  return v != nullptr && v[0] != '\0' && !(v[0] == '0' && v[1] == '\0');
+}
 
 constexpr int AMAX = 4;     // aggregators supported by the register-resident combine
 

@@ -48,7 +48,7 @@ namespace {
 
 constexpr int TH_SLAB = EGC_TOKEN_HEAD_SLAB;
 constexpr int TH_WAVES = 8, TH_THREADS = 64 * TH_WAVES, TH_ROWS = 16 * TH_WAVES;   // 512 threads, 128 rows per block
-constexpr int TH_MAX_K = 384, TH_KT = TH_MAX_K / 16;                               // k tiles of the dx accumulators
+constexpr int TH_MAX_K = EGC_TOKEN_HEAD_MAX_IN, TH_KT = TH_MAX_K / 16;                               // k tiles of the dx accumulators
 constexpr int TH_GP = TH_SLAB + 4;        // pitch of the g tile: rows 4 apart and rows 1 apart with columns 4 apart hit distinct banks
 constexpr int TH_CUS = 256;
 constexpr int TH_BLOCK = 256;             // threads of the combine / finalize / reduce kernels

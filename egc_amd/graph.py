@@ -150,7 +150,7 @@ class CSRGraph:
                      "egc_coo_to_csr_checked")
             g = cls._prepare(n, e, rowptr, col, edge_id, max_index, num_src_rows, plan=plan)
             g._status = status
-            if os.environ.get("EGC_CHECK_INDICES", "0") not in ("", "0"):
+            if _C.env_flag("EGC_CHECK_INDICES"):
                 g.check_indices()
             return g
 
@@ -195,7 +195,7 @@ class CSRGraph:
         g = cls(n, e, rowptr, col, edge_id, dis_raw, dis_looped, max_index, plan, ns)
         g.edge_dis_raw, g.edge_dis_looped = edr, edl
         g._status = status
-        if os.environ.get("EGC_CHECK_INDICES", "0") not in ("", "0"):
+        if _C.env_flag("EGC_CHECK_INDICES"):
             g.check_indices()
         return g
 

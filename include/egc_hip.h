@@ -670,9 +670,10 @@ int egc_nll_log_softmax_backward_f32(const float* x, const int64_t* y, const int
  * outside the limits), 16-byte aligned, any content; EGC_ERR_WORKSPACE if smaller.  Forward: three launches (two without
  * y), backward: two (one without d_x).
  * EGC_ERR_INVALID: a missing pointer, n_rows < 0, in_features, n_classes or seq_len <= 0; EGC_ERR_UNSUPPORTED: in_features % 4
- * != 0 or > 384, seq_len > EGC_TOKEN_HEAD_MAX_SEQ, n_classes or n_rows > 2^30, x / W_t / d_x / d_W_t not 16-byte aligned. */
+ * != 0 or > EGC_TOKEN_HEAD_MAX_IN, seq_len > EGC_TOKEN_HEAD_MAX_SEQ, n_classes or n_rows > 2^30, x / W_t / d_x / d_W_t not 16-byte aligned. */
 #define EGC_TOKEN_HEAD_MAX_SEQ 8
 #define EGC_TOKEN_HEAD_SLAB 64
+#define EGC_TOKEN_HEAD_MAX_IN 384   /* widest in_features */
 size_t egc_token_head_workspace_bytes(int64_t n_rows, int32_t in_features, int32_t n_classes, int32_t seq_len);
 int egc_token_head_forward_f32(const float* x, const float* const* weights, const float* const* biases, const int64_t* y,
                                int64_t n_rows, int32_t in_features, int32_t n_classes, int32_t seq_len, float* loss, float* lse,

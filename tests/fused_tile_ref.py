@@ -7,7 +7,9 @@ planner to both and states the one place they may differ.  Also the entry points
 fast_path_supported / wide_path_supported of egc_aggregate_fast.hip, without their per-launch terms)."""
 from collections import namedtuple
 
-OK, INVALID, UNSUPPORTED = 0, 1, 4                 # EGC_OK, EGC_ERR_INVALID, EGC_ERR_UNSUPPORTED of include/egc_hip.h
+from egc_amd import _C
+
+OK, INVALID, UNSUPPORTED = _C.OK, _C.ERR_INVALID, _C.ERR_UNSUPPORTED
 SUM, MEAN, MAX, MIN, VAR, STD, SYMNORM = range(7)  # EGC_AGGR_*
 ACT_NONE, ACT_SOFTMAX = 0, 1
 LAYOUT_HBA = 0

@@ -9,7 +9,7 @@ refuse).  ``recovered_count`` is the forward GEMM's ``rint(1 / (d * d))`` (egc_g
 
 ``tier_ladder`` is an edge list with one destination row of every length at which build_rows_kernel changes its sort -- one below,
 on and one above each tier constant.  The constants are READ FROM THE SOURCES (``constants()``: the ``constexpr int NAME = ...;``
-lines of egc_graph.hip and the two long-row ``#define``s of include/egc_hip.h), so the ladder follows the code when one moves;
+lines of egc_graph.hip and the two long-row ``#define``s of include/egc_hip.h as the binding reads them), so the ladder follows the code when one moves;
 the one tier edge that has no name there (a row of up to 16 entries is ranked through the lanes) is ``LANE_ROW`` below."""
 import functools
 import os
@@ -18,11 +18,11 @@ from collections import namedtuple
 
 import numpy as np
 
+from egc_amd import _C
 from nbr_ref import dis_tables, transposed_csr  # noqa: F401  (the graph tests import them from here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRAPH_HIP = os.path.join(ROOT, "egc_amd", "csrc", "egc_graph.hip")
-PUBLIC_H = os.path.join(ROOT, "include", "egc_hip.h")
 KERNEL_NAMES = ("BUILD_SCAN_ITEMS", "BUILD_LDS_SORT", "BUILD_WAVE_ROW", "BUILD_RANK_ROW", "BUILD_TILE", "BUILD_WIN",
                 "BUILD_MERGE_ROW", "PREP_ROWS", "PREP_HUGE", "ROWS_PER_BLOCK", "ROWS_PER_GROUP")
 HEADER_NAMES = ("EGC_LONG_ROW_THRESHOLD", "EGC_LONG_ROW_CHUNK")
@@ -37,14 +37,11 @@ def constants():
     """{name: value} of the tier and size constants, parsed from the sources (an expression may name earlier constants)."""
     with open(GRAPH_HIP) as f:
         hip = f.read()
-    with open(PUBLIC_H) as f:
-        hdr = f.read()
     out = {}
     for name in HEADER_NAMES:
-        m = re.search(r"^#define %s (\d+)\s*$" % name, hdr, re.M)
-        if m is None:
+        if name not in _C.ABI.constants:
             raise AssertionError(f"include/egc_hip.h no longer has '#define {name} <int>': tests/graph_ref.py takes the tiers from it")
-        out[name] = int(m.group(1))
+        out[name] = _C.ABI.constants[name]
     found = {m.group(1): m.group(2) for m in re.finditer(r"^constexpr int (\w+) = ([^;]+);", hip, re.M)}
     for name in KERNEL_NAMES:
         if name not in found:

@@ -29,7 +29,7 @@ from egc_amd.functional import make_spec
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "tests", "backward_plan", "_build", "backward_plan_check")
-UNSUPPORTED = 4                                   # EGC_ERR_UNSUPPORTED of include/egc_hip.h
+UNSUPPORTED = _C.ERR_UNSUPPORTED
 SWITCH_NAMES = ("EGC_BWD_GENERIC", "EGC_BWD_NO_REC", "EGC_BWD_REC_SEPARATE")
 MODES = ((), ("EGC_BWD_NO_REC",), ("EGC_BWD_REC_SEPARATE",), ("EGC_BWD_GENERIC",))     # of tests/test_backward_shapes_cpu.py
 SWITCHES = MODES + (("EGC_BWD_NO_REC", "EGC_BWD_GENERIC"),)

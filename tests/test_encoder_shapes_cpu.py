@@ -10,6 +10,7 @@ from pathlib import Path
 import torch
 
 import encoder_ref as ref
+from egc_amd import _C
 
 ROOT = Path(__file__).resolve().parent.parent
 HEADER = re.sub(r"[\s*]+", " ", (ROOT / "include" / "egc_hip.h").read_text())
@@ -18,7 +19,7 @@ HEADER = re.sub(r"[\s*]+", " ", (ROOT / "include" / "egc_hip.h").read_text())
 def test_the_header_states_the_order_restated_here():
     assert "nodes are cut into chunks of 256; inside a chunk the rows of one destination are added in ascending n" in HEADER
     assert "chunk sums are added in ascending chunk order" in HEADER
-    assert "#define EGC_ENCODER_MAX_TABLES 16" in HEADER and "#define EGC_ENCODER_MAX_WIDTH 1024" in HEADER
+    assert _C.ENCODER_MAX_TABLES == 16 and _C.ENCODER_MAX_WIDTH == 1024
     assert ref.ENC_CHUNK == 256 and max(ref.SWEEP_TABLE_COUNTS) == 16 and max(ref.SWEEP_WIDTHS) == 1024
 
 

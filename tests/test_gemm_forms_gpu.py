@@ -13,11 +13,13 @@ import numpy as np
 import pytest
 import torch
 
+from egc_amd import _C
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_forms.json")
 ROWS = (1, 17, 65, 200)
-GEMM_24BIT = 1                       # EGC_GEMM_24BIT of include/egc_hip.h
+GEMM_24BIT = _C.GEMM_24BIT
 
 # (f_in, f_g, w_cols, flags): what the plan program prints for each is behind it
 SHAPES = [
@@ -70,7 +72,6 @@ def _operands(n, f_in, cols, w_cols, seed):
 
 
 def _gemm(n, f_in, f_g, w_cols, flags, addend=False, transposed=False):
-    from egc_amd import _C
     lib = _C.load()
     st = torch.cuda.current_stream().cuda_stream
     x, wcat, bcat = _operands(n, f_in, f_g + w_cols, w_cols, seed=1000 * n + f_in + 7 * f_g + w_cols)

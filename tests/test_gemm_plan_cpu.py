@@ -26,8 +26,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "gemm_plan.json")
 _EDGES = (4, 32, 33, 64, 65, 96, 97, 128, 129, 132, 160, 224, 225, 228, 256, 257, 260, 288, 289, 292, 352, 384, 385, 388, 389)
 F_IN = sorted({v for e in _EDGES for v in (e - 1, e, e + 1)} | set(range(4, 401, 12)) | set(range(1, 401, 29)) | {400})
 COLS = (0, 1, 7, 16, 20, 32, 64, 124, 168, 176, 192, 208, 224, 300, 320, 512)     # f_g and w_cols
-GEMM_24BIT = 1                                    # EGC_GEMM_24BIT of include/egc_hip.h
-FLAGS = (0, GEMM_24BIT)
+FLAGS = (0, _C.GEMM_24BIT)
 ROWS = 200
 LAYOUT_CODE = {"BF16X3": "B", "F16X2": "H", "F16X2K": "K"}
 LDS_MAX = 160 * 1024
@@ -128,7 +127,7 @@ def test_launch_descriptions_obey_the_kernels_limits(plans):
         assert p["ldb"] == (p["f_g"] + 3) // 4 * 4 and p["NV"] % 32 == 0 and 0 <= p["NV"] - p["ldb"] - p["w_cols"] < 32, key
         assert p["KS"] == -(-p["f_in"] // 32) and p["NT"] == -(-p["ldb"] // 16) + -(-p["w_cols"] // 16), key
         assert p["refused"] is None, key                    # rows = 200: no family refuses a shape planned for it
-        if p["flags"] & GEMM_24BIT:
+        if p["flags"] & _C.GEMM_24BIT:
             assert p["layout"] == "BF16X3", key
         if p["layout"] == "F16X2K":
             assert 1 <= len(p["longk"]) <= 2 and sum(g["tiles"] for g in p["longk"]) == p["NT"], key

@@ -329,7 +329,8 @@ def test_gather_rows_equals_index_select(width, rows, table_rows, pad):
 
 
 def test_gather_rows_refuses_what_it_cannot_do_in_16_byte_pieces():
-    INVALID = 1                                                             # EGC_ERR_INVALID (include/egc_hip.h)
+    INVALID = _C.ERR_INVALID
+    assert INVALID == 1
     assert _C._STATUS[INVALID] == "EGC_ERR_INVALID"
     full = torch.randn(16, 16, device=DEV)
     idx = torch.arange(4, device=DEV)

@@ -26,7 +26,7 @@ def run(x, wcat, bcat, f_g, w_cols, mode):
         _C.check(lib.egc_basis_transform_f32(x.data_ptr(), wcat.data_ptr(), bcat.data_ptr(), n, f_in, f_g, w_cols, bases.data_ptr(),
                                              ldb, wt.data_ptr(), st), "f32")
     else:
-        flags = 1 if mode == "24bit" else 0   # EGC_GEMM_24BIT (include/egc_hip.h)
+        flags = _C.GEMM_24BIT if mode == "24bit" else 0
         nb = lib.egc_basis_pack_bytes(f_in, f_g, w_cols)
         planes = torch.empty(nb, dtype=torch.uint8, device=DEV)
         _C.check(lib.egc_basis_pack_ex(wcat.data_ptr(), f_in, f_g, w_cols, flags, planes.data_ptr(), nb, st), "pack")
