@@ -66,6 +66,11 @@ Public surface (mirrors the reference's layer API):
                        ``collate(ids)``, or ``set_epoch(perm)`` + ``next()`` with cursor and permutation read on the device, so
                        that ``next()`` recorded inside a GraphedStep makes one replay the whole iteration; malformed batches
                        are clamped, flagged and named by ``check()``
+  Adam(params, lr, betas, eps, weight_decay)
+                       drop-in for torch.optim.Adam at the reference's settings (L2 weight decay, no amsgrad; state dicts
+                       exchange with torch's): the step of ALL tensors of a parameter group -- parameter, both moments and,
+                       with ``step(zero_grad=True)``, the zeroed gradients -- as one launch that records into a GraphedStep;
+                       ``lr`` is a device scalar the kernel reads, so a scheduler changes the rate of a recorded step
 """
 from .graph import CSRGraph, GraphBatch, SparseTensor, GLOBAL_GRAPH_CACHE  # noqa: F401
 from .functional import egc_layer_forward, make_spec, LayerSpec  # noqa: F401
@@ -83,6 +88,7 @@ from ._token_head import TokenHead, token_head_argmax, token_head_loss  # noqa: 
 from ._head import GraphHead, l1_loss, masked_bce_with_logits  # noqa: F401
 from .hipgraph import GraphedStep  # noqa: F401
 from ._collate import EGC_COLLATE_MAX_FIELDS, BatchCollator, GraphStore  # noqa: F401
+from .optim import Adam  # noqa: F401
 from . import ops  # noqa: F401  (registers torch.ops.egc_amd.*)
 
 __version__ = "0.1.0"

@@ -9,14 +9,14 @@ OBJ="$HERE/obj"
 mkdir -p "$OUT" "$OBJ"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="-O3 --offload-arch=gfx950 -fPIC -std=c++17 -ffp-contract=off -I$ROOT/include -I$HERE -Wall -Wno-unused-function -Wno-pass-failed ${EGC_EXTRA_FLAGS:-}"
-SRCS="egc_graph egc_gather_plan egc_gemm egc_gemm_bf16x3 egc_gemm_f16x2 egc_gemm_f16x2k egc_gemm_xt egc_aggregate egc_aggregate_fast egc_aggregate_tile egc_fused_tile egc_fused_tile_wide1 egc_fused_tile_wide2 egc_fused_tile_wide3 egc_backward egc_tail egc_readout egc_encoder egc_softmax egc_token_head egc_head egc_typed_mean egc_mpnn egc_gatv2 egc_gat egc_pna egc_nbr_sum egc_collate"
+SRCS="egc_graph egc_gather_plan egc_gemm egc_gemm_bf16x3 egc_gemm_f16x2 egc_gemm_f16x2k egc_gemm_xt egc_aggregate egc_aggregate_fast egc_aggregate_tile egc_fused_tile egc_fused_tile_wide1 egc_fused_tile_wide2 egc_fused_tile_wide3 egc_backward egc_tail egc_readout egc_encoder egc_softmax egc_token_head egc_head egc_typed_mean egc_mpnn egc_gatv2 egc_gat egc_pna egc_nbr_sum egc_collate egc_adam"
 pids=()
 objs=()
 for src in $SRCS; do
   objs+=("$OBJ/$src.o")
   stale=0
   [ -f "$OBJ/$src.o" ] || stale=1
-  for dep in "$HERE/$src.hip" "$HERE"/*.h "$HERE"/*.inc "$ROOT/include/egc_hip.h"; do   # every header: an object does not say which it includes
+  for dep in "$HERE/$src.hip" "$HERE"/*.h "$HERE"/*.inc "$ROOT/include/egc_hip.h" "$ROOT/include/egc_optim.h"; do   # every header: an object does not say which it includes
     [ "$dep" -nt "$OBJ/$src.o" ] && stale=1
   done
   if [ $stale = 1 ]; then

@@ -39,7 +39,7 @@ the entire iteration, and an epoch a loop of replays with no host work (_collate
         h = model(col.fields["x"], col.edge_index, n_valid=col.n_valid)
         out = head(egc_amd.global_mean_pool(h, col.batch, size=G + 1))
         (((out - col.fields["y"]) ** 2 * col.graph_mask).sum() * col.inv_g).backward()
-        optimizer.step(); optimizer.zero_grad(set_to_none=False)
+        optimizer.step(zero_grad=True)                           # egc_amd.Adam: one launch, the gradients zeroed in it
     graphed = egc_amd.GraphedStep(step, params=model.parameters())   # (its warm-up runs are real steps and advance the cursor)
     for epoch in range(epochs):
         col.set_epoch(torch.randperm(M, device=dev))             # re-shuffling does not invalidate the recording
@@ -70,9 +70,10 @@ class GraphedStep:
 
     ``warmup`` eager runs on a side stream come first (torch's recipe): one-time work -- kernel attribute calls,
     workspaces cached on graph objects, the allocator's pools -- must not land in the recording.  They are real calls
-    of ``fn``: a step that also runs the optimizer (``torch.optim.Adam(..., capturable=True)`` followed by
-    ``zero_grad(set_to_none=False)`` -- the whole iteration is then one replay, parameters bit-identical to the eager
-    loop's, tests/test_hipgraph_gpu.py) has trained ``warmup + 1`` iterations when the constructor returns."""
+    of ``fn``: a step that also runs the optimizer (``egc_amd.Adam(...).step(zero_grad=True)``, one launch,
+    tests/test_adam_gpu.py; or ``torch.optim.Adam(..., capturable=True)`` followed by ``zero_grad(set_to_none=False)``,
+    tests/test_hipgraph_gpu.py -- the whole iteration is then one replay, parameters bit-identical to the eager loop's)
+    has trained ``warmup + 1`` iterations when the constructor returns."""
 
     def __init__(self, fn: Callable[[], None], params: Optional[Iterable[torch.nn.Parameter]] = None, warmup: int = 3,
                  pool=None):
