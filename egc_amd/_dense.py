@@ -89,11 +89,28 @@ def pack_layer_weights(bases, comb_w, comb_b, f_in, H, A, B, L, Ls, permute_hab:
     return wcat, (bcat if comb_b is not None else None)
 
 
+def third_stream_rides(f_in: int, k: int, e_cols: int) -> bool:
+    """Whether an [N, e_cols] array's column sums ride along with the [f_in, k] weight gradient: in the one-tile kernel only
+    (include/egc_hip.h; the fp32-MFMA form of EGC_GEMM_EXACT has no third stream either: the caller asks gemm_exact())."""
+    return f_in <= _C.WEIGHT_GRAD_TILE_ROWS and k <= _C.WEIGHT_GRAD_TILE_COLS and e_cols <= _C.WEIGHT_GRAD_MAX_SUM_COLS
+
+
+def _xt_operands(n, *operands) -> bool:
+    """Whether every operand is an [n, multiple of 4] matrix as the weight-gradient entry points take it: float32 on the device,
+    n > 0, unit column stride, row stride a multiple of 4, 16-byte aligned."""
+    return n > 0 and all(t.dim() == 2 and t.size(0) == n and t.size(1) % 4 == 0 and t.is_cuda and t.dtype == torch.float32
+                         and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 for t in operands)
+
+
+def _xt_workspace(lib, n, f_in, k, e_cols, dev):
+    return torch.empty(max(int(lib.egc_weight_grad_ex_workspace_bytes(n, f_in, k, e_cols)), 16), dtype=torch.uint8, device=dev)
+
+
 def _weight_grads(x: torch.Tensor, d: torch.Tensor, col_sums: bool = False, extra: torch.Tensor | None = None):
     """(x^T @ d, d.sum(0) or None[, extra.sum(0)]) for tall x [N, F], d [N, K]: the gradient of [bases_weight |
     comb_weights.weight], of comb_weights.bias and -- with ``extra`` = grad_out -- of the layer's bias (autograd's
     products behind optimized_layers.py:177-178,207-208) in one pass over the operands through egc_weight_grad_ex_f32:
-    split-bf16 matrix-core products with fp32-level accuracy over row ranges (outputs of up to 128 x 192) or exact fp32
+    split-bf16 matrix-core products with fp32-level accuracy over row ranges (outputs of one accumulator tile) or exact fp32
     products on a grid of output tiles (wider ones), added in a fixed order.  Shapes outside that entry point's envelope
     (a dimension not a multiple of 4) take torch's GEMM on the device.  (Rounds 2 - 5 also sent wide outputs on long
     reductions there; with the tall tiles and the per-XCD row split of round 6 the entry point is level with the library's
@@ -104,26 +121,20 @@ def _weight_grads(x: torch.Tensor, d: torch.Tensor, col_sums: bool = False, extr
 
     def done(w, s, e):
         return (w, s) if extra is None else (w, s, e)
-    if (n == 0 or f % 4 or k % 4 or not x.is_cuda or x.dtype != torch.float32 or d.dtype != torch.float32
-            or x.stride(1) != 1 or d.stride(1) != 1 or x.stride(0) % 4 or d.stride(0) % 4
-            or x.data_ptr() % 16 or d.data_ptr() % 16):
+    if not _xt_operands(n, x, d):
         return done(_xt_library(x, d), _column_sums(d) if col_sums else None, _column_sums(extra) if extra is not None else None)
     lib = _C.load()
     dev = x.device
-    ride = (extra is not None and col_sums and f <= 128 and k <= 192 and extra.dim() == 2 and extra.size(0) == n
-            and extra.size(1) % 4 == 0 and extra.size(1) <= 128 and extra.dtype == torch.float32 and extra.stride(1) == 1
-            and extra.stride(0) % 4 == 0 and extra.data_ptr() % 16 == 0 and not gemm_exact())   # (the fp32-MFMA form has no third stream)
+    ride = extra is not None and col_sums and _xt_operands(n, extra) and third_stream_rides(f, k, extra.size(1)) and not gemm_exact()
     with _device_guard(dev):
         out = torch.empty((f, k), dtype=torch.float32, device=dev)
         cs = torch.empty(k, dtype=torch.float32, device=dev) if col_sums else None
         e_cols = extra.size(1) if ride else 0
         es = torch.empty(e_cols, dtype=torch.float32, device=dev) if ride else None
-        nbytes = int(lib.egc_weight_grad_ex_workspace_bytes(n, f, k, e_cols))
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        _C.check(lib.egc_weight_grad_ex_f32(x.data_ptr(), x.stride(0), d.data_ptr(), d.stride(0), n, f, k, out.data_ptr(),
-                                            _ptr(cs), extra.data_ptr() if ride else None, extra.stride(0) if ride else 0, e_cols,
-                                            es.data_ptr() if ride else None, ws.data_ptr(), ws.numel(),
-                                            _stream_ptr(dev)), "egc_weight_grad_ex_f32")
+        ws = _xt_workspace(lib, n, f, k, e_cols, dev)
+        _C.check(lib.egc_weight_grad_ex_f32(x.data_ptr(), x.stride(0), d.data_ptr(), d.stride(0), n, f, k, out.data_ptr(), _ptr(cs),
+                                            extra.data_ptr() if ride else None, extra.stride(0) if ride else 0, e_cols, _ptr(es),
+                                            ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "egc_weight_grad_ex_f32")
     if extra is not None and not ride:
         es = _column_sums(extra)
     return done(out, cs, es)
@@ -136,11 +147,8 @@ def _weight_grads_into_params(x, d, extra, dims, permute, shapes, packed_b):
     d bias)."""
     f_in, H, A, B, L, Ls = dims
     n, k = x.size(0), d.size(1)
-    if (n == 0 or f_in > 128 or k > 192 or f_in % 4 or k % 4 or x.dtype != torch.float32 or d.dtype != torch.float32
-            or x.stride(1) != 1 or d.stride(1) != 1 or x.stride(0) % 4 or d.stride(0) % 4 or x.data_ptr() % 16 or d.data_ptr() % 16
-            or extra.dim() != 2 or extra.size(0) != n or extra.size(1) % 4 or extra.size(1) > 128 or extra.dtype != torch.float32
-            or extra.stride(1) != 1 or extra.stride(0) % 4 or extra.data_ptr() % 16 or gemm_exact()
-            or k != B * Ls + H * B * A):
+    if (not _xt_operands(n, x, d, extra) or not third_stream_rides(f_in, k, extra.size(1)) or gemm_exact()
+            or x.size(1) != f_in or k != B * Ls + H * B * A):
         return None
     lib = _C.load()
     dev = x.device
@@ -152,12 +160,10 @@ def _weight_grads_into_params(x, d, extra, dims, permute, shapes, packed_b):
         ptrs = (C.c_void_p * len(dparts))(*[p.data_ptr() for p in dparts])
         e_cols = extra.size(1)
         es = torch.empty(e_cols, dtype=torch.float32, device=dev)
-        nbytes = int(lib.egc_weight_grad_ex_workspace_bytes(n, f_in, k, e_cols))
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        ws = _xt_workspace(lib, n, f_in, k, e_cols, dev)
         _C.check(lib.egc_weight_grad_params_f32(x.data_ptr(), x.stride(0), d.data_ptr(), d.stride(0), n, f_in, H, A, B, L, Ls,
-                                                int(permute), ptrs, len(dparts), dcw.data_ptr(), _ptr(dcb), _ptr(dbc),
-                                                extra.data_ptr(), extra.stride(0),
-                                                e_cols, es.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev)),
+                                                int(permute), ptrs, len(dparts), dcw.data_ptr(), _ptr(dcb), _ptr(dbc), extra.data_ptr(),
+                                                extra.stride(0), e_cols, es.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev)),
                  "egc_weight_grad_params_f32")
     return dcw, dcb, dbc, dparts, es
 

@@ -516,25 +516,37 @@ __global__ void __launch_bounds__(256) xt_reduce_kernel(const float* __restrict_
   }
 }
 
+static_assert(X3_TM == EGC_WEIGHT_GRAD_TILE_ROWS && X3_TN == EGC_WEIGHT_GRAD_TILE_COLS && EGC_WEIGHT_GRAD_MAX_SUM_COLS <= X3_TM, "egc_hip.h states the one-tile kernel's envelope");
 struct XtPlan {
-  int mt, nt, wn, m_tiles, n_tiles, chunks;
+  int mt, nt, wn, m_tiles, n_tiles, chunks;   // mt == 0: EGC_XT_TILE names a tile that is not compiled
   int64_t rows_per_chunk;
+  bool one_tile;   // xt_gemm_bf16x3_kernel: the output is one X3_TM x X3_TN accumulator tile and exact fp32 is not forced
 };
 
 constexpr int XT_STAGE = 32;  // rows of the reduction per LDS stage
 
-// The compiled block tiles of xt_gemm_kernel: 32 mt rows of F by 16 wn nt columns of K, 2 x wn wavefronts (one workgroup per CU).
-// The tall ones (mt 5 / 7: 160 / 224 rows, 60 - 84 accumulator registers per lane) are for the reference's batched nets, whose
+// The compiled block tiles (mt, nt, wn) of xt_gemm_kernel: 32 mt rows of F by 16 wn nt columns of K, 2 x wn wavefronts (one workgroup
+// per CU).  The tall ones (mt 5 / 7: 160 / 224 rows, 60 - 84 accumulator registers per lane) are for the reference's batched nets, whose
 // outputs a grid of 128 x 192 tiles pads by half (224 x 272 of molhiv EGC-M -> 256 x 384; 296 x 180 of EGC-S re-read d five times
 // as 64-row tiles): round 6, DESIGN.md 3.7.
-struct XtShape { int mt, nt, wn; };
-constexpr XtShape XT_SHAPES[] = {{1, 1, 4}, {1, 2, 4}, {1, 3, 4}, {2, 1, 4}, {2, 2, 4}, {2, 3, 4}, {4, 1, 4}, {4, 2, 4}, {4, 3, 4},
-                                 {5, 2, 4}, {5, 3, 4}, {7, 2, 4}, {7, 3, 3}, {7, 3, 4}, {7, 5, 4}, {7, 3, 6}};
+#define EGC_XT_TILES(T) \
+  T(1, 1, 4) T(1, 2, 4) T(1, 3, 4) T(2, 1, 4) T(2, 2, 4) T(2, 3, 4) T(4, 1, 4) T(4, 2, 4) T(4, 3, 4) \
+  T(5, 2, 4) T(5, 3, 4) T(7, 2, 4) T(7, 3, 3) T(7, 3, 4) T(7, 5, 4) T(7, 3, 6)
+#define EGC_XT_SHAPE(MT, NT, WN) {MT, NT, WN},
+constexpr struct XtShape { int mt, nt, wn; } XT_SHAPES[] = {EGC_XT_TILES(EGC_XT_SHAPE)};
+#undef EGC_XT_SHAPE
+
+// Rows per LDS stage of a tile's instance: half a stage where a lane's loads of two whole stages in flight no longer fit next to its
+// 4 mt nt accumulator registers -- past 84 of those (7 x 5: 140), or at three wavefronts per SIMD (wn 6: 168 registers per lane, not 256).
+constexpr int xt_stage_rows(int mt, int nt, int wn) { return (mt * nt > 21 || wn > 4) ? XT_STAGE / 2 : XT_STAGE; }
+// The workspace: per row range one record of the F x K partial tile, the K column sums of d and the E column sums of e.
+constexpr int64_t xt_record_floats(int F, int K, int E) { return (int64_t)F * K + K + E; }
+int64_t xt_workspace_bytes(const XtPlan& p, int F, int K, int E) { return (int64_t)p.chunks * xt_record_floats(F, K, E) * 4; }
 
 // EGC_GEMM_EXACT=1 (the switch of the forward GEMMs): exact fp32 products on the fp32 MFMA
 // instead of the split-bf16 form
 // Read per call (a getenv is nothing next to a launch): the host side decides from the same variables at every call
-// (functional._weight_grads), and a value cached here at first use would disagree with it once the environment changes.
+// (_dense._weight_grads), and a value cached here at first use would disagree with it once the environment changes.
 bool xt_fp32_only() { return env_on("EGC_GEMM_EXACT"); }
 
 XtPlan xt_plan(int64_t n_rows, int F, int K) {
@@ -546,18 +558,17 @@ XtPlan xt_plan(int64_t n_rows, int F, int K) {
   // the tallest tile that fits the registers.
   XtPlan p{};
   double best = 1e300;
-  const bool one_tile = F <= 128 && K <= 192 && !xt_fp32_only();   // xt_gemm_bf16x3_kernel
+  const bool one_tile = p.one_tile = F <= X3_TM && K <= X3_TN && !xt_fp32_only();
   const int64_t n = n_rows > 0 ? n_rows : 1;
   const int64_t max_chunks = ceil_div(n, XT_STAGE);
   // EGC_XT_TILE="mt,nt,wn": this tile of XT_SHAPES for every multi-tile call (tools/xt_wide_time.py: how the model above was fitted)
   int force[3] = {0, 0, 0};
-  if (const char* e = getenv("EGC_XT_TILE")) {
-    if (sscanf(e, "%d,%d,%d", &force[0], &force[1], &force[2]) != 3) force[0] = 0;
-  }
+  const char* forced = getenv("EGC_XT_TILE");
+  if (forced != nullptr && sscanf(forced, "%d,%d,%d", &force[0], &force[1], &force[2]) != 3) force[0] = 0;
   for (const XtShape& sh : XT_SHAPES) {
-    if (one_tile && (sh.mt != 4 || sh.nt != 3 || sh.wn != 4)) continue;
-    if (!one_tile && force[0] != 0 && (sh.mt != force[0] || sh.nt != force[1] || sh.wn != force[2])) continue;
     const int tm = 32 * sh.mt, tn = 16 * sh.wn * sh.nt;
+    if (one_tile && (tm != X3_TM || tn != X3_TN)) continue;   // (the row split of that tile's shape)
+    if (!one_tile && force[0] != 0 && (sh.mt != force[0] || sh.nt != force[1] || sh.wn != force[2])) continue;
     const int64_t mtl = ceil_div(F, tm), ntl = ceil_div(K, tn), tiles = mtl * ntl;
     // row ranges: the tiles of a range share an XCD (xt_gemm_kernel's id mapping), 32 CUs each -- as many ranges as keep every
     // XCD at one round of workgroups (86 ranges of three tiles were 33 workgroups on some XCDs: two rounds, 206 instead of 99 us
@@ -572,13 +583,7 @@ XtPlan xt_plan(int64_t n_rows, int F, int K) {
     const double cost = (double)rounds * (double)rows * per_row + 2.0 * (double)chunks * F * K * 4.0 / 6.0;
     if (cost < best) {
       best = cost;
-      p.mt = sh.mt;
-      p.nt = sh.nt;
-      p.wn = sh.wn;
-      p.m_tiles = (int)mtl;
-      p.n_tiles = (int)ntl;
-      p.rows_per_chunk = rows;
-      p.chunks = (int)chunks;
+      p = XtPlan{sh.mt, sh.nt, sh.wn, (int)mtl, (int)ntl, (int)chunks, rows, one_tile};
     }
   }
   return p;
@@ -604,18 +609,16 @@ extern "C" {
 
 int64_t egc_weight_grad_ex_workspace_bytes(int64_t n_rows, int32_t f_in, int32_t k_cols, int32_t e_cols) {
   if (n_rows < 0 || f_in <= 0 || k_cols <= 0 || e_cols < 0) return 0;
-  const egc::XtPlan p = egc::xt_plan(n_rows, f_in, k_cols);
-  return (int64_t)p.chunks * ((int64_t)f_in * k_cols + k_cols + e_cols) * 4;
+  return egc::xt_workspace_bytes(egc::xt_plan(n_rows, f_in, k_cols), f_in, k_cols, e_cols);
 }
 
 int egc_weight_grad_plan(int64_t n_rows, int32_t f_in, int32_t k_cols, int32_t* plan8) {
   if (n_rows < 0 || f_in <= 0 || k_cols <= 0 || plan8 == nullptr) return EGC_ERR_INVALID;
   const egc::XtPlan p = egc::xt_plan(n_rows, f_in, k_cols);
   if (p.mt == 0) return EGC_ERR_UNSUPPORTED;   // (EGC_XT_TILE names a tile that is not compiled)
-  const bool one_tile = !egc::xt_fp32_only() && f_in <= egc::X3_TM && k_cols <= egc::X3_TN;
-  const int32_t v[8] = {one_tile ? 1 : 0, one_tile ? egc::X3_TM : 32 * p.mt, one_tile ? egc::X3_TN : 16 * p.wn * p.nt,
-                        one_tile ? 1 : p.m_tiles, one_tile ? 1 : p.n_tiles, p.chunks, (int32_t)p.rows_per_chunk,
-                        one_tile ? egc::X3_THREADS : 64 * egc::XT_WM * p.wn};
+  static_assert(egc::X3_THREADS == 64 * egc::XT_WM * 4, "a one-tile plan is the row split of the list's X3_TM x X3_TN tile, whose workgroup has the bf16x3 kernel's size");
+  const int32_t v[8] = {p.one_tile ? 1 : 0, 32 * p.mt, 16 * p.wn * p.nt, p.m_tiles, p.n_tiles, p.chunks, (int32_t)p.rows_per_chunk,
+                        64 * egc::XT_WM * p.wn};
   for (int i = 0; i < 8; ++i) plan8[i] = v[i];
   return EGC_OK;
 }
@@ -635,14 +638,11 @@ static int weight_grad_impl(const float* x, int64_t ldx, const float* d, int64_t
       !aligned16(out) || !aligned16(col_sums) || !aligned16(workspace) || (e_cols % 4) || (lde % 4) ||
       !aligned16(e) || !aligned16(e_sums))
     return EGC_ERR_UNSUPPORTED;
-  const bool fp32_only = xt_fp32_only();
-  const bool one_tile = !fp32_only && f_in <= X3_TM && k_cols <= X3_TN;
-  // the third array rides along only in the one-tile kernel, next to the column sums of d, 128 columns at most
-  const int want_sums = (col_sums != nullptr || sc != nullptr) ? 1 : 0;   // scatter mode: the sums are the bias gradient
-  if (e != nullptr && (!one_tile || e_cols > X3_TM || !want_sums)) return EGC_ERR_UNSUPPORTED;
-  if (workspace_bytes < egc_weight_grad_ex_workspace_bytes(n_rows, f_in, k_cols, e_cols) || workspace == nullptr)
-    return EGC_ERR_INVALID;
   const XtPlan p = xt_plan(n_rows, f_in, k_cols);
+  // the third array rides along only in the one-tile kernel, next to the column sums of d, EGC_WEIGHT_GRAD_MAX_SUM_COLS at most
+  const int want_sums = (col_sums != nullptr || sc != nullptr) ? 1 : 0;   // scatter mode: the sums are the bias gradient
+  if (e != nullptr && (!p.one_tile || e_cols > EGC_WEIGHT_GRAD_MAX_SUM_COLS || !want_sums)) return EGC_ERR_UNSUPPORTED;
+  if (workspace_bytes < xt_workspace_bytes(p, f_in, k_cols, e_cols) || workspace == nullptr) return EGC_ERR_INVALID;
   if (p.mt == 0) return EGC_ERR_UNSUPPORTED;
   // 32-bit buffer offsets inside a workgroup's row range (plus the look-ahead past its end)
   const int64_t widest = std::max(std::max(ldx, ldd), e != nullptr ? lde : (int64_t)0);
@@ -650,7 +650,7 @@ static int weight_grad_impl(const float* x, int64_t ldx, const float* d, int64_t
   const int64_t fk = (int64_t)f_in * k_cols;
   float* partial = static_cast<float*>(workspace);
   int rc = EGC_ERR_UNSUPPORTED;
-  if (one_tile) {   // one accumulator tile: the bf16x3 kernel
+  if (p.one_tile) {   // one accumulator tile: the bf16x3 kernel
     constexpr int lds_bytes = X3_LDS_BYTES;
     EGC_ALLOW_DYNAMIC_LDS(&xt_gemm_bf16x3_kernel, lds_bytes, "xt_gemm_bf16x3_kernel");
     xt_gemm_bf16x3_kernel<<<(unsigned)p.chunks, X3_THREADS, lds_bytes, stream>>>(
@@ -659,23 +659,16 @@ static int weight_grad_impl(const float* x, int64_t ldx, const float* d, int64_t
     rc = EGC_OK;
   } else {
 #define EGC_XT_CASE(MT, NT, WN) \
-  if (p.mt == MT && p.nt == NT && p.wn == WN) rc = launch_xt<MT, NT, WN, ((MT * NT > 21 || WN > 4) ? XT_STAGE / 2 : XT_STAGE)>(p, x, ldx, f_in, d, ldd, k_cols, n_rows, partial, want_sums, stream);
-  EGC_XT_CASE(1, 1, 4) EGC_XT_CASE(1, 2, 4) EGC_XT_CASE(1, 3, 4)
-  EGC_XT_CASE(2, 1, 4) EGC_XT_CASE(2, 2, 4) EGC_XT_CASE(2, 3, 4)
-  EGC_XT_CASE(4, 1, 4) EGC_XT_CASE(4, 2, 4) EGC_XT_CASE(4, 3, 4)
-  EGC_XT_CASE(5, 2, 4) EGC_XT_CASE(5, 3, 4)
-  EGC_XT_CASE(7, 2, 4) EGC_XT_CASE(7, 3, 3) EGC_XT_CASE(7, 3, 4) EGC_XT_CASE(7, 5, 4) EGC_XT_CASE(7, 3, 6)
+  if (p.mt == MT && p.nt == NT && p.wn == WN) rc = launch_xt<MT, NT, WN, xt_stage_rows(MT, NT, WN)>(p, x, ldx, f_in, d, ldd, k_cols, n_rows, partial, want_sums, stream);
+    EGC_XT_TILES(EGC_XT_CASE)
 #undef EGC_XT_CASE
   }
   if (rc != EGC_OK) return rc;
-  const int64_t record = fk + k_cols + e_cols;
+  const int64_t record = xt_record_floats(f_in, k_cols, e_cols);
   const int64_t used = !want_sums ? fk : (e != nullptr ? record : fk + k_cols);
-  if (sc != nullptr)
-    xt_reduce_kernel<true><<<(unsigned)ceil_div(used / 4, 16), 256, 0, stream>>>(partial, record, fk, p.chunks, out, col_sums, k_cols,
-                                                                                 e_sums, *sc);
-  else
-    xt_reduce_kernel<false><<<(unsigned)ceil_div(used / 4, 16), 256, 0, stream>>>(partial, record, fk, p.chunks, out, col_sums, k_cols,
-                                                                                  e_sums);
+  const unsigned blocks = (unsigned)ceil_div(used / 4, 16);
+  if (sc != nullptr) xt_reduce_kernel<true><<<blocks, 256, 0, stream>>>(partial, record, fk, p.chunks, out, col_sums, k_cols, e_sums, *sc);
+  else xt_reduce_kernel<false><<<blocks, 256, 0, stream>>>(partial, record, fk, p.chunks, out, col_sums, k_cols, e_sums);
   EGC_LAUNCH_CHECK("xt_reduce_kernel");
   return EGC_OK;
 }

@@ -180,9 +180,40 @@ std::vector<at::Tensor> train_forward_op(const at::Tensor& x, const at::Tensor& 
                        reinterpret_cast<const egc_layer*>(layer), workspace, stream, H, A, B, L, Ls, permute_hab, gemm_flags);
 }
 
+static bool third_stream_rides(int64_t f_in, int64_t k, int64_t e_cols) {   // (egc_hip.h: e's column sums ride in the one-tile kernel only)
+  return f_in <= EGC_WEIGHT_GRAD_TILE_ROWS && k <= EGC_WEIGHT_GRAD_TILE_COLS && e_cols <= EGC_WEIGHT_GRAD_MAX_SUM_COLS && (e_cols % 4) == 0;
+}
+
+// -> {d comb_w, d comb_b (packed_bias) or d bcat_direct, d basis parts ...}: x^T d_cat and the column sums of d_cat's weightings part
+// written straight into fresh gradients through the pack's index map (egc_weight_grad_params_f32: no d wcat array, no unpack launch).
+// `e` (or nullptr): [N, f_out], its column sums (the layer's bias gradient) ride along into `es` -- third_stream_rides says where.
+template <class PartShape>
+static std::vector<at::Tensor> weight_grads_into_params(const at::Tensor& x, const at::Tensor& d_cat, const at::Tensor* e, at::Tensor& es,
+                                                        int64_t H, int64_t A, int64_t B, int64_t L, int64_t Ls, bool permute_hab,
+                                                        bool packed_bias, at::IntArrayRef comb_w_shape, at::IntArrayRef comb_b_shape,
+                                                        int64_t n_parts, PartShape part_shape, egc_stream_t st) {
+  const auto opts = x.options();
+  const int64_t n = x.size(0), f_in = x.size(1), k = d_cat.size(1), e_cols = e != nullptr ? e->size(1) : 0;
+  std::vector<at::Tensor> g{at::empty(comb_w_shape, opts), packed_bias ? at::empty(comb_b_shape, opts) : at::empty({H * B * A}, opts)};
+  std::vector<float*> ptrs;
+  for (int64_t i = 0; i < n_parts; ++i) {
+    // (padding columns of a padded basis have no parameter behind them: every element of a part is written)
+    g.push_back(at::empty(part_shape(i), opts));
+    ptrs.push_back(g.back().data_ptr<float>());
+  }
+  at::Tensor gws = at::empty({std::max<int64_t>(egc_weight_grad_ex_workspace_bytes(n, (int32_t)f_in, (int32_t)k, (int32_t)e_cols), 16)}, opts.dtype(at::kByte));
+  check_status(egc_weight_grad_params_f32(x.data_ptr<float>(), f_in, d_cat.data_ptr<float>(), k, n, (int32_t)f_in, (int32_t)H, (int32_t)A,
+                                          (int32_t)B, (int32_t)L, (int32_t)Ls, permute_hab ? 1 : 0, ptrs.data(), (int32_t)n_parts,
+                                          g[0].data_ptr<float>(), packed_bias ? g[1].data_ptr<float>() : nullptr,
+                                          packed_bias ? nullptr : g[1].data_ptr<float>(), e != nullptr ? e->data_ptr<float>() : nullptr, e_cols,
+                                          (int32_t)e_cols, e != nullptr ? es.data_ptr<float>() : nullptr, gws.data_ptr(), gws.numel(), st),
+               "egc_weight_grad_params_f32");
+  return g;
+}
+
 // -> [dx (or empty), d comb_w, d comb_b or d bcat_direct (or empty), d bias (or empty), d basis matrices ...]
 // Requires (checked by the caller): ldb == B Ls, (ldb + W) % 4 == 0, f_in % 4 == 0, f_out % 4 == 0; a bias and a combination bias
-// present.  The one-pass dense-gradient kernel inside its envelope (f_in <= 128, ldb + W <= 192, f_out <= 128), the general
+// present.  The one-pass dense-gradient kernel inside its envelope (weight_grads_into_params: the third stream rides), the general
 // sequence outside it (round 6).
 // dx_addend (or nullptr): [N, f_in] added to d x -- the residual branch's gradient; joins the d x GEMM's store where the kernel
 // carries an addend (egc_basis_transform_packed_add), else one in-place add.  bias_grad (or nullptr): the column sums of grad_out
@@ -230,36 +261,16 @@ static std::vector<at::Tensor> train_backward_impl(const at::Tensor& grad_out, c
       check_status(rc, "egc_basis_transform_packed_add");
     }
   }
-  // (3) the dense gradients of the parameters: x^T d_cat with the column sums of d_cat (combination bias), written straight into
-  // the parameters' gradients through the pack's index map (egc_weight_grad_params_f32: no d wcat array, no unpack launch), at
-  // every width (round 6: the reference's own batched nets -- 168 / 224 / 296 wide, run_pretrained.sh:7,12,23,24 -- go through
-  // the exact-fp32 tile grid; same sums in the same order as egc_weight_grad_ex_f32 + egc_weights_pack_f32(grad = 1), the calls
-  // of egc_amd/functional.py's _layer_train_backward + _unpack_param_grads).  The column sums of grad_out (the layer's bias) ride
-  // along inside the one-tile kernel's envelope (f_in <= 128, ldb + W <= 192, f_out <= 128), come from the caller when it holds
-  // them (the block node's BatchNorm step), or take their own pass.
+  // (3) the dense gradients of the parameters (weight_grads_into_params: x^T d_cat with the column sums of d_cat), at every width
+  // (round 6: the reference's own batched nets -- 168 / 224 / 296 wide, run_pretrained.sh:7,12,23,24 -- go through the exact-fp32
+  // tile grid; same sums in the same order as egc_weight_grad_ex_f32 + egc_weights_pack_f32(grad = 1), the calls of
+  // egc_amd/functional.py's _layer_train_backward + _unpack_param_grads).  The column sums of grad_out (the layer's bias) ride along
+  // where the third stream does, come from the caller when it holds them (the block node's BatchNorm step), or take their own pass.
   const bool have_es = bias_grad != nullptr;
   at::Tensor es = have_es ? *bias_grad : at::empty({f_out}, opts);
-  at::Tensor dcw = at::empty(comb_w_shape, opts);
-  at::Tensor dcb = packed_bias ? at::empty(comb_b_shape, opts) : at::empty({W}, opts);
-  std::vector<at::Tensor> dparts;
-  std::vector<float*> ptrs;
-  for (int64_t i = 0; i < n_parts; ++i) {
-    // (padding columns of a padded basis have no parameter behind them: every element of a part is written)
-    dparts.push_back(at::empty(part_shape, opts));
-    ptrs.push_back(dparts.back().data_ptr<float>());
-  }
-  // e rides along only in the one-tile kernel (f_in <= 128, ldb + W <= 192) and for at most 128 columns
-  const bool ride = !have_es && f_in <= 128 && k <= 192 && f_out <= 128 && (f_out % 4) == 0;
-  {
-    const int64_t gbytes = (int64_t)egc_weight_grad_ex_workspace_bytes(n, (int32_t)f_in, (int32_t)k, ride ? (int32_t)f_out : 0);
-    at::Tensor gws = at::empty({std::max<int64_t>(gbytes, 16)}, opts.dtype(at::kByte));
-    check_status(egc_weight_grad_params_f32(x.data_ptr<float>(), f_in, d_cat.data_ptr<float>(), k, n, (int32_t)f_in, (int32_t)H,
-                                            (int32_t)A, (int32_t)B, (int32_t)L, (int32_t)Ls, permute_hab ? 1 : 0, ptrs.data(),
-                                            (int32_t)n_parts, dcw.data_ptr<float>(), packed_bias ? dcb.data_ptr<float>() : nullptr,
-                                            packed_bias ? nullptr : dcb.data_ptr<float>(), ride ? go.data_ptr<float>() : nullptr, f_out,
-                                            ride ? (int32_t)f_out : 0, ride ? es.data_ptr<float>() : nullptr, gws.data_ptr(), gws.numel(), st),
-                 "egc_weight_grad_params_f32");
-  }
+  const bool ride = !have_es && third_stream_rides(f_in, k, f_out);
+  std::vector<at::Tensor> out = weight_grads_into_params(x, d_cat, ride ? &go : nullptr, es, H, A, B, L, Ls, permute_hab, packed_bias,
+                                                         comb_w_shape, comb_b_shape, n_parts, [&](int64_t) { return part_shape; }, st);
   if (!have_es && !ride) {      // the layer's bias gradient on its own: the column sums of grad_out
     const int64_t parts = n_partials(n);
     at::Tensor psum = at::empty({parts, f_out}, opts);
@@ -268,8 +279,8 @@ static std::vector<at::Tensor> train_backward_impl(const at::Tensor& grad_out, c
     if (parts == 1) es = psum[0];
     else check_status(egc_sum_partials_f32(psum.data_ptr<float>(), (int32_t)parts, (int32_t)f_out, es.data_ptr<float>(), st), "egc_sum_partials_f32");
   }
-  std::vector<at::Tensor> out{dx, dcw, dcb, es};
-  out.insert(out.end(), dparts.begin(), dparts.end());
+  out.insert(out.begin(), dx);
+  out.insert(out.begin() + 3, es);
   return out;
 }
 
@@ -492,29 +503,17 @@ struct BatchBlockTrainFn : public torch::autograd::Function<BatchBlockTrainFn> {
                                                     reinterpret_cast<int32_t*>(s.host_flag), st), "egc_layer_backward_batch_fused_f32");
     out[0] = dx;
     // x^T d_cat + the column sums of d_cat's weightings part (combination bias) and of the layer's incoming gradient (its bias)
-    at::Tensor es = at::empty({f_out}, opts), dcw = at::empty(s.comb_w_shape, opts);
-    at::Tensor dcb = s.has_comb_b ? at::empty(s.comb_b_shape, opts) : at::empty({W}, opts);
-    std::vector<at::Tensor> dparts;
-    std::vector<float*> ptrs;
-    for (int64_t i = 0; i < n_parts_w; ++i) {
-      dparts.push_back(at::empty(s.part_shapes[i], opts));
-      ptrs.push_back(dparts.back().data_ptr<float>());
-    }
     // (the layer's bias gradient: from the BatchNorm step above where there is one, else -- and when nobody asks -- no third stream)
+    at::Tensor es = at::empty({f_out}, opts);
     const bool ride = s.has_bias && !dh_sums.defined();
-    const int64_t gbytes = egc_weight_grad_ex_workspace_bytes(n, (int32_t)f_in, (int32_t)k, ride ? (int32_t)f_out : 0);
-    at::Tensor gws = at::empty({std::max<int64_t>(gbytes, 16)}, opts.dtype(at::kByte));
-    check_status(egc_weight_grad_params_f32(x.data_ptr<float>(), f_in, d_cat.data_ptr<float>(), k, n, (int32_t)f_in, (int32_t)s.H, (int32_t)s.A,
-                                            (int32_t)s.B, (int32_t)s.L, (int32_t)s.Ls, s.permute_hab ? 1 : 0, ptrs.data(), (int32_t)n_parts_w,
-                                            dcw.data_ptr<float>(), s.has_comb_b ? dcb.data_ptr<float>() : nullptr,
-                                            s.has_comb_b ? nullptr : dcb.data_ptr<float>(), ride ? g_conv.data_ptr<float>() : nullptr, f_out,
-                                            ride ? (int32_t)f_out : 0, ride ? es.data_ptr<float>() : nullptr, gws.data_ptr(), gws.numel(), st),
-                 "egc_weight_grad_params_f32");
+    TORCH_CHECK(!ride || third_stream_rides(f_in, k, f_out), "batch_block_train: outside the envelope native_block_train admits");
+    const std::vector<at::Tensor> pg = weight_grads_into_params(x, d_cat, ride ? &g_conv : nullptr, es, s.H, s.A, s.B, s.L, s.Ls,
+        s.permute_hab, s.has_comb_b, s.comb_w_shape, s.comb_b_shape, n_parts_w, [&](int64_t i) { return at::IntArrayRef(s.part_shapes[i]); }, st);
     if (s.has_bias) out[1] = dh_sums.defined() ? dh_sums : es;
-    out[2] = dcw;
-    if (s.has_comb_b) out[3] = dcb;
-    if (s.has_bcat) out[4] = dcb;
-    for (int64_t i = 0; i < n_parts_w; ++i) out[7 + i] = dparts[i];
+    out[2] = pg[0];
+    if (s.has_comb_b) out[3] = pg[1];
+    if (s.has_bcat) out[4] = pg[1];
+    for (int64_t i = 0; i < n_parts_w; ++i) out[7 + i] = pg[2 + i];
     return out;
   }
 };

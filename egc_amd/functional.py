@@ -30,7 +30,7 @@ from ._bn_tail import (_BatchNormActResidualFunction, _bn_tail_operands, _f32_ve
                        batch_norm_act_residual_supported)
 from ._dense import (_PackWeightsFunction, _column_sums, _dense_param_grads, _dims, _dx_matmul, _pack_params,  # noqa: F401
                      _unpack_param_grads, _weight_grads, _weight_grads_into_params, _xt_library, gemm_exact,
-                     pack_layer_weights)
+                     pack_layer_weights, third_stream_rides)
 
 
 @dataclass
@@ -592,7 +592,7 @@ def _native_train_ops(graph, spec, x, bias, comb_w, comb_b, bcat_direct, bases):
     k = spec.ldb + spec.w_cols
     if not (spec.ldb == spec.f_g and k % 4 == 0 and spec.f_in % 4 == 0 and spec.f_out % 4 == 0):
         return None
-    if not (k <= 192 and spec.f_in <= 128 and spec.f_out <= 128):
+    if not third_stream_rides(spec.f_in, k, spec.f_out):
         # outside the one-pass dense-gradient kernel: the general sequence (round 6: the reference's own 168 / 224 / 296-wide
         # batched nets), where the split GEMMs take the shape and x^T d goes through the exact-fp32 tile grid
         if (k > 384 or spec.f_in > 384 or spec.f_out > 1024 or x.data_ptr() % 16
@@ -627,9 +627,8 @@ def native_block_train(call, bn=None, residual=True, with_tail=True):
     if comb_b is not None and bcat_direct is not None:
         return None
     k = spec.ldb + spec.w_cols
-    if not (spec.ldb == spec.f_g and k % 4 == 0 and k <= 192 and spec.f_in % 4 == 0 and spec.f_in <= 128
-            and spec.f_out % 4 == 0 and spec.f_out <= 128
-            and k == call.B * call.Ls + call.H * call.B * call.A):
+    if not (spec.ldb == spec.f_g and k % 4 == 0 and spec.f_in % 4 == 0 and spec.f_out % 4 == 0
+            and third_stream_rides(spec.f_in, k, spec.f_out) and k == call.B * call.Ls + call.H * call.B * call.A):
         return None
     if graph.n_nodes is None:
         graph.n_nodes = int(x.size(0))

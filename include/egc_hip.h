@@ -363,22 +363,25 @@ int egc_aggregate_combine_strided_f32(const egc_graph* graph, const egc_layer* l
  * egc_aggregate_combine_backward_f32), and, when col_sums != NULL, col_sums[k_cols] = the column sums of d (the
  * gradient of the combination Linear's bias).  Replaces what autograd runs for the reference's
  * `torch.matmul(x, self.bases_weight)` / `self.comb_weights(x)` (experiments/optimized_layers.py:177-178;
- * experiments/layers.py:110-111): exact fp32 products and sums on the fp32 matrix-core instruction, row ranges
- * added in a fixed order (deterministic).  f_in, k_cols, ldx, ldd multiples of 4 and 16-byte aligned pointers,
- * else EGC_ERR_UNSUPPORTED.  workspace: egc_weight_grad_workspace_bytes(n_rows, f_in, k_cols) bytes, contents
- * irrelevant on entry and on exit. */
+ * experiments/layers.py:110-111): split-bf16 products of fp32-level accuracy on the 16-bit matrix cores inside one
+ * accumulator tile (below), exact fp32 products on the fp32 matrix-core instruction beyond it and, with EGC_GEMM_EXACT=1,
+ * everywhere; fp32 sums, row ranges added in a fixed order (deterministic).  f_in, k_cols, ldx, ldd multiples of 4 and 16-byte
+ * aligned pointers, else EGC_ERR_UNSUPPORTED.  workspace: egc_weight_grad_workspace_bytes() bytes, contents irrelevant on entry and exit. */
 int64_t egc_weight_grad_workspace_bytes(int64_t n_rows, int32_t f_in, int32_t k_cols);
 /* How a call of that shape is laid out (host only, no GPU work; round 6): plan8 = {split-bf16 one-tile kernel (1) or exact-fp32
  * kernel (0), rows of an output tile, columns of an output tile, tiles along f_in, tiles along k_cols, row ranges, rows per range,
  * threads per workgroup}.  The exact-fp32 kernel is compiled for a list of tile shapes (32 .. 224 rows by 64 .. 320 columns) and
  * the host picks shape and row split together by modelled time; tests use this to see that every compiled shape is exercised. */
 int egc_weight_grad_plan(int64_t n_rows, int32_t f_in, int32_t k_cols, int32_t* plan8);
-/* The same with the column sums of a THIRD array riding along: e [n_rows][e_cols] (row stride lde; e_cols <= 128, a
+/* The same with the column sums of a THIRD array riding along: e [n_rows][e_cols] (row stride lde; e_cols a
  * multiple of 4) -> e_sums[e_cols].  A training step wants three reductions over the nodes -- the weight gradient, the
  * column sums of d weightings (bias of the combination Linear) and the column sums of grad_out (the layer's bias,
  * layers.py:137-138 / optimized_layers.py:207-208) -- and this is all three in one pass.  Only where the weight
- * gradient is one 128 x 192 accumulator tile (f_in <= 128, k_cols <= 192) and col_sums is requested; otherwise
+ * gradient is one accumulator tile (the limits below, EGC_GEMM_EXACT unset) and col_sums is requested; otherwise
  * EGC_ERR_UNSUPPORTED (use egc_column_sums_f32 for e).  e == NULL or e_sums == NULL: egc_weight_grad_f32. */
+#define EGC_WEIGHT_GRAD_TILE_ROWS 128    /* f_in <= this and */
+#define EGC_WEIGHT_GRAD_TILE_COLS 192    /* k_cols <= this: the one-tile (split-bf16) kernel */
+#define EGC_WEIGHT_GRAD_MAX_SUM_COLS 128 /* e_cols <= this */
 int64_t egc_weight_grad_ex_workspace_bytes(int64_t n_rows, int32_t f_in, int32_t k_cols, int32_t e_cols);
 int egc_weight_grad_ex_f32(const float* x, int64_t ldx, const float* d, int64_t ldd, int64_t n_rows, int32_t f_in,
                            int32_t k_cols, float* out, float* col_sums, const float* e, int64_t lde, int32_t e_cols,

@@ -33,7 +33,8 @@ def test_argument_lists_spelled_by_hand():
     assert _C.SYMBOLS["egc_last_error"] == (C.c_char_p, []) and _C.SYMBOLS["egc_version"] == (C.c_char_p, [])
     assert _C.SYMBOLS["egc_coo_to_csr_workspace_bytes"] == (Z, [L, L])
     assert _C.SYMBOLS["egc_gather_plan_launches"] == (L, []) and _C.SYMBOLS["egc_gather_plan_form"] == (I, [L, L, I])
-    assert len(_C.SYMBOLS) == 128 and len(_C.ABI.structs) == 9 and len(_C.ABI.constants) == 75
+    assert len(_C.SYMBOLS) == 128 and len(_C.ABI.structs) == 9 and len(_C.ABI.constants) == 78
+    assert (_C.WEIGHT_GRAD_TILE_ROWS, _C.WEIGHT_GRAD_TILE_COLS, _C.WEIGHT_GRAD_MAX_SUM_COLS) == (128, 192, 128)
 
 
 def test_struct_layouts_spelled_by_hand():
